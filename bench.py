@@ -17,12 +17,23 @@ mantissas, .pac bit packing and body assembly; with N > 1 the packed bitstream
 of every rank is then gathered to rank 0 over RCCL.  Weak scaling: every rank
 encodes its own 4096-frame shard.  Prints ONE JSON line on rank 0.
 
-Timing: after W warm-up steps the K-step region (barrier + synchronize on both sides,
-maximum over ranks) is timed --repeats times; `value` and `ms_per_step` come from the
-MEDIAN region, the spread is reported in config.  After the timing, outside it, 32
-channel-frames spread over the batch are re-encoded by the oracle (the CPU restatement of
-the reference) and their payload bytes compared with what the timed kernels left in the
-output buffers: `verified_cf`.  The body must also have fitted its buffer.
+Timing: after W warm-up steps (and more until --warmup-seconds, 0.2 s, have gone into warm-up:
+the card's clocks settle in the first tens of milliseconds under load) ONE region of exactly K
+steps (barrier + synchronize on both sides, maximum over ranks) is timed; `value` and
+`ms_per_step` come from it.  The body must have fitted its buffer.  That is all a plain run does.
+
+    python bench.py ... --dump-outputs DIR
+
+writes what the timed path computed in its last step (the packed body and the per-channel-frame
+codes, as float32 / float64 .npy; a fixed, seeded sample of channel-frames past 64 MB) to DIR.
+
+    python bench.py ... --full
+
+adds, after the headline region and outside it: further K-step regions (--repeats, --min-seconds;
+their median and spread go to config), the one-step-in-flight figure, the oracle check of the
+timed run's output (32 channel-frames spread over the batch re-encoded by the CPU restatement of
+the reference, payload bytes compared: `verified_cf`), the MDCT kernel's roofline, the
+host-to-host and decode figures, the committed per-kernel profile and the CPU baseline.
 
 --corpus: BASELINE configs[4]: the config-2 stream tiled, tile t scaled
 by 0.5 + 0.5 (t mod 16)/16, 1 048 576 stereo frames in all (--corpus-frames), sharded into
@@ -48,6 +59,8 @@ KBPS = 128
 MDCT_BYTES_PER_CF = 1024 * 2 + 1024 * 8      # int16 hop in + float64 lines out
 HBM_PEAK_GBS = 8000.0
 CORPUS_FRAMES = 1 << 20        # configs[4]: 1 048 576 stereo frames
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes of .npy data at most
+DUMP_SEED = 20261016           # --dump-outputs: the channel-frames sampled past DUMP_BUDGET
 # the reference ITSELF (its own Python, imported in the build container where /root/reference exists; it
 # cannot travel to the GPU box): BASELINE.md section 3.1, tools/ref_cpu_timing.py -- quoted, not measured here
 REFERENCE_CPU = {"one_process": 32.2, "pool8": 234.0, "unit": "channel-frames/s", "cores": 8,
@@ -204,6 +217,43 @@ def verify_against_oracle(pcm, sample_rate, kbps, vq_kbps, flags, payload_rows, 
     return ok
 
 
+# ------------------------------------------------------------------ --dump-outputs
+def dump_outputs(out_dir, codes, payload, body, flags, n_ch, budget=DUMP_BUDGET):
+    """What the timed path handed back in its last step, as DIR/<name>.npy: `body` (the .pac body, '<L nBytes' +
+    payload per channel-frame, uint8 -> float32), the per-channel-frame codes `codes` {name: int32 device tensor
+    [n_cf, ...]} (-> float64) and, block-switched, the per-frame `flags`.  Past `budget` bytes a fixed sample of
+    channel-frames (DUMP_SEED) is written instead: their codes, their payload rows (zero past n_bytes, which
+    is what the body holds of them), `flags` of their frames and `cf_index`.  Returns {name: shape}."""
+    import torch
+    n_cf = int(codes["n_bytes"].shape[0])
+    row = sum(8 * (int(t[0].numel()) if t.dim() > 1 else 1) for t in codes.values())
+    full = 4 * int(body.numel()) + n_cf * row + (8 * int(flags.numel()) if flags is not None else 0)
+    arrays, headers = {}, 4096                 # room for the .npy headers
+    if full + headers <= budget:
+        arrays["body"] = body.cpu().numpy().astype(np.float32)
+        for k, t in codes.items():
+            arrays[k] = t.cpu().numpy().astype(np.float64)
+        if flags is not None:
+            arrays["flags"] = flags.cpu().numpy().astype(np.float64)
+    else:
+        per_cf = row + 4 * int(payload.shape[1]) + 16
+        k = max(1, min(n_cf, (budget - headers) // per_cf))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_cf, k, replace=False))
+        sel = torch.as_tensor(idx, device=payload.device)
+        for name, t in codes.items():
+            arrays[name] = t.index_select(0, sel).cpu().numpy().astype(np.float64)
+        rows = payload.index_select(0, sel).cpu().numpy()
+        rows[np.arange(rows.shape[1])[None, :] >= arrays["n_bytes"][:, None]] = 0
+        arrays["payload"] = rows.astype(np.float32)
+        if flags is not None:
+            arrays["flags"] = flags.cpu().numpy()[idx // n_ch].astype(np.float64)
+        arrays["cf_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 # ------------------------------------------------------------------ N ranks from one command
 def _free_port():
     import socket
@@ -268,7 +318,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=10, help="timed K-step regions (at least); value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline (after it, outside its timed region): further K-step regions "
+                         "(--repeats, --min-seconds), the one-step-in-flight figure, the oracle check of the output "
+                         "(verified_cf), the MDCT roofline, the host-to-host and decode figures, the committed per-kernel "
+                         "profile and the CPU baseline.  Without it: set-up, warm-up, one timed region of --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of channel-frames past 64 MB)")
+    ap.add_argument("--warmup-seconds", type=float, default=0.2,
+                    help="warm-up: the --warmup steps, then more until this much wall time has gone into warm-up (the "
+                         "card's clocks settle during the first tens of milliseconds under load); 0 = --warmup steps only")
+    ap.add_argument("--repeats", type=int, default=10,
+                    help="--full: timed K-step regions in all (at least), the first being the headline's; their median "
+                         "and spread go to config")
     ap.add_argument("--no-decode-leg", action="store_true",
                     help="skip the decode figure (config.decode_cf_per_s: the timed run's payloads back to PCM; never `value`)")
     ap.add_argument("--gate-us", type=float, default=None,
@@ -277,8 +340,8 @@ def main():
                          "(engine.EncoderPool.align; DESIGN.md 5.0); 0 = off; default: 20 for all-long scalar batches "
                          "(the only workload with two timing modes), 0 otherwise")
     ap.add_argument("--min-seconds", type=float, default=1.5,
-                    help="keep timing K-step regions until this much wall time has gone into them (and --repeats regions "
-                         "are done): the median then describes the card under sustained load, clocks settled")
+                    help="--full: keep timing K-step regions until this much wall time has gone into them (and --repeats "
+                         "regions are done): their median then describes the card under sustained load, clocks settled")
     ap.add_argument("--frames", type=int, default=None, help="stereo frames per GPU and step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
@@ -299,7 +362,7 @@ def main():
                     help="scalar128 = BASELINE configs[1] (the headline); vq128 / vq96 = the gain-shape "
                          "coder of configs[3] (vq96 with SBR) on the same synthetic stream; bs128 = "
                          "configs[2]: block switching on, the castanet stream (the whole file as the "
-                         "reference's driver reads it, tests/golden/full_castanet.npz) tiled to --frames "
+                         "reference's driver reads it, tests/golden/full_castanet.part*.npz) tiled to --frames "
                          "hops (44.1 kHz), transient detector inside the step; shipped128 / shipped96 = the "
                          "settings the reference's own driver uses (coder/pacfile.py:699-707: gain-shape coder, "
                          "block switching, SBR below 128 kb/s) on that castanet stream")
@@ -319,6 +382,8 @@ def main():
                          "config.host_to_host_cf_per_s (pinned PCM in, packed bodies out, copies overlapped with the "
                          "kernels: audio-codec_amd/streaming.py); 0 = skip.  Never `value`.")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if (args.gpus > 1 or os.environ.get("PACX_BENCH_FORCE_DIST")) and "WORLD_SIZE" not in os.environ:
         # the plain command: start the N ranks ourselves, as children (nothing above has touched the GPU)
@@ -372,7 +437,9 @@ def main():
     else:
         n_frames = args.frames or FRAMES_PER_GPU
         if block_switched:
-            full = np.load(os.path.join(ROOT, "tests", "golden", "full_castanet.npz"))
+            sys.path.append(os.path.join(ROOT, "tests"))
+            from golden_io import load_npz          # the fixture is stored in parts below 1 MiB
+            full = load_npz("full_castanet")
             sample_rate = int(full["sr"])
             src = full["pcm"]
             src = src[:len(src) // 1024 * 1024]
@@ -515,23 +582,56 @@ def main():
             dt = float(t.item())
         return dt
 
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         step()
-    regions, t_begin = [], time.perf_counter()
-    while len(regions) < max(1, args.repeats) or (time.perf_counter() - t_begin < args.min_seconds and len(regions) < 20000):
-        regions.append(timed_region())
-        if multi and len(regions) >= max(1, args.repeats):      # ranks must agree on when to stop
-            flag = torch.tensor([1.0 if time.perf_counter() - t_begin < args.min_seconds else 0.0], dtype=torch.float64,
+    warm_steps = args.warmup
+    while args.warmup_seconds > 0:             # the card's clocks settle during the first tens of ms under load
+        sync_all()
+        going = time.perf_counter() - t_warm < args.warmup_seconds
+        if multi:                              # every rank runs the same steps (the gather is collective)
+            flag = torch.tensor([1.0 if going else 0.0], dtype=torch.float64,
                                 device=torch.device("cpu") if dist.get_backend() == "gloo" else dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            if float(flag.item()) == 0.0:
-                break
-    dt = float(np.median(regions))
+            going = float(flag.item()) == 1.0
+        if not going:
+            break
+        for _ in range(20):
+            step()
+        warm_steps += 20
+    # the headline: one region of exactly --steps steps
+    t_begin = time.perf_counter()
+    dt = timed_region()
+    regions = [dt]
+    dumped = None
+    if args.dump_outputs and rank == 0:        # the last step's outputs, before anything else runs on the pipelines
+        pl = pipes[(step_no[0] - 1) % in_flight[0]]
+        o = pl["vq_out"] if vq_kbps else pl["out"]
+        keys = ("overall", "bit_alloc", "status", "n_bytes") if vq_kbps else \
+            ("overall", "scale_factor", "bit_alloc", "status", "n_bytes")
+        dumped = dump_outputs(args.dump_outputs, {k: o[k] for k in keys}, o["payload"],
+                              pl["body"][:int(pl["total"].item())], pl["fl"][:n_frames] if block_switched else None, N_CH)
+
+    def another_region():
+        """--full: time one more K-step region?  Past --repeats, with several ranks, they decide together."""
+        if len(regions) < max(1, args.repeats):
+            return True
+        if len(regions) >= 20000:
+            return False
+        going = time.perf_counter() - t_begin < args.min_seconds
+        if multi:                                   # ranks must agree on when to stop
+            flag = torch.tensor([1.0 if going else 0.0], dtype=torch.float64,
+                                device=torch.device("cpu") if dist.get_backend() == "gloo" else dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            going = float(flag.item()) == 1.0
+        return going
+    while args.full and another_region():
+        regions.append(timed_region())
     if dump_regions and rank == 0:
         with open(dump_regions, "w") as f:
             f.write("\n".join(f"{r / args.steps * 1e3:.5f}" for r in regions) + "\n")
     regions_one = None
-    if P > 1 and not multi:                # the same K steps with one step in flight at a time (round 2's figure)
+    if args.full and P > 1 and not multi:  # the same K steps with one step in flight at a time (round 2's figure)
         in_flight[0] = 1
         step_no[0] = 0
         one_graph = None
@@ -543,7 +643,7 @@ def main():
         pipes[0]["enc"].set_side_fork(True)
         in_flight[0] = P
     regions_nogather = None
-    if corpus and multi:                   # with and without the gather
+    if args.full and corpus and multi:     # with and without the gather
         do_gather[0] = False
         regions_nogather = [timed_region() for _ in range(max(1, args.repeats))]
         do_gather[0] = True
@@ -559,7 +659,7 @@ def main():
     assert body_bytes == int(n_bytes_h.astype(np.int64).sum()) + 4 * int(np.count_nonzero(n_bytes_h)), \
         "body size is not the sum of its records"
     verified = 0
-    if not args.no_verify:                 # EVERY rank checks its own output (its own stream or shard)
+    if args.full and not args.no_verify:   # EVERY rank checks its own output (its own stream or shard)
         picks = sorted(set(np.linspace(0, n_frames - 1, 16).astype(int).tolist()))
         rows = {f * N_CH + ch: out["payload"][f * N_CH + ch].cpu().numpy() for f in picks for ch in range(N_CH)}
         flags_h = fl_buf[:n_frames].cpu().numpy() if block_switched else None
@@ -573,7 +673,7 @@ def main():
                 assert np.array_equal(pp["out"]["payload"][i].cpu().numpy()[:int(nb_q[i])], row[:int(nb_q[i])]), \
                     f"cf {i}: the pipelines' payloads differ"
     verified_per_rank = [verified]
-    if multi:                              # rank 0 reports every rank's count; a rank whose check fails has raised
+    if args.full and multi:                # rank 0 reports every rank's count; a rank whose check fails has raised
         cnt = torch.tensor([verified], dtype=torch.int64,
                            device=torch.device("cpu") if dist.get_backend() == "gloo" else dev)
         cnts = [torch.zeros_like(cnt) for _ in range(world)]
@@ -583,52 +683,65 @@ def main():
             assert min(verified_per_rank) > 0, f"a rank verified nothing: {verified_per_rank}"
         verified = sum(verified_per_rank)
 
-    # ---- MDCT kernel alone: HIP events on the stream the kernel runs on
-    mdct_cf = min(n_cf, 2 * FRAMES_PER_GPU) if corpus else n_cf
-    mview = view
-    if mdct_cf != n_cf:
-        mview = A.engine.PcmView.stream(planar[:, :(mdct_cf // N_CH + 1) * 1024].contiguous())
-    lines = torch.empty((mdct_cf, 1024), dtype=torch.float64, device=dev)
-    scale = torch.empty((mdct_cf,), dtype=torch.int32, device=dev)
+    # ---- MDCT kernel alone (--full): HIP events on the stream the kernel runs on
+    def mdct_roofline():
+        mdct_cf = min(n_cf, 2 * FRAMES_PER_GPU) if corpus else n_cf
+        mview = view
+        if mdct_cf != n_cf:
+            mview = A.engine.PcmView.stream(planar[:, :(mdct_cf // N_CH + 1) * 1024].contiguous())
+        lines = torch.empty((mdct_cf, 1024), dtype=torch.float64, device=dev)
+        scale = torch.empty((mdct_cf,), dtype=torch.int32, device=dev)
 
-    def mdct_once():
-        enc._call("pacx_mdct_batch", ctypes.byref(mview.c), None, 0, _ptr(lines), _ptr(scale), enc._stream())
-    for _ in range(5):
-        mdct_once()
-    torch.cuda.synchronize()
-    # HIP events on the launch stream around trains of back-to-back launches:
-    # (train time / launches) = kernel duration + the ~1 us kernel boundary, with
-    # the host launch latency hidden behind the previous kernel
-    train = 10
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(max(1, args.mdct_launches // train))]
-    for a, b in ev:
-        a.record()
-        for _ in range(train):
+        def mdct_once():
+            enc._call("pacx_mdct_batch", ctypes.byref(mview.c), None, 0, _ptr(lines), _ptr(scale), enc._stream())
+        for _ in range(5):
             mdct_once()
-        b.record()
-    torch.cuda.synchronize()
-    trains = [a.elapsed_time(b) / train for a, b in ev]
-    mdct_ms = float(np.median(trains))
-    mdct_gbs = mdct_cf * MDCT_BYTES_PER_CF / (mdct_ms * 1e-3) / 1e9
+        torch.cuda.synchronize()
+        # HIP events on the launch stream around trains of back-to-back launches:
+        # (train time / launches) = kernel duration + the ~1 us kernel boundary, with
+        # the host launch latency hidden behind the previous kernel
+        train = 10
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(max(1, args.mdct_launches // train))]
+        for a, b in ev:
+            a.record()
+            for _ in range(train):
+                mdct_once()
+            b.record()
+        torch.cuda.synchronize()
+        trains = [a.elapsed_time(b) / train for a, b in ev]
+        mdct_ms = float(np.median(trains))
+        mdct_gbs = mdct_cf * MDCT_BYTES_PER_CF / (mdct_ms * 1e-3) / 1e9
 
-    # HBM bytes of the MDCT kernel: NOT measured by this run (PMC counters need rocprofv3);
-    # the figure of the committed PMC passes of this same command is quoted, with its
-    # source, when the launch geometry matches
-    traffic, traffic_src = None, None
-    for name in ("r03_mdct_pmc.json", "r02_mdct_pmc.json", "r01_mdct_pmc.json"):
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-            if pmc["cf_per_launch"] == mdct_cf:
-                traffic, traffic_src = pmc["hbm_bytes_per_launch"], f"profiles/{name}"
-                break
-        except Exception:
-            pass
+        # HBM bytes of the MDCT kernel: NOT measured by this run (PMC counters need rocprofv3);
+        # the figure of the committed PMC passes of this same command is quoted, with its
+        # source, when the launch geometry matches
+        traffic, traffic_src = None, None
+        for name in ("r03_mdct_pmc.json", "r02_mdct_pmc.json", "r01_mdct_pmc.json"):
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                if pmc["cf_per_launch"] == mdct_cf:
+                    traffic, traffic_src = pmc["hbm_bytes_per_launch"], f"profiles/{name}"
+                    break
+            except Exception:
+                pass
+        return {"kernel": "k_mdct_long_x2p<8, 2, false> (the stand-alone launches of the kernel; the step launches the <8, 2, true> instantiation, which also initialises status words: window + MDCT, int16 in, float64 lines out; two frames per wave alternating on one FFT tile, PCM prefetched a whole iteration ahead)",
+                "bound": "hbm", "achieved": mdct_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": mdct_gbs / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_note": ("HBM bytes per launch from the COMMITTED rocprofv3 PMC passes of this "
+                                 f"command (2*FETCH_SIZE + WRITE_SIZE), {traffic_src}; not measured by this run")
+                                if traffic else "no committed PMC profile for this launch geometry",
+                "algorithmic_bytes_per_launch": mdct_cf * MDCT_BYTES_PER_CF,
+                "launch_ms": mdct_ms, "launch_ms_min": float(min(trains)), "launch_ms_max": float(max(trains)),
+                "timing": f"median of {len(trains)} HIP-event trains of {train} back-to-back launches",
+                "bytes_per_cf": MDCT_BYTES_PER_CF, "cf_per_launch": mdct_cf,
+                "mdct_cf_per_s": mdct_cf / (mdct_ms * 1e-3)}
+    roofline = mdct_roofline() if args.full else None
 
     # ---- host memory to host memory (never `value`): the same coder fed from pinned host buffers in chunks, the
     # PCIe copies of neighbouring chunks overlapping the kernels (streaming.HostStreamEncoder)
     host_stream = None
-    if rank == 0 and not multi and not corpus and args.host_stream_frames > 0:
+    if args.full and rank == 0 and not multi and not corpus and args.host_stream_frames > 0:
         hf = args.host_stream_frames
         hs = A.streaming.HostStreamEncoder(enc, N_CH, hf, depth=2, block_switching=block_switched)
         src_planar = shard[:, 1024:]                      # the workload's own stream, repeated to fill a chunk
@@ -663,7 +776,7 @@ def main():
     # ---- the other direction (never `value`): the timed run's payloads of pipeline 0 back to 16-bit PCM
     # (unpack / gain-shape decode, IMDCT, overlap-and-add), one step in flight on the current stream
     decode_leg = None
-    if rank == 0 and not multi and not corpus and not args.no_decode_leg:
+    if args.full and rank == 0 and not multi and not corpus and not args.no_decode_leg:
         o = pipes[0]["out"]
         e0 = pipes[0]["enc"]
 
@@ -739,12 +852,10 @@ def main():
                                         ".pac bit packing + body assembly" +
                                    (" + asynchronous RCCL gather of the bodies to rank 0" if multi else ""),
                        "stereo_frames_per_s": total_cf / N_CH * args.steps / dt,
-                       "timing": f"median of {len(regions)} regions of {args.steps} steps",
-                       "value_min": total_cf * args.steps / max(regions),
-                       "value_max": total_cf * args.steps / min(regions),
-                       "regions": len(regions),
-                       "ms_per_step_regions": [r / args.steps * 1e3 for r in (regions if len(regions) <= 24 else
-                                                                                regions[:8] + regions[-16:])],
+                       "timing": f"one region of {args.steps} steps after {args.warmup} warm-up steps",
+                       "warmup_steps_run": warm_steps,
+                       "warmup_note": f"the --warmup steps, then more until {args.warmup_seconds} s had gone into warm-up "
+                                      "(the card's clocks settle during the first tens of milliseconds under load)",
                        "host_enqueue_ms_per_step": float(np.median(enqueue_s)) / args.steps * 1e3 if enqueue_s else None,
                        "host_enqueue_note": "median over the regions of the time the host takes to queue the K steps of a region "
                                             "(Python + HIP launches), per step; the regions' own time is ms_per_step: where the "
@@ -754,15 +865,10 @@ def main():
                                           "that their first steps start together (EncoderPool.align): started together the two "
                                           "pipelines stay in phase, free-running they settle per region into one of two relations "
                                           "(47.0 or 51.4 M cf/s on the headline batch, DESIGN.md 5.0)",
-                       "ms_per_step_regions_note": "all regions" if len(regions) <= 24 else "the first 8 and the last 16 regions",
-                       # two steps in flight settle, region by region, into one of two phase relations of the pipelines
-                       # (DESIGN.md 5.0): the spread says how the regions of THIS run fell
-                       "ms_per_step_quantiles": {q: sorted(regions)[min(len(regions) - 1, int(len(regions) * f))] / args.steps * 1e3
-                                                 for q, f in (("p10", 0.10), ("p25", 0.25), ("p50", 0.50), ("p75", 0.75), ("p90", 0.90))},
                        "body_bytes_per_step": body_bytes,
                        "verified": f"{verified} channel-frames of the timed run's output re-encoded by the oracle, "
                                    "payload bytes equal" + (f" (per rank: {verified_per_rank})" if multi else "")
-                                   if verified else "not verified",
+                                   if verified else "not verified" + ("" if args.full else " (--full checks it)"),
                        "verified_per_rank": verified_per_rank,
                        "launch": ("hipGraph replay of the captured step" if graphs[0] is not None else "direct launches") +
                                  (f"; {P} steps in flight: consecutive steps alternate between {P} handles, each with its own "
@@ -771,18 +877,26 @@ def main():
                        "sharding": f"{world} x frame-range shards, no data-path collective; process group: "
                                    + (f"{dist.get_backend()} with {dist.get_world_size()} ranks" if multi
                                       else "none (one process)")},
-            "roofline": {"kernel": "k_mdct_long_x2p<8, 2, false> (the stand-alone launches of the kernel; the step launches the <8, 2, true> instantiation, which also initialises status words: window + MDCT, int16 in, float64 lines out; two frames per wave alternating on one FFT tile, PCM prefetched a whole iteration ahead)",
-                         "bound": "hbm", "achieved": mdct_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": mdct_gbs / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_note": ("HBM bytes per launch from the COMMITTED rocprofv3 PMC passes of this "
-                                          f"command (2*FETCH_SIZE + WRITE_SIZE), {traffic_src}; not measured by this run")
-                                         if traffic else "no committed PMC profile for this launch geometry",
-                         "algorithmic_bytes_per_launch": mdct_cf * MDCT_BYTES_PER_CF,
-                         "launch_ms": mdct_ms, "launch_ms_min": float(min(trains)), "launch_ms_max": float(max(trains)),
-                         "timing": f"median of {len(trains)} HIP-event trains of {train} back-to-back launches",
-                         "bytes_per_cf": MDCT_BYTES_PER_CF, "cf_per_launch": mdct_cf,
-                         "mdct_cf_per_s": mdct_cf / (mdct_ms * 1e-3)},
         }
+        if args.full:                          # the spread of all the K-step regions, the headline's first
+            d_med = float(np.median(regions))
+            res["config"].update({
+                "value_median_regions": total_cf * args.steps / d_med,
+                "ms_per_step_median_regions": d_med / args.steps * 1e3,
+                "timing_regions": f"median of {len(regions)} regions of {args.steps} steps, the first the headline's",
+                "value_min": total_cf * args.steps / max(regions),
+                "value_max": total_cf * args.steps / min(regions),
+                "regions": len(regions),
+                "ms_per_step_regions": [r / args.steps * 1e3 for r in (regions if len(regions) <= 24 else
+                                                                         regions[:8] + regions[-16:])],
+                "ms_per_step_regions_note": "all regions" if len(regions) <= 24 else "the first 8 and the last 16 regions",
+                # two steps in flight settle, region by region, into one of two phase relations of the pipelines
+                # (DESIGN.md 5.0): the spread says how the regions of THIS run fell
+                "ms_per_step_quantiles": {q: sorted(regions)[min(len(regions) - 1, int(len(regions) * f))] / args.steps * 1e3
+                                          for q, f in (("p10", 0.10), ("p25", 0.25), ("p50", 0.50), ("p75", 0.75), ("p90", 0.90))}})
+            res["roofline"] = roofline
+        if dumped is not None:
+            res["config"]["dumped_outputs"] = dumped
         if regions_one is not None:
             d1 = float(np.median(regions_one))
             res["config"]["value_one_step_in_flight"] = total_cf * args.steps / d1
@@ -793,14 +907,14 @@ def main():
         if decode_leg:
             res["config"]["decode_cf_per_s"] = decode_leg["cf_per_s"]
             res["config"]["decode"] = decode_leg
-        sk = step_kernels(args.workload, n_cf)
+        sk = step_kernels(args.workload, n_cf) if args.full else None
         if sk:
             res["config"]["step_kernels"] = sk
         if regions_nogather is not None:
             d2 = float(np.median(regions_nogather))
             res["config"]["value_without_gather"] = total_cf * args.steps / d2
             res["config"]["ms_per_step_without_gather"] = d2 / args.steps * 1e3
-        if not args.no_cpu_baseline and not multi:
+        if args.full and not args.no_cpu_baseline and not multi:
             if block_switched:
                 res["cpu_baseline"] = cpu_baseline_bs(pcm, sample_rate, vq_kbps=vq_kbps)
             else:

@@ -25,7 +25,8 @@ def tables():
 
 @pytest.fixture(scope="session")
 def stages():
-    return np.load(os.path.join(GOLDEN, "stages.npz"))
+    from golden_io import load_npz
+    return load_npz("stages")
 
 
 def load_excerpt(name):

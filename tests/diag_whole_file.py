@@ -6,10 +6,10 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import audio_codec_amd as A
 from oracle import pac_oracle as po
+from golden_io import load_npz
 name = sys.argv[1] if len(sys.argv) > 1 else "harpsichord"
 bs = len(sys.argv) > 2 and sys.argv[2] == "bs"
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-d = np.load(os.path.join(G, f"full_{name}.npz"))
+d = load_npz(f"full_{name}")
 pcm, sr, decl = d["pcm"], int(d["sr"]), int(d["declared"])
 max_hops = int(sys.argv[3]) if len(sys.argv) > 3 else None
 if max_hops:

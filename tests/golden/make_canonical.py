@@ -11,11 +11,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, os.path.dirname(HERE))
 from oracle import pac_oracle as po
 from pac_parse import canonical_sha256
+from golden_io import load_npz
 from multiprocessing import Pool
 
 def one(key):
     name, tag = key.split(":")
-    d = np.load(os.path.join(HERE, f"full_{name}.npz"))
+    d = load_npz(f"full_{name}")
     sr, decl = int(d["sr"]), int(d["declared"])
     data = po.encode_stream(d["pcm"], sr, 128, block_switching=(tag == "bs"), header_samples=decl)
     p = po.make_params(sr, 2, 128)

@@ -16,7 +16,8 @@ SURVEY.md section 8c): np.int/np.float aliases, writable cwd (pacfile creates
 Outputs
   tables.npz        band tables, windows, known answers of the reference's own
                     __main__ self-tests (mdct ramp, quantizer table, bitpack demo)
-  stages.npz        per-stage vectors for long and short channel-frames
+  stages.part*.npz  per-stage vectors for long and short channel-frames (stored in parts below
+                    1 MiB, as full_<wav>.part*.npz are: tests/golden_io.py)
   excerpt_<wav>.npz 64-hop int16 excerpts of the reference's test WAVs with the
                     scalar-path .pac bytes (long-only and block-switched)
   fullfile.json     (--full) sha256 + size of whole-file scalar-path encodes
@@ -51,6 +52,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 
 import numpy as np  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(HERE))
+from golden_io import save_npz  # noqa: E402  (fixtures past 1 MiB are stored in parts)
 
 np.int = int      # noqa
 np.float = float  # noqa
@@ -383,7 +387,7 @@ def make_stages(wavs):
         out[f"{kind}_n_peaks"] = np.array([c["n_peaks"] for c in caps])
         out[f"{kind}_n_mant"] = np.array([c["n_mant"] for c in caps])
         print(kind, len(caps), "channel-frames")
-    np.savez_compressed(os.path.join(HERE, "stages.npz"), **out)
+    save_npz("stages", out)
 
 
 # ----------------------------------------------------------------- excerpts
@@ -505,8 +509,7 @@ def make_full_inputs(names):
     for n in names:
         raw = open(os.path.join(REF, "test_signals", n + ".wav"), "rb").read()
         sr, pcm, declared = po.wav_effective_stream(raw)
-        np.savez_compressed(os.path.join(HERE, f"full_{n}.npz"), pcm=pcm, sr=np.array(sr),
-                            declared=np.array(declared))
+        save_npz(f"full_{n}", {"pcm": pcm, "sr": np.array(sr), "declared": np.array(declared)})
 
 
 def _vq_one(args):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import EXCERPTS, load_excerpt
+from golden_io import load_npz
 from oracle import pac_oracle as po
 
 pytestmark = pytest.mark.gpu
@@ -503,7 +504,7 @@ def test_whole_file_pac_sha256(A, name):
     import os
     from conftest import GOLDEN
     want = json.load(open(os.path.join(GOLDEN, "fullfile.json")))
-    d = np.load(os.path.join(GOLDEN, f"full_{name}.npz"))
+    d = load_npz(f"full_{name}")
     from pac_parse import canonical_sha256
     for tag, bs in (("long", False), ("bs", True)):
         w = want[f"{name}:{tag}"]

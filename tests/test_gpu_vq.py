@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import EXCERPTS, GOLDEN
+from golden_io import load_npz
 
 pytestmark = pytest.mark.gpu
 
@@ -126,7 +127,7 @@ def test_whole_file(A, key):
     name, kbps = key.split(":")
     rec = json.load(open(os.path.join(GOLDEN, "vqfile.json")))[key]
     crcs = np.load(os.path.join(GOLDEN, "vqfile.npz"))[f"{name}_{kbps}"]
-    full = np.load(os.path.join(GOLDEN, f"full_{name}.npz"))
+    full = load_npz(f"full_{name}")
     got = A.pacfile.encode_stream(full["pcm"], int(full["sr"]), int(kbps), block_switching=True,
                                   header_samples=int(full["declared"]), use_vq=True,
                                   use_sbr=int(kbps) < 128)
@@ -208,7 +209,7 @@ def test_whole_file_round_trip_matches_committed_wav(A, key):
     (test_decoded_full/<wav>_<rate>.wav)."""
     name, kbps = key.split(":")
     rec = json.load(open(os.path.join(GOLDEN, "vqwav.json")))[key]
-    full = np.load(os.path.join(GOLDEN, f"full_{name}.npz"))
+    full = load_npz(f"full_{name}")
     pac = A.pacfile.encode_stream(full["pcm"], int(full["sr"]), int(kbps), block_switching=True,
                                   header_samples=int(full["declared"]), use_vq=True, use_sbr=int(kbps) < 128)
     pcm = A.pacfile.decode_stream(pac)[:rec["n_samples"]]

@@ -252,15 +252,16 @@ def test_numpy_sum_order():
             assert pw([np.float64(v) for v in a]) == np.sum(a)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/test_signals"),
-                    reason="reference WAVs only exist in the build container")
 @pytest.mark.skipif(not os.environ.get("PACX_FULLFILE"),
                     reason="minutes of CPU; set PACX_FULLFILE=1")
 @pytest.mark.parametrize("name", EXCERPTS)
 def test_full_file_hash(name):
+    """the oracle's whole-file .pac of each test WAV (the PCM the reference's driver feeds the coder,
+    tests/golden/full_<wav>.part*.npz) has the sha256 of the file the reference itself wrote"""
+    from golden_io import load_npz
     want = json.load(open(os.path.join(GOLDEN, "fullfile.json")))
-    raw = open(f"/root/reference/test_signals/{name}.wav", "rb").read()
-    sr, pcm, declared = po.wav_effective_stream(raw)
+    d = load_npz(f"full_{name}")
+    sr, pcm, declared = int(d["sr"]), d["pcm"], int(d["declared"])
     for tag, bs in (("long", False), ("bs", True)):
         got = po.encode_stream(pcm, sr, 128, block_switching=bs, header_samples=declared)
         assert hashlib.sha256(got).hexdigest() == want[f"{name}:{tag}"]["sha256"]

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import EXCERPTS, GOLDEN
+from golden_io import load_npz
 from oracle import pac_oracle_vq as pv
 
 
@@ -94,7 +95,7 @@ def test_vqfile_records():
 
 @pytest.fixture(scope="module")
 def harpsichord_96_pac():
-    full = np.load(os.path.join(GOLDEN, "full_harpsichord.npz"))
+    full = load_npz("full_harpsichord")
     return pv.encode_stream_vq(full["pcm"], int(full["sr"]), 96,
                                header_samples=int(full["declared"]))
 

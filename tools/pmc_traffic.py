@@ -1,6 +1,6 @@
 """HBM traffic of the bench step from two rocprofv3 --pmc passes of bench.py:
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d A -- python3 bench.py --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d B -- python3 bench.py --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d A -- python3 bench.py --full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d B -- python3 bench.py --full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify
     python tools/pmc_traffic.py A B profiles/rNN_mdct_pmc.json [profiles/rNN_step_traffic.json]
 FETCH_SIZE / WRITE_SIZE are in KB; on gfx950 wide coalesced reads are counted as
 64-byte requests although 128 bytes move (MI355X_MICROARCH.md, HBM section):
@@ -34,7 +34,7 @@ cands = [k for k in per if "k_mdct_long_x2" in k or "k_mdct_long_v2" in k]
 mdct = ([k for k in cands if "false" in k] or cands)[0]       # the stand-alone instantiation (the bench's roofline trains) where both ran
 f_kb, w_kb = per[mdct]["FETCH_SIZE"]["mean"], per[mdct]["WRITE_SIZE"]["mean"]
 out = {
-    "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify",
+    "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-verify",
     "kernel": mdct, "cf_per_launch": N_CF,
     "FETCH_SIZE_KB_raw": f_kb, "WRITE_SIZE_KB": w_kb,
     "correction": "gfx950: FETCH_SIZE counts 128-B requests as 64 B for wide coalesced reads (MI355X_MICROARCH.md, HBM): read bytes = 2 x FETCH_SIZE; WRITE_SIZE exact for 16-B/lane stores",
