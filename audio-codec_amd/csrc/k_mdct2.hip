@@ -22,9 +22,6 @@
 #include "pacx_dev.h"
 #include "wave_fft.h"
 
-#include <stdlib.h>
-
-
 /* 8 waves per workgroup (8 KB tile each + 24 KB of tables, + 48 KB of transition windows
    with ANYWIN), one workgroup per CU, two waves per SIMD */
 #define MDCT2_WAVES 8
@@ -236,8 +233,7 @@ __global__ __launch_bounds__(64 * MDCT2_WAVES, 2) void k_mdct_long_v2(
 }
 
 void pacx_launch_mdct_x2(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
-                         int32_t *scale_out, int scale_stride, uint32_t *status_init, int n_cu, int waves,
-                         hipStream_t st);
+                         int32_t *scale_out, int scale_stride, uint32_t *status_init, int n_cu, hipStream_t st);
 
 void pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8_t *flags, long long n_cf,
                          int skip_cur, double *lines, int32_t *scale_out, int scale_stride,
@@ -248,29 +244,15 @@ void pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8
         return;
     if (status_init && (!scale_out || scale_stride != PACX_SUB))
         status_init = nullptr;                 /* the caller keeps its memsets */
-    /* PACX_MDCT_VARIANT (experiments and the kernel-equivalence test): -1 / unset = the
-       defaults below; 0 = this file's kernel also for batches without flags; 7 = the
-       two-tile kernel k_mdct_long_x2 */
-    static int variant = -2;
-    if (variant == -2) {
-        const char *e = getenv("PACX_MDCT_VARIANT");
-        variant = e ? atoi(e) : -1;
-    }
-    /* default: batches without per-frame flags (all sine windows) go to the pipelined
-       two-frames-per-wave kernel of k_mdct3.hip; batches with flags (transition
-       windows, frames left to the short kernel) stay here */
-    if (!flags && variant != 0) {
-        pacx_launch_mdct_x2(T, in, n_cf, lines, scale_out, scale_stride, status_init, n_cu, variant == 7 ? 8 : 0,
-                            st);
+    /* batches without per-frame flags (all sine windows) go to the pipelined two-frames-per-wave kernel of
+       k_mdct3.hip; batches with flags (transition windows, frames left to the short kernel) stay here */
+    if (!flags) {
+        pacx_launch_mdct_x2(T, in, n_cf, lines, scale_out, scale_stride, status_init, n_cu, st);
         return;
     }
     long long blocks = (n_cf + MDCT2_WAVES - 1) / MDCT2_WAVES;
     if (blocks > n_cu)
         blocks = n_cu;                         /* one persistent workgroup per CU */
-    if (flags)
-        hipLaunchKernelGGL((k_mdct_long_v2<true>), dim3((unsigned)blocks), dim3(64 * MDCT2_WAVES), 0, st, T, in,
-                           flags, n_cf, skip_cur, lines, scale_out, scale_stride, status_init, cf_list, cf_count);
-    else
-        hipLaunchKernelGGL((k_mdct_long_v2<false>), dim3((unsigned)blocks), dim3(64 * MDCT2_WAVES), 0, st, T, in,
-                           flags, n_cf, skip_cur, lines, scale_out, scale_stride, status_init, cf_list, cf_count);
+    hipLaunchKernelGGL((k_mdct_long_v2<true>), dim3((unsigned)blocks), dim3(64 * MDCT2_WAVES), 0, st, T, in,
+                       flags, n_cf, skip_cur, lines, scale_out, scale_stride, status_init, cf_list, cf_count);
 }

@@ -1375,7 +1375,7 @@ void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_ta
 void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
                         int payload_stride, const long long *offsets, const int32_t *n_bytes,
                         uint8_t *cf_flags, int32_t *overall, int32_t *bit_alloc, double *lines,
-                        uint8_t *sbr_flag, uint32_t *status, hipStream_t st)
+                        uint8_t *sbr_flag, uint32_t *status, int frame, hipStream_t st)
 {
     if (n_cf <= 0)
         return;
@@ -1396,11 +1396,9 @@ void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, c
     const size_t fixed = VQD_WORDS * 4 + PACX_M_LONG * 8 + (2 * PACX_SUB * PACX_MAX_BANDS + 4) * 4 +
                          VQD_WAVES * VQD_DEPTH * sizeof(VqdFrame);
     const size_t smem = fixed + (size_t)V.scr_off[VQD_WAVES] * 8;
-    /* the frame-level decoder first; k_vq_dec then takes the blocks it left (PACX_VQ_DEC_FRAME=0: k_vq_dec alone) */
-    const char *fe = getenv("PACX_VQ_DEC_FRAME");
-    A.redo = (fe && atoi(fe) == 0) ? 0 : 1;
-    if (PACX_SUB * T.nb_short > VQDF_VB || T.nb_long > VQDF_VB)
-        A.redo = 0;
+    /* the frame-level decoder first; k_vq_dec then takes the blocks it left (frame = 0, PACX_VQ_DEC_FRAME=0:
+       k_vq_dec alone) */
+    A.redo = frame != 0 && PACX_SUB * T.nb_short <= VQDF_VB && T.nb_long <= VQDF_VB;
     if (A.redo)
         hipLaunchKernelGGL(k_vq_dec_frame, dim3((unsigned)n_cf), dim3(64 * VQD_WAVES), (size_t)VQDF_SMEM, st, T, V, A);
     hipLaunchKernelGGL(k_vq_dec, dim3((unsigned)n_cf), dim3(64 * VQD_WAVES), smem, st, T, V, A);

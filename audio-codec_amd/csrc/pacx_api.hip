@@ -96,14 +96,15 @@ void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_ta
 void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
                         int payload_stride, const long long *offsets, const int32_t *n_bytes,
                         uint8_t *cf_flags, int32_t *overall, int32_t *bit_alloc, double *lines,
-                        uint8_t *sbr_flag, uint32_t *status, hipStream_t st);
+                        uint8_t *sbr_flag, uint32_t *status, int frame, hipStream_t st);
 
 /* k_vq.hip */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,
                     uint32_t *status, uint8_t *payload, int payload_stride, int32_t *n_bytes,
                     unsigned *unit_words, int32_t *unit_bits, pacx_vq_entry *log, int32_t *log_count,
-                    int log_cap, int stage, const int32_t *cf_list, const int32_t *cf_count, hipStream_t st);
+                    int log_cap, int stage, const int32_t *cf_list, const int32_t *cf_count, int frame, int bfs,
+                    hipStream_t st);
 size_t pacx_vq_view_size(void);
 void pacx_vq_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
                        const int32_t *k_of, const uint8_t *w_of, const double *half_log2, int l_max,
@@ -113,9 +114,45 @@ void pacx_vq_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, 
 #define PACX_PAYLOAD_STRIDE 2192
 #define PACX_VQ_UNIT_WORDS 548
 
+/* Path overrides.  Each forces a path that runs by default on some other input, so that the GPU tests can hold
+   the two implementations bit-identical on one batch.  Read once, when the handle is created; -1 (unset, or a
+   value the variable does not take): the default. */
+struct PacxOverrides {
+    int split_short;                  /* PACX_SPLIT_SHORT=0: block-switched batches on one stream */
+    int fuse_tail;                    /* PACX_FUSE_TAIL=0/1: the long frames' tail in k_tail_long / in k_mask */
+    int vq_fuse_alloc;                /* PACX_VQ_FUSE_ALLOC=0/1: the long frames' BitAlloc in k_bitalloc / in k_mask */
+    int vq_frame;                     /* PACX_VQ_FRAME=0: k_vq over every unit */
+    int vq_bfs;                       /* PACX_VQ_BFS=n: level walk from n shape bits (0: depth first only) */
+    int vq_dec_frame;                 /* PACX_VQ_DEC_FRAME=0: k_vq_dec over every block */
+};
+
+/* an integer in [lo, hi] from the environment, else -1 */
+static int env_override(const char *name, int lo, int hi)
+{
+    const char *e = getenv(name);
+    if (!e || !*e)
+        return -1;
+    char *end;
+    const long v = strtol(e, &end, 10);
+    return (*end || v < lo || v > hi) ? -1 : (int)v;
+}
+
+static PacxOverrides read_overrides(void)
+{
+    PacxOverrides o;
+    o.split_short = env_override("PACX_SPLIT_SHORT", 0, 0);
+    o.fuse_tail = env_override("PACX_FUSE_TAIL", 0, 1);
+    o.vq_fuse_alloc = env_override("PACX_VQ_FUSE_ALLOC", 0, 1);
+    o.vq_frame = env_override("PACX_VQ_FRAME", 0, 0);
+    o.vq_bfs = env_override("PACX_VQ_BFS", 0, 1 << 20);
+    o.vq_dec_frame = env_override("PACX_VQ_DEC_FRAME", 0, 0);
+    return o;
+}
+
 struct pacx_handle {
     int device;
     int n_cu;                         /* compute units (persistent-kernel grid sizing) */
+    PacxOverrides force;
     PacxTables T;
     std::vector<void *> owned;        /* table allocations                      */
     /* workspace (device), sized for ws_cf channel-frames */
@@ -137,9 +174,10 @@ struct pacx_handle {
     hipStream_t side_stream;
     hipEvent_t ev_fork, ev_join;
     /* mixed batches: the short-coded frames' chain (MDCT, side chain, mask, tail) runs on
-       streams of its own beside the long-coded frames' */
-    hipStream_t short_stream, short_side_stream;
-    hipEvent_t ev_short_side, ev_short_done, ev_lists;
+       a stream of its own beside the long-coded frames' */
+    hipStream_t short_stream;
+    hipStream_t spare_stream;         /* unused: keeps HIP's queue map of later streams (without it bs128 32.5 vs 34.9 M cf/s) */
+    hipEvent_t ev_short_done, ev_lists;
     std::vector<char> vq_view;        /* VqView of k_vq.hip (device pointers)   */
     std::vector<char> vqdec_view;     /* VqDecView of k_vq_dec.hip              */
     int tables_exact;                 /* every float64 table is the NumPy-evaluated one */
@@ -338,6 +376,7 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
 
     pacx_handle *h = new pacx_handle();
     h->device = cfg->device;
+    h->force = read_overrides();
     h->ws_cf = 0;
     h->ws_blocks_cf = 0;
     h->ws_blocks = nullptr;
@@ -347,8 +386,7 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->ev_fork = nullptr;
     h->ev_join = nullptr;
     h->short_stream = nullptr;
-    h->short_side_stream = nullptr;
-    h->ev_short_side = nullptr;
+    h->spare_stream = nullptr;
     h->ev_short_done = nullptr;
     h->ev_lists = nullptr;
     h->ws_mant_cf = 0;
@@ -379,8 +417,7 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
         hipStreamCreateWithFlags(&h->short_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->short_side_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_short_side, hipEventDisableTiming) != hipSuccess ||
+        hipStreamCreateWithFlags(&h->spare_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_short_done, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_lists, hipEventDisableTiming) != hipSuccess) {
         g_create_err = "pacx_create: could not create the side stream / events";
@@ -635,7 +672,7 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
 
 static void drain_internal(pacx_handle *h)
 {
-    for (hipStream_t s2 : {h->side_stream, h->short_stream, h->short_side_stream})
+    for (hipStream_t s2 : {h->side_stream, h->short_stream})
         if (s2)
             (void)hipStreamSynchronize(s2);
 }
@@ -669,16 +706,12 @@ extern "C" void pacx_destroy(pacx_handle *h)
     if (!h)
         return;
     (void)hipSetDevice(h->device);
-    if (h->side_stream) {
-        (void)hipStreamSynchronize(h->side_stream);
-        (void)hipStreamDestroy(h->side_stream);
-    }
-    for (hipStream_t s2 : {h->short_stream, h->short_side_stream})
+    for (hipStream_t s2 : {h->side_stream, h->short_stream, h->spare_stream})
         if (s2) {
             (void)hipStreamSynchronize(s2);
             (void)hipStreamDestroy(s2);
         }
-    for (hipEvent_t e2 : {h->ev_short_side, h->ev_short_done, h->ev_lists})
+    for (hipEvent_t e2 : {h->ev_short_done, h->ev_lists})
         if (e2)
             (void)hipEventDestroy(e2);
     if (h->ev_fork)
@@ -958,11 +991,9 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
         HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
     }
     /* mixed streams: compacted lists of the long- and of the short-coded frames -- every
-       persistent kernel below walks its own list.  The four-stream schedule forks first: the side
-       chains and the short-block MDCT go by the flags alone and start while the lists are made
-       (+2.3 % on the block-switched bench, A/B on one box) */
-    const char *split_env = getenv("PACX_SPLIT_SHORT");       /* 0: short frames on the long frames' streams */
-    const bool split = mixed && fast && !h->T.use_sbr && !(split_env && atoi(split_env) == 0);
+       persistent kernel below walks its own list.  The two-stream schedule forks first: the side
+       chains and the short-block MDCT go by the flags alone and start while the lists are made */
+    const bool split = mixed && fast && !h->T.use_sbr && h->force.split_short != 0;
     if (split)
         HIP_TRY(h, hipEventRecord(h->ev_fork, st));
     if (mixed)
@@ -977,9 +1008,8 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
        Measured A/B on the same box: block-switched batches are 2 % faster
        fused; all-long batches 2 % faster UNFUSED (the separate tail kernel pairs two frames per
        wave for BitAlloc and runs at 20 waves per CU instead of 12) -- the default follows the
-       clock, PACX_FUSE_TAIL=1 / 0 forces either (read per call: tests flip it). */
-    const char *fuse_env = getenv("PACX_FUSE_TAIL");
-    const int fuse = fuse_env ? (atoi(fuse_env) != 0) : mixed;
+       clock, PACX_FUSE_TAIL=1 / 0 forces either. */
+    const int fuse = h->force.fuse_tail >= 0 ? h->force.fuse_tail : mixed;
     MaskTail mt;
     mt.overall = overall_scale; mt.bit_alloc = bit_alloc; mt.scale_factor = scale_factor; mt.mantissa = mantissa;
     mt.status = status; mt.payload = payload; mt.n_bytes = n_bytes; mt.payload_stride = PACX_PAYLOAD_STRIDE;
@@ -1009,51 +1039,25 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
                          mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, list_short, counts + 1, 0, st);
         return post_launch(h, what);
     }
-    /* All-long batches: the whole step on the caller's stream, or (pacx_set_side_fork) the side chain, which only
-       reads the PCM, forked to the handle's second stream next to the transform.  The fork pays only where HIP puts
-       the two streams on ONE hardware queue -- with two handles in a process it does (50.6 against 49.3 M cf/s with
-       two steps in flight), with one handle it does not, and a fork and a join across hardware queues (13 + 12 us)
-       cost more than the 20 us of overlap: 39.1 against 42.6 M cf/s with one step in flight.
-       PACX_ONE_STREAM=0/1 forces either for every handle (read per call: a test flips it) */
-    const char *one_env = getenv("PACX_ONE_STREAM");
-    const bool one_stream = !split && (one_env ? atoi(one_env) != 0 : !h->fork_side);
-    hipStream_t side_st = one_stream ? st : h->side_stream;
-    if (!split && !one_stream)
-        HIP_TRY_FORKED(h, hipEventRecord(h->ev_fork, st));
-    if (!one_stream)
-        HIP_TRY_FORKED(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     if (split) {
         /* A block-switched batch is two independent chains that touch disjoint frames:
-             long-coded :  k_mdct_long_v2 || k_side_long  ->  k_mask<1024> (+ tail)
-             short-coded:  k_mdct_short  || k_side_short ->  k_mask<128> -> k_tail_short
-           Every one of these kernels is latency-bound at the occupancy its registers and LDS
-           allow and none fills the chip with half of the frames, so the two chains run side by
-           side on four streams and meet again before the body gather. */
-        /* The side chains run on their chains' own streams: two streams per handle, not four.  HIP maps a process's
-           streams onto four hardware queues; with two handles (two steps in flight) the short side chain of one
-           landed on the other's short-chain queue, behind its mask and tail kernels (kernel trace),
-           and alone the forks and joins of four streams cost more than the overlap of a side chain with its 40 us
-           transform: bs128 33.9 -> 35.4 M cf/s with two steps in flight, 25.9 -> 30.7 M with one.
-           PACX_BS_TWO_STREAMS=0: the four-stream schedule of round 2 */
-        const char *two_s = getenv("PACX_BS_TWO_STREAMS");             /* read per call: a test flips it */
-        const int two_env = (two_s && atoi(two_s) == 0) ? 0 : 1;
-        hipStream_t sl_st = two_env ? st : h->side_stream, ss_st = two_env ? h->short_stream : h->short_side_stream;
+             long-coded :  k_side_long,  k_mdct_long_v2 ->  k_mask<1024> (+ tail)     on the caller's stream
+             short-coded:  k_side_short, k_mdct_short   ->  k_mask<128> -> k_tail_short on short_stream
+           Every one of these kernels is latency-bound at the occupancy its registers and LDS allow and none fills
+           the chip with half of the frames, so the two chains run side by side and meet again before the body
+           gather.  Each side chain runs on its chain's own stream: with four streams per handle (a side stream
+           per chain) the short side chain of one handle landed on the other's short-chain hardware queue with two
+           steps in flight (kernel trace), and alone the forks and joins cost more than the overlap
+           of a side chain with its 40 us transform: bs128 33.9 -> 35.4 M cf/s with two steps in flight, 25.9 ->
+           30.7 M with one. */
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_fork, 0));
-        if (!two_env)
-            HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_side_stream, h->ev_fork, 0));
         pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, nullptr, nullptr, sl_st);
-        if (!two_env)
-            HIP_TRY_FORKED(h, hipEventRecord(h->ev_join, h->side_stream));
+                         h->ws_nkept, nullptr, nullptr, st);
         pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, nullptr, nullptr, ss_st);
-        if (!two_env)
-            HIP_TRY_FORKED(h, hipEventRecord(h->ev_short_side, h->short_side_stream));
+                         h->ws_nkept, nullptr, nullptr, h->short_stream);
         /* short chain */
         pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
                          h->short_stream);
-        if (!two_env)
-            HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_short_side, 0));
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_lists, 0));
         pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_nkept, h->ws_lines,
                          h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, nullptr, h->short_stream);
@@ -1064,8 +1068,6 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
         /* long chain */
         pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
                             list_long, counts, st);
-        if (!two_env)
-            HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_join, 0));
         pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_nkept, h->ws_lines,
                          h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, fuse ? &mt : nullptr, st);
         if (!fuse)
@@ -1073,6 +1075,17 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
                              mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, nullptr, nullptr, 2, st);
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_short_done, 0));       /* both chains done */
         return post_launch_forked(h, what);
+    }
+    /* All-long batches: the whole step on the caller's stream, or (pacx_set_side_fork) the side chain, which only
+       reads the PCM, forked to the handle's second stream next to the transform.  The fork pays only where HIP puts
+       the two streams on ONE hardware queue -- with two handles in a process it does (50.6 against 49.3 M cf/s with
+       two steps in flight), with one handle it does not, and a fork and a join across hardware queues (13 + 12 us)
+       cost more than the 20 us of overlap: 39.1 against 42.6 M cf/s with one step in flight */
+    const bool one_stream = !h->fork_side;
+    hipStream_t side_st = one_stream ? st : h->side_stream;
+    if (!one_stream) {
+        HIP_TRY_FORKED(h, hipEventRecord(h->ev_fork, st));
+        HIP_TRY_FORKED(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     }
     pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
                      nullptr, nullptr, side_st);
@@ -1178,9 +1191,8 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
     memset(&mt, 0, sizeof(mt));
     mt.bit_alloc = bit_alloc;
     mt.status = status;
-    int vq_stage = 0;
-    const char *split_env = getenv("PACX_SPLIT_SHORT");       /* 0: short frames on the long frames' stream */
-    if (mixed && fast && !(split_env && atoi(split_env) == 0)) {
+    const bool split = mixed && fast && h->force.split_short != 0;
+    if (split) {
         /* a block-switched batch: the long-coded and the short-coded frames are two independent chains up
            to the gain-shape coder (which takes all frames), as in the scalar entry point:
              long :  k_mdct_long_v2 -> k_side_long (folds max|FFT| into the overall scale of SBR blocks) ->
@@ -1189,10 +1201,7 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
            side by side on two streams; the side chains and the short MDCT go by the flags alone and start
            while the frame lists are made */
         int32_t *const list_long = h->ws_lists, *const list_short = h->ws_lists + n_cf, *const counts = h->ws_lists + 2 * n_cf;
-        const char *vfs_env = getenv("PACX_VQ_FUSE_ALLOC");     /* 0: k_bitalloc behind the mask kernel here too */
-        const int vq_fuse_split = vfs_env ? (atoi(vfs_env) != 0) : 1;
-        const char *ol_env = getenv("PACX_VQ_ONE_LAUNCH");
-        const bool one_launch = ol_env && atoi(ol_env) != 0;
+        const int vq_fuse_split = h->force.vq_fuse_alloc != 0;  /* PACX_VQ_FUSE_ALLOC=0: k_bitalloc behind the mask kernel */
         HIP_TRY(h, hipEventRecord(h->ev_fork, st));
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_fork, 0));
         pacx_launch_frame_lists(frame_flags, in->n_frames, n_ch, list_long, list_short, counts, st);
@@ -1207,15 +1216,13 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
                          h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, nullptr, h->short_stream);
         pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, 1, h->ws_smr, bit_alloc, status, h->short_stream);
         /* Each chain goes on into the gain-shape coder with its own frames: two k_vq_frame launches side by side on
-           the two streams (0.685 ms per shipped128 step with direct launches).  PACX_VQ_ONE_LAUNCH=1: ONE launch
-           over all frames behind the join of the two chains (0.74-0.77 ms) -- which is what to use when the step is
-           replayed from a hipGraph, where the two launches do not overlap (0.822 ms); bench.py therefore does not
-           capture gain-shape steps */
-        if (!one_launch)
-            pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                           h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                           h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_short, counts + 1,
-                           h->short_stream);
+           the two streams (0.685 ms per shipped128 step with direct launches, against 0.74-0.77 ms for one launch
+           over all frames behind the join of the two chains).  Replayed from a hipGraph the two launches do not
+           overlap (0.822 ms): bench.py does not capture gain-shape steps */
+        pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
+                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
+                       h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_short, counts + 1,
+                       h->force.vq_frame, h->force.vq_bfs, h->short_stream);
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_short_done, h->short_stream));
         /* long chain */
         pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
@@ -1226,12 +1233,11 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
                          h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, vq_fuse_split ? &mt : nullptr, st);
         if (!vq_fuse_split)       /* BitAlloc of the long frames in k_bitalloc behind the mask kernel (part 2 = long only) */
             pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, 2, h->ws_smr, bit_alloc, status, st);
-        if (!one_launch)
-            pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                           h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                           h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_long, counts, st);
+        pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
+                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
+                       h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_long, counts,
+                       h->force.vq_frame, h->force.vq_bfs, st);
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_short_done, 0));       /* both chains done */
-        vq_stage = one_launch ? 0 : 2;
     } else {
         if (mixed)
             pacx_launch_frame_lists(frame_flags, in->n_frames, n_ch, h->ws_lists, h->ws_lists + n_cf,
@@ -1254,15 +1260,15 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
         /* BitAlloc of the long frames inside the mask kernel or in k_bitalloc behind it: as with the scalar
            coder's tail, all-long batches are a little faster unfused (0.637 against 0.642 ms per step, A/B on one
            box); PACX_VQ_FUSE_ALLOC=0/1 forces either */
-        const char *vf_env = getenv("PACX_VQ_FUSE_ALLOC");
-        const int vq_fuse = vf_env ? (atoi(vf_env) != 0) : mixed;
+        const int vq_fuse = h->force.vq_fuse_alloc >= 0 ? h->force.vq_fuse_alloc : mixed;
         pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
                          nullptr, h->n_cu, h->ws_lists, h->ws_lists + n_cf, h->ws_lists + 2 * n_cf, vq_fuse ? &mt : nullptr, st);
         pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, vq_fuse, h->ws_smr, bit_alloc, status, st);
     }
     pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
                    h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                   h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, vq_stage, nullptr, nullptr, st);
+                   h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, split ? 2 : 0, nullptr, nullptr,
+                   h->force.vq_frame, h->force.vq_bfs, st);
     return post_launch(h, "pacx_encode_vq_batch");
 }
 
@@ -1651,7 +1657,8 @@ extern "C" int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_chan
     if (n_cf > 0) {
         HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
         pacx_launch_vq_dec(h->T, h->vqdec_view.data(), n_cf, payload, payload_stride, (const long long *)offsets,
-                           n_bytes, cf_flags, overall_scale, bit_alloc, ln, h->ws_dec_sbr, status, st);
+                           n_bytes, cf_flags, overall_scale, bit_alloc, ln, h->ws_dec_sbr, status, h->force.vq_dec_frame,
+                           st);
     }
     if (work || pcm)
         pacx_launch_decode(h->T, n_blocks, n_channels, cf_flags, overall_scale, nullptr, nullptr, nullptr, ln,

@@ -236,37 +236,35 @@ def test_large_batch_sampled_against_oracle(A, torch):
 
 # ------------------------------------------------ fused mask + tail kernel
 @pytest.mark.parametrize("mixed", [False, True])
-def test_fused_tail_equals_separate_kernels(A, torch, mixed):
+def test_fused_tail_equals_separate_kernels(A, torch, monkeypatch, mixed):
     """k_mask<1024, true> (SMRs, BitAlloc, scale factors, mantissas and payload of a long frame in
     one wave) against the same stages as separate kernels behind a boundary (PACX_FUSE_TAIL=0:
     k_mask<1024, false> + k_tail_long): every output bit for bit, on an all-long batch and on a
     block-switched one (long frames through the fused kernel, short ones through k_tail_short)."""
-    import os
     if mixed:
         ex = load_excerpt("castanet")
         sr, pcm = int(ex["sr"]), ex["pcm"][:48 * 1024]
     else:
         sr, pcm = 48000, A.synth.stream(300, 2)
-    enc = A.context.encoder(sr, 128 / (sr / 1000))
-    planar = A.pacfile.device_stream(enc, pcm)
-    view = A.engine.PcmView.stream(planar)
-    flags = enc.transient_flags(planar, len(pcm) // 1024)[1] if mixed else None
 
-    def run():
+    def handle(fuse):                          # the override is read when a handle is created
+        monkeypatch.setenv("PACX_FUSE_TAIL", fuse)
+        return A.engine.Encoder(sr, 128 / (sr / 1000))
+    sep, fused = handle("0"), handle("1")
+    monkeypatch.delenv("PACX_FUSE_TAIL")
+    planar = A.pacfile.device_stream(sep, pcm)
+    view = A.engine.PcmView.stream(planar)
+    flags = sep.transient_flags(planar, len(pcm) // 1024)[1] if mixed else None
+
+    def run(enc):
         out = enc.encode_pack(view, flags, want_mantissa=True)
         torch.cuda.synchronize()
         return {k: v.clone() for k, v in out.items() if v is not None}
-    old = os.environ.get("PACX_FUSE_TAIL")
     try:
-        os.environ["PACX_FUSE_TAIL"] = "0"
-        ref = run()
-        os.environ["PACX_FUSE_TAIL"] = "1"
-        got = run()
+        ref, got = run(sep), run(fused)
     finally:
-        if old is None:
-            os.environ.pop("PACX_FUSE_TAIL", None)
-        else:
-            os.environ["PACX_FUSE_TAIL"] = old
+        sep.close()
+        fused.close()
     for k in ("overall", "scale_factor", "bit_alloc", "mantissa", "status", "n_bytes"):
         assert torch.equal(got[k], ref[k]), k
     nb = ref["n_bytes"].cpu().numpy()

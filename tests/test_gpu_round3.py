@@ -1,7 +1,7 @@
 """Round-3 GPU tests: what round 2's review asked to see under the driver's eyes.
 
-* every PACX_* path switch (alternate kernels kept alive behind environment switches) gives the bytes of
-  the default path -- the hand-run record profiles/r02_env_switch_parity.txt as a test, including the
+* every PACX_* path override (each forces a path that runs by default on some other input; read when a
+  handle is created) gives the bytes of the default path -- the hand-run record profiles/r02_env_switch_parity.txt as a test, including the
   combinations ADVICE r2 listed as unrecorded (PACX_SPLIT_SHORT=0 with PACX_VQ_FUSE_ALLOC=0 and with
   PACX_FUSE_TAIL=0, PACX_VQ_FUSE_ALLOC=0 in the split branch);
 * pacx_reserve: a hipMalloc that fails mid-sequence releases what the call had allocated, leaves the
@@ -43,62 +43,74 @@ def _mixed_stream():
     return np.concatenate((pcm, syn)), int(ex["sr"])
 
 
-def _set(monkeypatch, env):
+@pytest.fixture
+def fresh_handles(A):
+    """the overrides are read when a handle is created: a test that sets them starts and ends with an empty handle
+    cache, so that no forced handle leaks into later tests"""
+    A.context.clear()
+    yield
+    A.context.clear()
+
+
+def _set(A, monkeypatch, env):
     for k in ("PACX_SPLIT_SHORT", "PACX_FUSE_TAIL", "PACX_VQ_FUSE_ALLOC", "PACX_VQ_FRAME", "PACX_VQ_BFS",
               "PACX_VQ_DEC_FRAME"):
         if k in env and env[k] is not None:
             monkeypatch.setenv(k, env[k])
         else:
             monkeypatch.delenv(k, raising=False)
+    A.context.clear()                              # encode_stream / decode_stream create handles that read them
 
 
-def test_scalar_coder_path_switches(A, monkeypatch):
-    """scalar coder, block-switched and all-long batches: PACX_FUSE_TAIL x PACX_SPLIT_SHORT"""
+def test_scalar_coder_path_switches(A, monkeypatch, fresh_handles):
+    """scalar coder, block-switched and all-long batches: PACX_FUSE_TAIL x PACX_SPLIT_SHORT, and the side chain
+    forked to the handle's second stream (pacx_set_side_fork)"""
     pcm, sr = _mixed_stream()
     for bs in (True, False):
-        _set(monkeypatch, {})
+        _set(A, monkeypatch, {})
         want = A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs)
         n = 0
         for fuse, split in itertools.product((None, "0", "1"), (None, "0")):
-            _set(monkeypatch, {"PACX_FUSE_TAIL": fuse, "PACX_SPLIT_SHORT": split})
+            _set(A, monkeypatch, {"PACX_FUSE_TAIL": fuse, "PACX_SPLIT_SHORT": split})
             assert A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs) == want, (bs, fuse, split)
             n += 1
         assert n == 6
-        _set(monkeypatch, {})
-        monkeypatch.setenv("PACX_BS_TWO_STREAMS", "0")   # round 2's four-stream schedule of block-switched batches
-        assert A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs) == want, (bs, "four streams")
-        monkeypatch.delenv("PACX_BS_TWO_STREAMS")
-        for fuse, one in itertools.product((None, "1"), ("1", "0")):   # all-long batches: the whole step on the caller's stream
-            _set(monkeypatch, {"PACX_FUSE_TAIL": fuse})                  # (a handle's default) / the side chain forked to a second one
-            monkeypatch.setenv("PACX_ONE_STREAM", one)
-            assert A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs) == want, (bs, fuse, "one stream", one)
-            monkeypatch.delenv("PACX_ONE_STREAM")
-    _set(monkeypatch, {})
+        for fuse, fork in itertools.product((None, "1"), (False, True)):   # all-long batches: the whole step on the caller's
+            _set(A, monkeypatch, {"PACX_FUSE_TAIL": fuse})                  # stream (a handle's default) / the side chain forked
+            A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs)       # creates the handle encode_stream uses
+            (enc,) = A.context._cache.values()
+            enc.set_side_fork(fork)
+            try:
+                assert A.pacfile.encode_stream(pcm, sr, 128, block_switching=bs) == want, (bs, fuse, "side fork", fork)
+                assert len(A.context._cache) == 1, "encode_stream ran on another handle"
+            finally:
+                enc.set_side_fork(False)
+    _set(A, monkeypatch, {})
 
 
 @pytest.mark.parametrize("kbps", [96, 128])
-def test_gain_shape_coder_path_switches(A, monkeypatch, kbps):
+def test_gain_shape_coder_path_switches(A, monkeypatch, fresh_handles, kbps):
     """gain-shape coder (+ SBR at 96 kb/s), block-switched and all-long: PACX_SPLIT_SHORT x
-    PACX_VQ_FUSE_ALLOC x (PACX_VQ_FRAME: unset = k_vq_frame, 2 = k_vq_frame2, 0 = k_vq with PACX_VQ_BFS) -- and
-    PACX_VQ_ONE_LAUNCH=1 (one coder launch behind both chains); then the two decoders on the default stream"""
+    PACX_VQ_FUSE_ALLOC x (PACX_VQ_FRAME: unset = k_vq_frame, 0 = k_vq with PACX_VQ_BFS), 18 combinations; then
+    the two decoders on the default stream"""
     pcm, sr = _mixed_stream()
     for bs in (True, False):
-        _set(monkeypatch, {})
+        _set(A, monkeypatch, {})
         want = A.pacfile.encode_stream(pcm, sr, kbps, block_switching=bs, use_vq=True, use_sbr=kbps < 128)
+        n = 0
         for split, alloc, (frame, bfs) in itertools.product((None, "0"), (None, "0", "1"),
-                                                            ((None, None), ("2", None), ("0", "0"), ("0", "1"))):
-            _set(monkeypatch, {"PACX_SPLIT_SHORT": split, "PACX_VQ_FUSE_ALLOC": alloc, "PACX_VQ_FRAME": frame,
-                               "PACX_VQ_BFS": bfs})
+                                                            ((None, None), ("0", "0"), ("0", "1"))):
+            _set(A, monkeypatch, {"PACX_SPLIT_SHORT": split, "PACX_VQ_FUSE_ALLOC": alloc, "PACX_VQ_FRAME": frame,
+                                  "PACX_VQ_BFS": bfs})
             got = A.pacfile.encode_stream(pcm, sr, kbps, block_switching=bs, use_vq=True, use_sbr=kbps < 128)
             assert got == want, (bs, split, alloc, frame, bfs)
-        _set(monkeypatch, {})
-        monkeypatch.setenv("PACX_VQ_ONE_LAUNCH", "1")
-        assert A.pacfile.encode_stream(pcm, sr, kbps, block_switching=bs, use_vq=True, use_sbr=kbps < 128) == want
-        monkeypatch.delenv("PACX_VQ_ONE_LAUNCH")
+            n += 1
+        assert n == 18
+        _set(A, monkeypatch, {})
         ref = A.pacfile.decode_stream(want)
-        _set(monkeypatch, {"PACX_VQ_DEC_FRAME": "0"})
+        _set(A, monkeypatch, {"PACX_VQ_DEC_FRAME": "0"})
         assert np.array_equal(A.pacfile.decode_stream(want), ref)
-    _set(monkeypatch, {})
+    _set(A, monkeypatch, {})
 
 
 def test_reserve_failure_releases_everything(A):

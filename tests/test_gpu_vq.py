@@ -403,9 +403,27 @@ def _decode_blocks_of(A, name, kbps, seen):
             p.nMDCTLines = p.nSamplesPerBlock = 1024
 
 
-def test_level_walk_equals_depth_first_walk(A, monkeypatch):
-    """Four coders for the split trees, same bytes: k_vq_frame (all bands of a block level by level, the
-    default; trees beyond its node store fall back to k_vq), k_vq_frame2 (PACX_VQ_FRAME=2: in place, one leaf per lane), k_vq walking a band level by level
+@pytest.fixture
+def fresh_handles(A):
+    """the PACX_* overrides are read when a handle is created: a test that sets them starts and ends with an empty
+    handle cache, so that no forced handle leaks into later tests"""
+    A.context.clear()
+    yield
+    A.context.clear()
+
+
+def _set_env(A, monkeypatch, env):
+    for k in ("PACX_VQ_FRAME", "PACX_VQ_BFS", "PACX_VQ_DEC_FRAME"):
+        if env.get(k) is not None:
+            monkeypatch.setenv(k, env[k])
+        else:
+            monkeypatch.delenv(k, raising=False)
+    A.context.clear()                              # encode_stream / decode_stream create handles that read them
+
+
+def test_level_walk_equals_depth_first_walk(A, monkeypatch, fresh_handles):
+    """Three coders for the split trees, same bytes: k_vq_frame (all bands of a block level by level, the
+    default; trees beyond its node store fall back to k_vq), k_vq walking a band level by level
     (vq_shape_bfs, PACX_VQ_FRAME=0 PACX_VQ_BFS=1) and k_vq depth first (PACX_VQ_BFS=0) -- at bit rates that
     give one-level trees, deep trees and trees beyond either node store."""
     rng = np.random.default_rng(11)
@@ -415,22 +433,15 @@ def test_level_walk_equals_depth_first_walk(A, monkeypatch):
     pcm = np.clip(np.round(pcm * 20000), -32767, 32767).astype(np.int16)
     for kbps in (64, 128, 256, 448):
         outs = []
-        for frame, bfs in ((None, None), ("2", None), ("0", "0"), ("0", "1"), ("0", None)):
-            if frame is None:
-                monkeypatch.delenv("PACX_VQ_FRAME", raising=False)
-            else:
-                monkeypatch.setenv("PACX_VQ_FRAME", frame)
-            if bfs is None:
-                monkeypatch.delenv("PACX_VQ_BFS", raising=False)
-            else:
-                monkeypatch.setenv("PACX_VQ_BFS", bfs)
+        for frame, bfs in ((None, None), ("0", "0"), ("0", "1"), ("0", None)):
+            _set_env(A, monkeypatch, {"PACX_VQ_FRAME": frame, "PACX_VQ_BFS": bfs})
             outs.append(A.pacfile.encode_stream(pcm, 48000, kbps, block_switching=True, use_vq=True,
                                                 use_sbr=kbps < 128))
-        monkeypatch.delenv("PACX_VQ_FRAME", raising=False)
-        assert outs[0] == outs[1] == outs[2] == outs[3] == outs[4], kbps
+        _set_env(A, monkeypatch, {})
+        assert outs[0] == outs[1] == outs[2] == outs[3], kbps
 
 
-def test_frame_decoder_equals_band_decoder(A, monkeypatch):
+def test_frame_decoder_equals_band_decoder(A, monkeypatch, fresh_handles):
     """k_vq_dec_frame (bands parsed one per lane, one leaf per lane, in-place combine; the default) and k_vq_dec
     (a wave per band, depth first; PACX_VQ_DEC_FRAME=0; also what takes the blocks whose trees do not fit the
     frame decoder's node store) give the same lines and the same PCM, at bit rates on both sides of that limit."""
@@ -443,9 +454,7 @@ def test_frame_decoder_equals_band_decoder(A, monkeypatch):
         pac = A.pacfile.encode_stream(pcm, 48000, kbps, block_switching=True, use_vq=True, use_sbr=kbps < 128)
         outs = []
         for mode in ("0", None):
-            if mode is None:
-                monkeypatch.delenv("PACX_VQ_DEC_FRAME", raising=False)
-            else:
-                monkeypatch.setenv("PACX_VQ_DEC_FRAME", mode)
+            _set_env(A, monkeypatch, {"PACX_VQ_DEC_FRAME": mode})
             outs.append(A.pacfile.decode_stream(pac))
+        _set_env(A, monkeypatch, {})
         assert np.array_equal(outs[0], outs[1]), kbps

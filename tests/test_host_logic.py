@@ -172,3 +172,50 @@ def test_synth_stream_is_deterministic(A, stages):
     tags = [str(t) for t in stages["long_tag"]]
     i = tags.index("synth:h2:c1")
     assert np.array_equal(a[1024:3072, 1], stages["long_x_i16"][i])
+
+
+def _functions_calling(src, ident):
+    """names of the top-level functions of a C++ source whose bodies mention `ident` (comments stripped)"""
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    names, depth, head_start, name = set(), 0, 0, None
+    for m in re.finditer(r"[{};]|\b%s\b" % ident, src):
+        t = m.group()
+        if t == "{":
+            if depth == 0:
+                head = src[head_start:m.start()].rstrip()
+                # the identifier in front of the parameter list (the '(' that matches the last ')')
+                i, d = len(head) - 1, 0
+                while i >= 0:
+                    d += {")": 1, "(": -1}.get(head[i], 0)
+                    if d == 0 and head[i] == "(":
+                        break
+                    i -= 1
+                found = re.search(r"(\w+)\s*$", head[:i]) if head.endswith(")") else None
+                name = found.group(1) if found else head
+            depth += 1
+        elif t == "}":
+            depth -= 1
+            if depth == 0:
+                head_start = m.end()
+        elif t == ";":
+            if depth == 0:
+                head_start = m.end()
+        else:
+            names.add(name if depth else "<file scope>")
+    return names
+
+
+def test_environment_is_read_in_one_function():
+    """the library reads its environment in ONE function (the path overrides, once per handle in pacx_create):
+    a getenv anywhere else in csrc/ -- a per-call read on an encode path, say -- fails here"""
+    csrc = os.path.join(ROOT, "audio-codec_amd", "csrc")
+    where = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".cpp")):
+            where |= {(f, n) for n in _functions_calling(open(os.path.join(csrc, f)).read(), "getenv")}
+    assert len(where) == 1, sorted(where)
+    # the scanner itself: a second function with a read, and a read at file scope, are told apart
+    assert _functions_calling("static int a(int x)\n{\n    return getenv(\"A\") != 0;\n}\n"
+                              "__global__ __launch_bounds__(64) void b(int *p) { if (1) { p[0] = getenv(\"B\"); } }\n"
+                              "static const char *c = getenv(\"C\");\n", "getenv") == {"a", "b", "<file scope>"}

@@ -31,13 +31,7 @@ print("role   split passes busy / wait at barrier 1   |  scalar or leaves busy /
 for r in range(4):
     b1, w1, b2, w2 = t[4 * r:4 * r + 4] / units
     print(f"  {r}    {b1:9.0f} / {w1:9.0f}                   | {b2:9.0f} / {w2:9.0f}")
-if os.environ.get("PACX_VQ_FRAME") == "1":
-    names = ["tables + lines into LDS + barrier", "band gains, x / gain + barrier", "header, roots, first classify + barriers",
-             "fields ORed in", "gains quantised + barrier"]
-    for k, n in enumerate(names):
-        print(f"  thread 0: {n:45s} {t[21 + k] / units:9.0f}")
-else:
-    names = ["phase A (lines, gains, header, roots, first sort)", "leaf lists + barrier", "small leaves, one per lane (wave 0)",
-             "larger leaves + barrier", "enumeration terms + barrier", "widths, positions", "fields, gains, hand-over"]
-    for k, n in enumerate(names):
-        print(f"  wave 0: {n:50s} {t[21 + k] / units:9.0f}")
+names = ["tables + lines into LDS + barrier", "band gains, x / gain + barrier", "header, roots, first classify + barriers",
+         "fields ORed in", "gains quantised + barrier"]
+for k, n in enumerate(names):
+    print(f"  thread 0: {n:45s} {t[21 + k] / units:9.0f}")
