@@ -194,7 +194,8 @@ __global__ __launch_bounds__(64) void k_sbr_scalar_lines(PacxTables T, long long
     }
     const bool coded = lane >= T.first_omitted && lane < T.nb_long && ba[lane] != 0;
     const bool sbr = routing == 2 || (routing == 1 && __builtin_amdgcn_ballot_w64(coded) != 0ull);
-    const int cut = T.band_lower_long[T.first_omitted];
+    /* first_omitted == nb_long on a handle without SBR: no omitted band, and band_lower_long has no entry there */
+    const int cut = T.first_omitted < T.nb_long ? T.band_lower_long[T.first_omitted] : PACX_M_LONG;
     for (int k = lane; k < PACX_M_LONG; k += 64) {
         int b = T.line_band_long[k];
         if (sbr && k >= cut)

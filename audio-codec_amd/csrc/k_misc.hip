@@ -103,75 +103,20 @@ __global__ void k_bitalloc_generic(long long n, int nb, const int32_t *__restric
 
 /* np.mean(np.abs(np.take(block, arange(upto), axis=1))) of coder/detect_transients.py:14 in NumPy's order, by ONE
  * lane: the [nCh, upto] array is summed flattened (channel-major; columns past the hop are the look-ahead
- * zeros) by NumPy's pairwise scheme -- up to 128 elements on eight interleaved accumulators folded
- * ((0+1)+(2+3))+((4+5)+(6+7)) plus a scalar tail, longer runs cut at n/2 rounded down to a multiple of 8 --
- * and divided by the element count.  The recursion runs on an explicit stack in LDS (depth <= 9 for 8 x 2048
- * elements).  Only k_transient's exact-tie path calls this. */
+ * zeros) in NumPy's order (pacx_np_add_reduce, pacx_exact.h: pairwise runs of up to 8192 elements, on a stack
+ * in LDS) and divided by the element count, at most PACX_NP_SUM_MAX_N.  k_transient's exact-tie path and
+ * k_transient_f64 call this. */
 template <typename At>
-__device__ __forceinline__ double np_pairwise_mean(long long n_el_ll, At at)
+__device__ __forceinline__ double np_pairwise_mean(int n_el, At at)
 {
-    __shared__ int st_lo[12], st_n[12], st_state[12];
-    __shared__ double st_left[12];
-    const long long n_el = n_el_ll;
-    auto block_sum = [&](int lo, int n) {
-        if (n < 8) {
-            double r = -0.0;
-            for (int i = 0; i < n; ++i)
-                r = r + at(lo + i);
-            return r;
-        }
-        double r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            r[j] = at(lo + j);
-        const int n8 = n - (n & 7);
-        for (int i = 8; i < n8; i += 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                r[j] = r[j] + at(lo + i + j);
-        }
-        double s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (int i = n8; i < n; ++i)
-            s = s + at(lo + i);
-        return s;
-    };
-    int top = 0;
-    st_lo[0] = 0;
-    st_n[0] = (int)n_el;
-    st_state[0] = 0;
-    double result = 0.0;
-    while (top >= 0) {
-        const int lo = st_lo[top], n = st_n[top], state = st_state[top];
-        int cut = n / 2;
-        cut -= cut % 8;
-        if (n <= 128) {
-            result = block_sum(lo, n);
-            --top;
-        } else if (state == 0) {
-            st_state[top] = 1;
-            ++top;
-            st_lo[top] = lo;
-            st_n[top] = cut;
-            st_state[top] = 0;
-        } else if (state == 1) {
-            st_left[top] = result;
-            st_state[top] = 2;
-            ++top;
-            st_lo[top] = lo + cut;
-            st_n[top] = n - cut;
-            st_state[top] = 0;
-        } else {
-            result = st_left[top] + result;
-            --top;
-        }
-    }
-    return result / (double)n_el;
+    __shared__ PacxPairwiseStack st;
+    return pacx_np_add_reduce(n_el, at, &st) / (double)n_el;
 }
 
 /* the int16 hop of k_transient: |x| = 2 (|c| & 32767) / 65535, zeros past the hop */
 __device__ __forceinline__ double transient_np_mean(const PacxPcmView &in, const short *base, int n_ch, int upto, int hop)
 {
-    return np_pairwise_mean((long long)n_ch * upto, [&](int i) {
+    return np_pairwise_mean(n_ch * upto, [&](int i) {
         const int ch = i / upto, col = i - ch * upto;
         if (col >= hop)
             return 0.0;
@@ -331,7 +276,7 @@ __global__ __launch_bounds__(64) void k_transient_f64(long long n_blocks, int n_
     }
     const int cols = upto < n ? upto : n;
     if (lane == 0) {
-        const double avg = np_pairwise_mean((long long)n_ch * cols, [&](int i) {
+        const double avg = np_pairwise_mean(n_ch * cols, [&](int i) {
             const int ch = i / cols, col = i - ch * cols;
             return fabs(x[(long long)ch * n + col]);
         });

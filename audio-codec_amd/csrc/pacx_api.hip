@@ -1495,7 +1495,7 @@ extern "C" int pacx_transient_detect_f64(pacx_handle *h, int64_t n_blocks, int n
         return PACX_OK;
     if (n_blocks < 0 || n_blocks > 0x7fffffffLL || n_channels < 1 || n_samples < 1 || !blocks || !result)
         return fail(h, PACX_E_ARG, "pacx_transient_detect_f64: bad argument");
-    if ((long long)n_channels * n_samples > 0x7fffffffLL)
+    if ((long long)n_channels * n_samples > PACX_NP_SUM_MAX_N)      /* the mean indexes its elements with ints */
         return fail(h, PACX_E_UNSUPPORTED, "pacx_transient_detect_f64: block too large");
     HIP_TRY(h, hipSetDevice(h->device));
     pacx_launch_transient_f64(n_blocks, n_channels, n_samples, blocks, thresh, result, (hipStream_t)stream);

@@ -207,6 +207,105 @@ PACX_HD double pacx_np_sum(const double *a, int n)
     return res;
 }
 
+/* np.add.reduce / np.sum / np.mean of a contiguous float64 vector of ANY length, in NumPy's order.  The reduction
+ * hands pairwise_sum runs of at most np.getbufsize() = 8192 elements and adds their sums left to right onto the
+ * identity 0.0; inside a run: up to 128 elements summed as pacx_np_sum sums them, longer runs cut at n/2
+ * rounded down to a multiple of 8, the two halves summed and added.  The recursion runs on an explicit stack
+ * that the caller supplies (the kernels keep it in LDS: a local array indexed at run time would go to scratch).
+ * Element i is at(i), so the caller decides the layout.
+ *
+ * Stack depth: the larger half of a run of n is at most floor(n/2) + 8 elements, a bound that grows with n, so
+ * iterating it from the longest run bounds the index of every entry pushed for any shorter run too.  Runs
+ * never exceed PACX_NP_BUFSIZE, whatever the length of the vector. */
+#define PACX_NP_BUFSIZE 8192               /* numpy's default ufunc buffer size (np.getbufsize()) */
+#define PACX_NP_SUM_MAX_N 0x7fffffff       /* int element indices; pacx_transient_detect_f64's size limit */
+#define PACX_PAIRWISE_STACK 8
+
+struct PacxPairwiseStack {
+    int lo[PACX_PAIRWISE_STACK], n[PACX_PAIRWISE_STACK], state[PACX_PAIRWISE_STACK];
+    double left[PACX_PAIRWISE_STACK];
+};
+
+static constexpr int pacx_pairwise_depth_bound(long long n)
+{
+    int d = 0;
+    while (n > 128) {
+        n = n / 2 + 8;
+        ++d;
+    }
+    return d;
+}
+static_assert(pacx_pairwise_depth_bound(PACX_NP_BUFSIZE) < PACX_PAIRWISE_STACK,
+              "the pairwise-sum stack must hold the deepest split of the longest run");
+
+/* numpy's pairwise_sum of elements lo .. lo + n_el - 1, n_el <= PACX_NP_BUFSIZE */
+template <typename At>
+PACX_HD double pacx_np_pairwise_sum(int lo0, int n_el, At at, PacxPairwiseStack *st)
+{
+    auto leaf = [&](int lo, int n) {
+        if (n < 8) {
+            double r = -0.0;
+            for (int i = lo; i < lo + n; ++i)
+                r = r + at(i);
+            return r;
+        }
+        double r0 = at(lo), r1 = at(lo + 1), r2 = at(lo + 2), r3 = at(lo + 3);
+        double r4 = at(lo + 4), r5 = at(lo + 5), r6 = at(lo + 6), r7 = at(lo + 7);
+        const int n8 = n - (n & 7);
+        for (int i = lo + 8; i < lo + n8; i += 8) {
+            r0 = r0 + at(i + 0); r1 = r1 + at(i + 1); r2 = r2 + at(i + 2); r3 = r3 + at(i + 3);
+            r4 = r4 + at(i + 4); r5 = r5 + at(i + 5); r6 = r6 + at(i + 6); r7 = r7 + at(i + 7);
+        }
+        double s = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+        for (int i = lo + n8; i < lo + n; ++i)
+            s = s + at(i);
+        return s;
+    };
+    int top = 0;
+    st->lo[0] = lo0;
+    st->n[0] = n_el;
+    st->state[0] = 0;
+    double result = 0.0;
+    while (top >= 0) {
+        const int lo = st->lo[top], n = st->n[top], state = st->state[top];
+        int cut = n / 2;
+        cut -= cut % 8;
+        if (n <= 128) {
+            result = leaf(lo, n);
+            --top;
+        } else if (state == 0) {
+            st->state[top] = 1;
+            ++top;
+            st->lo[top] = lo;
+            st->n[top] = cut;
+            st->state[top] = 0;
+        } else if (state == 1) {
+            st->left[top] = result;
+            st->state[top] = 2;
+            ++top;
+            st->lo[top] = lo + cut;
+            st->n[top] = n - cut;
+            st->state[top] = 0;
+        } else {
+            result = st->left[top] + result;
+            --top;
+        }
+    }
+    return result;
+}
+
+template <typename At>
+PACX_HD double pacx_np_add_reduce(int n_el, At at, PacxPairwiseStack *st)
+{
+    double r = 0.0;
+    for (int done = 0; done < n_el;) {
+        const int n = n_el - done < PACX_NP_BUFSIZE ? n_el - done : PACX_NP_BUFSIZE;
+        r = r + pacx_np_pairwise_sum(done, n, at, st);
+        done += n;
+    }
+    return r;
+}
+
 /* Budget rule of coder/codec.py:288-299.  use_vq: only the overall scale
  * factor is charged (:292-294).  sbr_long: a long block of an SBR file is
  * budgeted from the full halfN whatever its flags (EncodeSingleChannel_SBR,

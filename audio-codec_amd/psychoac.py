@@ -67,15 +67,24 @@ def _generic_tables(n, sample_rate, sf_bands, device):
     quiet of the MDCT lines: coder/psychoac.py:45-46, 28-42, 171-179, 183-186), cached per (N, rate, band layout)"""
     import torch
     from . import tables
+    # the reference slices mdct_spl[lowerLine:upperLine + 1] (coder/psychoac.py:283-289): a band that runs past the
+    # n/2 lines is cut short there, one that starts past them is empty and np.amax raises
     counts = true_line_counts(sf_bands)
-    key = (int(n), float(sample_rate), counts, str(device))
+    lo = getattr(sf_bands, "lowerLine", None)
+    if lo is not None and len(lo) == len(counts):
+        lower = tuple(int(v) for v in lo)
+    else:
+        lower = tuple(int(v) for v in np.concatenate(([0], np.cumsum(counts)[:-1])))
+    counts = tuple(min(c, n // 2 - l) for l, c in zip(lower, counts))
+    key = (int(n), float(sample_rate), lower, counts, str(device))
     t = _generic.get(key)
     if t is None:
+        if min(lower) < 0:
+            raise ValueError("a band starts before line 0")
         if min(counts) < 1:
             raise ValueError("zero-size array to reduction operation maximum which has no identity")   # np.amax, coder/psychoac.py:289
         m = np.arange(n) * (2.0 * np.pi / n)
         f = tables.line_freqs(n // 2, sample_rate)
-        lower = np.concatenate(([0], np.cumsum(counts)[:-1]))
         as_t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a, dtype=dt), device=device)
         t = {"hann": as_t(tables.hann(n), np.float64), "tw_cos": as_t(np.cos(m), np.float64),
              "tw_sin": as_t(np.sin(m), np.float64), "fft_norm": float(tables.fft_norm(n)),

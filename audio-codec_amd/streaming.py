@@ -58,7 +58,8 @@ class HostStreamEncoder:
         self.halo = torch.zeros((n_ch, HOP), dtype=torch.int16, device=dev)        # the hop before the next chunk
         self.carry = torch.zeros(2, dtype=torch.uint8, device=dev)                 # transient decisions of the two hops before it
         self.tr = torch.zeros(F, dtype=torch.uint8, device=dev)
-        self.fetch = [self.cap] * depth             # bytes fetched per chunk: the whole slot until a length is known
+        self.fetch = self.cap                       # bytes the next submit fetches: the whole slot until a length is known
+        self.fetched = [0] * depth                  # bytes the D2H of each slot's submit actually copied
         self.pending = [False] * depth
         self.n_hops_of = [0] * depth
         self.next_slot = 0
@@ -131,8 +132,9 @@ class HostStreamEncoder:
             self.ev_k[k].record(self.s_k)
         with torch.cuda.stream(self.s_out):
             self.s_out.wait_event(self.ev_k[k])
-            n = min(self.fetch[k], self.cap)
+            n = min(self.fetch, self.cap)
             self.host_body[k][:n].copy_(self.bodies[k][:n], non_blocking=True)
+            self.fetched[k] = n
             self.host_total[k].copy_(self.totals[k], non_blocking=True)
             self.ev_out[k].record(self.s_out)
         self.pending[k] = True
@@ -147,13 +149,15 @@ class HostStreamEncoder:
         n = int(self.host_total[k].item())
         if n > self.cap:
             raise RuntimeError(f"body of {n} bytes does not fit its {self.cap}-byte buffer")
-        if n > self.fetch[k]:                      # the fetch was sized from an earlier chunk: get the rest
+        got = self.fetched[k]
+        if n > got:                                # the fetch was sized from an earlier chunk: get the rest
             with torch.cuda.stream(self.s_out):
-                self.host_body[k][self.fetch[k]:n].copy_(self.bodies[k][self.fetch[k]:n], non_blocking=True)
+                self.host_body[k][got:n].copy_(self.bodies[k][got:n], non_blocking=True)
             self.s_out.synchronize()
-        # later chunks fetch what this one needed plus a margin instead of the whole slot
+        # later submits fetch what this chunk needed plus a margin instead of the whole slot; a slot already in
+        # flight keeps the count it was submitted with (fetched[k]), which is what its own result() tops up from
         per_hop = -(-n // max(self.n_hops_of[k], 1))
-        self.fetch = [min(self.cap, per_hop * self.F + (1 << 16))] * self.depth
+        self.fetch = min(self.cap, per_hop * self.F + (1 << 16))
         self.pending[k] = False
         return self.host_body[k][:n].numpy()
 

@@ -9,6 +9,14 @@ long long hc_quant_mag(double ax, int r) { return pacx_quant_mag(ax, r); }
 int hc_scale_factor(double ax, int nsb, int nmb) { return pacx_scale_factor(ax, nsb, nmb); }
 int hc_mantissa(double x, int scale, int nsb, int nmb) { return pacx_mantissa(x, scale, nsb, nmb); }
 double hc_np_sum(const double *a, int n) { return pacx_np_sum(a, n); }
+double hc_np_add_reduce(const double *a, int n)
+{
+    PacxPairwiseStack st;
+    return pacx_np_add_reduce(n, [a](int i) { return a[i]; }, &st);
+}
+int hc_pairwise_stack(void) { return PACX_PAIRWISE_STACK; }
+int hc_np_bufsize(void) { return PACX_NP_BUFSIZE; }
+int hc_np_sum_max_n(void) { return PACX_NP_SUM_MAX_N; }
 double hc_dequant_uniform(long long c, int r) { return pacx_dequant_uniform(c, r); }
 int hc_mantissa_fp(double x, int scale, int nsb, int nmb) { return pacx_mantissa_fp(x, scale, nsb, nmb); }
 double hc_dequantize_fp(long long m, int scale, int nsb, int nmb) { return pacx_dequantize_fp(m, scale, nsb, nmb); }

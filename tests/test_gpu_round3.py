@@ -364,6 +364,41 @@ def test_transient_detector_mirror_matches_oracle(A):
     assert A.detect_transients.parTransientDetect(tie) == po.transient_detect(tie)
 
 
+def _transient_totals():
+    """element counts around every split of NumPy's pairwise sum and its 8192-element buffers, to 2^21 + 1"""
+    for d in range(15):
+        offs = (-9, -8, -1, 0, 1, 7, 8, 9) if d < 8 else (-1, 0, 1) if d < 12 else (1,)
+        for o in offs:
+            yield 128 * 2 ** d + o
+
+
+def test_transient_detector_mean_is_numpys_at_every_size(A):
+    """k_transient_f64's mean over whole blocks of up to 2^21 elements, pinned to the last bit: the peak sits in the
+    last column of channel 0 (so the mean covers the block), the threshold is the reference's own peak / avg, and
+    parTransientDetect must say False there and True one ulp below it"""
+    rng = np.random.default_rng(21)
+    n_cases = 0
+    for total in _transient_totals():
+        for n_ch in (1, 2, 3, 5) if total < 1 << 18 else (1, 3):
+            n = -(-total // n_ch)
+            for seed in range(2 if total < 1 << 16 else 1):
+                blk = rng.choice((-1.0, 1.0), (n_ch, n)) * 10.0 ** rng.uniform(-12, 0, (n_ch, n))
+                blk[0, -1] = -2.0 if seed else 2.0
+                # the reference's expressions (oracle.pac_oracle.transient_detect)
+                mag = np.abs(blk)
+                cols = np.arange(min(max(np.argmax(mag, axis=1) + 500), n))
+                assert len(cols) == n
+                thresh = float(np.max(np.max(mag, axis=1) / np.mean(np.abs(np.take(blk, cols, axis=1)))))
+                below = float(np.nextafter(thresh, 0))
+                got = (A.detect_transients.parTransientDetect(blk, thresh), A.detect_transients.parTransientDetect(blk, below))
+                assert got == (False, True), (n_ch, n, seed, got)
+                n_cases += 1
+    assert n_cases > 500
+    zero = np.zeros((2, (1 << 20) + 1))
+    got = A.detect_transients.parTransientDetect(zero)
+    assert got == 0 and type(got) is int
+
+
 # ------------------------------------------------------------ host memory to host memory (VERDICT r2 missing #5)
 @pytest.mark.parametrize("coder", ["scalar", "scalar_bs", "shipped128", "shipped96"])
 def test_host_stream_chunks_equal_one_batch(A, coder):
@@ -378,6 +413,74 @@ def test_host_stream_chunks_equal_one_batch(A, coder):
     want = A.pacfile.encode_stream(pcm, sr, kbps, **kw)
     for chunk in (7, 16, 64):
         assert A.pacfile.encode_stream(pcm, sr, kbps, chunk_hops=chunk, **kw) == want, (coder, chunk)
+
+
+_RATE_F = 256                                       # hops per chunk: loud chunks' bodies are well over the 64 KB fetch margin
+_RATE_PLAN = "SSNNSNN"                              # S digital silence, N loud noise: rates rising and falling
+
+
+def _rate_programme():
+    """stereo 48 kHz chunks of _RATE_F hops after _RATE_PLAN, then a partial loud chunk"""
+    rng = np.random.default_rng(17)
+    parts = []
+    for kind in _RATE_PLAN + "n":
+        n = _RATE_F * 1024 if kind != "n" else 100 * 1024
+        if kind == "S":
+            parts.append(np.zeros((n, 2), np.int16))
+        else:
+            parts.append(np.clip(np.round(rng.standard_normal((n, 2)) * 12000), -32767, 32767).astype(np.int16))
+    return np.concatenate(parts)
+
+
+def _assert_fetch_margin_exceeded(lengths, gap):
+    """the programme's own precondition: some chunk's body is more than the 64 KB fetch margin larger than the body of
+    the chunk `gap` before it, whose length sized that chunk's first D2H copy (depth = gap)"""
+    assert any(lengths[i] - lengths[i - gap] > 65536 for i in range(gap, len(lengths))), (gap, lengths)
+
+
+@pytest.mark.parametrize("coder", ["scalar", "scalar_bs", "shipped128", "shipped96"])
+def test_host_stream_rising_rate_bodies_over_the_fetch_margin(A, coder):
+    """streaming.HostStreamEncoder with chunk bodies of well over 64 KB whose size jumps from chunk to chunk: the first
+    D2H copy of a chunk is sized from the chunk `depth` before it, and result() must top up from what that copy
+    actually fetched (it once topped up from the latest estimate, and the bytes in between were stale).  The
+    gain-shape coder's bodies follow the signal (silence is small); the scalar coder's water-filling spends the whole
+    budget on silence too, so its bodies stay within a few KB of one another and only the bytes are compared there"""
+    pcm = _rate_programme()
+    kw = {"scalar": dict(block_switching=False), "scalar_bs": dict(block_switching=True),
+          "shipped128": dict(block_switching=True, use_vq=True),
+          "shipped96": dict(block_switching=True, use_vq=True, use_sbr=True)}[coder]
+    kbps = 96 if coder == "shipped96" else 128
+    want = A.pacfile.encode_stream(pcm, 48000, kbps, **kw)
+    assert A.pacfile.encode_stream(pcm, 48000, kbps, chunk_hops=_RATE_F, **kw) == want, coder
+    _, head_len = A.pacfile.parse_header(want)
+    enc = A.context.encoder(48000, kbps / 48.0, use_vq=kw.get("use_vq", False), use_sbr=kw.get("use_sbr", False))
+    for depth in (2, 3):
+        hs = A.streaming.HostStreamEncoder(enc, 2, _RATE_F, depth=depth, block_switching=kw["block_switching"])
+        bodies = [bytes(b) for b in hs.encode(pcm)]
+        if kw.get("use_vq"):
+            _assert_fetch_margin_exceeded([len(b) for b in bodies], depth)
+        assert want[head_len:] == b"".join(bodies), (coder, depth)
+
+
+def test_host_stream_zero_copy_results_out_of_order(A):
+    """the zero-copy API with results taken newest first: each slot's top-up must start where ITS copy stopped, whatever
+    the other slot's result() estimated in the meantime (gain-shape coder: bodies that follow the signal)"""
+    pcm = _rate_programme()[:4 * _RATE_F * 1024]         # S S N N
+    want = A.pacfile.encode_stream(pcm, 48000, 128, use_vq=True)
+    _, head_len = A.pacfile.parse_header(want)
+    enc = A.context.encoder(48000, 128 / 48.0, use_vq=True)
+    hs = A.streaming.HostStreamEncoder(enc, 2, _RATE_F, depth=2)
+    got = {}
+    for pair in ((0, 1), (2, 3)):
+        for i in pair:
+            hs.input(i % 2)[:] = pcm[i * _RATE_F * 1024:(i + 1) * _RATE_F * 1024].T
+            hs.submit(i % 2)
+        for i in reversed(pair):
+            got[i] = bytes(hs.result(i % 2))
+    lengths = [len(got[i]) for i in range(4)]
+    assert lengths[2] - lengths[0] > 65536, lengths       # chunk 2 was fetched with chunk 0's estimate
+    body = b"".join(got[i] for i in range(4))
+    assert want[head_len:head_len + len(body)] == body
 
 
 def test_host_stream_zero_copy_api(A):
@@ -743,3 +846,64 @@ def test_streams_with_512_lines_against_the_reference(A, tag):
     assert len(pac) == len(want) and pac == want
     pcm = A.pacfile.decode_stream(want)
     assert pcm.shape == L512[f"dec_{tag}"].shape and np.array_equal(pcm, L512[f"dec_{tag}"])
+
+
+def _layouts(A, half, sr):
+    """band line counts of the reference's table for `half` lines, changed so that the last band straddles half, a band
+    lies wholly past it, or the bands stop short of it (every count > 12: the merge step leaves them as they are)"""
+    from oracle import pac_oracle as po
+    base = [int(c) for c in po.band_table(half, sr).nLines]
+    assert sum(base) == half and min(base) > 12
+    return {"straddles": base[:-1] + [base[-1] + 37], "past": base + [20], "short": base[:-1]}
+
+
+@pytest.mark.parametrize("half", [512, 256])
+def test_calc_smrs_band_layouts_off_the_block_length(A, half):
+    """CalcSMRs through k_smr_generic with band layouts that do not end at the last line: the reference slices
+    mdct_spl[lowerLine:upperLine + 1] (coder/psychoac.py:283-289), so a band that runs past the block is cut short
+    there (the oracle's SMRs to 1e-9 dB), one wholly past it is empty (np.amax raises ValueError), and bands that stop
+    short of it leave the last lines out"""
+    from oracle import pac_oracle as po
+    sr = 48000
+    lay = _layouts(A, half, sr)
+    xs = _blocks(2 * half, 6, 110 + half)
+    for name, counts in lay.items():
+        ours, theirs = A.psychoac.bands_from_counts(counts), po.BandTable(counts)
+        assert list(ours.lowerLine) == list(theirs.lowerLine) and list(ours.upperLine) == list(theirs.upperLine)
+        for x in xs:
+            lines = po.mdct_forward(po.sine_window(2 * half) * x, half, half)[:half]
+            ov = po.scale_factor(np.max(np.abs(lines)), 4)
+            if name == "past":
+                with pytest.raises(ValueError):
+                    po.calc_smrs(x, lines * (1 << ov), ov, sr, theirs)
+                with pytest.raises(ValueError):
+                    A.psychoac.CalcSMRs(x, lines * (1 << ov), ov, sr, ours)
+                continue
+            want = po.calc_smrs(x, lines * (1 << ov), ov, sr, theirs)
+            got = A.psychoac.CalcSMRs(x, lines * (1 << ov), ov, sr, ours)
+            assert got.shape == want.shape and np.abs(got - want).max() <= 1e-9, (name, np.abs(got - want).max())
+    # the straddling band's SMR is the maximum over the lines the block has, not over what lies beyond them
+    x = xs[0]
+    lines = po.mdct_forward(po.sine_window(2 * half) * x, half, half)[:half]
+    got = A.psychoac.CalcSMRs(x, lines, 0, sr, A.psychoac.bands_from_counts(lay["straddles"]))
+    full = A.psychoac.CalcSMRs(x, lines, 0, sr, A.psychoac.bands_from_counts(lay["straddles"][:-1] + [lay["straddles"][-1] - 37]))
+    assert np.array_equal(got, full)
+
+
+@pytest.mark.parametrize("half", [1024, 128])
+def test_tuned_smr_paths_refuse_layouts_past_the_block(A, half):
+    """at 1024 and 128 lines the layout goes into the handle (pacx_create's band table): one that covers more lines
+    than the block has is refused there, never evaluated"""
+    lay = _layouts(A, half, 48000)
+    x = _blocks(2 * half, 3, 130 + half)[-1]
+    from oracle import pac_oracle as po
+    lines = po.mdct_forward(po.sine_window(2 * half) * x, half, half)[:half]
+    for name in ("straddles", "past"):
+        with pytest.raises(A._lib.PacxError, match="exceed the number of MDCT lines"):
+            A.psychoac.CalcSMRs(x, lines, 0, 48000, A.psychoac.bands_from_counts(lay[name]))
+    if half == 128:
+        return
+    # a layout that stops short of the block is a layout the handle takes (above 48 kHz the reference's has that shape)
+    got = A.psychoac.CalcSMRs(x, lines, 0, 48000, A.psychoac.bands_from_counts(lay["short"]))
+    want = po.calc_smrs(x, lines.copy(), 0, 48000, po.BandTable(lay["short"]))
+    assert np.abs(got - want).max() <= 1e-9

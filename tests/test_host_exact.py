@@ -29,6 +29,8 @@ def hc(tmp_path_factory):
     lib.hc_mantissa.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.hc_np_sum.restype = ctypes.c_double
     lib.hc_np_sum.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.hc_np_add_reduce.restype = ctypes.c_double
+    lib.hc_np_add_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.hc_bit_budget.restype = ctypes.c_double
     lib.hc_bit_budget.argtypes = [ctypes.c_double] + [ctypes.c_int] * 6
     lib.hc_bit_alloc.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -113,6 +115,80 @@ def test_np_sum_order(hc):
         for _ in range(40):
             a = np.ascontiguousarray(rng.standard_normal(n) * 10.0 ** rng.integers(-6, 6, n))
             assert hc.hc_np_sum(a.ctypes.data, n) == np.sum(a)
+
+
+def _mixed_magnitudes(rng, n):
+    """random signs over twelve decades: the order of summation shows in the last bits"""
+    return rng.choice((-1.0, 1.0), n) * 10.0 ** rng.uniform(-12, 0, n)
+
+
+def _reduce_sizes():
+    sizes = list(range(1, 4097))
+    for d in range(17):                          # to 2^23 elements
+        sizes += [128 * 2 ** d + o for o in (-9, -8, -1, 0, 1, 7, 8, 9)]
+    return sorted(set(sizes))
+
+
+def _cut(n):
+    return n // 2 - (n // 2) % 8
+
+
+def _unbuffered_pairwise(a):
+    """NumPy's pairwise split over the WHOLE array (runs of up to 8192 are np.add.reduce's own pairwise sums)"""
+    if len(a) <= 8192:
+        return np.add.reduce(a)
+    c = _cut(len(a))
+    return _unbuffered_pairwise(a[:c]) + _unbuffered_pairwise(a[c:])
+
+
+def test_np_add_reduce_equals_numpy_at_every_length(hc):
+    """pacx_np_add_reduce (the mean of k_transient / k_transient_f64) against np.add.reduce and np.mean of the same
+    contiguous array, bit for bit: every length to 4096 and 128 * 2^d + {-9, -8, -1, 0, 1, 7, 8, 9} to d = 16.
+    Neither a left-to-right sum nor one pairwise split over the whole array gives NumPy's bits: NumPy sums runs of
+    np.getbufsize() elements pairwise and adds the run sums in order"""
+    assert hc.hc_np_bufsize() == np.getbufsize() == 8192
+    rng = np.random.default_rng(12)
+    n_seq = n_seq_differs = n_long = n_long_differs = 0
+    for n in _reduce_sizes():
+        a = _mixed_magnitudes(rng, n)
+        got = hc.hc_np_add_reduce(a.ctypes.data, n)
+        want = np.add.reduce(a)
+        assert got == want, (n, got, want)
+        assert got / n == np.mean(a), n
+        if n >= 16:
+            n_seq += 1
+            n_seq_differs += np.cumsum(a)[-1] != want            # cumsum adds left to right
+        if n > 2 * 8192:
+            n_long += 1
+            n_long_differs += _unbuffered_pairwise(a) != want
+    # the comparison tells the orders apart on most arrays
+    assert n_seq_differs > 0.9 * n_seq, (n_seq_differs, n_seq)
+    assert n_long_differs > 0.5 * n_long, (n_long_differs, n_long)
+    assert hc.hc_np_add_reduce(np.zeros(1).ctypes.data, 0) == 0.0
+
+
+def _split_depth(n, memo={}):
+    """deepest stack index that NumPy's pairwise_sum split (cut = n/2 - (n/2) % 8, runs of <= 128 are leaves)
+    reaches for a run of n"""
+    if n <= 128:
+        return 0
+    if n not in memo:
+        memo[n] = 1 + max(_split_depth(_cut(n)), _split_depth(n - _cut(n)))
+    return memo[n]
+
+
+def test_pairwise_stack_holds_the_deepest_split(hc):
+    """the stack capacity exported by pacx_exact.h exceeds the deepest index of the longest run it is given (one
+    buffer of 8192), whatever the length up to the largest block pacx_transient_detect_f64 accepts; one pairwise
+    walk over a whole block of that size would go 25 deep"""
+    assert hc.hc_np_sum_max_n() == 2 ** 31 - 1
+    assert _split_depth(2 ** 31 - 1) == 25
+    deepest = max(_split_depth(n) for n in range(1, hc.hc_np_bufsize() + 1))
+    assert deepest == 7                          # 8191 and its like split one level deeper than 8192
+    assert hc.hc_pairwise_stack() > deepest
+    # one level more at 128 * 2^d + 1 and not before
+    assert [_split_depth(128 * 2 ** d) for d in range(7)] == list(range(7))
+    assert [_split_depth(128 * 2 ** d + 1) for d in range(7)] == list(range(1, 8))
 
 
 def test_window_kind(hc):
