@@ -137,7 +137,10 @@ SIGNATURES = {
                                             _P, _P, _P, _P, _P]),
     "pacx_transient_flags": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P]),
     "pacx_bitalloc_generic": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "pacx_index_body": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P, _P, _P, _P]),
+    "pacx_overlap_add_pcm": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P]),
 }
+INDEX_SEGMENT = 8192          # PACX_IX_SEG (csrc/body_index.h): bytes mapped by one workgroup of pacx_index_body
 (WIN_SINE, WIN_START, WIN_STOP, WIN_STARTSTOP, WIN_SINE_SHORT, WIN_HANN, WIN_HANN_SHORT, WIN_KBD,
  WIN_KBD_SHORT) = range(9)
 MDCT_SHORT, MDCT_PREWINDOWED, MDCT_KBD = 1, 2, 4

@@ -12,6 +12,8 @@
  *   k_ola_pcm  : hop h = second half of block h-1 + first half of block h
  *                (coder/pacfile.py:289-295; the last half is flushed at EOF,
  *                :245-249), then the 16-bit PCM mapping of coder/pcmfile.py:127-134.
+ *   k_ola_tail_pcm : the same for one batch of a longer stream, the half-block
+ *                across the batch boundary carried by the caller (pacx_overlap_add_pcm).
  *
  * The IMDCT reuses the forward machinery: y = 2 * unfold(DCT4(X)) where DCT4 is the
  * same "pre-twiddle, N/4-point complex FFT, post-twiddle" pipeline the MDCT
@@ -386,7 +388,49 @@ __global__ void k_ola_pcm(long long n_blocks, int n_ch, const double *__restrict
     pcm[idx] = (int16_t)(neg ? -q : q);
 }
 
+/* k_ola_pcm for one batch of a longer stream: the half-block before the batch comes in through `tail`
+   ([n_ch][1024]) and the one after it goes out the same way.  Element (ch, i) of `tail` is read and
+   written by ONE lane, the one of hop 0 (read first, then written); the flush hop takes its samples
+   from the last block, not from the updated tail.  Sum and mapping as k_ola_pcm. */
+__global__ void k_ola_tail_pcm(long long n_blocks, int n_ch, const double *__restrict__ blocks, double *tail, int flush,
+                               int16_t *__restrict__ pcm)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;   /* (hop, sample, channel) */
+    const long long n_hops = n_blocks + (flush ? 1 : 0);
+    if (idx >= n_hops * PACX_M_LONG * n_ch)
+        return;
+    const int ch = (int)(idx % n_ch);
+    const long long t = idx / n_ch;
+    const long long h = t / PACX_M_LONG;
+    const int i = (int)(t % PACX_M_LONG);
+    double s;
+    if (h < n_blocks) {
+        const double prev = (h >= 1) ? blocks[((h - 1) * n_ch + ch) * PACX_N_LONG + PACX_M_LONG + i]
+                                     : tail[(long long)ch * PACX_M_LONG + i];
+        s = prev + blocks[(h * n_ch + ch) * PACX_N_LONG + i];
+        if (h == 0)
+            tail[(long long)ch * PACX_M_LONG + i] = blocks[((n_blocks - 1) * n_ch + ch) * PACX_N_LONG + PACX_M_LONG + i];
+    } else {
+        s = (h >= 1) ? blocks[((h - 1) * n_ch + ch) * PACX_N_LONG + PACX_M_LONG + i]
+                     : tail[(long long)ch * PACX_M_LONG + i];                 /* EOF flush */
+    }
+    const bool neg = signbit(s);
+    const long long q = pacx_quant_mag(fabs(s), 16);
+    pcm[idx] = (int16_t)(neg ? -q : q);
+}
+
 /* ------------------------------------------------------------- launchers */
+void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
+                          hipStream_t st)
+{
+    const long long n_hops = n_blocks + (flush ? 1 : 0);
+    if (n_hops <= 0)
+        return;                                                   /* nothing to write, the tail stays */
+    const long long total = n_hops * PACX_M_LONG * n_ch;
+    hipLaunchKernelGGL(k_ola_tail_pcm, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, n_blocks, n_ch, blocks,
+                       tail, flush, pcm);
+}
+
 void pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payload, int payload_stride,
                         const long long *offsets, const int32_t *n_bytes, uint8_t *flags_out, int32_t *overall,
                         int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/pacx.h"
+#include "body_index.h"
 #include "pacx_dev.h"
 #include "pacx_vq_tables.h"
 #include "pacx_tables_gen.h"
@@ -87,6 +88,12 @@ void pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const
                         const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
                         const int32_t *mantissa, const double *lines_in, double *blocks, int16_t *pcm,
                         hipStream_t st);
+void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
+                          hipStream_t st);
+/* k_index.hip */
+size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws);
+void pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
+                       long long max_records, long long *offsets, int32_t *n_bytes, long long *result, hipStream_t st);
 /* k_vq_dec.hip */
 size_t pacx_vqdec_view_size(void);
 void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
@@ -191,6 +198,8 @@ struct pacx_handle {
     long long ws_vq_cf;               /* capacity of the short-frame buffers    */
     unsigned *ws_unit_words;          /* [ws_vq_cf*8][548]                      */
     int32_t *ws_unit_bits;            /* [ws_vq_cf*8][2]                        */
+    size_t ws_index_bytes;            /* capacity of ws_index                   */
+    char *ws_index;                   /* pacx_index_body's tables (PacxIndexWs)  */
     std::string err;
 };
 
@@ -398,6 +407,8 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->ws_vq_cf = 0;
     h->ws_unit_words = nullptr;
     h->ws_unit_bits = nullptr;
+    h->ws_index_bytes = 0;
+    h->ws_index = nullptr;
     h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
     h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
     h->ws_lists = nullptr;
@@ -733,6 +744,8 @@ extern "C" void pacx_destroy(pacx_handle *h)
         (void)hipFree(h->ws_dec_sbr);
     if (h->ws_dec_status)
         (void)hipFree(h->ws_dec_status);
+    if (h->ws_index)
+        (void)hipFree(h->ws_index);
     for (void *p : h->owned)
         (void)hipFree(p);
     delete h;
@@ -1664,4 +1677,44 @@ extern "C" int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_chan
         pacx_launch_decode(h->T, n_blocks, n_channels, cf_flags, overall_scale, nullptr, nullptr, nullptr, ln,
                            work, pcm, st);
     return post_launch(h, "pacx_decode_vq_batch");
+}
+
+/* ---- decoding a stream in chunks: where the records start, and the half-block across a chunk boundary ---- */
+extern "C" int pacx_index_body(pacx_handle *h, const uint8_t *body, int64_t n_body, int n_channels, int final,
+                               int64_t max_records, int64_t *offsets, int32_t *n_bytes, int64_t *result, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (n_body < 0 || n_channels < 1 || max_records < 0 || !result || (n_body > 0 && !body) ||
+        (max_records > 0 && (!offsets || !n_bytes)))
+        return fail(h, PACX_E_ARG, "pacx_index_body: bad argument");
+    if (n_body / PACX_IX_SEG + 1 > 0x7FFFFFFFll)
+        return fail(h, PACX_E_UNSUPPORTED, "pacx_index_body: body too long for one call");
+    HIP_TRY(h, hipSetDevice(h->device));
+    PacxIndexWs ws;
+    const size_t need = pacx_index_ws_bytes(n_body, &ws);
+    if (need > h->ws_index_bytes) {
+        HIP_TRY(h, hipDeviceSynchronize());
+        if (h->ws_index)
+            (void)hipFree(h->ws_index);
+        h->ws_index = nullptr;
+        h->ws_index_bytes = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->ws_index, need));
+        h->ws_index_bytes = need;
+    }
+    pacx_launch_index(ws, h->ws_index, body, n_body, n_channels, final != 0, max_records, (long long *)offsets, n_bytes,
+                      (long long *)result, (hipStream_t)stream);
+    return post_launch(h, "pacx_index_body");
+}
+
+extern "C" int pacx_overlap_add_pcm(pacx_handle *h, int64_t n_blocks, int n_channels, const double *blocks, double *tail,
+                                    int flush, int16_t *pcm, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (n_blocks < 0 || n_channels < 1 || !tail || (n_blocks > 0 && !blocks) || ((n_blocks > 0 || flush) && !pcm))
+        return fail(h, PACX_E_ARG, "pacx_overlap_add_pcm: bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_ola_tail(n_blocks, n_channels, blocks, tail, flush != 0, pcm, (hipStream_t)stream);
+    return post_launch(h, "pacx_overlap_add_pcm");
 }

@@ -87,4 +87,17 @@ struct MaskTail {
     int payload_stride;
 };
 
+/* workspace of pacx_index_body (k_index.hip, body_index.h): byte offsets into one allocation of the handle,
+   sized by the call (pacx_index_ws_bytes) */
+struct PacxIndexWs {
+    long long n_seg, n_groups;
+    size_t tab;       /* uint32 [n_seg][PACX_IX_ENTRIES]     segment maps                     */
+    size_t gtab;      /* uint64 [n_groups][PACX_IX_ENTRIES]  composed groups                  */
+    size_t gentry;    /* int32 [n_groups]   entry offset of each group                        */
+    size_t gbase;     /* int64 [n_groups]   first record number of each group                 */
+    size_t entry;     /* int32 [n_seg]      entry offset of each segment, -1 off the chain    */
+    size_t base;      /* int64 [n_seg]      first record number of each segment               */
+    size_t fin;       /* int64 [3]          the call's result as the stitch knows it          */
+};
+
 #endif

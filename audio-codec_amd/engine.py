@@ -415,6 +415,35 @@ class Encoder:
                    _ptr(out["status"]), self._stream())
         return out
 
+    def index_body(self, body, n_channels, final=True, max_records=None):
+        """Record index of a .pac body that sits on the device (uint8 tensor starting at a length prefix), built
+        there (pacx_index_body): offsets int64 / n_bytes int32 [max_records] as unpack / decode_vq take them and
+        result int64 [3] = records returned (a multiple of n_channels), bytes consumed, position of the prefix at
+        which the chain broke or -1.  max_records None: as many as the body can hold."""
+        n_body = int(body.numel())
+        if max_records is None:
+            max_records = n_body // 5                  # a record is five bytes at least
+        max_records = int(max_records)
+        offsets = self._empty((max_records,), torch.int64)
+        n_bytes = self._empty((max_records,), torch.int32)
+        result = self._empty((3,), torch.int64)
+        self._call("pacx_index_body", _ptr(body), ctypes.c_int64(n_body), int(n_channels), int(bool(final)),
+                   ctypes.c_int64(max_records), _ptr(offsets), _ptr(n_bytes), _ptr(result), self._stream())
+        return offsets, n_bytes, result
+
+    def overlap_add(self, blocks, tail, flush):
+        """Overlap-and-add + PCM of one batch of a longer stream (pacx_overlap_add_pcm).  blocks: float64
+        [n_blocks*nCh, 2048] in stream order; tail: float64 [nCh, 1024], the half-block carried across the batch
+        boundary, updated in place.  -> int16 [(n_blocks + flush)*1024, nCh]."""
+        n_ch = int(tail.shape[0])
+        assert tail.is_contiguous() and tail.dtype == torch.float64 and tail.shape[1] == N_LONG
+        blocks = blocks.contiguous()
+        n_blocks = blocks.shape[0] // n_ch
+        pcm = self._empty(((n_blocks + int(bool(flush))) * N_LONG, n_ch), torch.int16)
+        self._call("pacx_overlap_add_pcm", ctypes.c_int64(n_blocks), n_ch, _ptr(blocks), _ptr(tail), int(bool(flush)),
+                   _ptr(pcm), self._stream())
+        return pcm
+
     # ------------------------------------------- function-level entry points
     def window(self, kind, x):
         """window * x for rows of x ([n, 2048] or [n, 256] float64 on the GPU)."""

@@ -22,6 +22,7 @@ BYTESIZE = 8
 _ST_VQ_UNDEFINED = 8          # include/pacx.h
 _ST_MALFORMED = 32
 _PARTIAL = "Only read a partial block of coded PACFile data"     # coder/pacfile.py:203-205
+_VQ_UNDEFINED = "stream holds a gain-shape block the reference's decoder fails on (PACX_ST_VQ_UNDEFINED)"
 
 
 def omitted_bands(sfBands, factor=2):
@@ -453,10 +454,102 @@ def record_chain(data, pos, max_record):
     return offs, sizes
 
 
-def decode_stream(data):
+def _decode_blockwise(f):
+    """the reference's decode loop (coder/pacfile.py:745-757) block by block through the PACFile mirror (function
+    level: nMDCTLines other than 1024): yields int16 [nMDCTLines, nCh] per hop"""
+    from .pcmfile import fraction_to_codes
+    cp = f.ReadFileHeader()
+    while True:
+        block = f.ReadDataBlock(cp)
+        if not block:
+            break
+        yield np.stack([fraction_to_codes(x) for x in block], axis=1).astype(np.int16)
+
+
+def _reader(source):
+    """read(n) over a bytes-like object (slices of it, no copy) or a binary file object"""
+    if hasattr(source, "read"):
+        return source.read
+    view = memoryview(source).cast("B")
+    at = [0]
+
+    def read(n):
+        piece = view[at[0]:at[0] + n]
+        at[0] += len(piece)
+        return piece
+    return read
+
+
+_stream_decoder = [None, None]      # (key, streaming.HostStreamDecoder) of the last iter_decode
+
+
+def iter_decode(source, chunk_bytes=16 << 20, max_blocks=None, depth=2):
+    """A .pac (bytes-like, or a binary file object positioned at its start) -> int16 [hops*1024, nCh] arrays,
+    chunk by chunk: at most chunk_bytes of the body and max_blocks hops are on the device at a time
+    (streaming.HostStreamDecoder; the records are found there, pacx_index_body) and a file object is read no
+    more than one buffer ahead.  Their concatenation is decode_stream's array.  max_blocks None: what
+    chunk_bytes holds at 128 bytes per record (a chunk of shorter records ends early; nothing is lost)."""
+    for _, pcm, pinned in _iter_decode(source, chunk_bytes, max_blocks, depth):
+        yield pcm.copy() if pinned else pcm                           # out of the pinned buffer, which a later chunk reuses
+
+
+def _iter_decode(source, chunk_bytes, max_blocks, depth):
+    """iter_decode's chunks as (CodingParams, array, array is a view of a pinned buffer)"""
+    import io
+    read = _reader(source)
+    head = bytes(read(4 + 22 + 4))                                    # coder/pacfile.py:136-151
+    if len(head) == 30:
+        head += bytes(read(2 * int.from_bytes(head[-4:], "little")))
+    cp, _ = parse_header(head)
+    if cp.nMDCTLines != 1024 and not cp.useVQ and not cp.useSBR:
+        f = PACFile("<memory>")
+        f.fp = io.BytesIO(head + source.read() if hasattr(source, "read") else bytes(source))
+        for pcm in _decode_blockwise(f):
+            yield cp, pcm, False
+        return
+    from .streaming import HostStreamDecoder
+    enc = context.encoder_for_params(cp)
+    chunk_bytes = int(chunk_bytes)
+    if max_blocks is None:
+        max_blocks = max(1, chunk_bytes // (128 * cp.nChannels))
+    key = (cp.nChannels, chunk_bytes, int(max_blocks), int(depth))
+    hs = _stream_decoder[1]
+    if _stream_decoder[0] != key or hs.enc is not enc or hs.in_use:
+        # the last decoder's buffers are kept (pinning them costs as much as decoding a short file); a decoder that
+        # another iter_decode is in the middle of is left alone
+        if hs is None or not hs.in_use:
+            _stream_decoder[:] = [None, None]
+        hs = HostStreamDecoder(enc, cp.nChannels, chunk_bytes, max_blocks, depth=depth)
+        if _stream_decoder[1] is None:
+            _stream_decoder[:] = [key, hs]
+    hs.in_use = True
+    try:
+        for pcm in hs.decode(read):
+            yield cp, pcm, True
+    finally:
+        hs.in_use = False
+
+
+def decode_stream(data, chunk_bytes=None, max_blocks=None, depth=2):
     """Whole .pac (bytes; scalar, gain-shape or gain-shape + SBR) -> int16 [n, nCh], batched on the GPU: what
-    the reference's decode loop (coder/pacfile.py:745-757) writes as PCM."""
+    the reference's decode loop (coder/pacfile.py:745-757) writes as PCM.  chunk_bytes: in chunks of that many
+    bytes through iter_decode (bounded memory, record index built on the device); None: the whole file in one
+    batch, its length prefixes walked on the host."""
     import torch
+    if chunk_bytes is not None:
+        # np.concatenate(list(iter_decode(...))) with one copy per sample instead of two: every chunk goes from its
+        # pinned buffer straight to its place in the result, sized from the header and grown if the body holds more
+        out, n = None, 0
+        for cp, pcm, _ in _iter_decode(data, chunk_bytes, max_blocks, depth):
+            if out is None:
+                most = (len(data) // (5 * cp.nChannels) + 2) * cp.nMDCTLines      # a record is five bytes at least
+                guess = min(int(cp.numSamples) + 4 * cp.nMDCTLines, most)         # the header's word is only a hint
+                out = np.empty((max(guess, len(pcm)), cp.nChannels), np.int16)
+            if n + len(pcm) > len(out):
+                out = np.concatenate((out[:n], np.empty((max(len(out), len(pcm)), out.shape[1]), np.int16)))
+            out[n:n + len(pcm)] = pcm
+            n += len(pcm)
+        return out[:n] if out is not None else np.zeros((0, parse_header(data)[0].nChannels), np.int16)
     cp, pos = parse_header(data)
     if cp.nMDCTLines != 1024 and not cp.useVQ and not cp.useSBR:
         # function level: the reference's decode loop block by block through the PACFile mirror
@@ -485,8 +578,7 @@ def decode_stream(data):
         if st & _ST_MALFORMED:
             raise RuntimeError(_PARTIAL)
         if st & _ST_VQ_UNDEFINED:
-            raise RuntimeError("stream holds a gain-shape block the reference's decoder fails on "
-                               "(PACX_ST_VQ_UNDEFINED)")
+            raise RuntimeError(_VQ_UNDEFINED)
         return out["pcm"].cpu().numpy()
     codes = enc.unpack(body, sizes_t, offs_t)
     if len(sizes) and int(codes["status"].max().item()) & _ST_MALFORMED:

@@ -15,7 +15,8 @@ body (round 2 measured this pipeline in tools/pcie_probe.py: 24.8 M cf/s at 131 
     body = hs.result(k)              # uint8 view of the pinned body of that chunk (waits for its D2H only)
 
 or, for a stream already in memory, `for body in hs.encode(pcm): ...` / `pacfile.encode_stream(...,
-chunk_hops=N)`, whose bytes equal the one-batch path's (tests/test_gpu_round3.py).
+chunk_hops=N)`, whose bytes equal the one-batch path's (tests/test_gpu_round3.py).  HostStreamDecoder (below) is
+the same arrangement for the way back: .pac bytes in, PCM out, `pacfile.decode_stream(..., chunk_bytes=N)`.
 
 Chunks are consecutive pieces of ONE stream: the one-hop halo (frame f spans hops f-1, f) and, with
 block switching, the transient decisions of the two hops before a chunk are carried from chunk to chunk
@@ -201,4 +202,231 @@ class HostStreamEncoder:
         self.halo.zero_()
         self.carry.zero_()
         self.raises.zero_()
+        self.pending = [False] * self.depth
+
+
+class HostStreamDecoder:
+    """The decode side of the same pipeline: a .pac body in host memory (or coming out of a file) to int16
+    PCM in host memory, in chunks of at most `chunk_bytes` bytes and `max_blocks` hops, so the memory in use is
+    bounded by the chunk and not by the stream.
+
+        hs = HostStreamDecoder(enc, n_channels=2, chunk_bytes=16 << 20, max_blocks=32768)
+        for pcm in hs.decode(read):      # read(n) -> up to n more bytes of the body, b"" at its end
+            ...                          # int16 [hops*1024, nCh]: a view of pinned memory, valid until the next one
+
+    Per chunk: the bytes go up on the copy-in stream and pacx_index_body finds the records there (no walk of the
+    length prefixes on the host); the host takes the 24-byte result, which tells it how many records to decode and
+    how many bytes they took, queues unpack + decode + pacx_overlap_add_pcm on the kernel stream and the PCM's way
+    back on the copy-out stream, moves the bytes the chunk did not consume to the front of the next pinned buffer,
+    tops that up from the source and submits it -- while the chunk before is still decoding.  The host waits for an
+    index result and for PCM it is about to hand out, never for a decode it has just queued.  The half-block
+    across a chunk boundary is the decoder's one `tail` (on the device); the last chunk flushes it as the
+    reference does at EOF (coder/pacfile.py:245-249).
+
+    A malformed stream raises what pacfile.decode_stream raises, when the chunk that holds the fault is reached:
+    the PCM of the chunks before it has been handed out by then, as in the reference's hop-by-hop loop."""
+
+    def __init__(self, enc, n_channels, chunk_bytes, max_blocks, depth=2, timing=False):
+        self.enc, self.n_ch = enc, int(n_channels)
+        self.chunk_bytes, self.max_blocks, self.depth = int(chunk_bytes), int(max_blocks), int(depth)
+        need = self.n_ch * (enc.payload_stride + 4)
+        if self.chunk_bytes < need:
+            raise ValueError(f"chunk_bytes below {need} (one hop of {self.n_ch} longest records) cannot guarantee progress")
+        if self.max_blocks < 1 or self.depth < 2:
+            raise ValueError("max_blocks must be at least 1 and depth at least 2")
+        dev, C, n_ch = enc.device, self.chunk_bytes, self.n_ch
+        self.max_cf = n_cf = self.max_blocks * n_ch
+        i32, i64, u8, f64 = torch.int32, torch.int64, torch.uint8, torch.float64
+        self.s_in, self.s_k, self.s_out = (torch.cuda.Stream(device=dev) for _ in range(3))
+        rng = range(self.depth)
+        self.host_in = [torch.empty(C, dtype=u8).pin_memory() for _ in rng]
+        self.dev_in = [torch.zeros(C + 8, dtype=u8, device=dev) for _ in rng]        # 8 bytes of slack for the parsers
+        self.offsets = [torch.empty(n_cf, dtype=i64, device=dev) for _ in rng]
+        self.sizes = [torch.empty(n_cf, dtype=i32, device=dev) for _ in rng]
+        self.index = [torch.zeros(3, dtype=i64, device=dev) for _ in rng]
+        self.host_index = [torch.zeros(3, dtype=i64).pin_memory() for _ in rng]
+        self.pcm = [torch.empty(((self.max_blocks + 1) * HOP, n_ch), dtype=torch.int16, device=dev) for _ in rng]
+        self.host_pcm = [torch.empty(((self.max_blocks + 1) * HOP, n_ch), dtype=torch.int16).pin_memory() for _ in rng]
+        self.status = [torch.zeros(1, dtype=i32, device=dev) for _ in rng]
+        self.host_status = [torch.zeros(1, dtype=i32).pin_memory() for _ in rng]
+        self.ev_in = [torch.cuda.Event() for _ in rng]
+        self.ev_k = [torch.cuda.Event() for _ in rng]
+        self.ev_out = [torch.cuda.Event() for _ in rng]
+        # what only the kernel stream touches exists once: the chunks' decodes run one after the other
+        self.blocks = torch.empty((n_cf, 2 * HOP), dtype=f64, device=dev)
+        self.codes = {"flags": torch.empty(n_cf, dtype=u8, device=dev),
+                      "overall": torch.empty((n_cf, _lib.SUB), dtype=i32, device=dev),
+                      "bit_alloc": torch.zeros((n_cf, enc.band_stride), dtype=i32, device=dev),
+                      "status": torch.zeros(n_cf, dtype=i32, device=dev)}
+        if not enc.use_vq:
+            self.codes["scale_factor"] = torch.zeros((n_cf, enc.band_stride), dtype=i32, device=dev)
+            self.codes["mantissa"] = torch.empty((n_cf, HOP), dtype=i32, device=dev)
+            if enc.use_sbr:
+                self.codes["status_sbr"] = torch.zeros(n_cf, dtype=i32, device=dev)
+        self.status_bits = torch.zeros(n_cf, dtype=i32, device=dev)
+        self.tail = torch.zeros((n_ch, HOP), dtype=f64, device=dev)               # the half-block before the next chunk
+        self.n_bytes_of, self.final_of, self.hops_of = [0] * self.depth, [False] * self.depth, [0] * self.depth
+        self.pending = [False] * self.depth
+        self.timing = [] if timing else None       # per chunk: (records, index events, decode events)
+        self.in_use = False                        # a decode() of this object is under way (pacfile.iter_decode keeps one)
+
+    # ------------------------------------------------------------------ the three queues
+    def input(self, k):
+        """pinned staging buffer of slot k: uint8 [chunk_bytes] as a NumPy view"""
+        return self.host_in[k].numpy()
+
+    def submit_index(self, k, n_bytes, final):
+        """queue the first n_bytes of slot k: H2D, pacx_index_body and its result's way back, all on the copy-in
+        stream (beside the decode of the chunk before).  final: the source has nothing more."""
+        enc, n = self.enc, int(n_bytes)
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if self.timing is not None else None
+        with torch.cuda.stream(self.s_in):
+            self.s_in.wait_event(self.ev_k[k])                       # the decode that last read dev_in[k] and its index is done
+            self.dev_in[k][:n].copy_(self.host_in[k][:n], non_blocking=True)
+            self.dev_in[k][n:n + 8].zero_()
+            if ev:
+                ev[0].record(self.s_in)
+            enc._call("pacx_index_body", _ptr(self.dev_in[k]), ctypes.c_int64(n), self.n_ch, int(bool(final)),
+                      ctypes.c_int64(self.max_cf), _ptr(self.offsets[k]), _ptr(self.sizes[k]), _ptr(self.index[k]),
+                      enc._stream())
+            if ev:
+                ev[1].record(self.s_in)
+            self.host_index[k].copy_(self.index[k], non_blocking=True)
+            self.ev_in[k].record(self.s_in)
+        self.n_bytes_of[k], self.final_of[k] = n, bool(final)
+        self._index_events = ev
+
+    def index_result(self, k):
+        """(records found, bytes they took, position of the prefix at which the chain broke or -1) of slot k: waits
+        for that chunk's copy-in and index only"""
+        self.ev_in[k].synchronize()
+        n_rec, consumed, error_at = (int(v) for v in self.host_index[k].tolist())
+        if not (0 <= n_rec <= self.max_cf and n_rec % self.n_ch == 0 and 0 <= consumed <= self.n_bytes_of[k]):
+            raise RuntimeError(f"pacx_index_body returned {n_rec} records, {consumed} bytes")
+        return n_rec, consumed, error_at
+
+    def submit_decode(self, k, n_records, flush):
+        """queue unpack + decode + overlap-and-add of the records index_result(k) reported on the kernel stream and
+        the PCM's copy to pinned memory on the copy-out stream.  Returns without waiting for any of it."""
+        enc, c, n = self.enc, self.codes, int(n_records)
+        n_blocks = n // self.n_ch
+        hops = n_blocks + int(bool(flush))
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if self.timing is not None else None
+        with torch.cuda.stream(self.s_k):
+            st = enc._stream()
+            self.s_k.wait_event(self.ev_in[k])
+            self.s_k.wait_event(self.ev_out[k])                      # the PCM that last sat in pcm[k] has left
+            if ev:
+                ev[0].record(self.s_k)
+            if n:
+                body, offs, sizes = _ptr(self.dev_in[k]), _ptr(self.offsets[k]), _ptr(self.sizes[k])
+                c["bit_alloc"][:n].zero_()                           # the one-batch path hands the kernels zeroed band arrays
+                if enc.use_vq:
+                    enc._call("pacx_decode_vq_batch", ctypes.c_int64(n_blocks), self.n_ch, body, 0, offs, sizes,
+                              _ptr(c["flags"]), _ptr(c["overall"]), _ptr(c["bit_alloc"]), None, _ptr(self.blocks), None,
+                              _ptr(c["status"]), st)
+                else:
+                    c["scale_factor"][:n].zero_()
+                    enc._call("pacx_unpack_batch", ctypes.c_int64(n), body, 0, offs, sizes, _ptr(c["flags"]),
+                              _ptr(c["overall"]), _ptr(c["scale_factor"]), _ptr(c["bit_alloc"]), _ptr(c["mantissa"]),
+                              _ptr(c["status"]), st)
+                    if enc.use_sbr:                                  # PACFile.Decode's routing (pacfile._decode_scalar)
+                        enc._call("pacx_decode_sbr_batch", ctypes.c_int64(n_blocks), self.n_ch, _ptr(c["flags"]),
+                                  _ptr(c["overall"]), _ptr(c["scale_factor"]), _ptr(c["bit_alloc"]), _ptr(c["mantissa"]),
+                                  0, None, _ptr(self.blocks), None, _ptr(c["status_sbr"]), st)
+                        torch.bitwise_or(c["status"][:n], c["status_sbr"][:n], out=c["status"][:n])
+                    else:
+                        enc._call("pacx_decode_batch", ctypes.c_int64(n_blocks), self.n_ch, _ptr(c["flags"]),
+                                  _ptr(c["overall"]), _ptr(c["scale_factor"]), _ptr(c["bit_alloc"]), _ptr(c["mantissa"]),
+                                  _ptr(self.blocks), None, st)
+                torch.bitwise_and(c["status"][:n], _lib.ST_MALFORMED | _lib.ST_VQ_UNDEFINED, out=self.status_bits[:n])
+                torch.amax(self.status_bits[:n], dim=0, keepdim=True, out=self.status[k])
+            else:
+                self.status[k].zero_()
+            if ev:
+                ev[1].record(self.s_k)
+            enc._call("pacx_overlap_add_pcm", ctypes.c_int64(n_blocks), self.n_ch, _ptr(self.blocks), _ptr(self.tail),
+                      int(bool(flush)), _ptr(self.pcm[k]), st)
+            self.ev_k[k].record(self.s_k)
+        with torch.cuda.stream(self.s_out):
+            self.s_out.wait_event(self.ev_k[k])
+            self.host_pcm[k][:hops * HOP].copy_(self.pcm[k][:hops * HOP], non_blocking=True)
+            self.host_status[k].copy_(self.status[k], non_blocking=True)
+            self.ev_out[k].record(self.s_out)
+        self.hops_of[k] = hops
+        self.pending[k] = True
+        if self.timing is not None:
+            self.timing.append((n, self._index_events, ev))
+
+    def result(self, k):
+        """int16 [hops*1024, nCh] of chunk k: a NumPy view of pinned memory, valid until slot k decodes again.  Waits
+        for that chunk's D2H copy only.  Raises what pacfile.decode_stream raises for a record the parsers reject."""
+        if not self.pending[k]:
+            raise RuntimeError(f"nothing was submitted in slot {k}")
+        self.ev_out[k].synchronize()
+        self.pending[k] = False
+        st = int(self.host_status[k].item())
+        if st:
+            from . import pacfile
+            if st & _lib.ST_MALFORMED:
+                raise RuntimeError(pacfile._PARTIAL)
+            if self.enc.use_vq:
+                raise RuntimeError(pacfile._VQ_UNDEFINED)
+            raise IndexError(pacfile._SBR_INDEX)
+        return self.host_pcm[k][:self.hops_of[k] * HOP].numpy()
+
+    # ------------------------------------------------------------------ a whole stream
+    def _fill(self, k, have, read):
+        """top slot k's pinned buffer up from the source -> (bytes in it, source exhausted)"""
+        buf = self.input(k)
+        while have < self.chunk_bytes:
+            piece = read(self.chunk_bytes - have)
+            if not len(piece):
+                return have, True
+            buf[have:have + len(piece)] = np.frombuffer(piece, dtype=np.uint8)
+            have += len(piece)
+        return have, False
+
+    def decode(self, read):
+        """read(n) -> up to n further bytes of the body (bytes-like), empty at its end.  Yields the chunks' PCM in
+        order; the source is read no more than one buffer ahead of the chunk being decoded."""
+        from . import pacfile
+        self.reset()
+        k, order = 0, []
+        have, exhausted = self._fill(k, 0, read)
+        self.submit_index(k, have, exhausted)
+        while True:
+            n_rec, consumed, error_at = self.index_result(k)
+            n_buf = self.n_bytes_of[k]
+            if error_at >= 0 or (n_rec == 0 and consumed < n_buf):
+                # a broken chain, or less than one whole hop where one must be (a full buffer, or the stream's end)
+                for j in order:
+                    yield self.result(j)
+                raise RuntimeError(pacfile._PARTIAL)
+            if self.pending[k]:
+                yield self.result(order.pop(0))                      # the chunk that last used this slot's PCM buffers
+            last = self.final_of[k] and consumed == n_buf
+            self.submit_decode(k, n_rec, last)
+            order.append(k)
+            if last:
+                break
+            k2 = (k + 1) % self.depth
+            rem = n_buf - consumed
+            self.input(k2)[:rem] = self.input(k)[consumed:n_buf]     # what this chunk did not take opens the next one
+            if not exhausted:
+                rem, exhausted = self._fill(k2, rem, read)
+            self.submit_index(k2, rem, exhausted)
+            k = k2
+        for j in order:
+            yield self.result(j)
+
+    def timings(self):
+        """[(records, index ms, decode-kernel ms)] per chunk since the decoder was made (timing=True): device-event times"""
+        torch.cuda.synchronize(self.enc.device)
+        return [(n, a[0].elapsed_time(a[1]), b[0].elapsed_time(b[1])) for n, a, b in self.timing]
+
+    def reset(self):
+        """start a new stream"""
+        torch.cuda.synchronize(self.enc.device)
+        self.tail.zero_()
         self.pending = [False] * self.depth

@@ -570,6 +570,46 @@ int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_channels, const
                          uint8_t *cf_flags, int32_t *overall_scale, int32_t *bit_alloc, double *lines,
                          double *blocks, int16_t *pcm, uint32_t *status, void *stream);
 
+/* ---- decoding a stream in chunks ------------------------------------------ */
+
+/*
+ * The record index of a .pac body, built on the device: where the payloads start and how long they
+ * are, in the form pacx_unpack_batch / pacx_decode_vq_batch take (offsets relative to `body`).
+ * body (device, n_body bytes) starts at a length prefix ('<L nBytes').  A record is valid when
+ * 1 <= nBytes <= pacx_payload_stride(h) and it ends at or before n_body.  Outputs (device):
+ *   offsets int64 [max_records], n_bytes int32 [max_records]: the records on the chain from byte 0,
+ *           in order;
+ *   result  int64 [3]: [0] records returned, always a multiple of n_channels; [1] bytes consumed
+ *           (the position of the first prefix not returned); [2] the position of the prefix at
+ *           which the chain broke, or -1.
+ * The chain stops without error at max_records and, when final == 0, at a record (or a prefix)
+ * that runs past n_body: the piece a caller carries into its next chunk.  With final != 0 such a
+ * tail is an error, as is a length outside 1..pacx_payload_stride(h) anywhere ON THE CHAIN (lengths
+ * that appear inside payload bytes mean nothing).  On an error the records before it are still
+ * returned.  Nothing at or past body + n_body is read.  Segments of 8192 bytes are mapped in
+ * parallel and stitched (csrc/body_index.h); the tables live in the handle (about 1.1 bytes per
+ * body byte, grow-only), so calls on one handle must not overlap each other.
+ */
+int pacx_index_body(pacx_handle *h, const uint8_t *body, int64_t n_body, int n_channels, int final,
+                    int64_t max_records, int64_t *offsets, int32_t *n_bytes, int64_t *result,
+                    void *stream);
+
+/*
+ * Overlap-and-add + 16-bit PCM mapping of one batch of a longer stream (the last stage of
+ * pacx_decode_batch with the half-block across the batch boundary in the caller's hands).
+ *   blocks: float64 [n_blocks*n_channels][2*n_lines_long], the `blocks` output of the decoders;
+ *   tail:   float64 [n_channels][n_lines_long], in and out: the second half of the block before this
+ *           batch (zeros at the start of a stream); on return the second half of the last block
+ *           (unchanged when n_blocks == 0);
+ *   pcm:    int16 [(n_blocks + (flush != 0)) * n_lines_long][n_channels]: hop 0 = tail + first half
+ *           of block 0, hop h = second half of block h-1 + first half of block h, and with flush
+ *           the half-block the reference writes at EOF (coder/pacfile.py:272-295) as one more hop.
+ * A zeroed tail with flush = 1 gives pacx_decode_batch's pcm bit for bit.  No state is kept in the
+ * handle.
+ */
+int pacx_overlap_add_pcm(pacx_handle *h, int64_t n_blocks, int n_channels, const double *blocks,
+                         double *tail, int flush, int16_t *pcm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
