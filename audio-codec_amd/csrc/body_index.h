@@ -32,7 +32,7 @@
 #endif
 
 #define PACX_IX_SEG 8192                            /* bytes of a segment: a power of two >= 4096 */
-#define PACX_IX_MAX_RECORD 2192                     /* = PACX_PAYLOAD_STRIDE: longest payload      */
+#define PACX_IX_MAX_RECORD 2192                     /* = PACX_PAYLOAD_STRIDE (k_index.hip asserts it): longest payload */
 #define PACX_IX_ENTRIES (PACX_IX_MAX_RECORD + 4)    /* offsets at which a segment can be entered   */
 #define PACX_IX_MAX_CHAIN (PACX_IX_SEG / 5 + 1)     /* records that start in one segment, at most  */
 #define PACX_IX_ROUNDS 12                           /* 2^(ROUNDS-1) >= MAX_CHAIN + 1               */

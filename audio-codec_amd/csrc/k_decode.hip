@@ -19,7 +19,7 @@
  * same "pre-twiddle, N/4-point complex FFT, post-twiddle" pipeline the MDCT
  * kernels apply to the folded input (tools/proto_wave_fft.py:imdct_via_dct4).
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"
 
 #define UNPACK_WORDS 552
@@ -420,7 +420,7 @@ __global__ void k_ola_tail_pcm(long long n_blocks, int n_ch, const double *__res
 }
 
 /* ------------------------------------------------------------- launchers */
-void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
+void pacx_k::pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
                           hipStream_t st)
 {
     const long long n_hops = n_blocks + (flush ? 1 : 0);
@@ -431,7 +431,7 @@ void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, do
                        tail, flush, pcm);
 }
 
-void pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payload, int payload_stride,
+void pacx_k::pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payload, int payload_stride,
                         const long long *offsets, const int32_t *n_bytes, uint8_t *flags_out, int32_t *overall,
                         int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,
                         hipStream_t st)
@@ -441,7 +441,7 @@ void pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payl
                            offsets, n_bytes, flags_out, overall, scale_factor, bit_alloc, mantissa, status);
 }
 
-void pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const uint8_t *cf_flags,
+void pacx_k::pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const uint8_t *cf_flags,
                         const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
                         const int32_t *mantissa, const double *lines_in, double *blocks, int16_t *pcm,
                         hipStream_t st)
@@ -460,7 +460,7 @@ void pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const
     }
 }
 
-void pacx_launch_sbr_scalar_lines(const PacxTables &T, long long n_cf, const uint8_t *cf_flags,
+void pacx_k::pacx_launch_sbr_scalar_lines(const PacxTables &T, long long n_cf, const uint8_t *cf_flags,
                                   const int32_t *scale_factor, const int32_t *bit_alloc, const int32_t *mantissa,
                                   double *lines, uint8_t *sbr_flag, int routing, hipStream_t st)
 {
@@ -470,7 +470,7 @@ void pacx_launch_sbr_scalar_lines(const PacxTables &T, long long n_cf, const uin
 }
 
 /* mdct.IMDCT for rows of 1024 lines (short_blocks: rows of 8 x 128 lines) -> 2048 samples each, unwindowed */
-void pacx_launch_imdct_plain(const PacxTables &T, long long n_rows, int short_blocks, const double *lines,
+void pacx_k::pacx_launch_imdct_plain(const PacxTables &T, long long n_rows, int short_blocks, const double *lines,
                              double *blocks, hipStream_t st)
 {
     if (n_rows <= 0)

@@ -8,7 +8,10 @@
  * records, prefixes everywhere) costs the same time as any other, never a hang.
  */
 #include "body_index.h"
-#include "pacx_dev.h"
+#include "pacx_launch.h"
+
+/* body_index.h is also compiled on its own (the CPU model of the index), so it names the bound itself */
+static_assert(PACX_IX_MAX_RECORD == PACX_PAYLOAD_STRIDE, "a record is at most one payload slot");
 
 #define IX_THREADS 256
 
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(64) void k_index_emit(const uint8_t *__restrict__ b
         pacx_ix_emit_segment(body, n_body, s, entry[s], base[s], fin[0], fin[1] < 0, offsets, n_bytes, result + 1);
 }
 
-size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws)
+size_t pacx_k::pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws)
 {
     const long long n_seg = pacx_ix_segments(n_body), n_groups = pacx_ix_groups(n_seg);
     size_t at = 0;
@@ -111,7 +114,7 @@ size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws)
     return at;
 }
 
-void pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
+void pacx_k::pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
                        long long max_records, long long *offsets, int32_t *n_bytes, long long *result, hipStream_t st)
 {
     uint32_t *tab = (uint32_t *)(mem + ws.tab);

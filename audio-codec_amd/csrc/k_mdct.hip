@@ -18,7 +18,7 @@
  * lane of PCM -> LDS (4 KB), two LDS exchanges of 8 KB inside the FFT, 1024
  * float64 lines out = 2 KB (new hop) + 8 KB algorithmic HBM bytes.
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"
 #include "pcm_stage.h"
 
@@ -245,7 +245,7 @@ static void launch_mdct(const PacxTables &T, const PacxPcmView &in, const uint8_
 
 /* mixed = 1: long kernel skips CUR frames, short kernel takes only CUR frames
  * (scale_out is then [n_cf][8]); otherwise short_blocks selects one of them. */
-void pacx_launch_mdct(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
+void pacx_k::pacx_launch_mdct(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
                       const uint8_t *flags, long long n_cf, int short_blocks, int mixed, int prewin,
                       double *lines, int32_t *scale_out, int scale_stride, uint32_t *status,
                       hipStream_t st)

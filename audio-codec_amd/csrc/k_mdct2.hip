@@ -19,7 +19,7 @@
  * HBM traffic per channel-frame: 2 KB of new PCM (the other half of the window
  * was read by the previous frame and is an L2 hit) + 8 KB of lines = 10 240 B.
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"
 
 /* 8 waves per workgroup (8 KB tile each + 24 KB of tables, + 48 KB of transition windows
@@ -232,10 +232,7 @@ __global__ __launch_bounds__(64 * MDCT2_WAVES, 2) void k_mdct_long_v2(
     }
 }
 
-void pacx_launch_mdct_x2(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
-                         int32_t *scale_out, int scale_stride, uint32_t *status_init, int n_cu, hipStream_t st);
-
-void pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8_t *flags, long long n_cf,
+void pacx_k::pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8_t *flags, long long n_cf,
                          int skip_cur, double *lines, int32_t *scale_out, int scale_stride,
                          uint32_t *status_init, int n_cu, const int32_t *cf_list, const int32_t *cf_count,
                          hipStream_t st)

@@ -7,7 +7,7 @@
  * twiddle, per-lane FFT twiddles) serves both frames.  LDS: one 8 KB FFT tile and
  * two 4 KB PCM landing buffers per wave + the 24 KB of tables.
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"
 
 /*
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mdct_long_x2p(PacxTables T
 
 #pragma clang diagnostic pop
 
-void pacx_launch_mdct_x2(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
+void pacx_k::pacx_launch_mdct_x2(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
                          int32_t *scale_out, int scale_stride, uint32_t *status_init, int n_cu, hipStream_t st)
 {
     long long blocks = (n_cf + 2 * 8 - 1) / (2 * 8);

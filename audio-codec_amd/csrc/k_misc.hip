@@ -8,7 +8,7 @@
  * implementation behind the same signature; the encode hot path uses the fused
  * kernels in k_mdct/k_psy/k_quant instead.
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 
 __global__ void k_window(const double *__restrict__ win, long long n_rows, int len,
                          const double *__restrict__ x, double *__restrict__ y)
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(LISTS_SMALL_THREADS) void k_frame_lists_small(const
     }
 }
 
-void pacx_launch_frame_lists(const uint8_t *flags, long long n_frames, int n_ch, int32_t *list_long,
+void pacx_k::pacx_launch_frame_lists(const uint8_t *flags, long long n_frames, int n_ch, int32_t *list_long,
                              int32_t *list_short, int32_t *counts, hipStream_t st)
 {
     if (n_frames <= 0)
@@ -436,7 +436,7 @@ void pacx_launch_frame_lists(const uint8_t *flags, long long n_frames, int n_ch,
                        n_ch, list_long, list_short, counts);
 }
 
-void pacx_launch_transient_f64(long long n_blocks, int n_ch, int n, const double *blocks, double thresh, uint8_t *out,
+void pacx_k::pacx_launch_transient_f64(long long n_blocks, int n_ch, int n, const double *blocks, double thresh, uint8_t *out,
                                hipStream_t st)
 {
     if (n_blocks > 0)
@@ -444,7 +444,7 @@ void pacx_launch_transient_f64(long long n_blocks, int n_ch, int n, const double
                            out);
 }
 
-void pacx_launch_transient(const PacxPcmView &in, long long n_hops, int hop, uint8_t *transient,
+void pacx_k::pacx_launch_transient(const PacxPcmView &in, long long n_hops, int hop, uint8_t *transient,
                            uint8_t *flags, hipStream_t st)
 {
     if (n_hops > 0)
@@ -454,7 +454,7 @@ void pacx_launch_transient(const PacxPcmView &in, long long n_hops, int hop, uin
                            transient, n_hops, flags);
 }
 
-void pacx_launch_window(const double *win, long long n_rows, int len, const double *x, double *y,
+void pacx_k::pacx_launch_window(const double *win, long long n_rows, int len, const double *x, double *y,
                         hipStream_t st)
 {
     const long long n = n_rows * len;
@@ -462,7 +462,7 @@ void pacx_launch_window(const double *win, long long n_rows, int len, const doub
         hipLaunchKernelGGL(k_window, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, win, n_rows, len, x, y);
 }
 
-void pacx_launch_quant_elem(int op, long long n, const double *x, int scale, int a, int b, int64_t *out,
+void pacx_k::pacx_launch_quant_elem(int op, long long n, const double *x, int scale, int a, int b, int64_t *out,
                             hipStream_t st)
 {
     if (n > 0)
@@ -470,7 +470,7 @@ void pacx_launch_quant_elem(int op, long long n, const double *x, int scale, int
                            a, b, out);
 }
 
-void pacx_launch_dequant_elem(int op, long long n, const int64_t *codes, int scale, int a, int b, double *out,
+void pacx_k::pacx_launch_dequant_elem(int op, long long n, const int64_t *codes, int scale, int a, int b, double *out,
                               hipStream_t st)
 {
     if (n > 0)
@@ -478,7 +478,7 @@ void pacx_launch_dequant_elem(int op, long long n, const int64_t *codes, int sca
                            a, b, out);
 }
 
-void pacx_launch_mdct_direct(long long n_rows, int a, int b, int inverse, const double *x, double *y, hipStream_t st)
+void pacx_k::pacx_launch_mdct_direct(long long n_rows, int a, int b, int inverse, const double *x, double *y, hipStream_t st)
 {
     const long long n = n_rows * (inverse ? (a + b) : (a + b) / 2);
     if (n > 0)
@@ -486,7 +486,7 @@ void pacx_launch_mdct_direct(long long n_rows, int a, int b, int inverse, const 
                            x, y);
 }
 
-void pacx_launch_bitalloc_generic(long long n, int nb, const int32_t *n_lines, const double *budget,
+void pacx_k::pacx_launch_bitalloc_generic(long long n, int nb, const int32_t *n_lines, const double *budget,
                                   int max_mant, const double *smr, int32_t *bits, hipStream_t st)
 {
     if (n > 0)

@@ -24,7 +24,7 @@
  *   Z[k] = E[k] + W_{N/2}^k O[k], Z[k+Q] = E[k] - W_{N/2}^k O[k];
  *   X[k] = (Z[k] + conj Z[N/2-k])/2 - (j/2) W_N^k (Z[k] - conj Z[N/2-k]).
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"
 #include "pcm_stage.h"
 #include "wave_np_sum.h"
@@ -1008,8 +1008,8 @@ __global__ __launch_bounds__(64 * mask_waves(M, TAIL), (M == PACX_M_LONG && !TAI
                 asm volatile("" : "+v"(tl));
                 /* the wave's 8 KB of per-line state now hold the tail's LDS (3.4 KB) */
                 char *base = (char *)buf;
-                unsigned *words = (unsigned *)base;                               /* 548 words       */
-                double *cp = (double *)(base + 2192);                             /* 2 x 32 doubles  */
+                unsigned *words = (unsigned *)base;                               /* PACX_PAYLOAD_WORDS */
+                double *cp = (double *)(base + PACX_PAYLOAD_STRIDE);              /* 2 x 32 doubles  */
                 unsigned long long *bmax = (unsigned long long *)(base + 2704);   /* 32              */
                 int *ba_s = (int *)(base + 2960), *sf_s = ba_s + PACX_MAX_BANDS;
                 int *offs = sf_s + PACX_MAX_BANDS, *lower_s = offs + PACX_MAX_BANDS + 1;
@@ -1043,7 +1043,7 @@ __global__ __launch_bounds__(64 * mask_waves(M, TAIL), (M == PACX_M_LONG && !TAI
                     const int k0 = 16 * tl;
                     int my_off = 0, a_mine = 0, end = 0;
                     if (tail.payload) {
-                        for (int i = tl; i < PACX_PACK_WORDS; i += 64)
+                        for (int i = tl; i < PACX_PAYLOAD_WORDS; i += 64)
                             words[i] = 0u;
                         wave_lds_fence();
                         a_mine = (tl < nb) ? ba_s[tl] : 0;
@@ -1234,13 +1234,13 @@ __global__ __launch_bounds__(SMRG_THREADS) void k_smr_generic(long long n_blocks
     }
 }
 
-size_t pacx_smr_generic_lds(int n)
+size_t pacx_k::pacx_smr_generic_lds(int n)
 {
     const int half = n / 2, n_bins = half + 1, max_pk = half / 2 + 1;
     return (size_t)(n + n_bins + (n_bins & 1)) * 8 + (size_t)max_pk * sizeof(PacxPeak);
 }
 
-void pacx_launch_smr_generic(long long n_blocks, int n, int nb, const double *data, const double *lines,
+void pacx_k::pacx_launch_smr_generic(long long n_blocks, int n, int nb, const double *data, const double *lines,
                              const double *hann, const double *tw_cos, const double *tw_sin, double norm, double fstep,
                              const double *bark, const double *quiet, const int32_t *band_lower,
                              const int32_t *band_count, double *smr, double *thr_out, int32_t *n_peaks_out,
@@ -1275,7 +1275,7 @@ static void launch_side(const PacxTables &T, const PacxPcmView &in, const uint8_
         hipLaunchKernelGGL((k_side_short<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed, peaks, n_peaks, n_kept);
 }
 
-void pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
+void pacx_k::pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
                       const uint8_t *flags, long long n_cf, int short_blocks, int mixed,
                       PacxPeak *peaks, int32_t *n_peaks, int32_t *n_kept, double *sbr_mean,
                       int32_t *sbr_overall, hipStream_t st)
@@ -1293,7 +1293,7 @@ void pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int
                               sbr_overall, st);
 }
 
-void pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+void pacx_k::pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                       int short_blocks, int mixed, const PacxPeak *peaks, const int32_t *n_peaks,
                       const double *lines, double *smr, double *thr_out, int n_cu,
                       const int32_t *list_long, const int32_t *list_short, const int32_t *counts,

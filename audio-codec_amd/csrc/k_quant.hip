@@ -14,7 +14,7 @@
  * All arithmetic that decides an integer code goes through pacx_exact.h and is
  * compiled with -ffp-contract=off.
  */
-#include "pacx_dev.h"
+#include "pacx_launch.h"
 #include "wave_fft.h"   /* wave_max */
 #include "quant_dev.h"
 
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(64) void k_pack(PacxTables T, const uint8_t *__rest
                                             uint8_t *__restrict__ payload, int payload_stride,
                                             int32_t *__restrict__ n_bytes, int only_short)
 {
-    __shared__ unsigned words[PACX_PACK_WORDS];
+    __shared__ unsigned words[PACX_PAYLOAD_WORDS];
     __shared__ int offs[PACX_MAX_BANDS + 1], ba_s[PACX_MAX_BANDS], lower_s[PACX_MAX_BANDS];
     const int lane = threadIdx.x;
     const long long cf = blockIdx.x;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(64) void k_pack(PacxTables T, const uint8_t *__rest
             n_bytes[cf] = 0;
         return;
     }
-    for (int i = lane; i < PACX_PACK_WORDS; i += 64)
+    for (int i = lane; i < PACX_PAYLOAD_WORDS; i += 64)
         words[i] = 0u;
     __syncthreads();
     if (lane == 0) {
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64, 4) void k_tail_long(PacxTables T, const uint8_t
                                                  uint8_t *__restrict__ payload, int payload_stride,
                                                  int32_t *__restrict__ n_bytes)
 {
-    __shared__ unsigned words[PACX_PACK_WORDS];
+    __shared__ unsigned words[PACX_PAYLOAD_WORDS];
     __shared__ double cp[2][32];
     __shared__ unsigned long long bmax[PACX_MAX_BANDS];
     __shared__ int ba_2[2][PACX_MAX_BANDS], sf_s[PACX_MAX_BANDS], offs[PACX_MAX_BANDS + 1], lower_s[PACX_MAX_BANDS];
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(64, 4) void k_tail_long(PacxTables T, const uint8_t
         int *ba_s = ba_2[c];
         __syncthreads();                                  /* ba_2 visible; words, offs free again */
         if (payload)
-            for (int i = lane; i < PACX_PACK_WORDS; i += 64)
+            for (int i = lane; i < PACX_PAYLOAD_WORDS; i += 64)
                 words[i] = 0u;
         __syncthreads();
         /* 2. scale factors + mantissas */
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void k_tail_short(PacxTables T, const uint8_t 
                                                    uint8_t *__restrict__ payload, int payload_stride,
                                                    int32_t *__restrict__ n_bytes)
 {
-    __shared__ unsigned words[PACX_PACK_WORDS];
+    __shared__ unsigned words[PACX_PAYLOAD_WORDS];
     __shared__ double cp[4][2][32];
     __shared__ int ba_s[PACX_SUB][9], sf_s[PACX_SUB][9], len_s[PACX_SUB];   /* [.][nb] = dummy band */
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, half = lane >> 5, l = lane & 31;
@@ -529,7 +529,7 @@ __global__ __launch_bounds__(256) void k_tail_short(PacxTables T, const uint8_t 
         if (cap && status && l == 0)
             atomicOr(&status[cf], ((cap & 1) ? 4u : 0u) | ((cap & 2) ? 16u : 0u));
     }
-    for (int i = tid; i < PACX_PACK_WORDS; i += 256)
+    for (int i = tid; i < PACX_PAYLOAD_WORDS; i += 256)
         words[i] = 0u;
     __syncthreads();
     /* 2. scale factors + mantissas of the wave's two sub-blocks */
@@ -810,7 +810,7 @@ __global__ __launch_bounds__(256) void k_gather_small(const int32_t *__restrict_
 }
 
 /* ------------------------------------------------------------- launchers */
-void pacx_launch_bitalloc(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+void pacx_k::pacx_launch_bitalloc(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                           int short_blocks, int mixed, int skip_long, const double *smr, int32_t *bit_alloc,
                           uint32_t *status, hipStream_t st)
 {
@@ -824,7 +824,7 @@ void pacx_launch_bitalloc(const PacxTables &T, const uint8_t *flags, int n_ch, l
                        n_cf, short_blocks, mixed, skip_long, smr, bit_alloc, status);
 }
 
-void pacx_launch_quantize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+void pacx_k::pacx_launch_quantize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                           int short_blocks, int mixed, const double *lines, const int32_t *overall,
                           int overall_stride, const int32_t *bit_alloc, int32_t *scale_factor,
                           int32_t *mantissa, hipStream_t st)
@@ -840,7 +840,7 @@ void pacx_launch_quantize(const PacxTables &T, const uint8_t *flags, int n_ch, l
                            scale_factor, mantissa);
 }
 
-void pacx_launch_pack(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+void pacx_k::pacx_launch_pack(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                       const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
                       const int32_t *mantissa, const uint32_t *status, uint8_t *payload,
                       int payload_stride, int32_t *n_bytes, hipStream_t st)
@@ -853,7 +853,7 @@ void pacx_launch_pack(const PacxTables &T, const uint8_t *flags, int n_ch, long 
 
 /* BitAlloc + quantize (+ pack when payload != NULL) of a whole batch: long frames
  * through the fused kernel, short frames (flags with CUR) through the separate ones. */
-void pacx_launch_tail(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const double *smr,
+void pacx_k::pacx_launch_tail(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const double *smr,
                       const double *lines, const int32_t *overall, int32_t *bit_alloc, int32_t *scale_factor,
                       int32_t *mantissa, uint32_t *status, uint8_t *payload, int payload_stride,
                       int32_t *n_bytes, const int32_t *list_short, const int32_t *count_short, int skip_long,
@@ -891,7 +891,7 @@ void pacx_launch_tail(const PacxTables &T, const uint8_t *flags, int n_ch, long 
     }
 }
 
-void pacx_launch_gather(long long n_cf, const uint8_t *payload, int payload_stride,
+void pacx_k::pacx_launch_gather(long long n_cf, const uint8_t *payload, int payload_stride,
                         const int32_t *n_bytes, long long *chunk_buf, long long *offs_buf, uint8_t *body,
                         long long capacity, long long *total, hipStream_t st)
 {

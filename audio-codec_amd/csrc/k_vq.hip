@@ -31,7 +31,10 @@
  * time, vectors in LDS, lanes across the vector's components).
  */
 #include "../../include/pacx.h"
-#include "pacx_dev.h"
+#include "pacx_launch.h"
+#include "pvq_dev.h"
+#include "quant_dev.h"  /* put_bits: the MSB-first bit writer into LDS words shared by the block's waves */
+#include "wave_fft.h"   /* wave_lds_fence */
 #include "wave_np_sum.h"
 
 #ifndef VQ_WAVES
@@ -41,15 +44,9 @@
 #define VQ_OCC 3                       /* waves per SIMD the register budget is set for */
 #endif
 #define VQ_DEPTH 16
-#define VQ_WORDS 548                   /* 2192-byte payload slot, as k_pack */
 
 struct VqView {
-    const uint64_t *n_tab, *p_tab;
-    const int32_t *row_off;
-    const int32_t *k_of;
-    const uint8_t *w_of;
-    const double *half_log2;
-    int l_max;
+    PvqTables tab;
     double log_mu1;                    /* np.log(1 + 255) */
     const double *log2_tan;            /* [2^12 - 1] log2(tan(theta_q) + eps), see pacx_config */
     /* work order: bands by decreasing size (SBR-omitted long bands count as 1);
@@ -67,46 +64,11 @@ template <typename T> __device__ __forceinline__ T ldc(const T *p)
     return *(const __attribute__((address_space(4))) T *)(unsigned long long)p;
 }
 
-/* The device library's atan / log / log2(tan) are polynomial evaluations with one or two dozen
-   64-bit coefficients.  Inlined into the band loop the compiler hoists every coefficient out
-   of the loops into a VGPR pair of its own -- some sixty registers held for constants, which
-   is what had this kernel at 168 VGPRs with 20 spilled (the spill reloads sat inside the
-   Horner chains).  As real calls (once or twice per tree node, wave-uniform arguments) the
-   coefficients live only inside the callee. */
-__device__ __attribute__((noinline)) double vq_atan(double x) { return atan(x); }
-__device__ __attribute__((noinline)) double vq_log(double x) { return log(x); }
-__device__ __attribute__((noinline)) double vq_log2_tan(double theta_q) { return log2(tan(fabs(theta_q)) + PACX_EPS); }
+PVQ_LIBM_CALL double vq_atan(double x) { return atan(x); }
+PVQ_LIBM_CALL double vq_log(double x) { return log(x); }
+PVQ_LIBM_CALL double vq_log2_tan(double theta_q) { return log2(tan(fabs(theta_q)) + PACX_EPS); }
 
 /* ---- table access --------------------------------------------------------- */
-__device__ __forceinline__ uint64_t vq_N(const VqView &V, int l, long long k)
-{
-    if (k < 0)
-        return 0;
-    if (l <= 0)
-        return k == 0 ? 1ull : 0ull;
-    if (k == 0)
-        return 1ull;
-    if (l == 1)
-        return 2ull;
-    if (l == 2)
-        return 4ull * (uint64_t)k;
-    return V.n_tab[V.row_off[l] + k];
-}
-
-/* sum_{j=0..k} N(l,j); 0 for k < 0 */
-__device__ __forceinline__ uint64_t vq_P(const VqView &V, int l, long long k)
-{
-    if (k < 0)
-        return 0;
-    if (l <= 0)
-        return 1ull;
-    if (l == 1)
-        return 1ull + 2ull * (uint64_t)k;
-    if (l == 2)
-        return 1ull + 2ull * (uint64_t)k * (uint64_t)(k + 1);
-    return V.p_tab[V.row_off[l] + k];
-}
-
 /* start of row l of the two tables, copied to LDS by every workgroup: the lookups of one
    index term then cost one LDS read and ONE round trip to L2 (four independent loads)
    instead of four dependent pairs (row offset, then entry) */
@@ -126,35 +88,20 @@ __device__ __forceinline__ unsigned long long vq_term(const VqView &V, int l1, l
     return (unsigned long long)(k + a + (neg ? 1 : 0) + l1);
 #endif
     if (l1 >= 3) {
-        const long long base = ROWS64 ? (l1 < VQ_ROWS_SMALL ? vq_row_off_small[l1] : V.row_off[l1]) : vq_row_off_s[l1];
+        const long long base = ROWS64 ? (l1 < VQ_ROWS_SMALL ? vq_row_off_small[l1] : V.tab.row_off[l1]) : vq_row_off_s[l1];
         const long long ka = k - a;
-        const uint64_t nk = V.n_tab[base + k], pk1 = V.p_tab[base + k - 1];
-        const uint64_t pka = V.p_tab[base + ka], nka = V.n_tab[base + ka];
+        const uint64_t nk = V.tab.n_tab[base + k], pk1 = V.tab.p_tab[base + k - 1];
+        const uint64_t pka = V.tab.p_tab[base + ka], nka = V.tab.n_tab[base + ka];
         return nk + 2ull * (pk1 - pka) + (neg ? nka : 0ull);
     }
-    unsigned long long term = vq_N(V, l1, k);
-    term += 2ull * (vq_P(V, l1, k - 1) - vq_P(V, l1, k - a));
+    unsigned long long term = pvq_N(V.tab, l1, k);
+    term += 2ull * (pvq_P(V.tab, l1, k - 1) - pvq_P(V.tab, l1, k - a));
     if (neg)
-        term += vq_N(V, l1, k - a);
+        term += pvq_N(V.tab, l1, k - a);
     return term;
 }
 
 /* ---- wave helpers --------------------------------------------------------- */
-__device__ __forceinline__ void vq_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 {
 #pragma unroll
@@ -163,29 +110,13 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-/* MSB-first bit writer into LDS words shared by the block's waves */
-__device__ __forceinline__ void vq_put32(unsigned *words, int pos, unsigned val, int width)
-{
-    if (width <= 0)
-        return;
-    val &= (width >= 32) ? 0xFFFFFFFFu : ((1u << width) - 1u);
-    const int w = pos >> 5, o = pos & 31;
-    const int room = 32 - o;
-    if (width <= room) {
-        atomicOr(&words[w], val << (room - width));
-    } else {
-        atomicOr(&words[w], val >> (width - room));
-        atomicOr(&words[w + 1], val << (32 - (width - room)));
-    }
-}
-
 __device__ __forceinline__ void vq_put64(unsigned *words, int pos, unsigned long long val, int width)
 {
     if (width > 32) {
-        vq_put32(words, pos, (unsigned)(val >> 32), width - 32);
-        vq_put32(words, pos + width - 32, (unsigned)val, 32);
+        put_bits(words, pos, (unsigned)(val >> 32), width - 32);
+        put_bits(words, pos + width - 32, (unsigned)val, 32);
     } else {
-        vq_put32(words, pos, (unsigned)val, width);
+        put_bits(words, pos, (unsigned)val, width);
     }
 }
 
@@ -295,9 +226,9 @@ __device__ __forceinline__ unsigned long long vq_leaf_idx(const VqView &V, const
     /* L1 norm in np.sum order */
     for (int i = lane; i < n; i += 64)
         t1[i] = fabs(xs[i]);
-    vq_fence();
+    wave_lds_fence();
     const double l1 = wave_np_sum(t1, n, lane);
-    vq_fence();
+    wave_lds_fence();
     ok = l1 > 0.0;
     if (!ok)
         return 0ull;
@@ -312,7 +243,7 @@ __device__ __forceinline__ unsigned long long vq_leaf_idx(const VqView &V, const
         part += y;                            /* integers: exact in any order */
     }
     const int missing = K - (int)wave_sum_f64(part);
-    vq_fence();
+    wave_lds_fence();
     if (missing > 0) {
         if (n <= 64) {
             /* the greedy loop hands one pulse each to the `missing` largest
@@ -347,10 +278,10 @@ __device__ __forceinline__ unsigned long long vq_leaf_idx(const VqView &V, const
                 }
                 if (lane == 0)
                     t2[best_i] += 1.0;
-                vq_fence();
+                wave_lds_fence();
             }
         }
-        vq_fence();
+        wave_lds_fence();
     }
     /* enumeration index: component i (l = n-i dimensions left, k pulses left)
        of magnitude a >= 1 adds N(l-1,k) + 2 sum_{j=1}^{a-1} N(l-1,k-j)
@@ -385,8 +316,8 @@ __device__ __forceinline__ unsigned long long vq_leaf_idx(const VqView &V, const
 __device__ __forceinline__ void vq_leaf(const VqView &V, VqOut &o, const double *xs, int n, int bits,
                                         double *t1, double *t2, int lane)
 {
-    const int K = ldc(&V.k_of[n * 33 + bits]);
-    const int width = ldc(&V.w_of[n * 33 + bits]);
+    const int K = ldc(&V.tab.k_of[n * 33 + bits]);
+    const int width = ldc(&V.tab.w_of[n * 33 + bits]);
     if (K < 0) {                              /* a 1-dimensional leaf: the reference never returns */
         o.flags |= PACX_ST_VQ_UNDEFINED;
         return;
@@ -502,8 +433,8 @@ __device__ __forceinline__ void vq_leaf_pair(const VqView &V, VqOut &o, const do
 {
     const int h = lane >> 5, l = lane & 31;
     const int bits = h ? bits_side : bits_mid;
-    const int K = ldc(&V.k_of[n * 33 + bits]);
-    const int width = ldc(&V.w_of[n * 33 + bits]);
+    const int K = ldc(&V.tab.k_of[n * 33 + bits]);
+    const int width = ldc(&V.tab.w_of[n * 33 + bits]);
     const double x = (l < n) ? (h ? side[l] : mid[l]) : 0.0;
     bool ok;
     const unsigned long long term = vq_leaf_group<32>(V, x, n, K, l, ok);
@@ -549,7 +480,7 @@ __device__ __forceinline__ bool vq_quad_try(const VqView &V, VqOut &o, const dou
     if (s_l2 != 0.0)
         sd = sd / s_l2;
     const double theta = (m_l2 == 0.0) ? 0.0 : vq_atan(s_l2 / m_l2);
-    const int a_theta = (int)floor((double)bits / (double)hh + ldc(&V.half_log2[hh]));
+    const int a_theta = (int)floor((double)bits / (double)hh + ldc(&V.tab.half_log2[hh]));
     int a_rest = bits - a_theta;
     if (a_rest < 0)
         a_rest = 0;
@@ -592,8 +523,8 @@ __device__ __forceinline__ bool vq_quad_try(const VqView &V, VqOut &o, const dou
     const double from_mid = __shfl(m, 32 * h + ll, 64);
     const double x = (ll < hh) ? ((q & 1) ? from_side : from_mid) : 0.0;
     const int lbits = (q & 1) ? a_side : a_mid;
-    const int K = ldc(&V.k_of[hh * 33 + lbits]);
-    const int width = ldc(&V.w_of[hh * 33 + lbits]);
+    const int K = ldc(&V.tab.k_of[hh * 33 + lbits]);
+    const int width = ldc(&V.tab.w_of[hh * 33 + lbits]);
     bool ok;
     const unsigned long long term = vq_leaf_group<16>(V, x, hh, K, ll, ok);
     const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
@@ -649,10 +580,10 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
                 if (s_l2 != 0.0)
                     sv[i] = sv[i] / s_l2;
             }
-            vq_fence();
+            wave_lds_fence();
             const double theta = (m_l2 == 0.0) ? 0.0 : vq_atan(s_l2 / m_l2);
             /* gain_shape_alloc(bits, half): floor(bits/half + 0.5 log2(half)) for the angle */
-            int a_theta = (int)floor((double)bits / (double)half + ldc(&V.half_log2[half]));
+            int a_theta = (int)floor((double)bits / (double)half + ldc(&V.tab.half_log2[half]));
             int a_rest = bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
@@ -862,7 +793,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
     bool undefined = false;                                /* per lane; joined at the end */
     const double *cur = x0;
     for (;;) {
-        vq_fence();
+        wave_lds_fence();
         /* the open level: its splits and its leaves */
         int n_split = 0, n_leaf = 0;
         for (int base = lev_b; base < lev_e; base += 64) {
@@ -879,7 +810,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             n_split += __popcll(ms);
             n_leaf += __popcll(ml);
         }
-        vq_fence();
+        wave_lds_fence();
         double *nxt = bufs[depth & 1];                     /* free while this level's leaves are coded */
         /* ---- leaves of this level (vectors in cur) */
         if (n_leaf) {
@@ -894,8 +825,8 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                 const int n = N.nn[node];
                 int bits = N.bb[node];
                 bits = bits > 32 ? 32 : bits;
-                const int K = ldc(&V.k_of[n * 33 + bits]);
-                const int width = ldc(&V.w_of[n * 33 + bits]);
+                const int K = ldc(&V.tab.k_of[n * 33 + bits]);
+                const int width = ldc(&V.tab.w_of[n * 33 + bits]);
                 bool ok = true;
                 const unsigned long long idx = vq_leaf_idx(V, cur + N.off[node], n, K, nxt, nxt + n, lane, ok);
                 if (!ok)
@@ -912,10 +843,10 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                 const bool small = lane < n_leaf && myn <= 32;
                 const unsigned long long msm = __builtin_amdgcn_ballot_w64(small);
                 const int n_small = __popcll(msm);
-                vq_fence();
+                wave_lds_fence();
                 if (small)
                     N.sl[__popcll(msm & below)] = (unsigned char)my;   /* the split list is rebuilt below */
-                vq_fence();
+                wave_lds_fence();
                 for (int p0 = 0; p0 < n_small; p0 += G) {
                     const int g = lane >> lw, l = lane & (W - 1);
                     const bool valid = p0 + g < n_small;
@@ -923,8 +854,8 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                     const int n = valid ? N.nn[node] : 0;
                     int bits = valid ? N.bb[node] : 0;
                     bits = bits > 32 ? 32 : bits;
-                    const int K = valid ? V.k_of[n * 33 + bits] : 0;
-                    const int width = valid ? V.w_of[n * 33 + bits] : 0;
+                    const int K = valid ? V.tab.k_of[n * 33 + bits] : 0;
+                    const int width = valid ? V.tab.w_of[n * 33 + bits] : 0;
                     const double x = (valid && l < n) ? cur[N.off[node] + l] : 0.0;
                     bool ok = false;
                     unsigned long long term;
@@ -946,7 +877,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                         undefined = true;
                 }
                 /* the split list again (the leaf passes borrowed it) */
-                vq_fence();
+                wave_lds_fence();
                 int ns2 = 0;
                 for (int base = lev_b; base < lev_e; base += 64) {
                     const int j = base + lane;
@@ -956,7 +887,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                         N.sl[ns2 + __popcll(ms & below)] = (unsigned char)j;
                     ns2 += __popcll(ms);
                 }
-                vq_fence();
+                wave_lds_fence();
             }
         }
         if (!n_split)
@@ -975,7 +906,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             N.tot[snode] = (unsigned short)noff;
         const unsigned long long wide = __builtin_amdgcn_ballot_w64(shalf > 64);
         const int hmax = wave_max_i32(shalf > 64 ? 0 : shalf);
-        vq_fence();
+        wave_lds_fence();
         /* nodes of more than 128 components: one at a time, lanes strided over the half */
         for (unsigned long long m = wide; m; m &= m - 1) {
             const int k = __builtin_ctzll(m);
@@ -1017,7 +948,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const int n_narrow = __popcll(mn);
             if (narrow)
                 N.ll[__popcll(mn & below)] = (unsigned char)snode;   /* the leaf list is done with */
-            vq_fence();
+            wave_lds_fence();
             for (int p0 = 0; p0 < n_narrow; p0 += G) {
                 const int g = lane >> lp, i = lane & (P - 1);
                 const bool valid = p0 + g < n_narrow;
@@ -1049,7 +980,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                     N.val[node] = (unsigned long long)__double_as_longlong(m_l2 == 0.0 ? -1.0 : s_l2 / m_l2);
             }
         }
-        vq_fence();
+        wave_lds_fence();
         /* ---- the level's scalar arithmetic, one split per lane; its children join the store */
         {
             const bool has = lane < n_split;
@@ -1057,7 +988,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const int half = has ? shalf : 1;
             const double q = has ? __longlong_as_double((long long)N.val[snode]) : -1.0;
             const double theta = (q < 0.0) ? 0.0 : vq_atan(q);
-            const int a_theta = (int)floor((double)bits / (double)half + V.half_log2[half]);
+            const int a_theta = (int)floor((double)bits / (double)half + V.tab.half_log2[half]);
             int a_rest = bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
@@ -1136,7 +1067,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
     /* ---- widths bottom-up, positions (and field numbers) top-down, then every field at once */
     if (lane == 0)
         N.lvl[depth + 1] = (unsigned char)count;
-    vq_fence();
+    wave_lds_fence();
     /* field counts ride in nn[] (lengths are not needed any more), field numbers in off[] */
     for (int d = depth; d >= 0; --d) {
         const int b = N.lvl[d], e = N.lvl[d + 1];
@@ -1148,13 +1079,13 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             N.tot[j] = (unsigned short)t;
             N.nn[j] = (unsigned short)f;
         }
-        vq_fence();
+        wave_lds_fence();
     }
     if (lane == 0) {
         N.pos[0] = (unsigned short)o.pos;
         N.off[0] = (unsigned short)o.log_n;
     }
-    vq_fence();
+    wave_lds_fence();
     for (int d = 0; d <= depth; ++d) {
         const int b = N.lvl[d], e = N.lvl[d + 1];
         for (int j = b + lane; j < e; j += 64) {
@@ -1171,7 +1102,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                 N.off[k1] = (unsigned short)r;
             }
         }
-        vq_fence();
+        wave_lds_fence();
     }
     for (int j = lane; j < count; j += 64) {
         const int w = N.wid[j];
@@ -1192,7 +1123,7 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
         o.flags |= PACX_ST_VQ_UNDEFINED;
     o.pos += N.tot[0];
     o.log_n += N.nn[0];
-    vq_fence();
+    wave_lds_fence();
     return true;
 }
 
@@ -1211,7 +1142,7 @@ struct VqArgs {
     uint8_t *payload;
     int payload_stride;
     int32_t *n_bytes;
-    unsigned *unit_words;      /* [cf*8][VQ_WORDS] short sub-block strings  */
+    unsigned *unit_words;      /* [cf*8][PACX_PAYLOAD_WORDS] short sub-block strings  */
     int32_t *unit_bits;        /* [cf*8][2]: written bits, size-rule bits   */
     pacx_vq_entry *log;
     int32_t *log_count;
@@ -1242,8 +1173,8 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
     long long vq_last = 0;
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned *words = (unsigned *)smem;                               /* VQ_WORDS        */
-    double *gain_s = (double *)(smem + VQ_WORDS * 4);                 /* 32              */
+    unsigned *words = (unsigned *)smem;                               /* PACX_PAYLOAD_WORDS        */
+    double *gain_s = (double *)(smem + PACX_PAYLOAD_WORDS * 4);                 /* 32              */
     int *ba_s = (int *)(gain_s + PACX_MAX_BANDS);                     /* 32              */
     int *start_s = ba_s + PACX_MAX_BANDS;                             /* 33              */
     int *ticket = start_s + PACX_MAX_BANDS + 1;                       /* 1 (+2 pad)      */
@@ -1283,10 +1214,10 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
     const double up = (double)(1 << ov);
     const int lead = is_short ? 0 : 3;
 
-    for (int i = tid; i < VQ_WORDS; i += 64 * VQ_WAVES)
+    for (int i = tid; i < PACX_PAYLOAD_WORDS; i += 64 * VQ_WAVES)
         words[i] = 0u;
-    for (int i = tid; i <= min(V.l_max, VQ_LMAX); i += 64 * VQ_WAVES)
-        vq_row_off_s[i] = V.row_off[i];
+    for (int i = tid; i <= min(V.tab.l_max, VQ_LMAX); i += 64 * VQ_WAVES)
+        vq_row_off_s[i] = V.tab.row_off[i];
     if (tid == 0)
         *ticket = VQ_WAVES;
     double *scr = scr_all + V.scr_off[wave];
@@ -1346,14 +1277,14 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
             start_s[nb] = head + incl;
         if (lane == 0) {
             if (!is_short) {
-                vq_put32(words, 0, fl & 1u, 1);
-                vq_put32(words, 1, (fl >> 1) & 1u, 1);
-                vq_put32(words, 2, (fl >> 2) & 1u, 1);
+                put_bits(words, 0, fl & 1u, 1);
+                put_bits(words, 1, (fl >> 1) & 1u, 1);
+                put_bits(words, 2, (fl >> 2) & 1u, 1);
             }
-            vq_put32(words, lead, (unsigned)ov, T.n_scale_bits);
+            put_bits(words, lead, (unsigned)ov, T.n_scale_bits);
         }
         if (lane < nb)
-            vq_put32(words, lead + T.n_scale_bits + T.n_mant_size_bits * lane, (unsigned)(ba ? ba - 1 : 0),
+            put_bits(words, lead + T.n_scale_bits + T.n_mant_size_bits * lane, (unsigned)(ba ? ba - 1 : 0),
                      T.n_mant_size_bits);
     }
     __syncthreads();
@@ -1398,7 +1329,7 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
         } else {
             const int lo = ldc(&lower[b]), cnt = ldc(&count[b]);
             const int r_bits = ba * cnt;
-            int bits_gain = (int)floor((double)r_bits / (double)cnt + ldc(&V.half_log2[cnt]));
+            int bits_gain = (int)floor((double)r_bits / (double)cnt + ldc(&V.tab.half_log2[cnt]));
             int bits_shape = r_bits - bits_gain;
             if (bits_shape < 0)
                 bits_shape = 0;
@@ -1448,7 +1379,7 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
         if (tid == 0)
             A.n_bytes[cf] = nbytes;
     } else {
-        unsigned *dst = A.unit_words + unit * VQ_WORDS;
+        unsigned *dst = A.unit_words + unit * PACX_PAYLOAD_WORDS;
         for (int i = tid; i < (written + 31) / 32; i += 64 * VQ_WAVES)
             dst[i] = words[i];
         if (tid == 0) {
@@ -1617,10 +1548,10 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #define VQF_T(k) do { } while (0)
 #endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned *words = (unsigned *)smem;                               /* VQ_WORDS        */
+    unsigned *words = (unsigned *)smem;                               /* PACX_PAYLOAD_WORDS        */
     /* a short-coded frame is ONE unit: its 8 x nb_short bands are the unit's (virtual) bands, band
        vb = 8 j + ... = j nb + b of sub-block j -- at most VQF_VB of them */
-    double *gain_s = (double *)(smem + VQ_WORDS * 4);                 /* VB              */
+    double *gain_s = (double *)(smem + PACX_PAYLOAD_WORDS * 4);                 /* VB              */
     int *ba_s = (int *)(gain_s + VQF_VB);                             /* VB              */
     int *start_s = ba_s + VQF_VB;                                     /* VB: first stream bit of the band's fields */
     int *end_s = start_s + VQF_VB;                                    /* VB: where they must end */
@@ -1631,7 +1562,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     double *buf0 = (double *)(smem + VQF_FIXED);                      /* two level buffers of VQF_BUF doubles */
     VqfStore N;
     N.bind(smem + VQF_FIXED + 2 * VQF_BUF * 8);
-    static_assert(VQ_WORDS * 4 + VQF_VB * 8 + 5 * VQF_VB * 4 + 8 * 4 + VQF_VB * 2 <= VQF_FIXED && VQF_FIXED % 16 == 0,
+    static_assert(PACX_PAYLOAD_WORDS * 4 + VQF_VB * 8 + 5 * VQF_VB * 4 + 8 * 4 + VQF_VB * 2 <= VQF_FIXED && VQF_FIXED % 16 == 0,
                   "fixed part of k_vq_frame's LDS");
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1680,14 +1611,14 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     /* band vb = j nb + b */
     auto sub_of = [&](int vb) { return is_short ? vb / nb : 0; };
 
-    for (int i = tid; i < VQ_WORDS; i += 64 * VQ_WAVES)
+    for (int i = tid; i < PACX_PAYLOAD_WORDS; i += 64 * VQ_WAVES)
         words[i] = 0u;
-    if (tid < VQ_ROWS_SMALL && tid <= V.l_max)
-        vq_row_off_small[tid] = V.row_off[tid];
+    if (tid < VQ_ROWS_SMALL && tid <= V.tab.l_max)
+        vq_row_off_small[tid] = V.tab.row_off[tid];
     /* the scalar stage of a level is one dependency chain, and it is what the kernel waits for: the two
        tables it reads sit in LDS as far as they are commonly needed (halves below 64, angles of up to 7 bits) */
-    if (tid < VQF_HL && tid <= V.l_max)
-        vqf_half_log2[tid] = V.half_log2[tid];
+    if (tid < VQF_HL && tid <= V.tab.l_max)
+        vqf_half_log2[tid] = V.tab.half_log2[tid];
     if (tid < VQF_LT)
         vqf_log2_tan[tid] = V.log2_tan[tid];
     if (tid < 8)
@@ -1765,22 +1696,22 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
             end_s[vb] = start + r_bits;
         }
         if (lane == 0) {
-            vq_put32(words, 0, fl & 1u, 1);
-            vq_put32(words, 1, (fl >> 1) & 1u, 1);
-            vq_put32(words, 2, (fl >> 2) & 1u, 1);
+            put_bits(words, 0, fl & 1u, 1);
+            put_bits(words, 1, (fl >> 1) & 1u, 1);
+            put_bits(words, 2, (fl >> 2) & 1u, 1);
             misc[2] = 3 + n_sub * head + total_bits;      /* bits written */
         }
         if (vb < n_vb) {
             const int sub_base = 3 + j * head + __shfl(before, vb - b, 64);
             if (b == 0)
-                vq_put32(words, sub_base, (unsigned)A.overall[cf * PACX_SUB + j], T.n_scale_bits);
-            vq_put32(words, sub_base + T.n_scale_bits + T.n_mant_size_bits * b, (unsigned)(ba ? ba - 1 : 0),
+                put_bits(words, sub_base, (unsigned)A.overall[cf * PACX_SUB + j], T.n_scale_bits);
+            put_bits(words, sub_base + T.n_scale_bits + T.n_mant_size_bits * b, (unsigned)(ba ? ba - 1 : 0),
                      T.n_mant_size_bits);
         }
         /* gain_shape_alloc of the band; an omitted band is one number: every bit to its gain */
         int bits_gain = ba, bits_shape = 0;
         if (vb < n_vb && b < first_omit && ba) {
-            bits_gain = (int)floor((double)r_bits / (double)cnt + V.half_log2[cnt]);
+            bits_gain = (int)floor((double)r_bits / (double)cnt + V.tab.half_log2[cnt]);
             bits_shape = r_bits - bits_gain;
             if (bits_shape < 0)
                 bits_shape = 0;
@@ -1922,8 +1853,8 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
                 const int K = valid ? (bits * 3) / (n > 8 ? 2 : 1) + 1 : 0;
                 const int width = valid ? bits : 0;
 #else
-                const int K = valid ? V.k_of[n * 33 + bits] : 0;
-                const int width = valid ? V.w_of[n * 33 + bits] : 0;
+                const int K = valid ? V.tab.k_of[n * 33 + bits] : 0;
+                const int width = valid ? V.tab.w_of[n * 33 + bits] : 0;
 #endif
                 const double x = (valid && l < n) ? cur[N.off[node] + l] : 0.0;
                 bool ok = false, near = false;
@@ -1961,8 +1892,8 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
                 const int n = N.nn[node];
                 int bits = N.bb[node];
                 bits = bits > 32 ? 32 : bits;
-                const int K = ldc(&V.k_of[n * 33 + bits]);
-                const int width = ldc(&V.w_of[n * 33 + bits]);
+                const int K = ldc(&V.tab.k_of[n * 33 + bits]);
+                const int width = ldc(&V.tab.w_of[n * 33 + bits]);
                 bool ok = true;
                 double *t1 = nxt + N.tot[node];
                 const unsigned long long idx = vq_leaf_idx<true>(V, cur + N.off[node], n, K, t1, t1 + n, lane, ok);
@@ -2093,7 +2024,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
             const double theta = (q < 0.0) ? 0.0 : vq_atan(q);
 #endif
             VQF_SUB(26);
-            const double hl = (half < VQF_HL) ? vqf_half_log2[half] : V.half_log2[half];
+            const double hl = (half < VQF_HL) ? vqf_half_log2[half] : V.tab.half_log2[half];
             const int a_theta = (int)floor((double)bits / (double)half + hl);
             int a_rest = bits - a_theta;
             if (a_rest < 0)
@@ -2218,7 +2149,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
             const int per = busy == 1 ? 3 : busy == 2 ? 8 : busy == 3 ? 7 : 4;
             /* one chunk of splits: wave 0 made all the children itself and sorts the next level at once */
             if (early && wave == 0) {
-                vq_fence();
+                wave_lds_fence();
                 if (!misc[1])
                     classify(lev_e, misc[0], (depth + 1) & 1);
             }
@@ -2428,7 +2359,7 @@ __global__ __launch_bounds__(64) void k_vq_join(PacxTables T, const uint8_t *__r
                                                uint8_t *__restrict__ payload, int payload_stride,
                                                int32_t *__restrict__ n_bytes, int redo)
 {
-    __shared__ unsigned words[VQ_WORDS];
+    __shared__ unsigned words[PACX_PAYLOAD_WORDS];
     const int lane = threadIdx.x;
     const long long cf = blockIdx.x;
     if (cf >= n_cf)
@@ -2448,23 +2379,23 @@ __global__ __launch_bounds__(64) void k_vq_join(PacxTables T, const uint8_t *__r
             n_bytes[cf] = 0;
         return;
     }
-    for (int i = lane; i < VQ_WORDS; i += 64)
+    for (int i = lane; i < PACX_PAYLOAD_WORDS; i += 64)
         words[i] = 0u;
     __syncthreads();
     if (lane == 0) {
-        vq_put32(words, 0, fl & 1u, 1);
-        vq_put32(words, 1, (fl >> 1) & 1u, 1);
-        vq_put32(words, 2, (fl >> 2) & 1u, 1);
+        put_bits(words, 0, fl & 1u, 1);
+        put_bits(words, 1, (fl >> 1) & 1u, 1);
+        put_bits(words, 2, (fl >> 2) & 1u, 1);
     }
     int pos = 3, size = 0;
     for (int sb = 0; sb < PACX_SUB; ++sb) {
         const long long unit = cf * PACX_SUB + sb;
         const int nbit = unit_bits[unit * 2];
         size += unit_bits[unit * 2 + 1];
-        const unsigned *src = unit_words + unit * VQ_WORDS;
+        const unsigned *src = unit_words + unit * PACX_PAYLOAD_WORDS;
         for (int w = lane; w < (nbit + 31) / 32; w += 64) {
             const int width = (nbit - 32 * w) >= 32 ? 32 : (nbit - 32 * w);
-            vq_put32(words, pos + 32 * w, src[w] >> (32 - width), width);
+            put_bits(words, pos + 32 * w, src[w] >> (32 - width), width);
         }
         pos += nbit;
     }
@@ -2478,7 +2409,7 @@ __global__ __launch_bounds__(64) void k_vq_join(PacxTables T, const uint8_t *__r
 }
 
 /* ---------------------------------------------------------------- launcher */
-void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
+void pacx_k::pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,
                     uint32_t *status, uint8_t *payload, int payload_stride, int32_t *n_bytes,
                     unsigned *unit_words, int32_t *unit_bits, pacx_vq_entry *log, int32_t *log_count,
@@ -2517,7 +2448,7 @@ void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *fla
        quicker depth first (the level walk has a fixed cost per level); the crossover was measured at 96-128 bits
        (tools/vq_bfs_sweep.sh) */
     A.bfs = bfs >= 0 ? bfs : 112;
-    const size_t fixed = VQ_WORDS * 4 + PACX_MAX_BANDS * 8 + (PACX_MAX_BANDS + PACX_MAX_BANDS + 1 + 3) * 4 +
+    const size_t fixed = PACX_PAYLOAD_WORDS * 4 + PACX_MAX_BANDS * 8 + (PACX_MAX_BANDS + PACX_MAX_BANDS + 1 + 3) * 4 +
                          VQ_WAVES * 2 * VQ_DEPTH * 4;
     static_assert(fixed % 8 == 0, "the shapes behind the fixed part are doubles");
     const size_t smem = fixed + PACX_M_LONG * 8 + (size_t)V.scr_off[VQ_WAVES] * 8 + (size_t)VQ_WAVES * VQ_NODE_BYTES;
@@ -2541,13 +2472,11 @@ void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *fla
                            unit_words, unit_bits, payload, payload_stride, n_bytes, A.redo);
 }
 
-size_t pacx_vq_view_size(void) { return sizeof(VqView); }
+size_t pacx_k::pacx_vq_view_size(void) { return sizeof(VqView); }
 
 /* sizes_long / sizes_short: vector dimension of every band as the coder sees it */
-void pacx_vq_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
-                       const int32_t *k_of, const uint8_t *w_of, const double *half_log2, int l_max,
-                       double log_mu1, const double *log2_tan, const int32_t *sizes_long, int nb_long,
-                       const int32_t *sizes_short, int nb_short)
+void pacx_k::pacx_vq_view_fill(void *dst, const PvqTables &tab, double log_mu1, const double *log2_tan,
+                                const int32_t *sizes_long, int nb_long, const int32_t *sizes_short, int nb_short)
 {
     VqView *v = (VqView *)dst;
     v->log2_tan = log2_tan;
@@ -2578,12 +2507,6 @@ void pacx_vq_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, 
         /* mid/side regions [2n + 4 depth] (the shape itself lives in the block's xs) */
         v->scr_off[w + 1] = v->scr_off[w] + ((2 * n + 4 * VQ_DEPTH + 1) & ~1);
     }
-    v->n_tab = n_tab;
-    v->p_tab = p_tab;
-    v->row_off = row_off;
-    v->k_of = k_of;
-    v->w_of = w_of;
-    v->half_log2 = half_log2;
-    v->l_max = l_max;
+    v->tab = tab;
     v->log_mu1 = log_mu1;
 }

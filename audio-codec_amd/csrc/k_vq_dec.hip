@@ -26,7 +26,9 @@
  * k_decode.hip, which also divide by 2^overallScale.
  */
 #include "../../include/pacx.h"
-#include "pacx_dev.h"
+#include "pacx_launch.h"
+#include "pvq_dev.h"
+#include "wave_fft.h"   /* wave_lds_fence */
 #include "wave_np_sum.h"
 
 #define VQD_WAVES 4
@@ -34,12 +36,7 @@
 #define VQD_WORDS 552
 
 struct VqDecView {
-    const uint64_t *n_tab, *p_tab;
-    const int32_t *row_off;
-    const int32_t *k_of;
-    const uint8_t *w_of;
-    const double *half_log2;
-    int l_max;
+    PvqTables tab;
     const double *log2_tan;       /* as VqView::log2_tan                       */
     const double *gauss;          /* [2r+1] normalised weights, centre at r   */
     int gauss_r;
@@ -49,54 +46,9 @@ struct VqDecView {
     int scr_off[VQD_WAVES + 1];
 };
 
-__device__ __forceinline__ uint64_t vqd_N(const VqDecView &V, int l, long long k)
-{
-    if (k < 0)
-        return 0;
-    if (l <= 0)
-        return k == 0 ? 1ull : 0ull;
-    if (k == 0)
-        return 1ull;
-    if (l == 1)
-        return 2ull;
-    if (l == 2)
-        return 4ull * (uint64_t)k;
-    return V.n_tab[V.row_off[l] + k];
-}
-
-__device__ __forceinline__ uint64_t vqd_P(const VqDecView &V, int l, long long k)
-{
-    if (k < 0)
-        return 0;
-    if (l <= 0)
-        return 1ull;
-    if (l == 1)
-        return 1ull + 2ull * (uint64_t)k;
-    if (l == 2)
-        return 1ull + 2ull * (uint64_t)k * (uint64_t)(k + 1);
-    return V.p_tab[V.row_off[l] + k];
-}
-
-__device__ __forceinline__ void vqd_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ double vqd_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
-/* device-library polynomials as real calls: inlined, their coefficients are hoisted out of the
-   band loops into registers of their own (see k_vq.hip) */
-__device__ __attribute__((noinline)) double vqd_cos(double x) { return cos(x); }
-__device__ __attribute__((noinline)) double vqd_sin(double x) { return sin(x); }
-__device__ __attribute__((noinline)) double vqd_pow256(double y) { return pow(256.0, y); }
+PVQ_LIBM_CALL double vqd_cos(double x) { return cos(x); }
+PVQ_LIBM_CALL double vqd_sin(double x) { return sin(x); }
+PVQ_LIBM_CALL double vqd_pow256(double y) { return pow(256.0, y); }
 
 /* up to 64 bits from the MSB-first word array */
 __device__ __forceinline__ unsigned long long vqd_get(const unsigned *words, int pos, int width)
@@ -123,7 +75,7 @@ __device__ __forceinline__ void vqd_pvq(const VqDecView &V, unsigned long long b
 {
     for (int i = lane; i < L; i += 64)
         y[i] = 0.0;
-    vqd_fence();
+    wave_lds_fence();
     unsigned long long xb = 0;
     long long k = K;
     int l = L;
@@ -134,30 +86,30 @@ __device__ __forceinline__ void vqd_pvq(const VqDecView &V, unsigned long long b
             k = 0;
             break;
         }
-        const unsigned long long n0 = vqd_N(V, l - 1, k);
+        const unsigned long long n0 = pvq_N(V.tab, l - 1, k);
         if (b - xb < n0)
             continue;                                   /* this component is zero */
         xb += n0;
         const unsigned long long r = b - xb;
-        const unsigned long long pk1 = vqd_P(V, l - 1, k - 1);
+        const unsigned long long pk1 = pvq_P(V.tab, l - 1, k - 1);
         long long lo = 1, hi = k;
         while (lo < hi) {
             const long long mid = (lo + hi) >> 1;
-            const unsigned long long c = 2ull * (pk1 - vqd_P(V, l - 1, k - mid - 1));
+            const unsigned long long c = 2ull * (pk1 - pvq_P(V.tab, l - 1, k - mid - 1));
             if (r < c)
                 hi = mid;
             else
                 lo = mid + 1;
         }
         const long long j = lo;
-        if (r >= 2ull * (pk1 - vqd_P(V, l - 1, k - j - 1))) {
+        if (r >= 2ull * (pk1 - pvq_P(V.tab, l - 1, k - j - 1))) {
             flags |= PACX_ST_VQ_UNDEFINED;              /* not an index of this codebook */
             break;
         }
-        const unsigned long long base = 2ull * (pk1 - vqd_P(V, l - 1, k - j));
+        const unsigned long long base = 2ull * (pk1 - pvq_P(V.tab, l - 1, k - j));
         /* the reference reaches the negative group by walking through the whole
            positive one at the next component (its step 3 -> step 1 restart) */
-        const unsigned long long group = vqd_N(V, l - 1, k - j);
+        const unsigned long long group = pvq_N(V.tab, l - 1, k - j);
         const bool neg = (r - base) >= group;
         if (lane == 0)
             y[i] = neg ? -(double)j : (double)j;
@@ -166,7 +118,7 @@ __device__ __forceinline__ void vqd_pvq(const VqDecView &V, unsigned long long b
     }
     if (k > 0)
         flags |= PACX_ST_VQ_UNDEFINED;                  /* pulses left over: the reference raises */
-    vqd_fence();
+    wave_lds_fence();
 }
 
 /* x /= ||x|| when the norm is not zero (np.linalg.norm: sqrt of the dot product) */
@@ -175,24 +127,24 @@ __device__ __forceinline__ void vqd_normalize(double *x, int n, int lane)
     double acc = 0.0;
     for (int i = lane; i < n; i += 64)
         acc = fma(x[i], x[i], acc);
-    const double nrm = sqrt(vqd_wave_sum(acc));
+    const double nrm = sqrt(wave_sum_f64(acc));
     if (nrm != 0.0)
         for (int i = lane; i < n; i += 64)
             x[i] = x[i] / nrm;
-    vqd_fence();
+    wave_lds_fence();
 }
 
 /* one PVQ leaf into out[0..n) */
 __device__ __forceinline__ void vqd_leaf(const VqDecView &V, const unsigned *words, int &pos, double *out, int n,
                                          int bits, int lane, unsigned &flags)
 {
-    const int K = V.k_of[n * 33 + bits];
-    const int width = V.w_of[n * 33 + bits];
+    const int K = V.tab.k_of[n * 33 + bits];
+    const int width = V.tab.w_of[n * 33 + bits];
     if (K < 0) {
         flags |= PACX_ST_VQ_UNDEFINED;
         for (int i = lane; i < n; i += 64)
             out[i] = 0.0;
-        vqd_fence();
+        wave_lds_fence();
         return;
     }
     const unsigned long long idx = vqd_get(words, pos, width);
@@ -211,15 +163,15 @@ __device__ __forceinline__ void vqd_leaf_pair(const VqDecView &V, const unsigned
 {
     const int h = lane >> 5, l = lane & 31;
     const int bits = h ? bits_side : bits_mid;
-    const int K = V.k_of[n * 33 + bits];
-    const int width = V.w_of[n * 33 + bits];
+    const int K = V.tab.k_of[n * 33 + bits];
+    const int width = V.tab.w_of[n * 33 + bits];
     const int w_mid = __shfl(width, 0, 64);
     const unsigned long long b = vqd_get(words, pos + (h ? w_mid : 0), width);
     pos += w_mid + __shfl(width, 32, 64);
     double *y = h ? side : mid;
     if (l < n)
         y[l] = 0.0;
-    vqd_fence();
+    wave_lds_fence();
     unsigned long long xb = 0;
     long long k = K;
     int ld = n;
@@ -236,28 +188,28 @@ __device__ __forceinline__ void vqd_leaf_pair(const VqDecView &V, const unsigned
             k = 0;
             continue;
         }
-        const unsigned long long n0 = vqd_N(V, ld - 1, k);
+        const unsigned long long n0 = pvq_N(V.tab, ld - 1, k);
         if (b - xb < n0)
             continue;                                    /* this component is zero */
         xb += n0;
         const unsigned long long r = b - xb;
-        const unsigned long long pk1 = vqd_P(V, ld - 1, k - 1);
+        const unsigned long long pk1 = pvq_P(V.tab, ld - 1, k - 1);
         long long lo = 1, hi = k;
         while (lo < hi) {
             const long long md = (lo + hi) >> 1;
-            const unsigned long long c = 2ull * (pk1 - vqd_P(V, ld - 1, k - md - 1));
+            const unsigned long long c = 2ull * (pk1 - pvq_P(V.tab, ld - 1, k - md - 1));
             if (r < c)
                 hi = md;
             else
                 lo = md + 1;
         }
         const long long j = lo;
-        if (r >= 2ull * (pk1 - vqd_P(V, ld - 1, k - j - 1))) {
+        if (r >= 2ull * (pk1 - pvq_P(V.tab, ld - 1, k - j - 1))) {
             bad = true;                                  /* not an index of this codebook */
             continue;
         }
-        const unsigned long long base = 2ull * (pk1 - vqd_P(V, ld - 1, k - j));
-        const unsigned long long group = vqd_N(V, ld - 1, k - j);
+        const unsigned long long base = 2ull * (pk1 - pvq_P(V.tab, ld - 1, k - j));
+        const unsigned long long group = pvq_N(V.tab, ld - 1, k - j);
         const bool neg = (r - base) >= group;
         if (l == 0)
             y[i] = neg ? -(double)j : (double)j;
@@ -266,7 +218,7 @@ __device__ __forceinline__ void vqd_leaf_pair(const VqDecView &V, const unsigned
     }
     if (__ballot(bad || k > 0))
         flags |= PACX_ST_VQ_UNDEFINED;
-    vqd_fence();
+    wave_lds_fence();
     /* x / ||x|| per half (sums of squares of integers: exact in any order) */
     const double v = (l < n) ? y[l] : 0.0;
     double acc = v * v;
@@ -276,7 +228,7 @@ __device__ __forceinline__ void vqd_leaf_pair(const VqDecView &V, const unsigned
     const double nrm = sqrt(acc);
     if (l < n && nrm != 0.0)
         y[l] = v / nrm;
-    vqd_fence();
+    wave_lds_fence();
 }
 
 /* frames of the split tree (per wave, in LDS) */
@@ -307,7 +259,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
                 return;
             }
             const int half = cur_n - cur_n / 2;
-            int a_theta = (int)floor((double)cur_bits / (double)half + V.half_log2[half]);
+            int a_theta = (int)floor((double)cur_bits / (double)half + V.tab.half_log2[half]);
             int a_rest = cur_bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
@@ -347,7 +299,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
                 F.reg = cur_reg;
                 F.state = 0;
             }
-            vqd_fence();
+            wave_lds_fence();
             const int mid_slot = cur_reg;
             if (a_mid > PACX_VQ_SPLIT_BITS) {
                 depth += 1;
@@ -369,7 +321,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
             } else {
                 for (int i = lane; i < half; i += 64)
                     scr[mid_slot + i] = 0.0;
-                vqd_fence();
+                wave_lds_fence();
             }
             phase = 1;
             continue;
@@ -379,7 +331,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
             const int side_slot = reg + half;
             if (lane == 0)
                 fr[depth].state = 1;
-            vqd_fence();
+            wave_lds_fence();
             if (a_side > PACX_VQ_SPLIT_BITS) {
                 depth += 1;
                 cur_out = side_slot;
@@ -394,7 +346,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
             } else {
                 for (int i = lane; i < half; i += 64)
                     scr[side_slot + i] = 0.0;
-                vqd_fence();
+                wave_lds_fence();
             }
             phase = 2;
             continue;
@@ -415,7 +367,7 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
                     out[i] = left;                          /* an odd band drops the last left value */
                 out[cut + i] = right;
             }
-            vqd_fence();
+            wave_lds_fence();
             vqd_normalize(out, F.n, lane);
         }
         if (depth == 0)
@@ -572,7 +524,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES) void k_vq_dec(PacxTables T, VqDecVi
             at = lower[T.first_omitted] + (b - T.first_omitted);
         }
         const int r_bits = ba * n;
-        int bits_gain = (int)floor((double)r_bits / (double)n + V.half_log2[n]);
+        int bits_gain = (int)floor((double)r_bits / (double)n + V.tab.half_log2[n]);
         int bits_shape = r_bits - bits_gain;
         if (bits_shape < 0)
             bits_shape = 0;
@@ -583,7 +535,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES) void k_vq_dec(PacxTables T, VqDecVi
         } else {
             for (int i = lane; i < n; i += 64)
                 scr[i] = 1.0;
-            vqd_fence();
+            wave_lds_fence();
         }
         /* gain: DequantizeUniform then the inverse mu-law, times L (:533-537) */
         double deq = 0.0;
@@ -603,7 +555,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES) void k_vq_dec(PacxTables T, VqDecVi
         double *dst = lines_s + (shrt ? s * PACX_M_SHORT : 0) + at;
         for (int i = lane; i < n; i += 64)
             dst[i] = gain * scr[i];
-        vqd_fence();
+        wave_lds_fence();
     }
     if (raised && lane == 0)
         atomicOr(&A.status[cf], raised);
@@ -669,26 +621,26 @@ __device__ __forceinline__ bool vqdf_pvq_lane(const VqDecView &V, unsigned long 
             k = 0;
             break;
         }
-        const unsigned long long n0 = vqd_N(V, l - 1, k);
+        const unsigned long long n0 = pvq_N(V.tab, l - 1, k);
         if (b - xb < n0)
             continue;                                   /* this component is zero */
         xb += n0;
         const unsigned long long r = b - xb;
-        const unsigned long long pk1 = vqd_P(V, l - 1, k - 1);
+        const unsigned long long pk1 = pvq_P(V.tab, l - 1, k - 1);
         long long lo = 1, hi = k;
         while (lo < hi) {
             const long long mid = (lo + hi) >> 1;
-            const unsigned long long c = 2ull * (pk1 - vqd_P(V, l - 1, k - mid - 1));
+            const unsigned long long c = 2ull * (pk1 - pvq_P(V.tab, l - 1, k - mid - 1));
             if (r < c)
                 hi = mid;
             else
                 lo = mid + 1;
         }
         const long long j = lo;
-        if (r >= 2ull * (pk1 - vqd_P(V, l - 1, k - j - 1)))
+        if (r >= 2ull * (pk1 - pvq_P(V.tab, l - 1, k - j - 1)))
             return false;                               /* not an index of this codebook */
-        const unsigned long long base = 2ull * (pk1 - vqd_P(V, l - 1, k - j));
-        const unsigned long long group = vqd_N(V, l - 1, k - j);
+        const unsigned long long base = 2ull * (pk1 - pvq_P(V.tab, l - 1, k - j));
+        const unsigned long long group = pvq_N(V.tab, l - 1, k - j);
         const bool neg = (r - base) >= group;
         y[i] = neg ? -(double)j : (double)j;
         xb += base + (neg ? group : 0ull);
@@ -849,7 +801,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
         if (live && sbr && b >= T.first_omitted)
             n = 1;
         const int r_bits = live ? item_ba[vb] * n : 0;
-        int bits_gain = live ? (int)floor((double)r_bits / (double)n + V.half_log2[n]) : 0;
+        int bits_gain = live ? (int)floor((double)r_bits / (double)n + V.tab.half_log2[n]) : 0;
         int bits_shape = r_bits - bits_gain;
         if (bits_shape < 0)
             bits_shape = 0;
@@ -925,7 +877,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
                 continue;
             }
             if (c_bits <= PACX_VQ_SPLIT_BITS) {
-                const int width = V.w_of[c_n * 33 + c_bits];
+                const int width = V.tab.w_of[c_n * 33 + c_bits];
                 N.kind[id] = 1;
                 N.bits[id] = (unsigned char)c_bits;
                 N.bitpos[id] = (unsigned short)pos;
@@ -941,7 +893,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
             }
             /* split: the angle, the bit split */
             const int half = c_n - c_n / 2;
-            const int a_theta = (int)floor((double)c_bits / (double)half + V.half_log2[half]);
+            const int a_theta = (int)floor((double)c_bits / (double)half + V.tab.half_log2[half]);
             int a_rest = c_bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
@@ -1039,8 +991,8 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
             continue;
         }
         const int bits = N.bits[j];
-        const int K = V.k_of[n * 33 + bits];
-        const int width = V.w_of[n * 33 + bits];
+        const int K = V.tab.k_of[n * 33 + bits];
+        const int width = V.tab.w_of[n * 33 + bits];
         if (K < 0) {
             undefined = true;
             for (int i = 0; i < n; ++i)
@@ -1109,7 +1061,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
                             rgt[u] = (mm - ss) / root2;
                         }
                     }
-                    vqd_fence();
+                    wave_lds_fence();
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         const int i = lane + 64 * u;
@@ -1119,7 +1071,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
                             o[cut + i] = rgt[u];
                         }
                     }
-                    vqd_fence();
+                    wave_lds_fence();
                 }
                 vqd_normalize(o, n, lane);
             }
@@ -1127,7 +1079,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1)
             my_max = max(my_max, __shfl_xor(my_max, off, 64));
-        vqd_fence();
+        wave_lds_fence();
         if (n_small) {
             int lq = 1;
             while ((1 << lq) < my_max)
@@ -1154,7 +1106,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
                         val = o[e];                         /* a root that is a leaf: normalised a second time */
                     }
                 }
-                vqd_fence();                                /* in place: everybody has read */
+                wave_lds_fence();                                /* in place: everybody has read */
                 double acc = fma(val, val, 0.0);
                 for (int off = Q >> 1; off > 0; off >>= 1)
                     acc = acc + __shfl_xor(acc, off, 64);
@@ -1163,7 +1115,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
                     val = val / nrm;
                 if (e < n)
                     o[e] = val;
-                vqd_fence();
+                wave_lds_fence();
             }
         }
         __syncthreads();
@@ -1305,13 +1257,13 @@ __global__ __launch_bounds__(SBR_THREADS) void k_sbr_recon(PacxTables T, VqDecVi
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1)
                 mx = fmax(mx, __shfl_xor(mx, off, 64));
-            vqd_fence();
+            wave_lds_fence();
             if (mx > 0.0) {
                 const double mean = wave_np_sum(mag, cnt, lane) / (double)cnt;
                 for (int i = lane; i < cnt; i += 64)
                     ln[lo + i] = ln[lo + i] * (smooth[lo - cut + i] / mean);
             }
-            vqd_fence();
+            wave_lds_fence();
         }
     }
     __syncthreads();
@@ -1320,7 +1272,7 @@ __global__ __launch_bounds__(SBR_THREADS) void k_sbr_recon(PacxTables T, VqDecVi
 }
 
 /* ---------------------------------------------------------------- launchers */
-size_t pacx_vqdec_view_size(void) { return sizeof(VqDecView); }
+size_t pacx_k::pacx_vqdec_view_size(void) { return sizeof(VqDecView); }
 
 static size_t sbr_recon_lds(void)
 {
@@ -1330,7 +1282,7 @@ static size_t sbr_recon_lds(void)
 
 /* Decode_SBR's reconstruction alone (scalar-mantissa SBR streams: the view carries the Gaussian weights and the
    line frequencies only) */
-void pacx_launch_sbr_recon(const PacxTables &T, const void *view, long long n_cf, const uint8_t *sbr_flag,
+void pacx_k::pacx_launch_sbr_recon(const PacxTables &T, const void *view, long long n_cf, const uint8_t *sbr_flag,
                            double *lines, uint32_t *status, hipStream_t st)
 {
     if (n_cf > 0)
@@ -1338,10 +1290,9 @@ void pacx_launch_sbr_recon(const PacxTables &T, const void *view, long long n_cf
                            *(const VqDecView *)view, n_cf, sbr_flag, lines, status);
 }
 
-void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
-                          const int32_t *k_of, const uint8_t *w_of, const double *half_log2, int l_max,
-                          const double *log2_tan, const double *gauss, int gauss_r, const double *line_freq,
-                          const int32_t *sizes_long, int nb_long, const int32_t *sizes_short, int nb_short)
+void pacx_k::pacx_vqdec_view_fill(void *dst, const PvqTables &tab, const double *log2_tan, const double *gauss,
+                                   int gauss_r, const double *line_freq, const int32_t *sizes_long, int nb_long,
+                                   const int32_t *sizes_short, int nb_short)
 {
     VqDecView *v = (VqDecView *)dst;
     /* ticket t codes band nb - 1 - t (mod nb; short frames: of sub-block t / nb).  Wave w owns ticket w; later
@@ -1360,19 +1311,13 @@ void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_ta
         v->scr_off[w + 1] = v->scr_off[w] + ((3 * n + 4 * VQD_DEPTH + 1) & ~1);
     }
     v->log2_tan = log2_tan;
-    v->n_tab = n_tab;
-    v->p_tab = p_tab;
-    v->row_off = row_off;
-    v->k_of = k_of;
-    v->w_of = w_of;
-    v->half_log2 = half_log2;
-    v->l_max = l_max;
+    v->tab = tab;
     v->gauss = gauss;
     v->gauss_r = gauss_r;
     v->line_freq = line_freq;
 }
 
-void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
+void pacx_k::pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
                         int payload_stride, const long long *offsets, const int32_t *n_bytes,
                         uint8_t *cf_flags, int32_t *overall, int32_t *bit_alloc, double *lines,
                         uint8_t *sbr_flag, uint32_t *status, int frame, hipStream_t st)

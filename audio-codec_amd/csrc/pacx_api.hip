@@ -14,112 +14,12 @@
 
 #include "../../include/pacx.h"
 #include "body_index.h"
-#include "pacx_dev.h"
+#include "pacx_launch.h"
+#include "pvq_dev.h"
 #include "pacx_vq_tables.h"
 #include "pacx_tables_gen.h"
 
-/* kernels (k_mdct.hip, k_psy.hip, k_quant.hip) */
-void pacx_launch_mdct(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
-                      const uint8_t *flags, long long n_cf, int short_blocks, int mixed, int prewin,
-                      double *lines, int32_t *scale_out, int scale_stride, uint32_t *status,
-                      hipStream_t st);
-void pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8_t *flags, long long n_cf,
-                         int skip_cur, double *lines, int32_t *scale_out, int scale_stride,
-                         uint32_t *status_init, int n_cu, const int32_t *cf_list, const int32_t *cf_count,
-                         hipStream_t st);
-void pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
-                      const uint8_t *flags, long long n_cf, int short_blocks, int mixed,
-                      PacxPeak *peaks, int32_t *n_peaks, int32_t *n_kept, double *sbr_mean,
-                      int32_t *sbr_overall, hipStream_t st);
-void pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
-                      int short_blocks, int mixed, const PacxPeak *peaks, const int32_t *n_peaks,
-                      const double *lines, double *smr, double *thr_out, int n_cu,
-                      const int32_t *list_long, const int32_t *list_short, const int32_t *counts,
-                      const MaskTail *tail, hipStream_t st);
-void pacx_launch_frame_lists(const uint8_t *flags, long long n_frames, int n_ch, int32_t *list_long,
-                             int32_t *list_short, int32_t *counts, hipStream_t st);
-void pacx_launch_bitalloc(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
-                          int short_blocks, int mixed, int skip_long, const double *smr, int32_t *bit_alloc,
-                          uint32_t *status, hipStream_t st);
-void pacx_launch_quantize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
-                          int short_blocks, int mixed, const double *lines, const int32_t *overall,
-                          int overall_stride, const int32_t *bit_alloc, int32_t *scale_factor,
-                          int32_t *mantissa, hipStream_t st);
-void pacx_launch_pack(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
-                      const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
-                      const int32_t *mantissa, const uint32_t *status, uint8_t *payload,
-                      int payload_stride, int32_t *n_bytes, hipStream_t st);
-void pacx_launch_tail(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const double *smr,
-                      const double *lines, const int32_t *overall, int32_t *bit_alloc, int32_t *scale_factor,
-                      int32_t *mantissa, uint32_t *status, uint8_t *payload, int payload_stride,
-                      int32_t *n_bytes, const int32_t *list_short, const int32_t *count_short, int skip_long,
-                      hipStream_t st);
-void pacx_launch_gather(long long n_cf, const uint8_t *payload, int payload_stride,
-                        const int32_t *n_bytes, long long *chunk_buf, long long *offs_buf, uint8_t *body,
-                        long long capacity, long long *total, hipStream_t st);
-
-void pacx_launch_window(const double *win, long long n_rows, int len, const double *x, double *y,
-                        hipStream_t st);
-void pacx_launch_dequant_elem(int op, long long n, const int64_t *codes, int scale, int a, int b, double *out,
-                              hipStream_t st);
-void pacx_launch_mdct_direct(long long n_rows, int a, int b, int inverse, const double *x, double *y, hipStream_t st);
-void pacx_launch_imdct_plain(const PacxTables &T, long long n_rows, int short_blocks, const double *lines,
-                             double *blocks, hipStream_t st);
-void pacx_launch_quant_elem(int op, long long n, const double *x, int scale, int a, int b, int64_t *out,
-                            hipStream_t st);
-void pacx_launch_bitalloc_generic(long long n, int nb, const int32_t *n_lines, const double *budget,
-                                  int max_mant, const double *smr, int32_t *bits, hipStream_t st);
-
-void pacx_launch_transient_f64(long long n_blocks, int n_ch, int n, const double *blocks, double thresh, uint8_t *out,
-                               hipStream_t st);
-void pacx_launch_transient(const PacxPcmView &in, long long n_hops, int hop, uint8_t *transient,
-                           uint8_t *flags, hipStream_t st);
-
-void pacx_launch_sbr_scalar_lines(const PacxTables &T, long long n_cf, const uint8_t *cf_flags,
-                                  const int32_t *scale_factor, const int32_t *bit_alloc, const int32_t *mantissa,
-                                  double *lines, uint8_t *sbr_flag, int routing, hipStream_t st);
-void pacx_launch_sbr_recon(const PacxTables &T, const void *view, long long n_cf, const uint8_t *sbr_flag,
-                           double *lines, uint32_t *status, hipStream_t st);
-void pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payload, int payload_stride,
-                        const long long *offsets, const int32_t *n_bytes, uint8_t *flags_out, int32_t *overall,
-                        int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,
-                        hipStream_t st);
-void pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const uint8_t *cf_flags,
-                        const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
-                        const int32_t *mantissa, const double *lines_in, double *blocks, int16_t *pcm,
-                        hipStream_t st);
-void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
-                          hipStream_t st);
-/* k_index.hip */
-size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws);
-void pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
-                       long long max_records, long long *offsets, int32_t *n_bytes, long long *result, hipStream_t st);
-/* k_vq_dec.hip */
-size_t pacx_vqdec_view_size(void);
-void pacx_vqdec_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
-                          const int32_t *k_of, const uint8_t *w_of, const double *half_log2, int l_max,
-                          const double *log2_tan, const double *gauss, int gauss_r, const double *line_freq,
-                          const int32_t *sizes_long, int nb_long, const int32_t *sizes_short, int nb_short);
-void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
-                        int payload_stride, const long long *offsets, const int32_t *n_bytes,
-                        uint8_t *cf_flags, int32_t *overall, int32_t *bit_alloc, double *lines,
-                        uint8_t *sbr_flag, uint32_t *status, int frame, hipStream_t st);
-
-/* k_vq.hip */
-void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
-                    const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,
-                    uint32_t *status, uint8_t *payload, int payload_stride, int32_t *n_bytes,
-                    unsigned *unit_words, int32_t *unit_bits, pacx_vq_entry *log, int32_t *log_count,
-                    int log_cap, int stage, const int32_t *cf_list, const int32_t *cf_count, int frame, int bfs,
-                    hipStream_t st);
-size_t pacx_vq_view_size(void);
-void pacx_vq_view_fill(void *dst, const uint64_t *n_tab, const uint64_t *p_tab, const int32_t *row_off,
-                       const int32_t *k_of, const uint8_t *w_of, const double *half_log2, int l_max,
-                       double log_mu1, const double *log2_tan, const int32_t *sizes_long, int nb_long,
-                       const int32_t *sizes_short, int nb_short);
-
-#define PACX_PAYLOAD_STRIDE 2192
-#define PACX_VQ_UNIT_WORDS 548
+using namespace pacx_k;
 
 /* Path overrides.  Each forces a path that runs by default on some other input, so that the GPU tests can hold
    the two implementations bit-identical on one batch.  Read once, when the handle is created; -1 (unset, or a
@@ -196,9 +96,9 @@ struct pacx_handle {
     uint32_t *ws_dec_status;          /* [cf] (scalar SBR decode without a caller's status) */
     double *ws_sbr_mean;              /* [ws_cf][8] omitted-band means           */
     long long ws_vq_cf;               /* capacity of the short-frame buffers    */
-    unsigned *ws_unit_words;          /* [ws_vq_cf*8][548]                      */
+    unsigned *ws_unit_words;          /* [ws_vq_cf*8][PACX_PAYLOAD_WORDS]       */
     int32_t *ws_unit_bits;            /* [ws_vq_cf*8][2]                        */
-    size_t ws_index_bytes;            /* capacity of ws_index                   */
+    long long ws_index_bytes;         /* capacity of ws_index                   */
     char *ws_index;                   /* pacx_index_body's tables (PacxIndexWs)  */
     std::string err;
 };
@@ -615,16 +515,17 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
         }
         TRY(upload(h, alloc_lines.data(), alloc_lines.size(), &T.band_lines_long_alloc));
     }
-    const uint64_t *d_n = nullptr, *d_p = nullptr;
-    const int32_t *d_off = nullptr, *d_k = nullptr;
-    const uint8_t *d_w = nullptr;
-    const double *d_hl = nullptr, *d_lt = nullptr;
-    int l_max = 1;
+    PvqTables tab;                         /* device copies, for both views */
+    memset(&tab, 0, sizeof(tab));
+    tab.l_max = 1;
+    const double *d_lt = nullptr;
     if (T.use_vq) {
+        int l_max = 1;
         for (int b = 0; b < T.nb_long; ++b)
             l_max = cfg->band_lines_long[b] > l_max ? cfg->band_lines_long[b] : l_max;
         for (int b = 0; b < T.nb_short; ++b)
             l_max = cfg->band_lines_short[b] > l_max ? cfg->band_lines_short[b] : l_max;
+        tab.l_max = l_max;
         PacxVqHostTables vt;
         /* NULL gain-shape tables: the built-in NumPy-evaluated copies (l_max <= 1024 always:
            a band cannot have more lines than the block) */
@@ -633,12 +534,12 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
             vt.n_tab.push_back(0);
             vt.p_tab.push_back(0);
         }
-        TRY(upload(h, vt.n_tab.data(), vt.n_tab.size(), &d_n));
-        TRY(upload(h, vt.p_tab.data(), vt.p_tab.size(), &d_p));
-        TRY(upload(h, vt.row_off.data(), vt.row_off.size(), &d_off));
-        TRY(upload(h, vt.k_of.data(), vt.k_of.size(), &d_k));
-        TRY(upload(h, vt.w_of.data(), vt.w_of.size(), &d_w));
-        TRY(upload(h, vt.half_log2.data(), vt.half_log2.size(), &d_hl));
+        TRY(upload(h, vt.n_tab.data(), vt.n_tab.size(), &tab.n_tab));
+        TRY(upload(h, vt.p_tab.data(), vt.p_tab.size(), &tab.p_tab));
+        TRY(upload(h, vt.row_off.data(), vt.row_off.size(), &tab.row_off));
+        TRY(upload(h, vt.k_of.data(), vt.k_of.size(), &tab.k_of));
+        TRY(upload(h, vt.w_of.data(), vt.w_of.size(), &tab.w_of));
+        TRY(upload(h, vt.half_log2.data(), vt.half_log2.size(), &tab.half_log2));
         h->vq_view.resize(pacx_vq_view_size());
         std::vector<int32_t> sizes_long(cfg->band_lines_long, cfg->band_lines_long + T.nb_long);
         for (int b = T.first_omitted; b < T.nb_long; ++b)
@@ -649,9 +550,8 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
                sizeof(double) * lt.size());
         static_assert(sizeof(PACX_GEN_VQ_LOG2_TAN) / 8 == (1u << PACX_VQ_THETA_TABLE_BITS) - 1, "log2-tan table");
         TRY(upload(h, lt.data(), lt.size(), &d_lt));
-        pacx_vq_view_fill(h->vq_view.data(), d_n, d_p, d_off, d_k, d_w, d_hl, l_max,
-                          cfg->log_mu1 != 0.0 ? cfg->log_mu1 : ((const double *)PACX_GEN_LOG_MU1)[0], d_lt, sizes_long.data(), T.nb_long,
-                          cfg->band_lines_short, T.nb_short);
+        pacx_vq_view_fill(h->vq_view.data(), tab, cfg->log_mu1 != 0.0 ? cfg->log_mu1 : ((const double *)PACX_GEN_LOG_MU1)[0],
+                          d_lt, sizes_long.data(), T.nb_long, cfg->band_lines_short, T.nb_short);
     }
     if (T.use_vq || T.use_sbr) {
         /* decode side: Gaussian weights of gaussian_filter1d(sigma=200) (radius
@@ -673,8 +573,8 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
         TRY(upload(h, gw.data(), gw.size(), &d_gw));
         TRY(upload(h, lf.data(), lf.size(), &d_lf));
         h->vqdec_view.resize(pacx_vqdec_view_size());
-        pacx_vqdec_view_fill(h->vqdec_view.data(), d_n, d_p, d_off, d_k, d_w, d_hl, l_max, d_lt, d_gw, gr, d_lf,
-                             cfg->band_lines_long, T.nb_long, cfg->band_lines_short, T.nb_short);
+        pacx_vqdec_view_fill(h->vqdec_view.data(), tab, d_lt, d_gw, gr, d_lf, cfg->band_lines_long, T.nb_long,
+                             cfg->band_lines_short, T.nb_short);
     }
 #undef TRY
     *out = h;
@@ -695,6 +595,60 @@ static int post_launch_forked(pacx_handle *h, const char *what)
         drain_internal(h);
         return fail(h, PACX_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
     }
+    return PACX_OK;
+}
+
+/* The buffers outside pacx_reserve's workspace: each group has a capacity of its own (channel-frames; bytes for
+   the index) and only ever grows, on the first call that needs more. */
+enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_INDEX, GROW_N };
+struct GrowGroup {
+    long long *cap;
+    struct { void **p; size_t unit; } buf[3];       /* unit: bytes per unit of capacity; p == nullptr ends the group */
+};
+
+static GrowGroup grow_group(pacx_handle *h, int which)
+{
+    switch (which) {
+    case GROW_MANT:
+        return {&h->ws_mant_cf, {{(void **)&h->ws_mant, PACX_M_LONG * sizeof(int32_t)}}};
+    case GROW_VQ_UNITS:
+        return {&h->ws_vq_cf, {{(void **)&h->ws_unit_words, PACX_SUB * PACX_PAYLOAD_WORDS * sizeof(unsigned)},
+                               {(void **)&h->ws_unit_bits, PACX_SUB * 2 * sizeof(int32_t)}}};
+    /* the decoders' own workspaces: windowed blocks when the caller wants PCM only; lines + SBR flags (+ status words) */
+    case GROW_DEC_BLOCKS:
+        return {&h->ws_blocks_cf, {{(void **)&h->ws_blocks, PACX_N_LONG * sizeof(double)}}};
+    case GROW_DEC_LINES:
+        return {&h->ws_dec_cf, {{(void **)&h->ws_dec_lines, PACX_M_LONG * sizeof(double)},
+                                {(void **)&h->ws_dec_sbr, 1},
+                                {(void **)&h->ws_dec_status, sizeof(uint32_t)}}};
+    default:
+        return {&h->ws_index_bytes, {{(void **)&h->ws_index, 1}}};
+    }
+}
+
+static void free_group(const GrowGroup &g)
+{
+    for (const auto &b : g.buf)
+        if (b.p && *b.p) {
+            (void)hipFree(*b.p);
+            *b.p = nullptr;
+        }
+    *g.cap = 0;
+}
+
+/* room for n units in one group.  A failing hipMalloc leaves the group at capacity 0 (a later call allocates
+   again, and frees what this one got first) */
+static int grow(pacx_handle *h, int which, long long n)
+{
+    const GrowGroup g = grow_group(h, which);
+    if (n <= *g.cap)
+        return PACX_OK;
+    HIP_TRY(h, hipDeviceSynchronize());
+    free_group(g);
+    for (const auto &b : g.buf)
+        if (b.p)
+            HIP_TRY(h, hipMalloc(b.p, (size_t)n * b.unit));
+    *g.cap = n;
     return PACX_OK;
 }
 
@@ -730,22 +684,8 @@ extern "C" void pacx_destroy(pacx_handle *h)
     if (h->ev_join)
         (void)hipEventDestroy(h->ev_join);
     free_ws(h);
-    if (h->ws_blocks)
-        (void)hipFree(h->ws_blocks);
-    if (h->ws_unit_words)
-        (void)hipFree(h->ws_unit_words);
-    if (h->ws_unit_bits)
-        (void)hipFree(h->ws_unit_bits);
-    if (h->ws_mant)
-        (void)hipFree(h->ws_mant);
-    if (h->ws_dec_lines)
-        (void)hipFree(h->ws_dec_lines);
-    if (h->ws_dec_sbr)
-        (void)hipFree(h->ws_dec_sbr);
-    if (h->ws_dec_status)
-        (void)hipFree(h->ws_dec_status);
-    if (h->ws_index)
-        (void)hipFree(h->ws_index);
+    for (int which = 0; which < GROW_N; ++which)
+        free_group(grow_group(h, which));
     for (void *p : h->owned)
         (void)hipFree(p);
     delete h;
@@ -894,13 +834,6 @@ extern "C" int pacx_smr_batch(pacx_handle *h, const pacx_pcm *in, const double *
     return post_launch(h, "pacx_smr_batch");
 }
 
-size_t pacx_smr_generic_lds(int n);
-void pacx_launch_smr_generic(long long n_blocks, int n, int nb, const double *data, const double *lines,
-                             const double *hann, const double *tw_cos, const double *tw_sin, double norm, double fstep,
-                             const double *bark, const double *quiet, const int32_t *band_lower,
-                             const int32_t *band_count, double *smr, double *thr_out, int32_t *n_peaks_out,
-                             hipStream_t st);
-
 extern "C" int pacx_smr_generic_batch(pacx_handle *h, int64_t n_blocks, int n_samples, const double *data,
                                       const double *lines, const pacx_smr_tables *t, double *smr, double *threshold,
                                       int32_t *n_peaks, void *stream)
@@ -955,6 +888,72 @@ extern "C" int pacx_quantize_batch(pacx_handle *h, int64_t n_cf, const double *l
     return post_launch(h, "pacx_quantize_batch");
 }
 
+/* What one encode call hands to every launch of its front end (frame lists -> long / short MDCT -> side chain ->
+   mask), filled once per call: the launches below name only what differs between them -- the stream, the part
+   of a block-switched batch (0, PACX_PART_LONG, PACX_PART_SHORT), the fused tail.  The schedules themselves (which
+   stream, which order, which events) stay with the two entry points: they differ for measured reasons. */
+struct EncodeStep {
+    pacx_handle *h;
+    PacxPcmView v;
+    int dtype, fast;
+    const uint8_t *frame_flags;
+    long long n_frames, n_cf;
+    int n_ch, mixed;                  /* mixed: per-frame flags (without them every frame is a long sine block) */
+    int32_t *list_long, *list_short, *counts;       /* h->ws_lists: long cf list, short cf list, the two counts */
+    int32_t *overall_scale;
+    uint32_t *status;
+
+    EncodeStep(pacx_handle *h_, const pacx_pcm *in, const PacxPcmView &v_, int fast_, const uint8_t *flags, long long n,
+               int32_t *overall, uint32_t *status_)
+        : h(h_), v(v_), dtype(in->dtype), fast(fast_), frame_flags(flags), n_frames(in->n_frames), n_cf(n),
+          n_ch(in->n_channels), mixed(flags ? 1 : 0), list_long(h_->ws_lists), list_short(h_->ws_lists + n),
+          counts(h_->ws_lists + 2 * n), overall_scale(overall), status(status_)
+    {
+    }
+
+    void lists(hipStream_t st) const
+    {
+        pacx_launch_frame_lists(frame_flags, n_frames, n_ch, list_long, list_short, counts, st);
+    }
+    /* fast batches.  Long frames: persistent roofline kernel (k_mdct_long_v2; it also initialises status and the
+       overall scales); short (CUR) frames: k_mdct_short */
+    void mdct_long(hipStream_t st) const
+    {
+        pacx_launch_mdct_v2(h->T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
+                            mixed ? list_long : nullptr, mixed ? counts : nullptr, st);
+    }
+    void mdct_short(hipStream_t st) const
+    {
+        pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
+                         st);
+    }
+    /* every frame's MDCT on one stream */
+    void mdct(hipStream_t st) const
+    {
+        if (fast) {
+            mdct_long(st);
+            if (mixed)
+                mdct_short(st);
+        } else {
+            pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale, PACX_SUB,
+                             status, st);
+        }
+    }
+    /* sbr: the side chain also leaves the omitted bands' means and folds max|FFT| into the overall scale the MDCT
+       wrote (so it runs behind the MDCT on that MDCT's stream) */
+    void side(int part, bool sbr, hipStream_t st) const
+    {
+        pacx_launch_side(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed | part, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
+                         sbr ? h->ws_sbr_mean : nullptr, sbr ? overall_scale : nullptr, st);
+    }
+    /* tail: the outputs of the work fused into the long mask kernel, or nullptr */
+    void mask(int part, const MaskTail *tail, hipStream_t st) const
+    {
+        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed | part, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                         nullptr, h->n_cu, list_long, list_short, counts, tail, st);
+    }
+};
+
 static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
                          int32_t *overall_scale, int32_t *scale_factor, int32_t *bit_alloc,
                          int32_t *mantissa, uint32_t *status, uint8_t *payload, int32_t *n_bytes,
@@ -982,27 +981,20 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
     hipStream_t st = (hipStream_t)stream;
     const PacxTables &T = h->T;
     const int mixed = frame_flags ? 1 : 0;     /* without flags every frame is a long sine block */
-    const int n_ch = in->n_channels;
     /* k_tail_short (and the tails of the long frames) pack from registers; only the separate-kernel fallback for
        layouts with more than 8 short bands (k_quantize<128> -> k_pack) reads the mantissas back from memory.  Round 3:
        the workspace copy is no longer written when nobody asked for mantissas (it was 4 KB per channel-frame of HBM
        writes in every block-switched step) */
     if (!mantissa && mixed && T.nb_short > 8) {
-        if (n_cf > h->ws_mant_cf) {
-            HIP_TRY(h, hipDeviceSynchronize());
-            if (h->ws_mant)
-                (void)hipFree(h->ws_mant);
-            h->ws_mant = nullptr;
-            h->ws_mant_cf = 0;
-            HIP_TRY(h, hipMalloc((void **)&h->ws_mant, (size_t)n_cf * PACX_M_LONG * sizeof(int32_t)));
-            h->ws_mant_cf = n_cf;
-        }
+        if ((rc = grow(h, GROW_MANT, n_cf)))
+            return rc;
         mantissa = h->ws_mant;
     }
     if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
         HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
         HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
     }
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
     /* mixed streams: compacted lists of the long- and of the short-coded frames -- every
        persistent kernel below walks its own list.  The two-stream schedule forks first: the side
        chains and the short-block MDCT go by the flags alone and start while the lists are made */
@@ -1010,8 +1002,7 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
     if (split)
         HIP_TRY(h, hipEventRecord(h->ev_fork, st));
     if (mixed)
-        pacx_launch_frame_lists(frame_flags, in->n_frames, n_ch, h->ws_lists, h->ws_lists + n_cf,
-                                h->ws_lists + 2 * n_cf, st);
+        s.lists(st);
     if (split)
         HIP_TRY(h, hipEventRecord(h->ev_lists, st));
     /* long frames: masked threshold, SMRs, BitAlloc, scale factors / mantissas and the payload
@@ -1026,7 +1017,12 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
     MaskTail mt;
     mt.overall = overall_scale; mt.bit_alloc = bit_alloc; mt.scale_factor = scale_factor; mt.mantissa = mantissa;
     mt.status = status; mt.payload = payload; mt.n_bytes = n_bytes; mt.payload_stride = PACX_PAYLOAD_STRIDE;
-    int32_t *const list_long = h->ws_lists, *const list_short = h->ws_lists + n_cf, *const counts = h->ws_lists + 2 * n_cf;
+    /* the tail as kernels of its own: the frames of a list (the short-coded ones), or every frame that skip_long
+       leaves */
+    auto tail = [&](const int32_t *cf_list, const int32_t *cf_count, int skip_long, hipStream_t s2) {
+        pacx_launch_tail(T, frame_flags, s.n_ch, n_cf, h->ws_smr, h->ws_lines, overall_scale, bit_alloc, scale_factor,
+                         mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, cf_list, cf_count, skip_long, s2);
+    };
     if (T.use_sbr) {
         /* scalar mantissas in an SBR file (coder/codec.py:426-482, 529-555; long blocks only, short
            ones take the plain path, coder/pacfile.py:639-643): the side chain folds max|FFT| into
@@ -1034,22 +1030,10 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
            the omitted bands as one line and budgets from the full block (T.use_sbr in the tail
            kernels), and a frame whose omitted band gets bits is where the reference raises:
            PACX_ST_REF_RAISES, n_bytes 0.  Not a tuned path -- the reference's driver never selects it. */
-        if (fast) {
-            pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status,
-                                h->n_cu, mixed ? list_long : nullptr, mixed ? counts : nullptr, st);
-            if (mixed)
-                pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale,
-                                 PACX_SUB, status, st);
-        } else {
-            pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale,
-                             PACX_SUB, status, st);
-        }
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
-                         h->ws_sbr_mean, overall_scale, st);
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                         nullptr, h->n_cu, list_long, list_short, counts, nullptr, st);
-        pacx_launch_tail(T, frame_flags, n_ch, n_cf, h->ws_smr, h->ws_lines, overall_scale, bit_alloc, scale_factor,
-                         mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, list_short, counts + 1, 0, st);
+        s.mdct(st);
+        s.side(0, true, st);
+        s.mask(0, nullptr, st);
+        tail(s.list_short, s.counts + 1, 0, st);
         return post_launch(h, what);
     }
     if (split) {
@@ -1064,28 +1048,19 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
            of a side chain with its 40 us transform: bs128 33.9 -> 35.4 M cf/s with two steps in flight, 25.9 ->
            30.7 M with one. */
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_fork, 0));
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, nullptr, nullptr, st);
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, nullptr, nullptr, h->short_stream);
+        s.side(PACX_PART_LONG, false, st);
+        s.side(PACX_PART_SHORT, false, h->short_stream);
         /* short chain */
-        pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
-                         h->short_stream);
+        s.mdct_short(h->short_stream);
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_lists, 0));
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_nkept, h->ws_lines,
-                         h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, nullptr, h->short_stream);
-        pacx_launch_tail(T, frame_flags, n_ch, n_cf, h->ws_smr, h->ws_lines, overall_scale, bit_alloc, scale_factor,
-                         mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, list_short, counts + 1, 1,
-                         h->short_stream);
+        s.mask(PACX_PART_SHORT, nullptr, h->short_stream);
+        tail(s.list_short, s.counts + 1, 1, h->short_stream);
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_short_done, h->short_stream));
         /* long chain */
-        pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
-                            list_long, counts, st);
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_nkept, h->ws_lines,
-                         h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, fuse ? &mt : nullptr, st);
+        s.mdct_long(st);
+        s.mask(PACX_PART_LONG, fuse ? &mt : nullptr, st);
         if (!fuse)
-            pacx_launch_tail(T, frame_flags, n_ch, n_cf, h->ws_smr, h->ws_lines, overall_scale, bit_alloc, scale_factor,
-                             mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, nullptr, nullptr, 2, st);
+            tail(nullptr, nullptr, 2, st);      /* every long-coded frame */
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_short_done, 0));       /* both chains done */
         return post_launch_forked(h, what);
     }
@@ -1100,29 +1075,16 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_fork, st));
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
     }
-    pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
-                     nullptr, nullptr, side_st);
+    s.side(0, false, side_st);
     if (!one_stream)
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_join, h->side_stream));
-    if (fast) {
-        /* long frames: persistent roofline kernel; short (CUR) frames: k_mdct_short */
-        pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status,
-                            h->n_cu, mixed ? list_long : nullptr, mixed ? counts : nullptr, st);
-        if (mixed)
-            pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale,
-                             PACX_SUB, status, st);
-    } else {
-        pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale,
-                         PACX_SUB, status, st);
-    }
+    s.mdct(st);
     if (!one_stream)
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_join, 0));       /* join */
-    pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                     nullptr, h->n_cu, list_long, list_short, counts, fuse ? &mt : nullptr, st);
+    s.mask(0, fuse ? &mt : nullptr, st);
     /* what is left: the long frames when not fused, the short-coded frames of a mixed batch */
     if (!fuse || mixed)
-        pacx_launch_tail(T, frame_flags, n_ch, n_cf, h->ws_smr, h->ws_lines, overall_scale, bit_alloc, scale_factor,
-                         mantissa, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, list_short, counts + 1, fuse, st);
+        tail(s.list_short, s.counts + 1, fuse, st);
     return post_launch_forked(h, what);
 }
 
@@ -1180,19 +1142,8 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
     hipStream_t st = (hipStream_t)stream;
     const PacxTables &T = h->T;
     const int mixed = frame_flags ? 1 : 0;
-    const int n_ch = in->n_channels;
-    if (mixed && n_cf > h->ws_vq_cf) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        if (h->ws_unit_words) (void)hipFree(h->ws_unit_words);
-        if (h->ws_unit_bits) (void)hipFree(h->ws_unit_bits);
-        h->ws_unit_words = nullptr;
-        h->ws_unit_bits = nullptr;
-        h->ws_vq_cf = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->ws_unit_words,
-                             (size_t)n_cf * PACX_SUB * PACX_VQ_UNIT_WORDS * sizeof(unsigned)));
-        HIP_TRY(h, hipMalloc((void **)&h->ws_unit_bits, (size_t)n_cf * PACX_SUB * 2 * sizeof(int32_t)));
-        h->ws_vq_cf = n_cf;
-    }
+    if (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf)))
+        return rc;
     if (!fast) {
         HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
         HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
@@ -1204,6 +1155,18 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
     memset(&mt, 0, sizeof(mt));
     mt.bit_alloc = bit_alloc;
     mt.status = status;
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
+    /* BitAlloc as a kernel of its own; skip_long: 0 every frame, 1 the short-coded frames only, 2 the long-coded only */
+    auto bitalloc = [&](int skip_long, hipStream_t s2) {
+        pacx_launch_bitalloc(T, frame_flags, s.n_ch, n_cf, 0, mixed, skip_long, h->ws_smr, bit_alloc, status, s2);
+    };
+    /* the gain-shape coder; stage 1: k_vq_frame over the frames of a list, 2: what follows it, 0: both over every frame */
+    auto vq = [&](int stage, const int32_t *cf_list, const int32_t *cf_count, hipStream_t s2) {
+        pacx_launch_vq(T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
+                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words, h->ws_unit_bits,
+                       entries, entry_count, entries ? entries_per_band : 0, stage, cf_list, cf_count, h->force.vq_frame,
+                       h->force.vq_bfs, s2);
+    };
     const bool split = mixed && fast && h->force.split_short != 0;
     if (split) {
         /* a block-switched batch: the long-coded and the short-coded frames are two independent chains up
@@ -1213,75 +1176,47 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
              short:  k_mdct_short -> k_side_short -> k_mask<128> -> k_bitalloc
            side by side on two streams; the side chains and the short MDCT go by the flags alone and start
            while the frame lists are made */
-        int32_t *const list_long = h->ws_lists, *const list_short = h->ws_lists + n_cf, *const counts = h->ws_lists + 2 * n_cf;
         const int vq_fuse_split = h->force.vq_fuse_alloc != 0;  /* PACX_VQ_FUSE_ALLOC=0: k_bitalloc behind the mask kernel */
         HIP_TRY(h, hipEventRecord(h->ev_fork, st));
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_fork, 0));
-        pacx_launch_frame_lists(frame_flags, in->n_frames, n_ch, list_long, list_short, counts, st);
+        s.lists(st);
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_lists, st));
         /* short chain */
-        pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
-                         h->short_stream);
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, nullptr, nullptr, h->short_stream);
+        s.mdct_short(h->short_stream);
+        s.side(PACX_PART_SHORT, false, h->short_stream);
         HIP_TRY_FORKED(h, hipStreamWaitEvent(h->short_stream, h->ev_lists, 0));
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_SHORT, h->ws_peaks, h->ws_nkept, h->ws_lines,
-                         h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, nullptr, h->short_stream);
-        pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, 1, h->ws_smr, bit_alloc, status, h->short_stream);
+        s.mask(PACX_PART_SHORT, nullptr, h->short_stream);
+        bitalloc(1, h->short_stream);
         /* Each chain goes on into the gain-shape coder with its own frames: two k_vq_frame launches side by side on
            the two streams (0.685 ms per shipped128 step with direct launches, against 0.74-0.77 ms for one launch
            over all frames behind the join of the two chains).  Replayed from a hipGraph the two launches do not
            overlap (0.822 ms): bench.py does not capture gain-shape steps */
-        pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                       h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_short, counts + 1,
-                       h->force.vq_frame, h->force.vq_bfs, h->short_stream);
+        vq(1, s.list_short, s.counts + 1, h->short_stream);
         HIP_TRY_FORKED(h, hipEventRecord(h->ev_short_done, h->short_stream));
         /* long chain */
-        pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
-                            list_long, counts, st);
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_npeaks,
-                         h->ws_nkept, T.use_sbr ? h->ws_sbr_mean : nullptr, T.use_sbr ? overall_scale : nullptr, st);
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed | PACX_PART_LONG, h->ws_peaks, h->ws_nkept, h->ws_lines,
-                         h->ws_smr, nullptr, h->n_cu, list_long, list_short, counts, vq_fuse_split ? &mt : nullptr, st);
+        s.mdct_long(st);
+        s.side(PACX_PART_LONG, T.use_sbr, st);
+        s.mask(PACX_PART_LONG, vq_fuse_split ? &mt : nullptr, st);
         if (!vq_fuse_split)       /* BitAlloc of the long frames in k_bitalloc behind the mask kernel (part 2 = long only) */
-            pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, 2, h->ws_smr, bit_alloc, status, st);
-        pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                       h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, 1, list_long, counts,
-                       h->force.vq_frame, h->force.vq_bfs, st);
+            bitalloc(2, st);
+        vq(1, s.list_long, s.counts, st);
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_short_done, 0));       /* both chains done */
     } else {
         if (mixed)
-            pacx_launch_frame_lists(frame_flags, in->n_frames, n_ch, h->ws_lists, h->ws_lists + n_cf,
-                                    h->ws_lists + 2 * n_cf, st);
-        if (fast) {
-            pacx_launch_mdct_v2(T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status,
-                                h->n_cu, mixed ? h->ws_lists : nullptr, mixed ? h->ws_lists + 2 * n_cf : nullptr, st);
-            if (mixed)
-                pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale,
-                                 PACX_SUB, status, st);
-        } else {
-            pacx_launch_mdct(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale,
-                             PACX_SUB, status, st);
-        }
+            s.lists(st);
+        s.mdct(st);
         /* the side chain follows the MDCT on the same stream: with SBR it folds max|FFT| into the overall scale
            the MDCT wrote, and without SBR a fork to a second stream costs more than it hides here (0.677 against
            0.661 ms per step, A/B on one box) */
-        pacx_launch_side(T, v, in->dtype, fast, frame_flags, n_cf, 0, mixed, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
-                         T.use_sbr ? h->ws_sbr_mean : nullptr, T.use_sbr ? overall_scale : nullptr, st);
+        s.side(0, T.use_sbr, st);
         /* BitAlloc of the long frames inside the mask kernel or in k_bitalloc behind it: as with the scalar
            coder's tail, all-long batches are a little faster unfused (0.637 against 0.642 ms per step, A/B on one
            box); PACX_VQ_FUSE_ALLOC=0/1 forces either */
         const int vq_fuse = h->force.vq_fuse_alloc >= 0 ? h->force.vq_fuse_alloc : mixed;
-        pacx_launch_mask(T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                         nullptr, h->n_cu, h->ws_lists, h->ws_lists + n_cf, h->ws_lists + 2 * n_cf, vq_fuse ? &mt : nullptr, st);
-        pacx_launch_bitalloc(T, frame_flags, n_ch, n_cf, 0, mixed, vq_fuse, h->ws_smr, bit_alloc, status, st);
+        s.mask(0, vq_fuse ? &mt : nullptr, st);
+        bitalloc(vq_fuse, st);
     }
-    pacx_launch_vq(T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                   h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words,
-                   h->ws_unit_bits, entries, entry_count, entries ? entries_per_band : 0, split ? 2 : 0, nullptr, nullptr,
-                   h->force.vq_frame, h->force.vq_bfs, st);
+    vq(split ? 2 : 0, nullptr, nullptr, st);
     return post_launch(h, "pacx_encode_vq_batch");
 }
 
@@ -1533,40 +1468,6 @@ extern "C" int pacx_unpack_batch(pacx_handle *h, int64_t n_cf, const uint8_t *pa
     return post_launch(h, "pacx_unpack_batch");
 }
 
-/* the decoders' own workspaces: windowed blocks when the caller wants PCM only; lines + SBR flags (+ status words) */
-static int reserve_dec_blocks(pacx_handle *h, long long n_cf)
-{
-    if (n_cf <= h->ws_blocks_cf)
-        return PACX_OK;
-    HIP_TRY(h, hipDeviceSynchronize());
-    if (h->ws_blocks)
-        (void)hipFree(h->ws_blocks);
-    h->ws_blocks = nullptr;
-    h->ws_blocks_cf = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->ws_blocks, (size_t)n_cf * PACX_N_LONG * sizeof(double)));
-    h->ws_blocks_cf = n_cf;
-    return PACX_OK;
-}
-
-static int reserve_dec_lines(pacx_handle *h, long long n_cf)
-{
-    if (n_cf <= h->ws_dec_cf)
-        return PACX_OK;
-    HIP_TRY(h, hipDeviceSynchronize());
-    if (h->ws_dec_lines) (void)hipFree(h->ws_dec_lines);
-    if (h->ws_dec_sbr) (void)hipFree(h->ws_dec_sbr);
-    if (h->ws_dec_status) (void)hipFree(h->ws_dec_status);
-    h->ws_dec_lines = nullptr;
-    h->ws_dec_sbr = nullptr;
-    h->ws_dec_status = nullptr;
-    h->ws_dec_cf = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->ws_dec_lines, (size_t)n_cf * PACX_M_LONG * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void **)&h->ws_dec_sbr, (size_t)n_cf));
-    HIP_TRY(h, hipMalloc((void **)&h->ws_dec_status, (size_t)n_cf * sizeof(uint32_t)));
-    h->ws_dec_cf = n_cf;
-    return PACX_OK;
-}
-
 static int decode_scalar(pacx_handle *h, const char *what, int64_t n_blocks, int n_channels, const uint8_t *cf_flags,
                          const int32_t *overall_scale, const int32_t *scale_factor, const int32_t *bit_alloc,
                          const int32_t *mantissa, double *lines, double *blocks, int16_t *pcm, uint32_t *status,
@@ -1586,7 +1487,7 @@ static int decode_scalar(pacx_handle *h, const char *what, int64_t n_blocks, int
     const long long n_cf = n_blocks * n_channels;
     double *work = blocks;
     if (!work && pcm && n_cf > 0) {
-        const int rc = reserve_dec_blocks(h, n_cf);
+        const int rc = grow(h, GROW_DEC_BLOCKS, n_cf);
         if (rc != PACX_OK)
             return rc;
         work = h->ws_blocks;
@@ -1597,7 +1498,7 @@ static int decode_scalar(pacx_handle *h, const char *what, int64_t n_blocks, int
     if (n_cf > 0 && (routing || lines)) {
         /* an SBR file (PACFile.Decode, coder/pacfile.py:645-668: long blocks with a coded omitted band are
            Decode_SBR's, coder/codec.py:95-222 scalar branch), or a caller who wants the dequantised lines */
-        const int rc = reserve_dec_lines(h, n_cf);
+        const int rc = grow(h, GROW_DEC_LINES, n_cf);
         if (rc != PACX_OK)
             return rc;
         double *ln = lines ? lines : h->ws_dec_lines;
@@ -1655,14 +1556,14 @@ extern "C" int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_chan
     const long long n_cf = n_blocks * n_channels;
     hipStream_t st = (hipStream_t)stream;
     {
-        const int rc = reserve_dec_lines(h, n_cf);
+        const int rc = grow(h, GROW_DEC_LINES, n_cf);
         if (rc != PACX_OK)
             return rc;
     }
     double *ln = lines ? lines : h->ws_dec_lines;
     double *work = blocks;
     if (!work && pcm && n_cf > 0) {
-        const int rc = reserve_dec_blocks(h, n_cf);
+        const int rc = grow(h, GROW_DEC_BLOCKS, n_cf);
         if (rc != PACX_OK)
             return rc;
         work = h->ws_blocks;
@@ -1692,16 +1593,9 @@ extern "C" int pacx_index_body(pacx_handle *h, const uint8_t *body, int64_t n_bo
         return fail(h, PACX_E_UNSUPPORTED, "pacx_index_body: body too long for one call");
     HIP_TRY(h, hipSetDevice(h->device));
     PacxIndexWs ws;
-    const size_t need = pacx_index_ws_bytes(n_body, &ws);
-    if (need > h->ws_index_bytes) {
-        HIP_TRY(h, hipDeviceSynchronize());
-        if (h->ws_index)
-            (void)hipFree(h->ws_index);
-        h->ws_index = nullptr;
-        h->ws_index_bytes = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->ws_index, need));
-        h->ws_index_bytes = need;
-    }
+    const int rc = grow(h, GROW_INDEX, (long long)pacx_index_ws_bytes(n_body, &ws));
+    if (rc)
+        return rc;
     pacx_launch_index(ws, h->ws_index, body, n_body, n_channels, final != 0, max_records, (long long *)offsets, n_bytes,
                       (long long *)result, (hipStream_t)stream);
     return post_launch(h, "pacx_index_body");

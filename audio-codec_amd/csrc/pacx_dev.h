@@ -16,6 +16,10 @@
 #define PACX_SUB 8            /* short sub-blocks per frame                   */
 #define PACX_SHORT_FIRST 448  /* first sub-block starts here (long/2-short/2) */
 #define PACX_MAX_PEAKS 512    /* strict local maxima of 1025 bins             */
+/* payload slot of one channel-block, bytes and 32-bit words: >= 3 + 8*(4+8*16) + 1024*16 bits.  The packers
+   build a record in this many LDS words, pacx_payload_stride() reports it and no record is longer */
+#define PACX_PAYLOAD_STRIDE 2192
+#define PACX_PAYLOAD_WORDS (PACX_PAYLOAD_STRIDE / 4)
 
 /* Tables resident in HBM for the life of a handle (all float64 / complex128). */
 struct PacxTables {

@@ -1,0 +1,133 @@
+/*
+ * pacx_launch.h -- every function of the library that crosses a translation unit without being part
+ * of the C ABI: the kernel launchers and the sizing / view helpers the k_*.hip files define and
+ * pacx_api.hip (or another k_*.hip) calls.  pacx_api.hip and each defining file include this header, and
+ * the definitions are written qualified (void pacx_k::pacx_launch_mdct(...)): a definition whose
+ * argument list differs from the declaration here does not compile, where an unqualified one would
+ * be a new overload and show only as an unresolved symbol when the library is loaded.
+ */
+#ifndef PACX_LAUNCH_H
+#define PACX_LAUNCH_H
+
+#include "../../include/pacx.h"
+#include "pacx_dev.h"
+
+struct PvqTables;        /* pvq_dev.h */
+
+namespace pacx_k {
+
+/* k_mdct.hip, k_mdct2.hip (long frames of 16-byte-aligned int16 batches), k_mdct3.hip (those without flags) */
+void pacx_launch_mdct(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
+                      const uint8_t *flags, long long n_cf, int short_blocks, int mixed, int prewin,
+                      double *lines, int32_t *scale_out, int scale_stride, uint32_t *status,
+                      hipStream_t st);
+void pacx_launch_mdct_v2(const PacxTables &T, const PacxPcmView &in, const uint8_t *flags, long long n_cf,
+                         int skip_cur, double *lines, int32_t *scale_out, int scale_stride,
+                         uint32_t *status_init, int n_cu, const int32_t *cf_list, const int32_t *cf_count,
+                         hipStream_t st);
+void pacx_launch_mdct_x2(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
+                         int32_t *scale_out, int scale_stride, uint32_t *status_init, int n_cu, hipStream_t st);
+
+/* k_psy.hip */
+void pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
+                      const uint8_t *flags, long long n_cf, int short_blocks, int mixed,
+                      PacxPeak *peaks, int32_t *n_peaks, int32_t *n_kept, double *sbr_mean,
+                      int32_t *sbr_overall, hipStream_t st);
+void pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                      int short_blocks, int mixed, const PacxPeak *peaks, const int32_t *n_peaks,
+                      const double *lines, double *smr, double *thr_out, int n_cu,
+                      const int32_t *list_long, const int32_t *list_short, const int32_t *counts,
+                      const MaskTail *tail, hipStream_t st);
+size_t pacx_smr_generic_lds(int n);
+void pacx_launch_smr_generic(long long n_blocks, int n, int nb, const double *data, const double *lines,
+                             const double *hann, const double *tw_cos, const double *tw_sin, double norm, double fstep,
+                             const double *bark, const double *quiet, const int32_t *band_lower,
+                             const int32_t *band_count, double *smr, double *thr_out, int32_t *n_peaks_out,
+                             hipStream_t st);
+
+/* k_quant.hip */
+void pacx_launch_bitalloc(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                          int short_blocks, int mixed, int skip_long, const double *smr, int32_t *bit_alloc,
+                          uint32_t *status, hipStream_t st);
+void pacx_launch_quantize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                          int short_blocks, int mixed, const double *lines, const int32_t *overall,
+                          int overall_stride, const int32_t *bit_alloc, int32_t *scale_factor,
+                          int32_t *mantissa, hipStream_t st);
+void pacx_launch_pack(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                      const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
+                      const int32_t *mantissa, const uint32_t *status, uint8_t *payload,
+                      int payload_stride, int32_t *n_bytes, hipStream_t st);
+void pacx_launch_tail(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const double *smr,
+                      const double *lines, const int32_t *overall, int32_t *bit_alloc, int32_t *scale_factor,
+                      int32_t *mantissa, uint32_t *status, uint8_t *payload, int payload_stride,
+                      int32_t *n_bytes, const int32_t *list_short, const int32_t *count_short, int skip_long,
+                      hipStream_t st);
+void pacx_launch_gather(long long n_cf, const uint8_t *payload, int payload_stride,
+                        const int32_t *n_bytes, long long *chunk_buf, long long *offs_buf, uint8_t *body,
+                        long long capacity, long long *total, hipStream_t st);
+
+/* k_misc.hip */
+void pacx_launch_frame_lists(const uint8_t *flags, long long n_frames, int n_ch, int32_t *list_long,
+                             int32_t *list_short, int32_t *counts, hipStream_t st);
+void pacx_launch_window(const double *win, long long n_rows, int len, const double *x, double *y,
+                        hipStream_t st);
+void pacx_launch_quant_elem(int op, long long n, const double *x, int scale, int a, int b, int64_t *out,
+                            hipStream_t st);
+void pacx_launch_dequant_elem(int op, long long n, const int64_t *codes, int scale, int a, int b, double *out,
+                              hipStream_t st);
+void pacx_launch_mdct_direct(long long n_rows, int a, int b, int inverse, const double *x, double *y, hipStream_t st);
+void pacx_launch_bitalloc_generic(long long n, int nb, const int32_t *n_lines, const double *budget,
+                                  int max_mant, const double *smr, int32_t *bits, hipStream_t st);
+void pacx_launch_transient_f64(long long n_blocks, int n_ch, int n, const double *blocks, double thresh, uint8_t *out,
+                               hipStream_t st);
+void pacx_launch_transient(const PacxPcmView &in, long long n_hops, int hop, uint8_t *transient,
+                           uint8_t *flags, hipStream_t st);
+
+/* k_decode.hip */
+void pacx_launch_imdct_plain(const PacxTables &T, long long n_rows, int short_blocks, const double *lines,
+                             double *blocks, hipStream_t st);
+void pacx_launch_sbr_scalar_lines(const PacxTables &T, long long n_cf, const uint8_t *cf_flags,
+                                  const int32_t *scale_factor, const int32_t *bit_alloc, const int32_t *mantissa,
+                                  double *lines, uint8_t *sbr_flag, int routing, hipStream_t st);
+void pacx_launch_unpack(const PacxTables &T, long long n_cf, const uint8_t *payload, int payload_stride,
+                        const long long *offsets, const int32_t *n_bytes, uint8_t *flags_out, int32_t *overall,
+                        int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,
+                        hipStream_t st);
+void pacx_launch_decode(const PacxTables &T, long long n_blocks, int n_ch, const uint8_t *cf_flags,
+                        const int32_t *overall, const int32_t *scale_factor, const int32_t *bit_alloc,
+                        const int32_t *mantissa, const double *lines_in, double *blocks, int16_t *pcm,
+                        hipStream_t st);
+void pacx_launch_ola_tail(long long n_blocks, int n_ch, const double *blocks, double *tail, int flush, int16_t *pcm,
+                          hipStream_t st);
+
+/* k_index.hip */
+size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws);
+void pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
+                       long long max_records, long long *offsets, int32_t *n_bytes, long long *result, hipStream_t st);
+
+/* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
+void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
+                    const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,
+                    uint32_t *status, uint8_t *payload, int payload_stride, int32_t *n_bytes,
+                    unsigned *unit_words, int32_t *unit_bits, pacx_vq_entry *log, int32_t *log_count,
+                    int log_cap, int stage, const int32_t *cf_list, const int32_t *cf_count, int frame, int bfs,
+                    hipStream_t st);
+size_t pacx_vq_view_size(void);
+void pacx_vq_view_fill(void *dst, const PvqTables &tab, double log_mu1, const double *log2_tan,
+                       const int32_t *sizes_long, int nb_long, const int32_t *sizes_short, int nb_short);
+
+/* k_vq_dec.hip */
+size_t pacx_vqdec_view_size(void);
+void pacx_vqdec_view_fill(void *dst, const PvqTables &tab, const double *log2_tan, const double *gauss,
+                          int gauss_r, const double *line_freq, const int32_t *sizes_long, int nb_long,
+                          const int32_t *sizes_short, int nb_short);
+void pacx_launch_vq_dec(const PacxTables &T, const void *view, long long n_cf, const uint8_t *payload,
+                        int payload_stride, const long long *offsets, const int32_t *n_bytes,
+                        uint8_t *cf_flags, int32_t *overall, int32_t *bit_alloc, double *lines,
+                        uint8_t *sbr_flag, uint32_t *status, int frame, hipStream_t st);
+void pacx_launch_sbr_recon(const PacxTables &T, const void *view, long long n_cf, const uint8_t *sbr_flag,
+                           double *lines, uint32_t *status, hipStream_t st);
+
+}  // namespace pacx_k
+
+#endif

@@ -286,8 +286,6 @@ __device__ __forceinline__ void quantize_long_core(const PacxTables &T, const do
 }
 
 /* -------------------------------------------------------------------- pack */
-#define PACX_PACK_WORDS 548            /* 2192 bytes >= 3 + 8*(4+8*16) + 1024*16 bits */
-
 __device__ __forceinline__ void put_bits(unsigned *words, int pos, unsigned val, int width)
 {
     /* stream bit p lives in word p>>5 at bit 31-(p&31) (MSB first) */
