@@ -139,7 +139,13 @@ SIGNATURES = {
     "pacx_bitalloc_generic": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P, _P]),
     "pacx_index_body": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P, _P, _P, _P]),
     "pacx_overlap_add_pcm": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P]),
+    "pacx_nmr_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pacx_nmr_summary": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
 }
+# the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
+NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320
+NMR_HIST_LO, NMR_HIST_STEP = -120.0, 0.5
+NMR_SUMMARY_WORDS = NMR_HIST + NMR_HIST_BINS + 2
 INDEX_SEGMENT = 8192          # PACX_IX_SEG (csrc/body_index.h): bytes mapped by one workgroup of pacx_index_body
 (WIN_SINE, WIN_START, WIN_STOP, WIN_STARTSTOP, WIN_SINE_SHORT, WIN_HANN, WIN_HANN_SHORT, WIN_KBD,
  WIN_KBD_SHORT) = range(9)

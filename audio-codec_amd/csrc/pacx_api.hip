@@ -100,6 +100,8 @@ struct pacx_handle {
     int32_t *ws_unit_bits;            /* [ws_vq_cf*8][2]                        */
     long long ws_index_bytes;         /* capacity of ws_index                   */
     char *ws_index;                   /* pacx_index_body's tables (PacxIndexWs)  */
+    long long ws_thr_cf;              /* capacity of ws_thr (0 until the first pacx_nmr_batch) */
+    double *ws_thr;                   /* [cf][1024] masked threshold, dB SPL     */
     std::string err;
 };
 
@@ -309,6 +311,8 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->ws_unit_bits = nullptr;
     h->ws_index_bytes = 0;
     h->ws_index = nullptr;
+    h->ws_thr_cf = 0;
+    h->ws_thr = nullptr;
     h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
     h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
     h->ws_lists = nullptr;
@@ -600,7 +604,7 @@ static int post_launch_forked(pacx_handle *h, const char *what)
 
 /* The buffers outside pacx_reserve's workspace: each group has a capacity of its own (channel-frames; bytes for
    the index) and only ever grows, on the first call that needs more. */
-enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_INDEX, GROW_N };
+enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_N };
 struct GrowGroup {
     long long *cap;
     struct { void **p; size_t unit; } buf[3];       /* unit: bytes per unit of capacity; p == nullptr ends the group */
@@ -621,6 +625,9 @@ static GrowGroup grow_group(pacx_handle *h, int which)
         return {&h->ws_dec_cf, {{(void **)&h->ws_dec_lines, PACX_M_LONG * sizeof(double)},
                                 {(void **)&h->ws_dec_sbr, 1},
                                 {(void **)&h->ws_dec_status, sizeof(uint32_t)}}};
+    /* pacx_nmr_batch: the masked threshold of every line */
+    case GROW_NMR:
+        return {&h->ws_thr_cf, {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)}}};
     default:
         return {&h->ws_index_bytes, {{(void **)&h->ws_index, 1}}};
     }
@@ -695,10 +702,17 @@ extern "C" int pacx_reserve(pacx_handle *h, int64_t n_cf)
 {
     if (!h || n_cf < 0)
         return fail(h, PACX_E_ARG, "pacx_reserve: bad argument");
-    if (n_cf <= h->ws_cf)
-        return PACX_OK;
     if (n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, "pacx_reserve: too many channel-frames for one call");
+    /* a handle that has served pacx_nmr_batch keeps its threshold buffer as large as the workspace */
+    if (h->ws_thr_cf > 0 && n_cf > h->ws_thr_cf) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        int rc = grow(h, GROW_NMR, n_cf);
+        if (rc)
+            return rc;
+    }
+    if (n_cf <= h->ws_cf)
+        return PACX_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipDeviceSynchronize());
     free_ws(h);
@@ -1611,4 +1625,55 @@ extern "C" int pacx_overlap_add_pcm(pacx_handle *h, int64_t n_blocks, int n_chan
     HIP_TRY(h, hipSetDevice(h->device));
     pacx_launch_ola_tail(n_blocks, n_channels, blocks, tail, flush != 0, pcm, (hipStream_t)stream);
     return post_launch(h, "pacx_overlap_add_pcm");
+}
+
+/* ---- quality of an encode: noise-to-mask ratios ---- */
+extern "C" int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, const double *dec_lines,
+                              const int32_t *overall_scale, const uint32_t *status, double *noise, double *mask,
+                              double *nmr_db, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (n_cf == 0)
+        return PACX_OK;
+    if (!dec_lines || !overall_scale || !noise || !mask || !nmr_db)
+        return fail(h, PACX_E_ARG, "pacx_nmr_batch: null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    /* the encoder's own front end on one stream: the original's lines in ws_lines (its overall scales go to the
+       workspace and are not used: the noise is taken against the scales the decoder read), the maskers, then the
+       masked threshold of every line */
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, nullptr);
+    if (s.mixed)
+        s.lists(st);
+    s.mdct(st);
+    s.side(0, false, st);
+    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    pacx_launch_nmr(h->T, frame_flags, s.n_ch, n_cf, h->ws_lines, dec_lines, overall_scale, h->ws_thr, status, noise, mask,
+                    nmr_db, st);
+    return post_launch(h, "pacx_nmr_batch");
+}
+
+extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
+                                const double *nmr_db, uint64_t *summary, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (n_cf == 0)
+        return PACX_OK;
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB || n_channels < 1 || !nmr_db || !summary)
+        return fail(h, PACX_E_ARG, "pacx_nmr_summary: bad argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_nmr_summary(h->T, frame_flags, n_channels, n_cf, nmr_db, (unsigned long long *)summary,
+                            (hipStream_t)stream);
+    return post_launch(h, "pacx_nmr_summary");
 }

@@ -105,6 +105,13 @@ size_t pacx_index_ws_bytes(long long n_body, PacxIndexWs *ws);
 void pacx_launch_index(const PacxIndexWs &ws, char *mem, const uint8_t *body, long long n_body, int n_ch, int final,
                        long long max_records, long long *offsets, int32_t *n_bytes, long long *result, hipStream_t st);
 
+/* k_nmr.hip */
+void pacx_launch_nmr(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const double *lines,
+                     const double *dec_lines, const int32_t *overall, const double *thr, const uint32_t *status,
+                     double *noise, double *mask, double *nmr_db, hipStream_t st);
+void pacx_launch_nmr_summary(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                             const double *nmr_db, unsigned long long *summary, hipStream_t st);
+
 /* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,

@@ -444,6 +444,39 @@ class Encoder:
                    _ptr(pcm), self._stream())
         return pcm
 
+    # --------------------------------------------------- quality of an encode
+    def nmr(self, view, flags, dec_lines, overall_scale, status=None):
+        """Noise-to-mask ratio of every band of every coded block (pacx_nmr_batch, include/pacx.h): view is the
+        ORIGINAL PCM, flags the frame flags the blocks were coded with, dec_lines [n_cf, 1024] the decoders' `lines`
+        (before / 2^overall), overall_scale int32 [n_cf, 8]; status (optional, int32 [n_cf]): frames without a defined
+        payload get NaN.  -> dict of float64 [n_cf, band_stride]: noise (N_b), mask (M_b), nmr_db; unused slots NaN."""
+        n_cf = view.n_cf
+        fl = self.flags_tensor(flags, view.n_frames)
+        dec_lines = dec_lines.contiguous().view(n_cf, N_LONG)
+        overall_scale = overall_scale.contiguous().view(n_cf, _lib.SUB)
+        assert dec_lines.dtype == torch.float64 and overall_scale.dtype == torch.int32
+        if status is not None:
+            status = status.contiguous()
+            assert status.dtype == torch.int32 and status.numel() == n_cf
+        out = {k: self._empty((n_cf, self.band_stride), torch.float64) for k in ("noise", "mask", "nmr_db")}
+        self._call("pacx_nmr_batch", ctypes.byref(view.c), _ptr(fl), _ptr(dec_lines), _ptr(overall_scale), _ptr(status),
+                   _ptr(out["noise"]), _ptr(out["mask"]), _ptr(out["nmr_db"]), self._stream())
+        return out
+
+    def nmr_summary(self, nmr_db, n_channels, flags=None, summary=None):
+        """Adds the values of nmr_db [n_cf, band_stride] to `summary` (pacx_nmr_summary: int64 device tensor
+        [2, 32, NMR_SUMMARY_WORDS] holding the library's uint64 words -- long blocks / short sub-blocks, per band
+        index: count, count above 0 dB, maximum as an ordered key, 0.5 dB histogram); None: a zeroed one.  Chunks
+        of a stream accumulate in one summary.  quality.Summary reads it."""
+        nmr_db = nmr_db.contiguous()
+        n_cf = nmr_db.shape[0]
+        fl = self.flags_tensor(flags, n_cf // n_channels)
+        if summary is None:
+            summary = torch.zeros((2, _lib.NMR_MAX_BANDS, _lib.NMR_SUMMARY_WORDS), dtype=torch.int64, device=self.device)
+        self._call("pacx_nmr_summary", ctypes.c_int64(n_cf), int(n_channels), _ptr(fl), _ptr(nmr_db), _ptr(summary),
+                   self._stream())
+        return summary
+
     # ------------------------------------------- function-level entry points
     def window(self, kind, x):
         """window * x for rows of x ([n, 2048] or [n, 256] float64 on the GPU)."""

@@ -1,0 +1,360 @@
+"""How good is an encode: per-band noise-to-mask ratios (NMR) of a .pac stream, computed on the GPU.
+
+The reference judges an encode by eye (test_sbr.py / test_blockswitch.py plot spectrograms).  Here every coded
+band of every block gets the standard number of a perceptual coder: the coding noise in the band against the
+masked threshold the encoder's own psychoacoustic model computed for it,
+
+    NMR_b = 10 log10((mean 4 (X - Xh)^2 + eps) / mean 10^((T - 96) / 10))        (include/pacx.h, pacx_nmr_batch)
+
+with X the original's MDCT lines, Xh the lines the decoder hands to the IMDCT and T getMaskedThreshold of the
+original block.  Above 0 dB the noise of the band is predicted to be audible.
+
+    pac, rep = encode_stream_report(pcm, 48000, 96)          # the bytes of pacfile.encode_stream + a Report
+    rep = nmr_of_file(pcm, pac_bytes)                        # a .pac made elsewhere, e.g. by the reference itself
+    rep.percentile(50), rep.share_audible(), rep.nmr_db[hop, ch, band]
+
+Both work through the stream in chunks of at most chunk_hops blocks: PCM in, payloads decoded to lines by the
+existing decoders, pacx_nmr_batch, pacx_nmr_summary; the summary accumulates on the device across chunks and
+only the three band arrays (3 x band_stride doubles per channel-block) come back per chunk.
+"""
+import numpy as np
+
+from . import _lib
+
+HOP = 1024
+_NO_PAYLOAD = _lib.ST_ZERO_SUBBLOCK | _lib.ST_VQ_UNDEFINED | _lib.ST_MALFORMED | _lib.ST_REF_RAISES
+_LO, _STEP, _BINS = _lib.NMR_HIST_LO, _lib.NMR_HIST_STEP, _lib.NMR_HIST_BINS
+
+
+class Summary:
+    """Counts, counts above 0 dB, maxima and 0.5 dB histograms of NMR values per band index, long blocks (kind 0)
+    and short sub-blocks (kind 1) apart: the host's view of pacx_nmr_summary's words.
+
+      count, audible  int64 [2, 32];   max  float64 [2, 32] (NaN: no value);
+      hist            int64 [2, 32, BINS + 2]: [0] below -120 dB, [1 + i] the bin from -120 + i/2 dB, [-1] from +40 dB."""
+
+    def __init__(self, count, audible, maximum, hist):
+        self.count, self.audible = np.asarray(count, np.int64), np.asarray(audible, np.int64)
+        self.max, self.hist = np.asarray(maximum, np.float64), np.asarray(hist, np.int64)
+
+    @classmethod
+    def from_words(cls, words):
+        """words: uint64 [2, 32, NMR_SUMMARY_WORDS] as the library keeps them (an int64 array holding them is fine)"""
+        w = np.ascontiguousarray(words).view(np.uint64).reshape(2, _lib.NMR_MAX_BANDS, _lib.NMR_SUMMARY_WORDS)
+        key = w[:, :, _lib.NMR_MAX]
+        bits = np.where(key >> np.uint64(63), key & np.uint64(0x7FFFFFFFFFFFFFFF), ~key)     # the ordered key undone
+        maximum = np.where(key == 0, np.nan, bits.astype(np.uint64).view(np.float64))
+        return cls(w[:, :, _lib.NMR_COUNT].astype(np.int64), w[:, :, _lib.NMR_AUDIBLE].astype(np.int64), maximum,
+                   w[:, :, _lib.NMR_HIST:].astype(np.int64))
+
+    @classmethod
+    def from_values(cls, nmr_db, short, n_bands_long, n_bands_short):
+        """The same summary from the band arrays, on the host: nmr_db [hops, nCh, band_stride], short bool [hops]."""
+        nmr_db, short = np.asarray(nmr_db, np.float64), np.asarray(short, bool)
+        nb = _lib.NMR_MAX_BANDS
+        count, audible = np.zeros((2, nb), np.int64), np.zeros((2, nb), np.int64)
+        maximum, hist = np.full((2, nb), np.nan), np.zeros((2, nb, _BINS + 2), np.int64)
+        for kind, (sel, n_b, per) in enumerate(((~short, n_bands_long, 1), (short, n_bands_short, _lib.SUB))):
+            rows = nmr_db[sel]
+            if not rows.size:
+                continue
+            vals = rows[:, :, :per * n_b].reshape(-1, per, n_b)
+            for b in range(n_b):
+                v = vals[:, :, b].ravel()
+                v = v[~np.isnan(v)]
+                if not v.size:
+                    continue
+                count[kind, b], audible[kind, b], maximum[kind, b] = v.size, np.count_nonzero(v > 0.0), v.max()
+                pos = np.floor((v - _LO) / _STEP)
+                idx = np.where(pos < 0, 0, np.where(pos >= _BINS, _BINS + 1, 1 + np.clip(pos, 0, _BINS - 1))).astype(np.int64)
+                hist[kind, b] = np.bincount(idx, minlength=_BINS + 2)
+        return cls(count, audible, maximum, hist)
+
+    def __eq__(self, other):
+        return (np.array_equal(self.count, other.count) and np.array_equal(self.audible, other.audible) and
+                np.array_equal(self.hist, other.hist) and np.array_equal(self.max, other.max, equal_nan=True))
+
+    def _pick(self, arr, kind, band):
+        a = arr if kind is None else arr[kind:kind + 1]
+        return a if band is None else a[:, band:band + 1]
+
+    def share_audible(self, kind=None, band=None):
+        """share of the values above 0 dB (NaN without values); kind 0 / 1: long blocks / short sub-blocks only"""
+        n = int(self._pick(self.count, kind, band).sum())
+        return float(self._pick(self.audible, kind, band).sum()) / n if n else float("nan")
+
+    def maximum(self, kind=None, band=None):
+        m = self._pick(self.max, kind, band)
+        return float(np.nanmax(m)) if np.any(~np.isnan(m)) else float("nan")
+
+    def percentile(self, q, kind=None, band=None):
+        """The q-th percentile (0..100) of the values, read from the histogram: the value of rank ceil(q/100 n) lies
+        in the bin this finds, and the answer is placed inside that bin by its rank -- within one bin width (0.5 dB)
+        of the order statistic.  A rank in the underflow bin gives -120 dB, one in the overflow bin the maximum."""
+        h = self._pick(self.hist, kind, band).reshape(-1, _BINS + 2).sum(axis=0)
+        n = int(h.sum())
+        if not n:
+            return float("nan")
+        rank = min(max(int(np.ceil(q / 100.0 * n)), 1), n)
+        cum = np.cumsum(h)
+        i = int(np.searchsorted(cum, rank))
+        if i == 0:
+            return _LO
+        if i == _BINS + 1:
+            return self.maximum(kind, band)
+        before = int(cum[i - 1])
+        return _LO + _STEP * ((i - 1) + (rank - before - 0.5) / int(h[i]))
+
+
+class Report:
+    """NMR of a stream, per block the driver writes (every hop, the last hop a second time, the Close block):
+
+      nmr_db, noise, mask  float64 [hops, nCh, band_stride]: NMR_b in dB, N_b, M_b; a short-coded block holds
+                           8 x n_bands_short values (sub-block j at [j * n_bands_short ...]); unused slots are NaN, and
+                           so is a block without a payload (a dropped short-coded hop, PACX_ST_REF_RAISES, a record
+                           the decoder reports as malformed or undefined);
+      short                bool [hops]: coded as eight short sub-blocks;
+      record               int64 [hops]: index of the block's first record in the file, -1 for a dropped hop;
+      summary              Summary (from the device when the report was computed there, else from the arrays).
+
+    Constructible from arrays alone (no GPU): Report(nmr_db, noise, mask, short, n_bands_long, n_bands_short)."""
+
+    def __init__(self, nmr_db, noise, mask, short, n_bands_long, n_bands_short, summary=None, record=None):
+        self.nmr_db, self.noise, self.mask = (np.asarray(a, np.float64) for a in (nmr_db, noise, mask))
+        self.short = np.asarray(short, bool)
+        self.n_bands_long, self.n_bands_short = int(n_bands_long), int(n_bands_short)
+        assert self.nmr_db.ndim == 3 and self.nmr_db.shape == self.noise.shape == self.mask.shape
+        assert self.short.shape == (self.nmr_db.shape[0],)
+        self.record = None if record is None else np.asarray(record, np.int64)
+        self.summary = summary if summary is not None else self.host_summary()
+
+    def host_summary(self):
+        return Summary.from_values(self.nmr_db, self.short, self.n_bands_long, self.n_bands_short)
+
+    def percentile(self, q, kind=None, band=None):
+        return self.summary.percentile(q, kind, band)
+
+    def median(self, kind=None, band=None):
+        return self.summary.percentile(50, kind, band)
+
+    def share_audible(self, kind=None, band=None):
+        return self.summary.share_audible(kind, band)
+
+    def maximum(self, kind=None, band=None):
+        return self.summary.maximum(kind, band)
+
+
+# ------------------------------------------------------------------------------------------- the hop-to-record map
+def flags_from_transients(tr):
+    """Flag bytes (last | cur << 1 | next << 2) of the n + 2 blocks the driver writes for n hops, from the
+    detector's decision per hop (coder/pacfile.py:717-741: the decision about hop h is `next` of block h, `cur`
+    of block h + 1, `last` of block h + 2; the pass after EOF detects nothing and Close writes 0, 0, 0)."""
+    tr = (np.asarray(tr) != 0).astype(np.uint8)
+    n = len(tr)
+    ext = np.concatenate((np.zeros(2, np.uint8), tr, np.zeros(2, np.uint8)))
+    flags = ext[:n + 2] | (ext[1:n + 3] << 1) | (ext[2:n + 4] << 2)
+    if n + 2:
+        flags[-1] = 0
+    return flags.astype(np.uint8)
+
+
+def padded_stream(pcm, hop=HOP):
+    """int16 [nCh, (n_hops + 3) * hop]: zeros, the hops, the last hop again, zeros -- block f of the driver is
+    hops f, f + 1 of this (pacfile.device_stream's layout, on the host)."""
+    n, n_ch = pcm.shape
+    n_hops = n // hop
+    buf = np.zeros((n_ch, (n_hops + 3) * hop), dtype=np.int16)
+    buf[:, hop:hop + n] = pcm.T
+    if n_hops:
+        buf[:, hop + n:2 * hop + n] = pcm[n - hop:].T
+    return buf
+
+
+def dropped_blocks(buf, flags, hop=HOP):
+    """bool per block: short-coded with an all-zero 256-sample sub-block in some channel -- the reference writes
+    nothing for such a hop (coder/pacfile.py:530-533).  -32768 reads as -0.0 (coder/pcmfile.py:89-99)."""
+    n_blocks = len(flags)
+    out = np.zeros(n_blocks, bool)
+    for f in np.nonzero(np.asarray(flags) & _lib.FLAG_CUR)[0]:
+        full = np.abs(buf[:, f * hop:(f + 2) * hop].astype(np.int32)) & 32767
+        for j in range(_lib.SUB):
+            at = hop // 2 - 64 + 128 * j
+            if np.any(np.all(full[:, at:at + 256] == 0, axis=1)):
+                out[f] = True
+                break
+    return out
+
+
+def record_map(flags, dropped, n_channels):
+    """index of the first record of every block (-1: dropped) and the number of records the file must hold"""
+    rec = np.full(len(flags), -1, np.int64)
+    kept = ~np.asarray(dropped, bool)
+    rec[kept] = np.arange(int(kept.sum()), dtype=np.int64) * n_channels
+    return rec, int(kept.sum()) * n_channels
+
+
+# ------------------------------------------------------------------------------------------------- the chunk loop
+class _Accumulator:
+    def __init__(self, enc, n_blocks, n_ch):
+        import torch
+        self.enc, self.n_ch = enc, n_ch
+        shape = (n_blocks, n_ch, enc.band_stride)
+        self.arrays = {k: np.empty(shape, np.float64) for k in ("nmr_db", "noise", "mask")}
+        self.words = torch.zeros((2, _lib.NMR_MAX_BANDS, _lib.NMR_SUMMARY_WORDS), dtype=torch.int64, device=enc.device)
+
+    def chunk(self, f0, view, flags, payload, n_bytes, status):
+        """decode the chunk's payloads (slot layout) to lines, NMR against the original in `view`, add to the summary"""
+        import torch
+        enc, n_ch = self.enc, self.n_ch
+        if enc.use_vq:
+            dec = enc.decode_vq(payload, n_bytes, n_ch, want_lines=True, want_pcm=False)
+            lines, overall, dec_status = dec["lines"], dec["overall"], dec["status"]
+        else:
+            codes = enc.unpack(payload, n_bytes)
+            extra = {}
+            enc.decode(codes, n_ch, want_pcm=False, extra=extra)
+            lines, overall, dec_status = extra["lines"], codes["overall"], codes["status"] | extra["status"]
+        status = (status | dec_status) & _NO_PAYLOAD
+        status = torch.where(n_bytes > 0, status, torch.full_like(status, _lib.ST_ZERO_SUBBLOCK))
+        r = enc.nmr(view, flags, lines, overall, status)
+        enc.nmr_summary(r["nmr_db"], n_ch, flags, self.words)
+        n = view.n_frames
+        for k, a in self.arrays.items():
+            a[f0:f0 + n] = r[k].cpu().numpy().reshape(n, n_ch, -1)
+
+    def report(self, enc, flags, record):
+        short = (np.asarray(flags) & _lib.FLAG_CUR) != 0
+        return Report(self.arrays["nmr_db"], self.arrays["noise"], self.arrays["mask"], short, enc.sfBands.nBands,
+                      enc.sfBandsShort.nBands, Summary.from_words(self.words.cpu().numpy()), record)
+
+
+def _transients(enc, buf, n_hops, chunk_hops):
+    """the detector's decision per hop, chunk by chunk on the GPU (pacx_transient_flags)"""
+    import ctypes
+    import torch
+    from .engine import _ptr
+    tr = np.zeros(n_hops, np.uint8)
+    n_ch = buf.shape[0]
+    for h0 in range(0, n_hops, chunk_hops):
+        n = min(chunk_hops, n_hops - h0)
+        dev = torch.as_tensor(np.ascontiguousarray(buf[:, (h0 + 1) * HOP:(h0 + 1 + n) * HOP]), device=enc.device)
+        hops = _lib.PacxPcm(dev.data_ptr(), _lib.PCM_I16, n_ch, n, HOP, n * HOP, 1)
+        out = torch.empty(n, dtype=torch.uint8, device=enc.device)
+        enc._call("pacx_transient_flags", ctypes.byref(hops), _ptr(out), None, enc._stream())
+        tr[h0:h0 + n] = out.cpu().numpy()
+    return tr
+
+
+def _chunk_view(enc, buf, f0, n):
+    import torch
+    from .engine import PcmView
+    planar = torch.as_tensor(np.ascontiguousarray(buf[:, f0 * HOP:(f0 + n + 1) * HOP]), device=enc.device)
+    return PcmView.stream(planar, HOP)
+
+
+def _check_stream(pcm, n_lines):
+    if int(n_lines) != HOP:
+        raise NotImplementedError("the NMR report covers streams of nMDCTLines = 1024")
+    pcm = np.ascontiguousarray(pcm)
+    if pcm.ndim != 2 or pcm.dtype != np.int16 or len(pcm) % HOP:
+        raise ValueError("pcm: int16 [n, nCh], n a multiple of 1024")
+    return pcm
+
+
+def encode_stream_report(pcm, sample_rate, kbps_per_channel, block_switching=False, header_samples=None,
+                         n_scale_bits=4, n_mant_size_bits=12, use_vq=False, use_sbr=False, chunk_hops=4096, n_lines=1024):
+    """pacfile.encode_stream with a Report: -> (.pac bytes, Report).  The bytes are encode_stream's for the same
+    arguments; the report is computed from the payloads just written (unpacked / decoded to lines by the existing
+    decoders).  At most chunk_hops blocks are on the device at a time."""
+    import torch
+    from . import context, pacfile
+    from .audiofile import CodingParams
+    pcm = _check_stream(pcm, n_lines)
+    chunk_hops = max(1, int(chunk_hops or 4096))
+    cp = CodingParams()
+    cp.sampleRate, cp.nChannels = int(sample_rate), pcm.shape[1]
+    cp.numSamples = len(pcm) if header_samples is None else int(header_samples)
+    cp.nMDCTLines = cp.nSamplesPerBlock = HOP
+    cp.nScaleBits, cp.nMantSizeBits = n_scale_bits, n_mant_size_bits
+    cp.targetBitsPerSample = kbps_per_channel / (cp.sampleRate / 1000)
+    cp.useSBR, cp.useVQ = bool(use_sbr), bool(use_vq)
+    parts = [pacfile.header_bytes(cp)]
+    enc = context.encoder_for_params(cp)
+    n_ch, n_hops = pcm.shape[1], len(pcm) // HOP
+    buf = padded_stream(pcm)
+    n_blocks = n_hops + 2
+    flags = flags_from_transients(_transients(enc, buf, n_hops, chunk_hops)) if block_switching \
+        else np.zeros(n_blocks, np.uint8)
+    acc = _Accumulator(enc, n_blocks, n_ch)
+    written = np.zeros(n_blocks, bool)
+    for f0 in range(0, n_blocks, chunk_hops):
+        n = min(chunk_hops, n_blocks - f0)
+        view = _chunk_view(enc, buf, f0, n)
+        fl = torch.as_tensor(flags[f0:f0 + n], device=enc.device) if block_switching else None
+        if use_vq:
+            out = enc.encode_vq(view, fl)
+        else:
+            out = enc.encode_pack(view, fl)
+            pacfile._raise_like_reference(out)
+        body, total = enc.gather_body(out["payload"], out["n_bytes"])
+        parts.append(body[:int(total.item())].cpu().numpy().tobytes())
+        written[f0:f0 + n] = out["n_bytes"].view(n, n_ch)[:, 0].cpu().numpy() > 0
+        acc.chunk(f0, view, fl, out["payload"], out["n_bytes"], out["status"])
+    record, _ = record_map(flags, ~written, n_ch)
+    return b"".join(parts), acc.report(enc, flags, record)
+
+
+def nmr_of_file(pcm, pac_bytes, block_switching=None, chunk_hops=4096):
+    """Report of a .pac made elsewhere (by the reference itself, say) against the PCM it was made from.  The
+    hop-to-record map is re-derived the way the writer makes it: the transient detector gives the flags, a
+    short-coded hop with an all-zero sub-block is absent from the file, the last hop is written twice and Close
+    adds a block of zeros.  block_switching None: a file none of whose records carries a flag and that holds
+    every block was written without block switching.  ValueError when a record's flag bits or the number of
+    records disagree with the map (the PCM is not what the file was made from)."""
+    import torch
+    from . import context, pacfile
+    data = bytes(pac_bytes)
+    cp, pos = pacfile.parse_header(data)
+    pcm = _check_stream(pcm, cp.nMDCTLines)
+    if pcm.shape[1] != cp.nChannels:
+        raise ValueError(f"the file has {cp.nChannels} channels, the PCM {pcm.shape[1]}")
+    chunk_hops = max(1, int(chunk_hops or 4096))
+    enc = context.encoder_for_params(cp)
+    n_ch, n_hops = cp.nChannels, len(pcm) // HOP
+    n_blocks = n_hops + 2
+    offs, sizes = pacfile.record_chain(data, pos, enc.payload_stride)
+    raw = np.frombuffer(data, np.uint8)
+    first = raw[np.asarray(offs, np.int64)] if offs else np.zeros(0, np.uint8)
+    rec_flags = ((first >> 7) & 1) | (((first >> 6) & 1) << 1) | (((first >> 5) & 1) << 2)      # last | cur | next, MSB first
+    buf = padded_stream(pcm)
+    if block_switching is None:
+        block_switching = bool(rec_flags.any()) or len(offs) != n_blocks * n_ch
+    flags = flags_from_transients(_transients(enc, buf, n_hops, chunk_hops)) if block_switching \
+        else np.zeros(n_blocks, np.uint8)
+    dropped = dropped_blocks(buf, flags)
+    record, n_records = record_map(flags, dropped, n_ch)
+    if len(offs) != n_records:
+        raise ValueError(f"the file holds {len(offs)} records, this PCM gives {n_records}")
+    want = np.repeat(flags[~dropped], n_ch)
+    if not np.array_equal(rec_flags, want):
+        bad = int(np.nonzero(rec_flags != want)[0][0])
+        raise ValueError(f"record {bad} carries the flags {int(rec_flags[bad])}, this PCM gives {int(want[bad])}")
+    acc = _Accumulator(enc, n_blocks, n_ch)
+    slot = enc.payload_stride
+    for f0 in range(0, n_blocks, chunk_hops):
+        n = min(chunk_hops, n_blocks - f0)
+        payload = np.zeros((n * n_ch, slot), np.uint8)
+        n_bytes = np.zeros(n * n_ch, np.int32)
+        for i in range(n):
+            r = record[f0 + i]
+            if r < 0:
+                continue
+            for ch in range(n_ch):
+                o, s = offs[r + ch], sizes[r + ch]
+                payload[i * n_ch + ch, :s] = raw[o:o + s]
+                n_bytes[i * n_ch + ch] = s
+        view = _chunk_view(enc, buf, f0, n)
+        fl = torch.as_tensor(flags[f0:f0 + n], device=enc.device) if block_switching else None
+        acc.chunk(f0, view, fl, torch.as_tensor(payload, device=enc.device), torch.as_tensor(n_bytes, device=enc.device),
+                  torch.zeros(n * n_ch, dtype=torch.int32, device=enc.device))
+    return acc.report(enc, flags, record)

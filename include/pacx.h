@@ -610,6 +610,64 @@ int pacx_index_body(pacx_handle *h, const uint8_t *body, int64_t n_body, int n_c
 int pacx_overlap_add_pcm(pacx_handle *h, int64_t n_blocks, int n_channels, const double *blocks,
                          double *tail, int flush, int16_t *pcm, void *stream);
 
+/* ---- quality of an encode: noise-to-mask ratios ---------------------------- */
+
+/*
+ * Per-band noise-to-mask ratio of coded blocks against the masked threshold the encoder's own
+ * psychoacoustic model gives for the original (no function of the reference: it judges an encode by
+ * plotting spectrograms, test_sbr.py / test_blockswitch.py).  In the reference's conventions, for one
+ * block (1024 lines and the long band table, or a 128-line sub-block and the short table):
+ *   X[k]   MDCT lines of the original with the window the frame flags select, not multiplied by
+ *          2^overallScale (pacx_mdct_batch's lines);
+ *   Xh[k]  the lines the decoder hands to the IMDCT: dec_lines[k] / 2^overall_scale;
+ *   T[k]   getMaskedThreshold of the original block in dB SPL (coder/psychoac.py:163-217,
+ *          pacx_smr_batch's threshold);
+ *   n[k] = 4 (X[k] - Xh[k])^2   the MDCT intensity normalisation of coder/psychoac.py:250-253;
+ *   m[k] = 10^((T[k] - 96) / 10)   Intensity(), coder/psychoac.py:28-32;
+ *   per band b: N_b = mean(n), M_b = mean(m) over the band's lines and
+ *   NMR_b = 10 log10((N_b + eps) / M_b), eps = 2^-52 as in the reference's SPL() -- a noiseless band
+ *   gets a finite value; SPL()'s clamps and its "exact zero -> 1e-8" rule are left out.
+ * NMR_b > 0 dB: the coding noise of the band is predicted to be audible.  Lines beyond the last band
+ * (sample rates above 48 kHz) are ignored.
+ *   in, frame_flags: the original PCM and the flags the blocks were coded with (PACX_FLAG_CUR: eight
+ *          short sub-blocks); NULL flags = all long sine blocks;
+ *   dec_lines:     float64 [n_cf][n_lines_long], the `lines` output of pacx_decode_sbr_batch /
+ *                  pacx_decode_vq_batch (BEFORE the division by 2^overallScale; short: 8 x n_lines_short);
+ *   overall_scale: int32 [n_cf][8] as the decoders and encoders write it (long frames use [0]);
+ *   status (optional): uint32 [n_cf]; a cf with PACX_ST_ZERO_SUBBLOCK, PACX_ST_MALFORMED,
+ *                  PACX_ST_VQ_UNDEFINED or PACX_ST_REF_RAISES has no defined payload: its outputs are NaN;
+ *   noise, mask, nmr_db: float64 [n_cf][band_stride]: N_b, M_b and NMR_b (short: sub-block j at
+ *                  [j*n_bands_short ...], the layout of pacx_smr_batch); unused slots hold NaN.
+ * Runs MDCT -> side chain -> masked threshold -> k_nmr on `stream`.  The threshold lives in the handle's
+ * workspace (8 KB per cf, grow-only, allocated by the first call; from then on pacx_reserve sizes it too).
+ */
+int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, const double *dec_lines,
+                   const int32_t *overall_scale, const uint32_t *status, double *noise, double *mask,
+                   double *nmr_db, void *stream);
+
+/* the summary of pacx_nmr_summary: uint64 [2][PACX_NMR_MAX_BANDS][PACX_NMR_SUMMARY_WORDS], [0] long blocks,
+ * [1] short sub-blocks, per band index.  Words: */
+#define PACX_NMR_MAX_BANDS 32
+#define PACX_NMR_COUNT 0          /* values (NaN slots are not counted)                          */
+#define PACX_NMR_AUDIBLE 1        /* values above 0 dB                                           */
+#define PACX_NMR_MAX 2            /* the maximum as a key: the bits b of the double, ~b if its sign
+                                     bit is set, else b | 2^63 (unsigned order = numeric order); 0: none */
+#define PACX_NMR_HIST 3           /* [0] v < PACX_NMR_HIST_LO, [1 + i] bin i = floor((v - LO) / STEP),
+                                     [1 + PACX_NMR_HIST_BINS] v >= LO + BINS * STEP                */
+#define PACX_NMR_HIST_BINS 320
+#define PACX_NMR_HIST_LO (-120.0) /* dB */
+#define PACX_NMR_HIST_STEP 0.5    /* dB */
+#define PACX_NMR_SUMMARY_WORDS (PACX_NMR_HIST + PACX_NMR_HIST_BINS + 2)
+
+/*
+ * Adds the nmr_db values of a batch ([n_cf][band_stride], as pacx_nmr_batch writes them) to `summary`
+ * (device; the caller zeroes it before the first batch of a stream, so chunks accumulate).  Integer
+ * atomics and a maximum only: the result does not depend on the order the values arrive in.
+ * Percentiles are read from the histogram on the host.
+ */
+int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
+                     const double *nmr_db, uint64_t *summary, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
