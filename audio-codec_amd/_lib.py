@@ -11,6 +11,9 @@ PCM_I16, PCM_F64 = 0, 1
 FLAG_LAST, FLAG_CUR, FLAG_NEXT = 1, 2, 4
 ST_SHORT, ST_ZERO_SUBBLOCK, ST_ALLOC_CAP, ST_VQ_UNDEFINED, ST_GUARD, ST_MALFORMED = 1, 2, 4, 8, 16, 32
 ST_REF_RAISES = 64
+ST_RATE_CAP = 128
+RATE_STEP = 32             # PACX_RATE_STEP: budgets of the constant-quality mode are multiples of this many bits
+E_ARG, E_UNSUPPORTED = -1, -2
 # what the reference raises where PACX_ST_REF_RAISES is set (coder/quantize.py:74, see include/pacx.h)
 REF_SCALAR_SBR_ERROR = "'numpy.int64' object does not support item assignment"
 MAX_BANDS = 32
@@ -141,6 +144,10 @@ SIGNATURES = {
     "pacx_overlap_add_pcm": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, ctypes.c_int, _P, _P]),
     "pacx_nmr_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P]),
     "pacx_nmr_summary": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int, _P, _P, _P, _P]),
+    "pacx_encode_pack_nmr_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, ctypes.c_double,
+                                                  _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pacx_encode_pack_budget_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                     _P]),
 }
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320

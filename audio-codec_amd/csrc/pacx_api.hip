@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -1661,6 +1662,85 @@ extern "C" int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t 
     pacx_launch_nmr(h->T, frame_flags, s.n_ch, n_cf, h->ws_lines, dec_lines, overall_scale, h->ws_thr, status, noise, mask,
                     nmr_db, st);
     return post_launch(h, "pacx_nmr_batch");
+}
+
+/* ---- coding to a target noise-to-mask ratio ---- */
+/* the front end of pacx_nmr_batch on one stream (lines, SMRs and, for the search, the threshold of every line), the
+   allocation by k_rate_search or from the caller's budgets, then the separate-kernel chain k_quantize -> k_pack */
+static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, bool search,
+                           double target_nmr_db, double max_bits_per_sample, const int32_t *budget_in,
+                           int32_t *overall_scale, int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa,
+                           uint32_t *status, uint8_t *payload, int32_t *n_bytes, int32_t *budget_out, void *stream,
+                           const char *what)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (search && !std::isfinite(target_nmr_db))
+        return fail(h, PACX_E_ARG, std::string(what) + ": target_nmr_db is not finite");
+    if (search && !(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (!overall_scale || !scale_factor || !bit_alloc || !status || !payload || !n_bytes ||
+        (search ? !budget_out : !budget_in))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = pacx_reserve(h, n_cf)) || (search && (rc = grow(h, GROW_NMR, n_cf))))
+        return rc;
+    if (!mantissa) {                           /* k_pack reads the mantissas back from memory */
+        if ((rc = grow(h, GROW_MANT, n_cf)))
+            return rc;
+        mantissa = h->ws_mant;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
+    }
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
+    if (s.mixed)
+        s.lists(st);
+    s.mdct(st);
+    s.side(0, false, st);
+    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                     search ? h->ws_thr : nullptr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    if (search)
+        pacx_launch_rate_search(h->T, frame_flags, s.n_ch, n_cf, target_nmr_db, max_bits_per_sample, h->ws_lines,
+                                h->ws_thr, h->ws_smr, overall_scale, budget_out, bit_alloc, status, st);
+    else
+        pacx_launch_bitalloc_budget(h->T, frame_flags, s.n_ch, n_cf, budget_in, h->ws_smr, bit_alloc, status, st);
+    pacx_launch_quantize(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_lines, overall_scale, PACX_SUB, bit_alloc,
+                         scale_factor, mantissa, st);
+    pacx_launch_pack(h->T, frame_flags, s.n_ch, n_cf, overall_scale, scale_factor, bit_alloc, mantissa, status, payload,
+                     PACX_PAYLOAD_STRIDE, n_bytes, st);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_encode_pack_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                          double target_nmr_db, double max_bits_per_sample, int32_t *overall_scale,
+                                          int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,
+                                          uint8_t *payload, int32_t *n_bytes, int32_t *budget, void *stream)
+{
+    return encode_budgeted(h, in, frame_flags, true, target_nmr_db, max_bits_per_sample, nullptr, overall_scale,
+                           scale_factor, bit_alloc, mantissa, status, payload, n_bytes, budget, stream,
+                           "pacx_encode_pack_nmr_batch");
+}
+
+extern "C" int pacx_encode_pack_budget_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                             const int32_t *budget, int32_t *overall_scale, int32_t *scale_factor,
+                                             int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
+                                             int32_t *n_bytes, void *stream)
+{
+    return encode_budgeted(h, in, frame_flags, false, 0.0, 0.0, budget, overall_scale, scale_factor, bit_alloc, mantissa,
+                           status, payload, n_bytes, nullptr, stream, "pacx_encode_pack_budget_batch");
 }
 
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,

@@ -112,6 +112,16 @@ void pacx_launch_nmr(const PacxTables &T, const uint8_t *flags, int n_ch, long l
 void pacx_launch_nmr_summary(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                              const double *nmr_db, unsigned long long *summary, hipStream_t st);
 
+/* k_rate.hip: the budget search of pacx_encode_pack_nmr_batch (one wave per long block / short sub-block; budget
+   int32 [n_cf][8], long frames use [0]) and BitAlloc with the caller's budgets */
+void pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                             double target_nmr_db, double max_bits_per_sample, const double *lines,
+                             const double *thr, const double *smr, const int32_t *overall, int32_t *budget,
+                             int32_t *bit_alloc, uint32_t *status, hipStream_t st);
+void pacx_launch_bitalloc_budget(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                                 const int32_t *budget, const double *smr, int32_t *bit_alloc, uint32_t *status,
+                                 hipStream_t st);
+
 /* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,

@@ -275,6 +275,49 @@ class Encoder:
         out["flags"] = fl
         return out
 
+    def _call_rate(self, name, *args):
+        """the constant-quality entry points: PACX_E_UNSUPPORTED (a gain-shape or SBR handle) is NotImplementedError"""
+        rc = getattr(self.lib, name)(self.h, *args)
+        if rc == _lib.E_UNSUPPORTED:
+            msg = self.lib.pacx_last_error(self.h)
+            raise NotImplementedError(f"{name}: {msg.decode() if msg else 'unsupported'}")
+        _lib.check(self.lib, self.h, rc, name)
+
+    def encode_pack_nmr(self, pcm, flags, target_nmr_db, max_bits_per_sample, out=None, want_mantissa=False):
+        """Constant quality (pacx_encode_pack_nmr_batch, include/pacx.h): every long block and short sub-block gets the
+        BitAlloc budget a bisection finds for it -- predicted noise at most target_nmr_db of the mask in every band,
+        at most the budget of the cap rate max_bits_per_sample.  Returns encode_pack()'s dict plus budget
+        [n_cf, 8] int32 (bits; long frames use [:, 0]); status carries ST_RATE_CAP where the cap was reached."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        if out is None:
+            out = self.alloc_outputs(n_cf, with_payload=True)
+        if "budget" not in out:
+            out["budget"] = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
+        self._call_rate("pacx_encode_pack_nmr_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(target_nmr_db),
+                        ctypes.c_double(max_bits_per_sample), _ptr(out["overall"]), _ptr(out["scale_factor"]),
+                        _ptr(out["bit_alloc"]), _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]),
+                        _ptr(out["payload"]), _ptr(out["n_bytes"]), _ptr(out["budget"]), self._stream())
+        out["flags"] = fl
+        return out
+
+    def encode_pack_budget(self, pcm, flags, budget, out=None, want_mantissa=False):
+        """encode_pack() with the BitAlloc budget of every long block / short sub-block given by the caller
+        (pacx_encode_pack_budget_batch): budget int32 [n_cf, 8] in bits, long frames use [:, 0]."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        budget = torch.as_tensor(budget, device=self.device).to(torch.int32).contiguous()
+        if tuple(budget.shape) != (n_cf, _lib.SUB):
+            raise ValueError(f"budget: int32 [{n_cf}, {_lib.SUB}]")
+        if out is None:
+            out = self.alloc_outputs(n_cf, with_payload=True)
+        self._call_rate("pacx_encode_pack_budget_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(budget),
+                        _ptr(out["overall"]), _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
+                        _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]), _ptr(out["payload"]),
+                        _ptr(out["n_bytes"]), self._stream())
+        out["flags"], out["budget"] = fl, budget
+        return out
+
     def encode_vq(self, pcm, flags=None, out=None, want_entries=False, entries_per_band=160):
         """The shipped configuration (gain-shape PVQ, SBR if the handle has it) from
         PCM to finished payloads.  Returns dict: overall [n_cf,8], bit_alloc

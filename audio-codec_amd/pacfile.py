@@ -413,6 +413,51 @@ def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False, hea
     return head + body[:n].cpu().numpy().tobytes()
 
 
+def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples):
+    """(.pac bytes, the outputs of Encoder.encode_pack_nmr for the n + 2 blocks the driver writes, the encoder)"""
+    from .audiofile import CodingParams
+    pcm = np.ascontiguousarray(pcm)
+    hop = 1024
+    if pcm.ndim != 2 or pcm.dtype != np.int16 or len(pcm) % hop:
+        raise ValueError("pcm: int16 [n, nCh], n a multiple of 1024")
+    cp = CodingParams()
+    cp.sampleRate, cp.nChannels = int(sample_rate), pcm.shape[1]
+    cp.numSamples = len(pcm) if header_samples is None else int(header_samples)
+    cp.nMDCTLines = cp.nSamplesPerBlock = hop
+    cp.nScaleBits, cp.nMantSizeBits = 4, 12
+    # the header carries no rate and the budgets are the search's: the handle's own rate is not used
+    cp.targetBitsPerSample = max_kbps_per_channel / (cp.sampleRate / 1000)
+    if not 0.0 < cp.targetBitsPerSample <= 16.0:
+        raise ValueError(f"max_kbps_per_channel = {max_kbps_per_channel} at {cp.sampleRate} Hz is "
+                         f"{cp.targetBitsPerSample:.3g} bits per sample: the cap must lie in (0, 16] bits per sample "
+                         f"(at most {16 * cp.sampleRate / 1000:g} kb/s here)")
+    cp.useSBR = cp.useVQ = False
+    enc = context.encoder_for_params(cp)
+    planar = device_stream(enc, pcm, hop)
+    view = PcmView.stream(planar, hop)
+    flags = enc.transient_flags(planar, len(pcm) // hop, hop)[1] if block_switching else None
+    out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
+    body, total = enc.gather_body(out["payload"], out["n_bytes"])
+    return header_bytes(cp) + body[:int(total.item())].cpu().numpy().tobytes(), out, enc
+
+
+def encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
+                      header_samples=None, use_vq=False, use_sbr=False, chunk_hops=None, n_lines=1024):
+    """Whole-stream encode at constant quality instead of constant rate -> .pac bytes: the smallest stream (by the
+    bisection of include/pacx.h, pacx_encode_pack_nmr_batch) whose predicted noise stays at or below target_nmr_db
+    of the masked threshold in every band of every block, no block above the budget of max_kbps_per_channel.  An
+    ordinary scalar .pac: every decoder of encode_stream's output takes it.  Scalar mantissas, 1024 lines, one
+    batch: gain-shape / SBR streams, other block sizes and the chunked host-to-host encoder are not covered.
+    The cap is at most 16 bits per sample (the widest mantissa; it bounds the search, include/pacx.h): with the
+    default 320 kb/s that needs a sample rate of 20 kHz or more, below it pass a smaller max_kbps_per_channel
+    (ValueError otherwise)."""
+    # use_vq, use_sbr, chunk_hops, n_lines: encode_stream's keywords, taken here only so that a caller who switches
+    # from encode_stream gets NotImplementedError for what this mode does not cover, not a TypeError
+    if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
+        raise NotImplementedError("constant-quality streams: scalar mantissas, nMDCTLines 1024, one batch")
+    return _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples)[0]
+
+
 def parse_header(data):
     """coder/pacfile.py:142-151 -> (CodingParams, header length)."""
     from struct import unpack, calcsize

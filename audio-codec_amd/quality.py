@@ -304,6 +304,31 @@ def encode_stream_report(pcm, sample_rate, kbps_per_channel, block_switching=Fal
     return b"".join(parts), acc.report(enc, flags, record)
 
 
+def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
+                         header_samples=None):
+    """pacfile.encode_stream_nmr with a Report: -> (.pac bytes, Report, info).  The report is nmr_of_file's of the
+    finished bytes.  info, for the n + 2 blocks the driver submits:
+      budget   int32 [blocks, nCh, 8]: the BitAlloc budget of every long block ([..., 0]) / short sub-block, bits;
+      capped   bool  [blocks, nCh]: some unit of the block reached the cap (PACX_ST_RATE_CAP) and may miss the target;
+      written  bool  [blocks]: the block is in the file (a dropped short-coded hop is not);
+      kbps_per_channel: the records of the file, their length prefixes included, over the duration of the blocks
+                        submitted."""
+    from . import pacfile
+    data, out, enc = pacfile._encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching,
+                                                header_samples)
+    n_ch = np.asarray(pcm).shape[1]
+    n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
+    n_blocks = len(n_bytes)
+    body = int(np.sum(n_bytes[n_bytes > 0] + 4))
+    info = {
+        "budget": out["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB),
+        "capped": (out["status"].cpu().numpy().reshape(n_blocks, n_ch) & _lib.ST_RATE_CAP) != 0,
+        "written": n_bytes[:, 0] > 0,
+        "kbps_per_channel": 8.0 * body / (n_blocks * HOP / float(sample_rate)) / n_ch / 1000.0,
+    }
+    return data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info
+
+
 def nmr_of_file(pcm, pac_bytes, block_switching=None, chunk_hops=4096):
     """Report of a .pac made elsewhere (by the reference itself, say) against the PCM it was made from.  The
     hop-to-record map is re-derived the way the writer makes it: the transient detector gives the flags, a

@@ -117,6 +117,9 @@ extern "C" {
                                       frame's n_bytes is 0, its other outputs are unspecified, and the
                                       host mirror raises the reference's error                      */
 
+#define PACX_ST_RATE_CAP    128u   /* pacx_encode_pack_nmr_batch: a long block or a short sub-block of this cf
+                                      misses the target NMR even with the cap budget and was coded with it */
+
 #define PACX_SHORT_PER_FRAME 8    /* sub-blocks of a short frame (coder/pacfile.py:527) */
 
 typedef struct pacx_handle pacx_handle;
@@ -667,6 +670,62 @@ int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flag
  */
 int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                      const double *nmr_db, uint64_t *summary, void *stream);
+
+/* ---- coding to a target noise-to-mask ratio -------------------------------- */
+
+#define PACX_RATE_STEP 32         /* budgets found by the search are multiples of this many bits */
+
+/*
+ * Constant quality instead of constant rate, for the scalar coder (long and short blocks, 1024 lines): every
+ * long block and every short sub-block ("unit") gets the BitAlloc budget a bisection finds for it, the smallest
+ * on its path whose predicted noise stays at or below target_nmr_db of the mask in every band.  The .pac format
+ * carries no rate, every record its own length and every band its own allocation, so the result is an ordinary
+ * scalar .pac stream (no function of the reference: its only control is the rate of the whole file).
+ *
+ * The search, per unit, on the quantities of pacx_encode_pack_batch -- lines X (not multiplied by
+ * 2^overallScale), the overall scale, the band SMRs, the masked threshold T[k]:
+ *
+ *   cap = the budget rule of coder/codec.py:288-299 (pacx_bit_budget, csrc/pacx_exact.h) with
+ *         max_bits_per_sample in place of the handle's rate, same flags and short-block handling
+ *   J   = max(floor(cap / PACX_RATE_STEP), 0)
+ *   ok(B): alloc = BitAlloc(double(B), maxMantBits, bands, SMR)           the encoder's own arithmetic
+ *          per band the scale factor and the mantissas exactly as the encoder makes them, then vDequantize
+ *          Xh = dequantised / 2^overallScale (0 in a band without bits)
+ *          NMR_b as pacx_nmr_batch defines it (n = 4 (X - Xh)^2, m = 10^((T - 96) / 10), band means, eps = 2^-52)
+ *          return max_b NMR_b <= target_nmr_db
+ *   if not ok(32 J):  budget = 32 J, status |= PACX_ST_RATE_CAP
+ *   else: lo = -1, hi = J; while hi - lo > 1: mid = (lo + hi) / 2; if ok(32 mid) hi = mid else lo = mid
+ *         budget = 32 hi
+ *
+ * ok() is not strictly monotone in B (BitAlloc's rounding ladder and its 200-pass guard), so the result is the
+ * bisection's, not a global minimum: ok holds at the budget returned and failed at the last budget tried below
+ * it.  Every loop has a constant bound: at most 1 + ceil(log2(J + 1)) evaluations with J <= 512
+ * (max_bits_per_sample <= 16, the widest mantissa), each with BitAlloc's own 200-pass guard.  A short-coded hop
+ * the reference drops (PACX_ST_ZERO_SUBBLOCK) stays dropped; its budgets are 0.
+ *
+ *   target_nmr_db:       finite; 0 = noise at the mask, negative = below it
+ *   max_bits_per_sample: cap rate, kb/s per channel / (sampleRate / 1000); 0 < . <= 16
+ *   budget (out):        int32 [n_cf][8], long frames use [0] (the rest is 0)
+ *   mantissa:            optional; the other outputs as pacx_encode_pack_batch, bit_alloc being the allocation
+ *                        of the budget found
+ * Runs MDCT -> side chain -> masked threshold (kept in the handle's workspace as pacx_nmr_batch keeps it) ->
+ * k_rate_search -> scale factors + mantissas -> pack on `stream`.  PACX_E_UNSUPPORTED on a handle created with
+ * use_vq or use_sbr; PACX_E_ARG for a null output, a non-finite target, a cap rate outside (0, 16].
+ */
+int pacx_encode_pack_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, double target_nmr_db,
+                               double max_bits_per_sample, int32_t *overall_scale, int32_t *scale_factor,
+                               int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
+                               int32_t *n_bytes, int32_t *budget, void *stream);
+
+/*
+ * The same path without the search: BitAlloc of every unit with the caller's budget (int32 [n_cf][8] in bits,
+ * any value; long frames use [0]), then scale factors, mantissas and payloads -- the second pass of a two-pass
+ * rate control.  With the budgets pacx_encode_pack_nmr_batch returned it writes that call's payloads again.
+ */
+int pacx_encode_pack_budget_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                  const int32_t *budget, int32_t *overall_scale, int32_t *scale_factor,
+                                  int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
+                                  int32_t *n_bytes, void *stream);
 
 #ifdef __cplusplus
 }
