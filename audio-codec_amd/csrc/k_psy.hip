@@ -190,15 +190,169 @@ __device__ __forceinline__ double pair_intensity(cplx a, cplx bz, cplx w, double
     return norm * fma(xr, xr, xi * xi);
 }
 
+/* the two twiddle sets of a lane, straight from the global W512 table */
+__device__ __forceinline__ void load_lane_twiddles(const PacxTables &T, int lane, cplx tw1[7], cplx tw2[7])
+{
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        tw1[k - 1] = T.w512[(lane * k) & 511];
+        tw2[k - 1] = T.w512[(8 * (lane & 7) * k) & 511];
+    }
+}
+
+/* ------------------------------------------------- long: fused front end */
+/* The MDCT of one long sine-window frame by the wave that runs the frame's side chain (k_front_long): the
+ * arithmetic of k_mdct_long_x2p (k_mdct3.hip) for one frame, operation by operation -- window value
+ * win_long[i] * kscale, the fold's fma forms, c_mul with tw_long[n], fft512n, the post-twiddle, the lane reversal
+ * and the ballot-bisected overall scale -- so the lines and the scale are the same bits.  What differs is where the
+ * operands come from: window and pre/post twiddles are read from the global tables (L2), not from a workgroup's LDS
+ * copy, the FFT's per-lane twiddles from the global W512 table as the side chain's are, and the PCM goes through
+ * registers to LDS (plain loads and stores) for the fold's scattered 16-bit reads.
+ * The transform's operands are fetched while the side chain still works on its maskers (its registers are all
+ * but idle by then) and the transform itself runs when the side chain is done with region B: raw PCM (4 KB) until
+ * the fold is done, then the FFT tile (8 KB).  Nothing waits for the line stores -- the wave ends behind them. */
+struct FrontArgs {
+    const short *src;                 /* the frame's 2048 samples (unit stride, 16-byte aligned) */
+    double *lines;
+    int32_t *scale_out;               /* overall scales, stride PACX_SUB */
+    uint32_t *status;
+};
+struct MdctOperands {
+    int q[16];                        /* PCM: 64 lanes x 16 bytes per load, the frame's 4 KB in four */
+    double w[16];                     /* window values of the fold, (wa, wb) of input n = lane + 64 n1 */
+    cplx twl[8];                      /* tw_long[lane + 64 k]: pre-twiddle of input, post-twiddle of output lane + 64 k */
+};
+
+__device__ __forceinline__ void mdct_fetch(const PacxTables &T, const short *__restrict__ src, int lane,
+                                           MdctOperands &m)
+{
+    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
+    const double *__restrict__ win = T.win_long;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int4 t = *(const int4 *)(src + 8 * (lane + 64 * j));
+        m.q[4 * j] = t.x; m.q[4 * j + 1] = t.y; m.q[4 * j + 2] = t.z; m.q[4 * j + 3] = t.w;
+    }
+#pragma unroll
+    for (int n1 = 0; n1 < 8; ++n1) {
+        const int n = lane + 64 * n1;
+        if (n1 < 4) {
+            m.w[2 * n1] = win[Q + 2 * n];                 /* w[i3] = w[i0] */
+            m.w[2 * n1 + 1] = win[Q - 1 - 2 * n];         /* w[i2] = w[i1] */
+        } else {
+            const int mm = 2 * n - Q;
+            m.w[2 * n1] = win[mm];                        /* w[i0] = w[i3] */
+            m.w[2 * n1 + 1] = win[M - 1 - mm];            /* w[i1] = w[i2] */
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        m.twl[k] = T.tw_long[lane + 64 * k];
+}
+
+__device__ __forceinline__ void mdct_long_one(const PacxTables &T, long long cf, char *regB, int lane,
+                                              const MdctOperands &m, double *__restrict__ lines,
+                                              int32_t *__restrict__ scale_out, uint32_t *__restrict__ status)
+{
+    short *raw = (short *)regB;
+    cplx *tile = (cplx *)regB;
+    cplx tw1[7], tw2[7];               /* the FFT's per-lane twiddles W512^(lane k), W64^((lane & 7) k), as the side chain's */
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        tw1[k - 1] = T.w512[(lane * k) & 511];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        *(int4 *)(raw + 8 * (lane + 64 * j)) = make_int4(m.q[4 * j], m.q[4 * j + 1], m.q[4 * j + 2], m.q[4 * j + 3]);
+    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
+    const double kscale = (2.0 / 65535.0) * (2.0 / PACX_N_LONG);
+    wave_lds_fence();
+    cplx v[8];
+    for (int pass = 0;; ++pass) {
+        int lowest = 0;
+#pragma unroll
+        for (int n1 = 0; n1 < 8; ++n1) {
+            const int n = lane + 64 * n1;
+            int i0, i1, i2, i3;
+            const double wa = m.w[2 * n1] * kscale, wb = m.w[2 * n1 + 1] * kscale;
+            if (n1 < 4) {
+                i0 = 3 * Q - 1 - 2 * n; i1 = 3 * Q + 2 * n; i2 = Q - 1 - 2 * n; i3 = Q + 2 * n;
+            } else {
+                const int mm = 2 * n - Q;
+                i0 = mm; i1 = M - 1 - mm; i2 = 2 * Q + mm; i3 = 4 * Q - 1 - mm;
+            }
+            int c0 = raw[i0], c1 = raw[i1], c2 = raw[i2], c3 = raw[i3];
+            lowest = min(lowest, min(min(c0, c1), min(c2, c3)));
+            double re, im;
+            if (n1 < 4) {
+                re = -fma(wb, (double)c1, wa * (double)c0);
+                im = fma(wb, (double)c2, -(wa * (double)c3));
+            } else {
+                re = fma(wa, (double)c0, -(wb * (double)c1));
+                im = -fma(wb, (double)c2, wa * (double)c3);
+            }
+            v[n1] = c_mul(make_double2(re, im), m.twl[n1]);
+        }
+        if (pass || !__builtin_amdgcn_ballot_w64(lowest == -32768))
+            break;
+        /* the code -32768 counts as 0 (coder/pcmfile.py:93-97): rewrite the staged codes of such a frame
+           and fold again */
+        wave_lds_fence();
+        unsigned *rw = (unsigned *)raw;
+        for (int j = 0; j < 16; ++j) {
+            unsigned x = rw[lane + 64 * j];
+            if ((x & 0xFFFFu) == 0x8000u) x &= 0xFFFF0000u;
+            if ((x >> 16) == 0x8000u) x &= 0x0000FFFFu;
+            rw[lane + 64 * j] = x;
+        }
+        wave_lds_fence();
+    }
+    /* the second exchange's twiddles: fetched here and not with the first's, where they would be 28 more registers
+       alive through the fold (scratch); they have the first radix-8 pass and exchange to arrive */
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        tw2[k - 1] = T.w512[(8 * (lane & 7) * k) & 511];
+    wave_lds_fence();                  /* raw is consumed: region B becomes the FFT tile */
+    fft512n(v, tile, tw1, 1, tw2, 1, lane);
+    /* post-twiddle, lane reversal, overall scale and guard: k_mdct_long_x2p's epilogue */
+    double a[8], b[8];
+    double mx = 0.0;
+#pragma unroll
+    for (int k3 = 0; k3 < 8; ++k3) {
+        const cplx d = m.twl[k3];
+        a[k3] = fma(v[k3].x, d.x, -(v[k3].y * d.y));      /* Re y = X[2k] */
+        b[k3] = -fma(v[k3].x, d.y, v[k3].y * d.x);        /* -Im y = X[1023 - 2k] */
+        mx = fmax(mx, fmax(fabs(a[k3]), fabs(b[k3])));
+    }
+    double odd[8];
+#pragma unroll
+    for (int k3 = 0; k3 < 8; ++k3)
+        odd[k3] = __shfl(b[7 - k3], 63 - lane, 64);
+    int lo = 0;
+    const int s = pacx_scale_factor(mx, T.n_scale_bits, 5);
+    for (int bit = T.n_scale_bits - 1; bit >= 0; --bit)
+        if (!__builtin_amdgcn_ballot_w64(s < lo + (1 << bit)))
+            lo += 1 << bit;
+    const bool guard = T.guard && s == lo && pacx_scale_guard(mx, T.n_scale_bits, 5, 2.0 * PACX_GUARD_LINE_ERR * mx);
+    double2 *__restrict__ out = (double2 *)(lines + cf * PACX_M_LONG);
+#pragma unroll
+    for (int k3 = 0; k3 < 8; ++k3)
+        out[lane + 64 * k3] = make_double2(a[k3], odd[k3]);
+    if (lane == 0)
+        scale_out[cf * PACX_SUB] = lo;
+    if (__builtin_amdgcn_ballot_w64(guard) && lane == 0)
+        status[cf] = 16u;                          /* PACX_ST_GUARD, after this lane's own zero store */
+}
+
 /* one long channel-frame by one wave; every barrier is wave-local (the wave
- * owns its LDS slice) */
-template <int DT, bool FAST, bool COMPACT>
+ * owns its LDS slice).  FRONT: the frame's MDCT as well (k_front_long, *fa) */
+template <int DT, bool FAST, bool COMPACT, bool FRONT = false>
 __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcmView &in, long long cf,
                                               char *regA, char *regB, int lane,
                                               PacxPeak *__restrict__ peaks, int32_t *__restrict__ n_peaks,
                                               int32_t *__restrict__ n_kept_out,
                                               double *__restrict__ sbr_mean,
-                                              int32_t *__restrict__ sbr_overall)
+                                              int32_t *__restrict__ sbr_overall,
+                                              const FrontArgs *fa = nullptr)
 {
     typedef typename PcmStage<DT>::elem E;
     cplx *tile = (cplx *)(COMPACT ? regB : regA);
@@ -214,11 +368,7 @@ __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcm
     /* the FFTs' per-lane twiddles W512^(lane k1) and W64^(r k2) are fetched here, with the PCM
        and the window: one round trip to L2 for all of them instead of one per FFT stage */
     cplx tw1[7], tw2[7];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        tw1[k - 1] = T.w512[(lane * k) & 511];
-        tw2[k - 1] = T.w512[(8 * (lane & 7) * k) & 511];
-    }
+    load_lane_twiddles(T, lane, tw1, tw2);
     if constexpr (DT == 0 && FAST) {
         /* int16, unit stride, aligned rows: lane (lane, n1) needs the four consecutive
            samples 4 (lane + 64 n1) .. +3 -- one 8-byte load, no staging through LDS; the
@@ -425,6 +575,14 @@ __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcm
         wave_lds_fence();
     }
     SIDE_T(5);
+    MdctOperands mo;
+    int mlane = lane;
+    if constexpr (FRONT) {
+        /* the transform works its addresses out from the lane number afresh: left to itself the compiler keeps the
+           FFT twiddles of the side chain's start (or their addresses) for it -- in scratch */
+        asm volatile("" : "+v"(mlane));
+        mdct_fetch(T, fa->src, mlane, mo);      /* in flight while the maskers are worked out */
+    }
     /* pass 3: the kept maskers, one per lane, 64 at a time: exact Bark value, SPL and upper
        slope (coder/psychoac.py:321-328, :61-68), straight to HBM in Bark order */
     {
@@ -439,6 +597,11 @@ __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcm
         }
     }
     SIDE_T(6);
+    if constexpr (FRONT) {
+        wave_lds_fence();                       /* the intensities are dead: region B is the transform's */
+        mdct_long_one(T, cf, regB, mlane, mo, fa->lines, fa->scale_out, fa->status);
+        return;
+    }
     /* SBR files (EncodeSingleChannel_SBR, coder/codec.py:459-472, 503-505): the
        same spectrum as |rfft|/halfN also bounds the overall scale factor and
        gives each omitted band its one coded value, the mean magnitude.
@@ -498,6 +661,42 @@ __global__ __launch_bounds__(64, DT == 0 ? 3 : 2) void k_side_long(PacxTables T,
         return;
     side_long_one<DT, FAST, COMPACT>(T, in, cf, regA, regB, threadIdx.x, peaks, n_peaks, n_kept_out, sbr_mean,
                                      sbr_overall);
+}
+
+/* k_side_long<0, true, true> with the frame's MDCT in the same wave (all-long batches of aligned unit-stride int16
+ * PCM, no per-frame flags, no SBR): one kernel where the step had the side chain and, behind it on the same
+ * hardware queue, the one kernel that holds a whole CU's LDS.  Same grid, same XCD-aware frame order, same LDS as
+ * k_side_long.  Side jobs of k_mdct_long_x2p<.., true>: the status word (0 here, PACX_ST_GUARD later from the same
+ * lane) and the sub-block scales 1..7 of the frame. */
+__global__ __launch_bounds__(64, 3) void k_front_long(PacxTables T, PacxPcmView in, long long n_cf,
+                                                      double *__restrict__ lines, int32_t *__restrict__ scale_out,
+                                                      uint32_t *__restrict__ status, PacxPeak *__restrict__ peaks,
+                                                      int32_t *__restrict__ n_peaks, int32_t *__restrict__ n_kept_out)
+{
+    __shared__ __attribute__((aligned(16))) char regA[SideLongLds<0, true>::A_BYTES];
+    __shared__ __attribute__((aligned(16))) char regB[SideLongLds<0, true>::B_BYTES];
+    static_assert(SideLongLds<0, true>::B_BYTES >= (int)sizeof(cplx) * WFFT_TILE_N, "region B holds the FFT tile");
+    long long cf = blockIdx.x;
+    if ((n_cf & 2047) == 0 && gridDim.x == (unsigned)n_cf) {          /* as in k_side_long */
+        const unsigned b = blockIdx.x, idx = b >> 3;
+        cf = (long long)(idx >> 8) * 2048 + (b & 7u) * 256 + (idx & 255u);
+    }
+    if (cf >= n_cf)
+        return;
+    const int lane = threadIdx.x;
+    if (lane == 0)
+        status[cf] = 0u;
+    if (lane >= 1 && lane < PACX_SUB)
+        scale_out[cf * PACX_SUB + lane] = 0;
+    const long long f = cf / in.n_ch;
+    const int ch = (int)(cf - f * in.n_ch);
+    FrontArgs fa;
+    fa.src = (const short *)in.base + f * in.frame_stride + ch * in.ch_stride;
+    fa.lines = lines;
+    fa.scale_out = scale_out;
+    fa.status = status;
+    side_long_one<0, true, true, true>(T, in, cf, regA, regB, lane, peaks, n_peaks, n_kept_out, nullptr, nullptr,
+                                       &fa);
 }
 
 /* ----------------------------------------------------------------- short */
@@ -1291,6 +1490,15 @@ void pacx_k::pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dt
     else
         launch_side<1, false>(T, in, flags, n_cf, short_blocks, mixed, peaks, n_peaks, n_kept, sbr_mean,
                               sbr_overall, st);
+}
+
+void pacx_k::pacx_launch_front_long(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
+                                    int32_t *overall_scale, uint32_t *status, PacxPeak *peaks, int32_t *n_peaks,
+                                    int32_t *n_kept, hipStream_t st)
+{
+    if (n_cf > 0)
+        hipLaunchKernelGGL(k_front_long, dim3((unsigned)n_cf), dim3(64), 0, st, T, in, n_cf, lines, overall_scale,
+                           status, peaks, n_peaks, n_kept);
 }
 
 void pacx_k::pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,

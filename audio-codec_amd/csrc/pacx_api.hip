@@ -28,11 +28,14 @@ using namespace pacx_k;
 struct PacxOverrides {
     int split_short;                  /* PACX_SPLIT_SHORT=0: block-switched batches on one stream */
     int fuse_tail;                    /* PACX_FUSE_TAIL=0/1: the long frames' tail in k_tail_long / in k_mask */
+    int fuse_front;                   /* PACX_FUSE_FRONT=0/1: all-long steps' MDCT in k_mdct_long_x2p / in k_front_long */
     int vq_fuse_alloc;                /* PACX_VQ_FUSE_ALLOC=0/1: the long frames' BitAlloc in k_bitalloc / in k_mask */
     int vq_frame;                     /* PACX_VQ_FRAME=0: k_vq over every unit */
     int vq_bfs;                       /* PACX_VQ_BFS=n: level walk from n shape bits (0: depth first only) */
     int vq_dec_frame;                 /* PACX_VQ_DEC_FRAME=0: k_vq_dec over every block */
 };
+
+#define PACX_FUSE_FRONT_DEFAULT 1     /* follows the measurement of DESIGN.md 5.4 */
 
 /* an integer in [lo, hi] from the environment, else -1 */
 static int env_override(const char *name, int lo, int hi)
@@ -50,6 +53,7 @@ static PacxOverrides read_overrides(void)
     PacxOverrides o;
     o.split_short = env_override("PACX_SPLIT_SHORT", 0, 0);
     o.fuse_tail = env_override("PACX_FUSE_TAIL", 0, 1);
+    o.fuse_front = env_override("PACX_FUSE_FRONT", 0, 1);
     o.vq_fuse_alloc = env_override("PACX_VQ_FUSE_ALLOC", 0, 1);
     o.vq_frame = env_override("PACX_VQ_FRAME", 0, 0);
     o.vq_bfs = env_override("PACX_VQ_BFS", 0, 1 << 20);
@@ -961,6 +965,13 @@ struct EncodeStep {
         pacx_launch_side(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed | part, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
                          sbr ? h->ws_sbr_mean : nullptr, sbr ? overall_scale : nullptr, st);
     }
+    /* all-long fast batches without SBR: transform and side chain of a frame in one wave (k_front_long), which
+       also initialises status and the overall scales */
+    void front_long(hipStream_t st) const
+    {
+        pacx_launch_front_long(h->T, v, n_cf, h->ws_lines, overall_scale, status, h->ws_peaks, h->ws_npeaks,
+                               h->ws_nkept, st);
+    }
     /* tail: the outputs of the work fused into the long mask kernel, or nullptr */
     void mask(int part, const MaskTail *tail, hipStream_t st) const
     {
@@ -1079,8 +1090,21 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
         HIP_TRY_FORKED(h, hipStreamWaitEvent(st, h->ev_short_done, 0));       /* both chains done */
         return post_launch_forked(h, what);
     }
-    /* All-long batches: the whole step on the caller's stream, or (pacx_set_side_fork) the side chain, which only
-       reads the PCM, forked to the handle's second stream next to the transform.  The fork pays only where HIP puts
+    /* Fast all-long batches: MDCT and side chain in ONE kernel (k_front_long), the step a plain chain on the
+       caller's stream whatever fork_side says.  HIP puts a handle's two streams on one hardware queue, so the
+       forked step was a serial chain already -- side chain, then the transform, which holds a whole CU's LDS and
+       leaves the vector unit three-quarters idle; in the side chain's wave the transform's memory traffic runs
+       under arithmetic.  Same bits (tests/test_gpu_fused_front.py); measured in DESIGN.md 5.4; PACX_FUSE_FRONT=0 / 1
+       forces either. */
+    if (!mixed && fast && (h->force.fuse_front >= 0 ? h->force.fuse_front : PACX_FUSE_FRONT_DEFAULT)) {
+        s.front_long(st);
+        s.mask(0, fuse ? &mt : nullptr, st);
+        if (!fuse)
+            tail(s.list_short, s.counts + 1, fuse, st);
+        return post_launch(h, what);
+    }
+    /* Other batches without a split (and PACX_FUSE_FRONT=0): the whole step on the caller's stream, or
+       (pacx_set_side_fork) the side chain, which only reads the PCM, forked to the handle's second stream next to the transform.  The fork pays only where HIP puts
        the two streams on ONE hardware queue -- with two handles in a process it does (50.6 against 49.3 M cf/s with
        two steps in flight), with one handle it does not, and a fork and a join across hardware queues (13 + 12 us)
        cost more than the 20 us of overlap: 39.1 against 42.6 M cf/s with one step in flight */

@@ -33,6 +33,12 @@ void pacx_launch_side(const PacxTables &T, const PacxPcmView &in, int dtype, int
                       const uint8_t *flags, long long n_cf, int short_blocks, int mixed,
                       PacxPeak *peaks, int32_t *n_peaks, int32_t *n_kept, double *sbr_mean,
                       int32_t *sbr_overall, hipStream_t st);
+/* the fused front end of an all-long step (k_front_long): MDCT lines, overall scale (stride PACX_SUB, sub-block
+   scales zeroed), status initialisation and the side chain of every frame, for 16-byte-aligned unit-stride int16
+   batches without per-frame flags on handles without SBR */
+void pacx_launch_front_long(const PacxTables &T, const PacxPcmView &in, long long n_cf, double *lines,
+                            int32_t *overall_scale, uint32_t *status, PacxPeak *peaks, int32_t *n_peaks,
+                            int32_t *n_kept, hipStream_t st);
 void pacx_launch_mask(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                       int short_blocks, int mixed, const PacxPeak *peaks, const int32_t *n_peaks,
                       const double *lines, double *smr, double *thr_out, int n_cu,
