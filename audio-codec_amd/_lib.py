@@ -13,6 +13,7 @@ ST_SHORT, ST_ZERO_SUBBLOCK, ST_ALLOC_CAP, ST_VQ_UNDEFINED, ST_GUARD, ST_MALFORME
 ST_REF_RAISES = 64
 ST_RATE_CAP = 128
 RATE_STEP = 32             # PACX_RATE_STEP: budgets of the constant-quality mode are multiples of this many bits
+RATE_TARGET_GRID = 64      # PACX_RATE_TARGET_GRID: targets of pacx_rate_solve are multiples of 1 / 64 dB
 E_ARG, E_UNSUPPORTED = -1, -2
 # what the reference raises where PACX_ST_REF_RAISES is set (coder/quantize.py:74, see include/pacx.h)
 REF_SCALAR_SBR_ERROR = "'numpy.int64' object does not support item assignment"
@@ -148,6 +149,11 @@ SIGNATURES = {
                                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pacx_encode_pack_budget_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                      _P]),
+    "pacx_rate_curve_layout": (ctypes.c_int, [_P, ctypes.c_double, c_int32_p, c_int32_p]),
+    "pacx_rate_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, ctypes.c_int32, _P, _P, _P,
+                                             _P]),
+    "pacx_rate_solve": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64,
+                                       ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
 }
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320

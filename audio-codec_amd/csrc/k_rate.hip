@@ -1,6 +1,7 @@
 /*
  * k_rate.hip -- coding to a target noise-to-mask ratio (pacx_encode_pack_nmr_batch / pacx_encode_pack_budget_batch,
- * include/pacx.h): the BitAlloc budget of every long block and every short sub-block is a number of its own.
+ * include/pacx.h): the BitAlloc budget of every long block and every short sub-block is a number of its own; and to
+ * an average bit rate (pacx_rate_curve_batch / pacx_rate_solve): one target for the stream, found on stored curves.
  *
  *   k_rate_search<M>   one wave per unit (M = 1024: a long block, M = 128: a short sub-block).  Reads the unit's
  *                      lines, masked threshold and SMRs once; keeps the lines, the band tables, the band maxima of
@@ -12,6 +13,13 @@
  *                      then the bisection of include/pacx.h: at most 1 + ceil(log2(J + 1)) evaluations, J <= 512.
  *                      Writes the budget, the allocation that passed (or the cap's) and the status bits.
  *   k_bitalloc_budget  k_bitalloc with the budget of every unit read from the caller's array, two units per wave.
+ *   k_rate_curve<M>    k_rate_search's units, preamble (rate_unit) and evaluation (rate_eval), every step j = 0 ... J
+ *                      instead of a bisection: worst[j] = max_b NMR_b and bits[j] = what pack_body writes for the
+ *                      allocation of budget 32 j (pacx_rate_curve_batch).
+ *   k_solve_pick       pacx_rate_solve: one channel-frame per thread picks the budget of each of its units from the
+ *                      curve at the target in flight, sums the frame's bytes; one 64-bit atomicAdd per workgroup.
+ *   k_solve_step       one thread: the bisection's decision on that total.  The host enqueues a fixed number of
+ *                      pick / step pairs and waits for none; pairs after the answer is known do nothing.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
  */
@@ -38,6 +46,143 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+/* what a unit's evaluations share, in LDS */
+template <int M>
+struct RateLds {
+    double v[M];                                   /* m[k] while the band means are taken, then n[k] of an evaluation */
+    double x[M];                                   /* the unit's lines */
+    uint8_t band[M];                               /* band of every line (nb: none) */
+    double cp[2][32];
+    double mm[PACX_MAX_BANDS];                     /* M_b */
+    unsigned long long bmax[RATE_SLOTS];
+    int ba[RATE_SLOTS], sf[RATE_SLOTS], lower[PACX_MAX_BANDS], cnt[PACX_MAX_BANDS];
+};
+
+/* and in registers */
+struct RateUnit {
+    int nb, nl, max_mant, J;
+    bool has;                                      /* BitAlloc's lanes: band l on the first half wave */
+    double sv, up, inv;
+};
+
+/* the preamble of k_rate_search and k_rate_curve: lines, line bands, band maxima and the band means of the mask into
+   LDS, the unit's SMRs and J into registers.  Called by the whole wave. */
+template <int M>
+__device__ __forceinline__ RateUnit rate_unit(const PacxTables &T, RateLds<M> &S, long long cf, int sb, unsigned fl,
+                                              double max_bps, const double *__restrict__ lines,
+                                              const double *__restrict__ thr, const double *__restrict__ smr,
+                                              const int32_t *__restrict__ overall)
+{
+    constexpr bool SHORT = (M == PACX_M_SHORT);
+    constexpr int PER = M / 64;                    /* lines per lane */
+    const int lane = threadIdx.x, half = lane >> 5, l = lane & 31;
+    RateUnit u;
+    u.nb = SHORT ? T.nb_short : T.nb_long;
+    const int nb = u.nb;
+    const long long boff = cf * T.band_stride + sb * nb;
+    u.has = half == 0 && l < nb;
+    /* ---- what every evaluation shares: line lane + 64 j belongs to lane `lane` (coalesced, and LDS without bank
+       conflicts); the lines stay in LDS, so the evaluations' line loop need not be unrolled */
+    const long long loff = cf * PACX_M_LONG + sb * PACX_M_SHORT;
+    const uint8_t *__restrict__ band_of = SHORT ? T.line_band_short : T.line_band_long;
+    const int ov = overall[cf * PACX_SUB + sb];
+    u.up = (double)(1 << ov);                      /* mdctLines *= (1 << overallScale) */
+    u.inv = ldexp(1.0, -ov);                       /* the decoder's division: a power of two, exact */
+    const double up = u.up;
+    if (lane < RATE_SLOTS) {
+        S.bmax[lane] = 0ull;
+        S.ba[lane] = 0;
+        S.sf[lane] = 0;
+    }
+    const int32_t *__restrict__ lower = SHORT ? T.band_lower_short : T.band_lower_long;
+    const int32_t *__restrict__ count = SHORT ? T.band_lines_short : T.band_lines_long;
+    if (lane < nb) {
+        int cnt = count[lane];
+        if (lower[lane] + cnt > M)                 /* a table that runs past the block (build_bands refuses it) */
+            cnt = M - lower[lane];
+        S.lower[lane] = lower[lane];
+        S.cnt[lane] = cnt;
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int k = lane + 64 * j;
+        const double xv = lines[loff + k];
+        S.x[k] = xv;
+        S.band[k] = band_of[k];
+        /* 10^y by exp2(y log2 10), as k_nmr */
+        S.v[k] = exp2(((thr[loff + k] - 96.0) / 10.0) * 3.32192809488736234787);
+        /* band maxima of |x 2^overall| on the bit pattern (quant_dev.h, long_scale_factors): they do not depend on the
+           allocation, only the scale factor taken from them does */
+        atomicMax(&S.bmax[band_of[k]], (unsigned long long)__double_as_longlong(fabs(xv * up)));
+    }
+    wave_lds_fence();
+    for (int b = 0; b < nb; ++b) {
+        double sm = 0.0;
+        for (int k = lane; k < S.cnt[b]; k += 64)
+            sm += S.v[S.lower[b] + k];
+        sm = wave_sum(sm);
+        if (lane == 0)
+            S.mm[b] = sm / (double)S.cnt[b];
+    }
+    wave_lds_fence();
+
+    u.sv = u.has ? smr[boff + l] : 0.0;
+    u.nl = u.has ? count[l] : 0;
+    u.max_mant = 1 << T.n_mant_size_bits;
+    if (u.max_mant > 16)
+        u.max_mant = 16;
+    /* the existing rule with the cap rate in place of the handle's */
+    u.J = pacx_rate_steps(max_bps, M, SHORT ? 1 : 0, (fl & 5u) != 0, T.n_scale_bits, T.n_mant_size_bits, nb);
+    return u;
+}
+
+/* One evaluation, the only one: the unit coded with BitAlloc budget 32 step -> max_b NMR_b, the allocation of band l
+   in `bits` (lanes with u.has) and BitAlloc's guard bits in `acap`.  ok(B) of include/pacx.h is lane 0's
+   rate_eval(...) <= target: both kernels take lane 0's value.  Leaves S.v, S.ba, S.sf free for the next call. */
+template <int M>
+__device__ __forceinline__ double rate_eval(const PacxTables &T, RateLds<M> &S, const RateUnit &u, int step, int &bits,
+                                            int &acap)
+{
+    constexpr int PER = M / 64;
+    const int lane = threadIdx.x, half = lane >> 5, l = lane & 31;
+    const int nb = u.nb;
+    const double up = u.up, inv = u.inv;
+    bits = 0;
+    acap = 0;
+    bitalloc_half(half == 0, u.has, u.sv, u.nl, (double)(32 * step), u.max_mant, S.cp[half], half, l, bits, acap,
+                  T.guard != 0, nb);
+    if (u.has) {
+        S.ba[l] = bits;
+        S.sf[l] = pacx_scale_factor(__longlong_as_double((long long)S.bmax[l]), T.n_scale_bits, bits);
+    }
+    wave_lds_fence();
+#pragma unroll 1
+    for (int j = 0; j < PER; ++j) {
+        const int k = lane + 64 * j;
+        const int b = S.band[k];
+        const int ba = S.ba[b];
+        const double xv = S.x[k];
+        double d = 0.0;
+        if (ba)
+            d = pacx_dequantize(pacx_mantissa(xv * up, S.sf[b], T.n_scale_bits, ba), S.sf[b], T.n_scale_bits, ba);
+        const double e = xv - d * inv;
+        S.v[k] = (e * e) * 4.0;
+    }
+    wave_lds_fence();
+    double worst = -INFINITY;
+    for (int b = 0; b < nb; ++b) {
+        double sn = 0.0;
+        for (int k = lane; k < S.cnt[b]; k += 64)
+            sn += S.v[S.lower[b] + k];
+        sn = wave_sum(sn);
+        const double r = 10.0 * log10((sn / (double)S.cnt[b] + PACX_EPS) / S.mm[b]);
+        worst = r > worst ? r : worst;
+    }
+    wave_lds_fence();                              /* v, ba, sf free for the next evaluation */
+    return worst;
+}
+
 template <int M>
 __global__ __launch_bounds__(64) void k_rate_search(PacxTables T, const uint8_t *__restrict__ flags, int n_ch,
                                                    long long n_units, double target_db, double max_bps,
@@ -47,14 +192,7 @@ __global__ __launch_bounds__(64) void k_rate_search(PacxTables T, const uint8_t 
                                                    uint32_t *__restrict__ status)
 {
     constexpr bool SHORT = (M == PACX_M_SHORT);
-    constexpr int PER = M / 64;                    /* lines per lane */
-    __shared__ double v_l[M];                      /* m[k] while the band means are taken, then n[k] of an evaluation */
-    __shared__ double x_l[M];                      /* the unit's lines */
-    __shared__ uint8_t band_l[M];                  /* band of every line (nb: none) */
-    __shared__ double cp[2][32];
-    __shared__ double mm_s[PACX_MAX_BANDS];        /* M_b */
-    __shared__ unsigned long long bmax[RATE_SLOTS];
-    __shared__ int ba_s[RATE_SLOTS], sf_s[RATE_SLOTS], lower_s[PACX_MAX_BANDS], cnt_s[PACX_MAX_BANDS];
+    __shared__ RateLds<M> S;
     const int lane = threadIdx.x, half = lane >> 5, l = lane & 31;
     const long long unit = blockIdx.x;
     if (unit >= n_units)
@@ -84,62 +222,8 @@ __global__ __launch_bounds__(64) void k_rate_search(PacxTables T, const uint8_t 
             return;
         }
     }
-
-    /* ---- what every evaluation shares: line lane + 64 j belongs to lane `lane` (coalesced, and LDS without bank
-       conflicts); the lines stay in LDS, so the evaluations' line loop need not be unrolled */
-    const long long loff = cf * PACX_M_LONG + sb * PACX_M_SHORT;
-    const uint8_t *__restrict__ band_of = SHORT ? T.line_band_short : T.line_band_long;
-    const int ov = overall[cf * PACX_SUB + sb];
-    const double up = (double)(1 << ov);           /* mdctLines *= (1 << overallScale) */
-    const double inv = ldexp(1.0, -ov);            /* the decoder's division: a power of two, exact */
-    if (lane < RATE_SLOTS) {
-        bmax[lane] = 0ull;
-        ba_s[lane] = 0;
-        sf_s[lane] = 0;
-    }
-    const int32_t *__restrict__ lower = SHORT ? T.band_lower_short : T.band_lower_long;
-    const int32_t *__restrict__ count = SHORT ? T.band_lines_short : T.band_lines_long;
-    if (lane < nb) {
-        int cnt = count[lane];
-        if (lower[lane] + cnt > M)                 /* a table that runs past the block (build_bands refuses it) */
-            cnt = M - lower[lane];
-        lower_s[lane] = lower[lane];
-        cnt_s[lane] = cnt;
-    }
-    wave_lds_fence();
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int k = lane + 64 * j;
-        const double xv = lines[loff + k];
-        x_l[k] = xv;
-        band_l[k] = band_of[k];
-        /* 10^y by exp2(y log2 10), as k_nmr */
-        v_l[k] = exp2(((thr[loff + k] - 96.0) / 10.0) * 3.32192809488736234787);
-        /* band maxima of |x 2^overall| on the bit pattern (quant_dev.h, long_scale_factors): they do not depend on the
-           allocation, only the scale factor taken from them does */
-        atomicMax(&bmax[band_of[k]], (unsigned long long)__double_as_longlong(fabs(xv * up)));
-    }
-    wave_lds_fence();
-    for (int b = 0; b < nb; ++b) {
-        double sm = 0.0;
-        for (int k = lane; k < cnt_s[b]; k += 64)
-            sm += v_l[lower_s[b] + k];
-        sm = wave_sum(sm);
-        if (lane == 0)
-            mm_s[b] = sm / (double)cnt_s[b];
-    }
-    wave_lds_fence();
-
-    const double sv = has ? smr[boff + l] : 0.0;
-    const int nl = has ? count[l] : 0;
-    int max_mant = 1 << T.n_mant_size_bits;
-    if (max_mant > 16)
-        max_mant = 16;
-    /* the existing rule with the cap rate in place of the handle's */
-    const double cap = pacx_bit_budget(max_bps, M, SHORT ? 1 : 0, (fl & 5u) != 0, T.n_scale_bits, T.n_mant_size_bits, nb,
-                                       0, 0);
-    const double jf = floor(cap / 32.0);
-    const int J = jf > 0.0 ? (jf < 2047.0 ? (int)jf : 2047) : 0;
+    const RateUnit u = rate_unit<M>(T, S, cf, sb, fl, max_bps, lines, thr, smr, overall);
+    const int J = u.J;
 
     /* ---- the search: 32 J first, then the bisection */
     int lo = -1, hi = J, mid = J;
@@ -147,37 +231,7 @@ __global__ __launch_bounds__(64) void k_rate_search(PacxTables T, const uint8_t 
     bool capped = false;
     for (int it = 0; it < RATE_MAX_EVAL; ++it) {
         int bits = 0, acap = 0;
-        bitalloc_half(half == 0, has, sv, nl, (double)(32 * mid), max_mant, cp[half], half, l, bits, acap, T.guard != 0,
-                      nb);
-        if (has) {
-            ba_s[l] = bits;
-            sf_s[l] = pacx_scale_factor(__longlong_as_double((long long)bmax[l]), T.n_scale_bits, bits);
-        }
-        wave_lds_fence();
-#pragma unroll 1
-        for (int j = 0; j < PER; ++j) {
-            const int k = lane + 64 * j;
-            const int b = band_l[k];
-            const int ba = ba_s[b];
-            const double xv = x_l[k];
-            double d = 0.0;
-            if (ba)
-                d = pacx_dequantize(pacx_mantissa(xv * up, sf_s[b], T.n_scale_bits, ba), sf_s[b], T.n_scale_bits, ba);
-            const double e = xv - d * inv;
-            v_l[k] = (e * e) * 4.0;
-        }
-        wave_lds_fence();
-        double worst = -INFINITY;
-        for (int b = 0; b < nb; ++b) {
-            double sn = 0.0;
-            for (int k = lane; k < cnt_s[b]; k += 64)
-                sn += v_l[lower_s[b] + k];
-            sn = wave_sum(sn);
-            const double r = 10.0 * log10((sn / (double)cnt_s[b] + PACX_EPS) / mm_s[b]);
-            worst = r > worst ? r : worst;
-        }
-        const bool ok = __shfl(worst <= target_db ? 1 : 0, 0, 64) != 0;       /* wave-uniform */
-        wave_lds_fence();                          /* v_l, ba_s, sf_s free for the next evaluation */
+        const bool ok = __shfl(rate_eval<M>(T, S, u, mid, bits, acap) <= target_db ? 1 : 0, 0, 64) != 0;   /* wave-uniform */
         if (it == 0) {
             best = bits;
             best_cap = acap;
@@ -204,6 +258,63 @@ __global__ __launch_bounds__(64) void k_rate_search(PacxTables T, const uint8_t 
         if (st)
             atomicOr(&status[cf], st);             /* PACX_ST_RATE_CAP, _ALLOC_CAP, _GUARD */
     }
+}
+
+/* Every budget of a unit instead of a bisection over them: worst[j] = rate_eval(j) and bits[j] = what pack_body
+   (k_quant.hip) writes for the allocation of budget 32 j, j = 0 ... J.  Row layout of include/pacx.h
+   (pacx_rate_curve_batch): sub-block sb at sb * sub_stride; steps[cf][8] = J of every unit, -1 where there is none. */
+template <int M>
+__global__ __launch_bounds__(64) void k_rate_curve(PacxTables T, const uint8_t *__restrict__ flags, int n_ch,
+                                                  long long n_units, double max_bps, int row, int sub_stride,
+                                                  const double *__restrict__ lines, const double *__restrict__ thr,
+                                                  const double *__restrict__ smr, const int32_t *__restrict__ overall,
+                                                  const uint32_t *__restrict__ status, double *__restrict__ worst_out,
+                                                  int32_t *__restrict__ bits_out, int32_t *__restrict__ steps)
+{
+    constexpr bool SHORT = (M == PACX_M_SHORT);
+    __shared__ RateLds<M> S;
+    const int lane = threadIdx.x;
+    const long long unit = blockIdx.x;
+    if (unit >= n_units)
+        return;
+    const long long cf = SHORT ? unit / PACX_SUB : unit;
+    const int sb = SHORT ? (int)(unit % PACX_SUB) : 0;
+    const long long frame = cf / n_ch;
+    const unsigned fl = flags ? flags[frame] : 0u;
+    if (SHORT != ((fl & 2u) != 0))
+        return;                                    /* the other instance's */
+    if (!SHORT && lane < PACX_SUB)
+        steps[cf * PACX_SUB + lane] = -1;          /* long frames use [0], written below by lane 0 again */
+    if (SHORT) {
+        unsigned st = 0;                           /* a hop the reference drops, as in k_rate_search */
+        for (int c = 0; c < n_ch; ++c)
+            st |= status[frame * n_ch + c];
+        if (st & 2u) {
+            if (lane == 0)
+                steps[cf * PACX_SUB + sb] = -1;
+            return;
+        }
+    }
+    const RateUnit u = rate_unit<M>(T, S, cf, sb, fl, max_bps, lines, thr, smr, overall);
+    const long long at = cf * (long long)row + (long long)sb * sub_stride;
+    int J = u.J;
+    if (sb * sub_stride + J >= row)                /* the entry point refuses such a row; never write past it */
+        J = row - 1 - sb * sub_stride < -1 ? -1 : row - 1 - sb * sub_stride;
+    for (int j = 0; j <= J; ++j) {
+        int bits = 0, acap = 0;
+        const double w = rate_eval<M>(T, S, u, j, bits, acap);
+        /* pack_body: the overall scale, then per band its size, its scale factor and its mantissas */
+        int n = u.has ? T.n_mant_size_bits + T.n_scale_bits + bits * u.nl : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            n += __shfl_xor(n, off, 64);
+        if (lane == 0) {
+            worst_out[at + j] = w;
+            bits_out[at + j] = n + T.n_scale_bits;
+        }
+    }
+    if (lane == 0)
+        steps[cf * PACX_SUB + sb] = J;
 }
 
 /* k_bitalloc (k_quant.hip) with a budget per unit: budget[cf][8], long frames use [0] */
@@ -242,7 +353,185 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
         atomicOr(&status[cf], ((cap & 1) ? 4u : 0u) | ((cap & 2) ? 16u : 0u));   /* ALLOC_CAP, GUARD */
 }
 
+/* ---- the solve of pacx_rate_solve (include/pacx.h): one target for the whole stream, on the stored curves ---- */
+constexpr int SOLVE_THREADS = 256;
+constexpr int SOLVE_MAX_LOOKUP = 12;               /* 1 + ceil(log2(J + 1)) for J < 2048, as RATE_MAX_EVAL */
+
+/* lo / hi / mid on the target grid, t = 64 T */
+struct SolveState {
+    int lo, hi, mid;
+    int phase;                                     /* 0: total(t_hi) is being taken, 1: the bisection */
+    int done, met;
+    unsigned long long total;                      /* of the pick in flight */
+};
+
+__device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either sign */
+{
+    return (a - (a < 0 ? 1 : 0)) / 2;
+}
+
+__global__ void k_solve_init(SolveState *s, int t_lo, int t_hi)
+{
+    s->lo = t_lo - 1;
+    s->hi = t_hi;
+    s->mid = t_hi;
+    s->phase = 0;
+    s->done = 0;
+    s->met = 0;
+    s->total = 0ull;
+}
+
+/* pick(unit, T) of every unit of one channel-frame per thread, the frame's bytes, their sum over the workgroup and
+   one atomicAdd.  final: the last launch, at the target found, which also writes the outputs. */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s, long long n_cf, int row,
+                                                             int sub_stride, const double *__restrict__ worst,
+                                                             const int32_t *__restrict__ bits,
+                                                             const int32_t *__restrict__ steps, int final,
+                                                             int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
+                                                             uint8_t *__restrict__ capped)
+{
+    __shared__ unsigned long long part[SOLVE_THREADS / 64];
+    if (s->done && !final)
+        return;                                    /* the answer is known: this launch does nothing */
+    const double target = (double)s->mid / 64.0;
+    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    unsigned long long mine = 0ull;
+    if (cf < n_cf) {
+        int sum = 0, units = 0;
+        bool cap = false;
+        for (int sb = 0; sb < PACX_SUB; ++sb) {
+            int J = steps[cf * PACX_SUB + sb];
+            int b = 0;
+            if (J >= 0) {
+                const int base = sb * sub_stride;
+                if (base + J >= row)               /* never read past the row */
+                    J = row - 1 - base;
+            }
+            if (J >= 0) {
+                const long long at = cf * (long long)row + sb * sub_stride;
+                int hi = J;
+                if (!(worst[at + J] <= target)) {
+                    cap = true;
+                } else {
+                    int lo = -1;
+                    for (int it = 0; it < SOLVE_MAX_LOOKUP && hi - lo > 1; ++it) {
+                        const int mid = (lo + hi) / 2;
+                        if (worst[at + mid] <= target)
+                            hi = mid;
+                        else
+                            lo = mid;
+                    }
+                }
+                sum += bits[at + hi];
+                b = 32 * hi;
+                ++units;
+            }
+            if (final)
+                budget[cf * PACX_SUB + sb] = b;
+        }
+        const int nby = units ? (sum + 4 + 7) >> 3 : 0;
+        if (nby > 0)
+            mine = (unsigned long long)nby + 4ull;
+        if (final) {
+            n_bytes[cf] = nby;
+            capped[cf] = cap ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0)
+        part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0ull;
+        for (int w = 0; w < SOLVE_THREADS / 64; ++w)
+            all += part[w];
+        if (all)
+            atomicAdd(&s->total, all);
+    }
+}
+
+/* one thread: the decision of include/pacx.h on the total the pick before it left.  final: write the result */
+__global__ void k_solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
+{
+    const unsigned long long total = s->total;
+    s->total = 0ull;
+    if (final) {
+        result->t = s->mid;
+        result->met = s->met;
+        result->total = (int64_t)total;
+        return;
+    }
+    if (s->done)
+        return;
+    const bool fits = total <= (unsigned long long)limit;
+    if (s->phase == 0) {
+        if (!fits) {                               /* unreachable: the largest target, met = 0 */
+            s->done = 1;
+            return;                                /* mid stays t_hi */
+        }
+        s->met = 1;
+        s->phase = 1;
+    } else if (fits) {
+        s->hi = s->mid;
+    } else {
+        s->lo = s->mid;
+    }
+    if (s->hi - s->lo > 1) {
+        s->mid = floor_half(s->lo + s->hi);
+    } else {
+        s->mid = s->hi;
+        s->done = 1;
+    }
+}
+
 }  // namespace
+
+size_t pacx_k::pacx_rate_solve_ws_bytes(void) { return sizeof(SolveState); }
+
+int pacx_k::pacx_rate_solve_pairs(int t_lo, int t_hi)
+{
+    /* the probe of t_hi, ceil(log2(t_hi - t_lo + 2)) halvings at most, the pick that writes the outputs */
+    int n = 0;
+    while ((1ll << n) < (long long)t_hi - t_lo + 2)
+        ++n;
+    return 2 + n;
+}
+
+void pacx_k::pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                                    double max_bits_per_sample, int row, int sub_stride, const double *lines,
+                                    const double *thr, const double *smr, const int32_t *overall, const uint32_t *status,
+                                    double *worst, int32_t *bits, int32_t *steps, hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    hipLaunchKernelGGL((k_rate_curve<PACX_M_LONG>), dim3((unsigned)n_cf), dim3(64), 0, st, T, flags, n_ch, n_cf,
+                       max_bits_per_sample, row, sub_stride, lines, thr, smr, overall, status, worst, bits, steps);
+    if (flags)
+        hipLaunchKernelGGL((k_rate_curve<PACX_M_SHORT>), dim3((unsigned)(n_cf * PACX_SUB)), dim3(64), 0, st, T, flags,
+                           n_ch, n_cf * PACX_SUB, max_bits_per_sample, row, sub_stride, lines, thr, smr, overall, status,
+                           worst, bits, steps);
+}
+
+void pacx_k::pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
+                                    const int32_t *bits, const int32_t *steps, long long limit, int t_lo, int t_hi,
+                                    int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+                                    hipStream_t st)
+{
+    SolveState *s = (SolveState *)ws;
+    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi);
+    const unsigned grid = (unsigned)((n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
+    hipLaunchKernelGGL(k_solve_init, dim3(1), dim3(1), 0, st, s, t_lo, t_hi);
+    for (int p = 0; p < pairs; ++p) {
+        const int final = p == pairs - 1;
+        if (grid)
+            hipLaunchKernelGGL(k_solve_pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, s, n_cf, row, sub_stride, worst,
+                               bits, steps, final, budget, n_bytes, capped);
+        hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, s, limit, final, result);
+    }
+}
+
 
 void pacx_k::pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                                      double target_nmr_db, double max_bits_per_sample, const double *lines,

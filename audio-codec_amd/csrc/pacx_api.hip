@@ -107,6 +107,9 @@ struct pacx_handle {
     char *ws_index;                   /* pacx_index_body's tables (PacxIndexWs)  */
     long long ws_thr_cf;              /* capacity of ws_thr (0 until the first pacx_nmr_batch) */
     double *ws_thr;                   /* [cf][1024] masked threshold, dB SPL     */
+    uint32_t *ws_rate_status;         /* [cf] status words of pacx_rate_curve_batch's front end (capacity ws_thr_cf) */
+    long long ws_solve_n;             /* 1 once ws_solve exists                  */
+    char *ws_solve;                   /* pacx_rate_solve's state                 */
     std::string err;
 };
 
@@ -318,6 +321,9 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->ws_index = nullptr;
     h->ws_thr_cf = 0;
     h->ws_thr = nullptr;
+    h->ws_rate_status = nullptr;
+    h->ws_solve_n = 0;
+    h->ws_solve = nullptr;
     h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
     h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
     h->ws_lists = nullptr;
@@ -609,7 +615,7 @@ static int post_launch_forked(pacx_handle *h, const char *what)
 
 /* The buffers outside pacx_reserve's workspace: each group has a capacity of its own (channel-frames; bytes for
    the index) and only ever grows, on the first call that needs more. */
-enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_N };
+enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_SOLVE, GROW_N };
 struct GrowGroup {
     long long *cap;
     struct { void **p; size_t unit; } buf[3];       /* unit: bytes per unit of capacity; p == nullptr ends the group */
@@ -630,9 +636,12 @@ static GrowGroup grow_group(pacx_handle *h, int which)
         return {&h->ws_dec_cf, {{(void **)&h->ws_dec_lines, PACX_M_LONG * sizeof(double)},
                                 {(void **)&h->ws_dec_sbr, 1},
                                 {(void **)&h->ws_dec_status, sizeof(uint32_t)}}};
-    /* pacx_nmr_batch: the masked threshold of every line */
+    /* pacx_nmr_batch: the masked threshold of every line; pacx_rate_curve_batch: its status words as well */
     case GROW_NMR:
-        return {&h->ws_thr_cf, {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)}}};
+        return {&h->ws_thr_cf, {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)},
+                                {(void **)&h->ws_rate_status, sizeof(uint32_t)}}};
+    case GROW_SOLVE:
+        return {&h->ws_solve_n, {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()}}};
     default:
         return {&h->ws_index_bytes, {{(void **)&h->ws_index, 1}}};
     }
@@ -1765,6 +1774,119 @@ extern "C" int pacx_encode_pack_budget_batch(pacx_handle *h, const pacx_pcm *in,
 {
     return encode_budgeted(h, in, frame_flags, false, 0.0, 0.0, budget, overall_scale, scale_factor, bit_alloc, mantissa,
                            status, payload, n_bytes, nullptr, stream, "pacx_encode_pack_budget_batch");
+}
+
+/* ---- coding to an average bit rate: the curve of every unit, then one target for the stream ---- */
+/* row and sub_stride of a curve: J + 1 of the widest long block, eight times J + 1 of the widest short sub-block */
+static void rate_curve_layout(const PacxTables &T, double max_bps, int *row, int *sub_stride)
+{
+    int j_long = 0, j_short = 0;
+    for (int lon = 0; lon < 2; ++lon) {
+        const int jl = pacx_rate_steps(max_bps, PACX_M_LONG, 0, lon, T.n_scale_bits, T.n_mant_size_bits, T.nb_long);
+        const int js = pacx_rate_steps(max_bps, PACX_M_SHORT, 1, lon, T.n_scale_bits, T.n_mant_size_bits, T.nb_short);
+        j_long = jl > j_long ? jl : j_long;
+        j_short = js > j_short ? js : j_short;
+    }
+    *sub_stride = j_short + 1;
+    *row = j_long + 1 > PACX_SUB * (j_short + 1) ? j_long + 1 : PACX_SUB * (j_short + 1);
+}
+
+extern "C" int pacx_rate_curve_layout(const pacx_handle *h, double max_bits_per_sample, int32_t *row,
+                                      int32_t *sub_stride)
+{
+    if (!h || !row || !sub_stride)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return PACX_E_UNSUPPORTED;
+    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+        return PACX_E_ARG;
+    int r, s;
+    rate_curve_layout(h->T, max_bits_per_sample, &r, &s);
+    *row = r;
+    *sub_stride = s;
+    return PACX_OK;
+}
+
+extern "C" int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                     double max_bits_per_sample, int32_t row, double *worst, int32_t *bits,
+                                     int32_t *steps, void *stream)
+{
+    const char *what = "pacx_rate_curve_batch";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (!worst || !bits || !steps)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    int need, sub_stride;
+    rate_curve_layout(h->T, max_bits_per_sample, &need, &sub_stride);
+    if (row < need)
+        return fail(h, PACX_E_ARG, std::string(what) + ": row is smaller than pacx_rate_curve_layout's (" +
+                                       std::to_string(need) + ")");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    /* the front end of pacx_encode_pack_nmr_batch; overall scales and status words stay in the workspace */
+    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
+    }
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
+    if (s.mixed)
+        s.lists(st);
+    s.mdct(st);
+    s.side(0, false, st);
+    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    pacx_launch_rate_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, row, sub_stride, h->ws_lines, h->ws_thr,
+                           h->ws_smr, h->ws_overall, h->ws_rate_status, worst, bits, steps, st);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                               const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db,
+                               double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
+                               pacx_rate_result *result, void *stream)
+{
+    const char *what = "pacx_rate_solve";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (!result || (n_cf > 0 && (!worst || !bits || !steps || !budget || !n_bytes || !capped)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1)
+        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    const double bound = 1048576.0;
+    if (!std::isfinite(nmr_lo_db) || !std::isfinite(nmr_hi_db) || fabs(nmr_lo_db) > bound || fabs(nmr_hi_db) > bound)
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be finite (at most 2^20 dB in magnitude)");
+    const double lo64 = nmr_lo_db * PACX_RATE_TARGET_GRID, hi64 = nmr_hi_db * PACX_RATE_TARGET_GRID;
+    if (lo64 != floor(lo64) || hi64 != floor(hi64))
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be multiples of 1/64 dB");
+    if (lo64 > hi64)
+        return fail(h, PACX_E_ARG, std::string(what) + ": nmr_lo_db is above nmr_hi_db");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = grow(h, GROW_SOLVE, 1);
+    if (rc)
+        return rc;
+    pacx_launch_rate_solve(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, limit_bytes, (int)lo64, (int)hi64,
+                           budget, n_bytes, capped, result, (hipStream_t)stream);
+    return post_launch(h, what);
 }
 
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,

@@ -326,6 +326,17 @@ PACX_HD double pacx_bit_budget(double target_bits_per_sample, int half_n, int is
     return budget;
 }
 
+/* J of a unit of the rate search and the rate curve (include/pacx.h): the scalar budget rule with the cap rate, in
+ * steps of PACX_RATE_STEP = 32 bits. */
+PACX_HD int pacx_rate_steps(double max_bits_per_sample, int half_n, int is_short, int last_or_next, int n_scale_bits,
+                            int n_mant_size_bits, int n_bands)
+{
+    const double cap = pacx_bit_budget(max_bits_per_sample, half_n, is_short, last_or_next, n_scale_bits,
+                                       n_mant_size_bits, n_bands, 0, 0);
+    const double jf = floor(cap / 32.0);
+    return jf > 0.0 ? (jf < 2047.0 ? (int)jf : 2047) : 0;
+}
+
 /* A11 -- BitAlloc, coder/bitalloc.py:77-121.  Returns the number of passes;
  * *hit_cap is set when the loop left through its 200-pass guard. */
 PACX_HD int pacx_bit_alloc(double budget, int max_mant_bits, int n_bands,

@@ -127,6 +127,19 @@ void pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch
 void pacx_launch_bitalloc_budget(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                                  const int32_t *budget, const double *smr, int32_t *bit_alloc, uint32_t *status,
                                  hipStream_t st);
+/* the rate curve of pacx_rate_curve_batch (k_rate_search's units and evaluation, every step j = 0 ... J) and the
+   solve of pacx_rate_solve on it: ws holds pacx_rate_solve_ws_bytes() bytes, the solve enqueues
+   pacx_rate_solve_pairs(t_lo, t_hi) pick / step pairs and never waits for one */
+void pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                            double max_bits_per_sample, int row, int sub_stride, const double *lines,
+                            const double *thr, const double *smr, const int32_t *overall, const uint32_t *status,
+                            double *worst, int32_t *bits, int32_t *steps, hipStream_t st);
+size_t pacx_rate_solve_ws_bytes(void);
+int pacx_rate_solve_pairs(int t_lo, int t_hi);
+void pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
+                            const int32_t *bits, const int32_t *steps, long long limit, int t_lo, int t_hi,
+                            int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+                            hipStream_t st);
 
 /* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,

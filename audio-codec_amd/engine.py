@@ -318,6 +318,59 @@ class Encoder:
         out["flags"], out["budget"] = fl, budget
         return out
 
+    def rate_curve_layout(self, max_bits_per_sample):
+        """(row, sub_stride) of a rate curve with this cap rate (pacx_rate_curve_layout)"""
+        row, sub = ctypes.c_int32(0), ctypes.c_int32(0)
+        self._call_rate("pacx_rate_curve_layout", ctypes.c_double(max_bits_per_sample), ctypes.byref(row),
+                        ctypes.byref(sub))
+        return row.value, sub.value
+
+    def rate_curve(self, pcm, flags, max_bits_per_sample, out=None):
+        """The rate-distortion curve of every long block / short sub-block (pacx_rate_curve_batch, include/pacx.h):
+        for every BitAlloc budget 32 j up to the cap rate's, worst [n_cf, row] float64 (max_b NMR_b, dB) and bits
+        [n_cf, row] int32 (what the packer writes); sub-block sb of a short-coded frame at [sb * sub_stride ...].
+        steps [n_cf, 8] int32: J of every unit, -1 where there is none.  Entries no unit uses are not written (they
+        keep what `out` held; NaN / 0 in a dict made here).  -> dict worst, bits, steps, row, sub_stride."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        row, sub = self.rate_curve_layout(max_bits_per_sample)
+        if out is None:
+            out = {"worst": torch.full((n_cf, row), float("nan"), dtype=torch.float64, device=self.device),
+                   "bits": torch.zeros((n_cf, row), dtype=torch.int32, device=self.device),
+                   "steps": torch.full((n_cf, _lib.SUB), -1, dtype=torch.int32, device=self.device)}
+        if tuple(out["worst"].shape) != (n_cf, row) or tuple(out["bits"].shape) != (n_cf, row) or \
+                tuple(out["steps"].shape) != (n_cf, _lib.SUB):
+            raise ValueError(f"rate curve: worst, bits [{n_cf}, {row}], steps [{n_cf}, {_lib.SUB}]")
+        self._call_rate("pacx_rate_curve_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(max_bits_per_sample),
+                        row, _ptr(out["worst"]), _ptr(out["bits"]), _ptr(out["steps"]), self._stream())
+        out["row"], out["sub_stride"], out["flags"] = row, sub, fl
+        return out
+
+    def rate_solve(self, curve, flags, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """One target NMR for the whole stream (pacx_rate_solve, include/pacx.h): the bisection over the grid of
+        1/64 dB in [nmr_lo_db, nmr_hi_db] for the smallest target whose body -- every unit at the budget
+        encode_pack_nmr's bisection would give it, read from the curve -- stays within limit_bytes.  flags: as
+        given to rate_curve (the curve's steps already carry what the solve needs of them).  -> dict
+        target_nmr_db, met (False: not even nmr_hi_db fits; the outputs are then that target's), total_bytes,
+        budget [n_cf, 8] int32 for encode_pack_budget, n_bytes [n_cf] int32 (predicted), capped [n_cf] bool."""
+        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
+        n_cf, row = worst.shape
+        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
+                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
+            raise ValueError("rate_solve: a curve as rate_curve returns it")
+        budget = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
+        n_bytes = torch.zeros((n_cf,), dtype=torch.int32, device=self.device)
+        capped = torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)
+        result = torch.zeros((4,), dtype=torch.int32, device=self.device)        # pacx_rate_result: t, met, total (int64)
+        self._call_rate("pacx_rate_solve", ctypes.c_int64(n_cf), int(row), int(curve["sub_stride"]), _ptr(worst),
+                        _ptr(bits), _ptr(steps), ctypes.c_int64(int(limit_bytes)), ctypes.c_double(nmr_lo_db),
+                        ctypes.c_double(nmr_hi_db), _ptr(budget), _ptr(n_bytes), _ptr(capped), _ptr(result),
+                        self._stream())
+        res = result.cpu().numpy()
+        t, met, total = int(res[0]), bool(res[1]), int(res.view(np.int64)[1])
+        return {"target_nmr_db": t / float(_lib.RATE_TARGET_GRID), "met": met, "total_bytes": total, "budget": budget,
+                "n_bytes": n_bytes, "capped": capped.bool()}
+
     def encode_vq(self, pcm, flags=None, out=None, want_entries=False, entries_per_band=160):
         """The shipped configuration (gain-shape PVQ, SBR if the handle has it) from
         PCM to finished payloads.  Returns dict: overall [n_cf,8], bit_alloc

@@ -413,8 +413,8 @@ def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False, hea
     return head + body[:n].cpu().numpy().tobytes()
 
 
-def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples):
-    """(.pac bytes, the outputs of Encoder.encode_pack_nmr for the n + 2 blocks the driver writes, the encoder)"""
+def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples):
+    """(CodingParams, encoder, PCM view, flags) of the one-batch scalar path with the cap rate as the handle's"""
     from .audiofile import CodingParams
     pcm = np.ascontiguousarray(pcm)
     hop = 1024
@@ -436,6 +436,12 @@ def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, bl
     planar = device_stream(enc, pcm, hop)
     view = PcmView.stream(planar, hop)
     flags = enc.transient_flags(planar, len(pcm) // hop, hop)[1] if block_switching else None
+    return cp, enc, view, flags
+
+
+def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples):
+    """(.pac bytes, the outputs of Encoder.encode_pack_nmr for the n + 2 blocks the driver writes, the encoder)"""
+    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
     out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
     body, total = enc.gather_body(out["payload"], out["n_bytes"])
     return header_bytes(cp) + body[:int(total.item())].cpu().numpy().tobytes(), out, enc
@@ -456,6 +462,78 @@ def encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320,
     if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
         raise NotImplementedError("constant-quality streams: scalar mantissas, nMDCTLines 1024, one batch")
     return _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples)[0]
+
+
+def _abr_limit(cp, view, head, kbps_per_channel, max_bytes):
+    """the body limit in bytes of one of the two ways to give a size"""
+    if (kbps_per_channel is None) == (max_bytes is None):
+        raise ValueError("give exactly one of kbps_per_channel and max_bytes")
+    if max_bytes is not None:
+        limit = int(max_bytes) - len(head)
+    else:
+        if not kbps_per_channel > 0:
+            raise ValueError("kbps_per_channel must be positive")
+        # all the blocks the driver writes, at this rate: tests/rate_model.kbps_per_channel's convention
+        limit = int(np.floor(kbps_per_channel * 1000.0 * cp.nChannels * view.n_frames * 1024 / cp.sampleRate / 8.0))
+    if limit < 0:
+        raise ValueError(f"max_bytes = {max_bytes} is smaller than the file's header ({len(head)} bytes)")
+    return limit
+
+
+def _abr_range(nmr_range_db):
+    try:
+        lo, hi = (float(v) for v in nmr_range_db)
+    except (TypeError, ValueError):
+        raise ValueError("nmr_range_db: (lowest, highest) target in dB") from None
+    grid = _lib.RATE_TARGET_GRID
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi or lo * grid != np.floor(lo * grid) or \
+            hi * grid != np.floor(hi * grid):
+        raise ValueError(f"nmr_range_db = {nmr_range_db}: finite, lowest <= highest, multiples of 1/{grid} dB")
+    return lo, hi
+
+
+def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db):
+    """One curve, one solve + second pass per size.  sizes: list of (kbps_per_channel, max_bytes).
+    -> list of (.pac bytes, solve dict, outputs of encode_pack_budget, body limit), the encoder"""
+    lo, hi = _abr_range(nmr_range_db)
+    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
+    head = header_bytes(cp)
+    limits = [_abr_limit(cp, view, head, k, b) for k, b in sizes]
+    curve = enc.rate_curve(view, flags, cp.targetBitsPerSample)
+    done = []
+    for limit in limits:
+        sol = enc.rate_solve(curve, flags, limit, lo, hi)
+        if not sol["met"]:
+            raise ValueError(f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
+                             f"{sol['total_bytes']} bytes ({len(head) + sol['total_bytes']} with the header), the "
+                             f"smallest size this range of targets gives")
+        out = enc.encode_pack_budget(view, flags, sol["budget"])
+        body, total = enc.gather_body(out["payload"], out["n_bytes"])
+        done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, limit))
+    return done, enc
+
+
+def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
+                      block_switching=False, header_samples=None, nmr_range_db=(-30, 30), use_vq=False, use_sbr=False,
+                      chunk_hops=None, n_lines=1024):
+    """Whole-stream encode to an average bit rate -> .pac bytes: the best constant quality that fits a size.  One
+    target NMR for the whole stream, the smallest on the grid of 1/64 dB in nmr_range_db (by the bisection of
+    include/pacx.h, pacx_rate_solve) at which the stream of encode_stream_nmr(target) stays within the size; the
+    bytes are that call's.  Give exactly one size:
+      kbps_per_channel  the body (records and their length prefixes) takes at most
+                        floor(kbps * 1000 * nCh * blocks * 1024 / sampleRate / 8) bytes, blocks = the n + 2 blocks the
+                        driver writes;
+      max_bytes         the whole file, header included.
+    max_kbps_per_channel caps every block as in encode_stream_nmr.  ValueError when even the highest target of the
+    range does not fit; the message names the smallest size reachable.  The rate-distortion curve of every block is
+    taken once (Encoder.rate_curve), the solve reads only that (Encoder.rate_solve), the second pass is
+    Encoder.encode_pack_budget: quality.rate_curve gives the curve for several sizes.  Scalar mantissas, 1024 lines,
+    one batch, as encode_stream_nmr."""
+    if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
+        raise NotImplementedError("average-bit-rate streams: scalar mantissas, nMDCTLines 1024, one batch")
+    done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
+                                 block_switching, header_samples, nmr_range_db)
+    return done[0][0]
 
 
 def parse_header(data):

@@ -329,6 +329,60 @@ def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=3
     return data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info
 
 
+def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
+                          block_switching=False, header_samples=None, nmr_range_db=(-30, 30)):
+    """pacfile.encode_stream_abr with a Report: -> (.pac bytes, Report, info).  A list for kbps_per_channel or for
+    max_bytes gives a list of such triples, all solved from one rate curve.  info, for the n + 2 blocks the driver
+    submits, is encode_stream_to_nmr's (budget, capped, written, kbps_per_channel: achieved) and
+      target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
+      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written)."""
+    from . import pacfile
+    many = isinstance(kbps_per_channel, (list, tuple)) or isinstance(max_bytes, (list, tuple))
+    if many:
+        if kbps_per_channel is not None and max_bytes is not None:
+            raise ValueError("give exactly one of kbps_per_channel and max_bytes")
+        sizes = [(k, None) for k in kbps_per_channel] if kbps_per_channel is not None else [(None, b) for b in max_bytes]
+    else:
+        sizes = [(kbps_per_channel, max_bytes)]
+    done, enc = pacfile._encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching,
+                                           header_samples, nmr_range_db)
+    n_ch = np.asarray(pcm).shape[1]
+    res = []
+    for data, sol, out, limit in done:
+        n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
+        n_blocks = len(n_bytes)
+        info = {
+            "target_nmr_db": sol["target_nmr_db"],
+            "limit_bytes": limit,
+            "total_bytes": sol["total_bytes"],
+            "n_bytes": sol["n_bytes"].cpu().numpy().reshape(n_blocks, n_ch),
+            "budget": sol["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB),
+            "capped": sol["capped"].cpu().numpy().reshape(n_blocks, n_ch),
+            "written": n_bytes[:, 0] > 0,
+            "kbps_per_channel": 8.0 * int(np.sum(n_bytes[n_bytes > 0] + 4)) / (n_blocks * HOP / float(sample_rate)) /
+            n_ch / 1000.0,
+        }
+        res.append((data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info))
+    return res if many else res[0]
+
+
+def rate_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False):
+    """The rate-distortion curve of every long block / short sub-block of a stream, for plotting rate against
+    quality: -> dict of NumPy arrays for the n + 2 blocks the driver submits,
+      worst  float64 [blocks, nCh, row]: max_b NMR_b (dB) with BitAlloc budget 32 j, sub-block sb of a short-coded
+             block at [sb * sub_stride + j]; NaN where there is no unit or no such budget;
+      bits   int32 [blocks, nCh, row]: the bits of the unit in the file with that budget;
+      steps  int32 [blocks, nCh, 8]: the largest j of every unit (the cap rate's budget), -1 where there is none
+    and the ints row, sub_stride."""
+    from . import pacfile
+    cp, enc, view, flags = pacfile._rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, None)
+    c = enc.rate_curve(view, flags, cp.targetBitsPerSample)
+    n_ch = cp.nChannels
+    return {"worst": c["worst"].cpu().numpy().reshape(-1, n_ch, c["row"]),
+            "bits": c["bits"].cpu().numpy().reshape(-1, n_ch, c["row"]),
+            "steps": c["steps"].cpu().numpy().reshape(-1, n_ch, _lib.SUB), "row": c["row"], "sub_stride": c["sub_stride"]}
+
+
 def nmr_of_file(pcm, pac_bytes, block_switching=None, chunk_hops=4096):
     """Report of a .pac made elsewhere (by the reference itself, say) against the PCM it was made from.  The
     hop-to-record map is re-derived the way the writer makes it: the transient detector gives the flags, a

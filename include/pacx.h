@@ -729,6 +729,80 @@ int pacx_encode_pack_budget_batch(pacx_handle *h, const pacx_pcm *in, const uint
                                   int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
                                   int32_t *n_bytes, void *stream);
 
+/* ---- coding to an average bit rate: one target NMR per stream ---------------- */
+
+#define PACX_RATE_TARGET_GRID 64  /* targets of pacx_rate_solve are multiples of 1 / 64 dB */
+
+/*
+ * "The best constant quality that fits N bytes", in two steps that share nothing but arrays: the rate-distortion
+ * curve of every unit (pacx_rate_curve_batch, one analysis of the PCM), then one cheap solve per size wanted
+ * (pacx_rate_solve).  The budgets it returns go to pacx_encode_pack_budget_batch, whose n_bytes equal the ones
+ * predicted here.  Scalar coder, 1024 lines, as pacx_encode_pack_nmr_batch.
+ *
+ * The curve.  Units, cap, J and the evaluation are those of pacx_encode_pack_nmr_batch (one device function serves
+ * both, so the same unit, budget and target give the same decision bit for bit).  For j = 0 ... J:
+ *
+ *   worst[j] = max_b NMR_b of the unit coded with BitAlloc budget 32 j        what ok(32 j) compares with the target
+ *   bits[j]  = nScaleBits + sum_b (nMantSizeBits + nScaleBits + alloc_b * lines_b)      what the packer writes for it
+ *
+ * One row of `row` entries per channel-frame: a long frame uses [0 ... J], a short-coded frame keeps sub-block sb
+ * at [sb * sub_stride ... sb * sub_stride + J]; entries beyond are not written.  steps int32 [n_cf][8] holds J of
+ * every unit and -1 where there is none: slots 1-7 of a long frame, every slot of a hop the reference drops
+ * (PACX_ST_ZERO_SUBBLOCK).  pacx_rate_curve_layout (host only) gives row and sub_stride = J_short_max + 1 for a
+ * handle and a cap rate, the maximum over the flag combinations (the budget rule depends on them).
+ *
+ *   max_bits_per_sample: as pacx_encode_pack_nmr_batch, 0 < . <= 16
+ *   row:                 at least pacx_rate_curve_layout's
+ *   worst (out):         float64 [n_cf][row];  bits (out): int32 [n_cf][row];  steps (out): int32 [n_cf][8]
+ * Runs MDCT -> side chain -> masked threshold -> k_rate_curve on `stream`; the lines, thresholds, overall scales
+ * and status words stay in the handle's workspace.  PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr;
+ * PACX_E_ARG for a null output, a cap rate outside (0, 16], a row that is too small.
+ */
+int pacx_rate_curve_layout(const pacx_handle *h, double max_bits_per_sample, int32_t *row, int32_t *sub_stride);
+int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, double max_bits_per_sample,
+                          int32_t row, double *worst, int32_t *bits, int32_t *steps, void *stream);
+
+typedef struct pacx_rate_result {
+    int32_t t;                    /* the target found, in 1 / PACX_RATE_TARGET_GRID dB */
+    int32_t met;                  /* 1: total <= limit_bytes; 0: not even at nmr_hi_db (t is then its grid value) */
+    int64_t total;                /* body bytes at t, the 4-byte length prefixes included */
+} pacx_rate_result;
+
+/*
+ * The solve.  The target lives on a grid, T = t / 64 dB, t an integer in [t_lo, t_hi] = 64 [nmr_lo_db, nmr_hi_db]:
+ *
+ *   pick(unit, T): the bisection of pacx_encode_pack_nmr_batch with ok(32 j) := worst[j] <= T
+ *                  -> j*; not (worst[J] <= T): j* = J and the channel-frame is marked capped
+ *   bytes(cf, T) = 0 for a dropped hop, else ((sum over its units of bits[j*]) + 4 + 7) >> 3
+ *   total(T)     = sum over cf with bytes > 0 of (bytes + 4)                  the .pac body, length prefixes included
+ *   if total(t_hi) > limit_bytes:  met = 0, t = t_hi
+ *   else: lo = t_lo - 1, hi = t_hi; while hi - lo > 1: mid = floor((lo + hi) / 2);
+ *                                                      if total(mid) <= limit_bytes: hi = mid else lo = mid
+ *         t = hi, met = 1
+ *
+ * worst[j] is not monotone in j (see the search above) and total need not be monotone in t, so the result is this
+ * bisection's, not a global optimum: total(t) <= limit_bytes holds at the t returned and failed at the last t
+ * tried below it.  On the device: a pick kernel (one channel-frame per thread, at most 8 x 11 look-ups, a
+ * workgroup reduction, one 64-bit integer atomicAdd per workgroup) and a one-thread step kernel, enqueued as
+ * 2 + ceil(log2(t_hi - t_lo + 2)) pairs whatever the data; pairs after the answer is known do nothing, and the
+ * host waits for none.  Integer sums: the result does not depend on the order of execution.  The solve's few
+ * words of state live in the handle: solves of one handle belong on one stream, as all its calls do.
+ *
+ *   worst, bits, steps, row, sub_stride: a curve as pacx_rate_curve_batch writes it (row >= 7 sub_stride + 1); a
+ *                  J that would leave its row is cut to the row
+ *   limit_bytes:   >= 0, for the body (the file's header is not counted)
+ *   nmr_lo_db <= nmr_hi_db: finite, multiples of 1 / 64 dB, at most 2^20 dB in magnitude
+ *   budget (out):  int32 [n_cf][8], the layout pacx_encode_pack_budget_batch takes (0 where there is no unit)
+ *   n_bytes (out): int32 [n_cf], bytes(cf, T) at the t returned
+ *   capped (out):  uint8 [n_cf]
+ *   result (out):  device memory
+ * PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr; PACX_E_ARG for a null pointer, a bad row, bounds
+ * that are not finite, inverted or off the grid, a negative limit.
+ */
+int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                    const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                    int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
