@@ -19,7 +19,7 @@
  * float64 lines out = 2 KB (new hop) + 8 KB algorithmic HBM bytes.
  */
 #include "pacx_launch.h"
-#include "wave_fft.h"
+#include "mdct_dev.h"
 #include "pcm_stage.h"
 
 
@@ -38,10 +38,8 @@ __global__ __launch_bounds__(64) void k_mdct_long(PacxTables T, PacxPcmView in,
     if (cf >= n_cf)
         return;
     const unsigned fl = flags ? flags[cf / in.n_ch] : 0u;
-    if ((skip_cur & 1) && (fl & 2u))
+    if (skip_cur && (fl & 2u))
         return;
-    if ((skip_cur & 2) && pacx_window_kind(fl) == 0)
-        return;                              /* sine frames were done by k_mdct_long_v2 */
     /* prewin: 0 = the window the flags select, 1 = none (mdct.MDCT on windowed data),
        2 = KBDWindow (coder/window.py:45-57) */
     const double *__restrict__ w = prewin == 1 ? T.ones : prewin == 2 ? T.kbd_long
@@ -50,19 +48,18 @@ __global__ __launch_bounds__(64) void k_mdct_long(PacxTables T, PacxPcmView in,
     stage_samples<DT, FAST>(raw, in, cf, 0, PACX_N_LONG, lane);
     __syncthreads();
 
-    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
+    const int M = PACX_M_LONG;
     cplx v[8];
 #pragma unroll
     for (int n1 = 0; n1 < 8; ++n1) {
         const int n = lane + 64 * n1;
+        int i0, i1, i2, i3;
+        mdct_fold_index<PACX_N_LONG>(n1, n, i0, i1, i2, i3);
         double re, im;
         if (n1 < 4) {            /* n < Q/2 */
-            const int i0 = 3 * Q - 1 - 2 * n, i1 = 3 * Q + 2 * n, i2 = Q - 1 - 2 * n, i3 = Q + 2 * n;
             re = -(w[i0] * PcmStage<DT>::get(raw, i0)) - w[i1] * PcmStage<DT>::get(raw, i1);
             im = w[i2] * PcmStage<DT>::get(raw, i2) - w[i3] * PcmStage<DT>::get(raw, i3);
         } else {
-            const int m = 2 * n - Q;
-            const int i0 = m, i1 = M - 1 - m, i2 = 2 * Q + m, i3 = 4 * Q - 1 - m;
             re = w[i0] * PcmStage<DT>::get(raw, i0) - w[i1] * PcmStage<DT>::get(raw, i1);
             im = -(w[i2] * PcmStage<DT>::get(raw, i2)) - w[i3] * PcmStage<DT>::get(raw, i3);
         }
@@ -139,7 +136,6 @@ __global__ __launch_bounds__(64) void k_mdct_short(PacxTables T, PacxPcmView in,
 
     const int g = lane >> 3, r = lane & 7;
     const E *sub = raw + g * PACX_M_SHORT;
-    const int Q = PACX_N_SHORT / 4, M = PACX_M_SHORT;
 
     /* coder/pacfile.py:530-533: an all-zero sub-block makes the writer drop the hop */
     if (status) {
@@ -158,14 +154,13 @@ __global__ __launch_bounds__(64) void k_mdct_short(PacxTables T, PacxPcmView in,
 #pragma unroll
     for (int n1 = 0; n1 < 8; ++n1) {
         const int n = r + 8 * n1;
+        int i0, i1, i2, i3;
+        mdct_fold_index<PACX_N_SHORT>(n1, n, i0, i1, i2, i3);
         double re, im;
         if (n1 < 4) {
-            const int i0 = 3 * Q - 1 - 2 * n, i1 = 3 * Q + 2 * n, i2 = Q - 1 - 2 * n, i3 = Q + 2 * n;
             re = -(w[i0] * PcmStage<DT>::get(sub, i0)) - w[i1] * PcmStage<DT>::get(sub, i1);
             im = w[i2] * PcmStage<DT>::get(sub, i2) - w[i3] * PcmStage<DT>::get(sub, i3);
         } else {
-            const int m = 2 * n - Q;
-            const int i0 = m, i1 = M - 1 - m, i2 = 2 * Q + m, i3 = 4 * Q - 1 - m;
             re = w[i0] * PcmStage<DT>::get(sub, i0) - w[i1] * PcmStage<DT>::get(sub, i1);
             im = -(w[i2] * PcmStage<DT>::get(sub, i2)) - w[i3] * PcmStage<DT>::get(sub, i3);
         }
@@ -224,17 +219,6 @@ static void launch_mdct(const PacxTables &T, const PacxPcmView &in, const uint8_
                            scale_out, status);
         return;
     }
-    /* mixed = 2 / 3 (kept for callers that run v2 on sine-window frames only): the
-       long kernel takes the transition-window frames (3: and skips CUR frames),
-       the short kernel only CUR frames (3) */
-    if (mixed == 2 || mixed == 3) {
-        hipLaunchKernelGGL((k_mdct_long<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf,
-                           mixed == 3 ? 3 : 2, prewin, lines, scale_out, scale_stride);
-        if (mixed == 3)
-            hipLaunchKernelGGL((k_mdct_short<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, 1,
-                               prewin, lines, scale_out, status);
-        return;
-    }
     if (!short_blocks || mixed)
         hipLaunchKernelGGL((k_mdct_long<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed,
                            prewin, lines, scale_out, scale_stride);
@@ -243,8 +227,8 @@ static void launch_mdct(const PacxTables &T, const PacxPcmView &in, const uint8_
                            prewin, lines, scale_out, status);
 }
 
-/* mixed = 1: long kernel skips CUR frames, short kernel takes only CUR frames
- * (scale_out is then [n_cf][8]); otherwise short_blocks selects one of them. */
+/* mixed = 1: long kernel skips CUR frames, short kernel takes only CUR frames (scale_out is then
+ * [n_cf][8]); mixed = 4: only the short kernel, on the CUR frames; mixed = 0: short_blocks selects one. */
 void pacx_k::pacx_launch_mdct(const PacxTables &T, const PacxPcmView &in, int dtype, int fast,
                       const uint8_t *flags, long long n_cf, int short_blocks, int mixed, int prewin,
                       double *lines, int32_t *scale_out, int scale_stride, uint32_t *status,

@@ -1,14 +1,14 @@
 /*
  * k_mdct3.hip -- k_mdct_long_v2 with TWO channel-frames in flight per wave
  * (sine window, no per-frame flags: the headline batch).  Same arithmetic, frame
- * by frame, as k_mdct2.hip; what changes is the instruction stream: the stages of
+ * by frame, as k_mdct2.hip (both call mdct_dev.h); what changes is the instruction stream: the stages of
  * frames A and B are interleaved, so one frame's LDS round trips hide behind the
  * other's arithmetic, and every table value read from LDS (window, pre/post
  * twiddle, per-lane FFT twiddles) serves both frames.  LDS: one 8 KB FFT tile and
  * two 4 KB PCM landing buffers per wave + the 24 KB of tables.
  */
 #include "pacx_launch.h"
-#include "wave_fft.h"
+#include "mdct_dev.h"
 
 /*
  * k_mdct_long_x2p: the two frames of a wave take turns on ONE 8 KB FFT tile, exchange
@@ -39,11 +39,6 @@ extern "C" int pacx_debug_read(long long *out, int n)
 #else
 #define DBG_T(k) do { } while (0)
 #endif
-/* 16-byte line stores per epilogue (1024 lines = 64 lanes x 8 stores x 2 doubles).  The counted
-   wait of k_mdct_long_x2p is derived from it; tests/test_build_isa.py reads this constant and
-   checks the compiled code against it. */
-constexpr int EPI_STORES = 8;
-
 /* STEP: the instantiation the whole-path entry points launch (it also initialises the frames' status words and
    sub-block scales); the stand-alone pacx_mdct_batch launches STEP = false.  Two symbols, so that a kernel trace
    tells the stand-alone launches -- the ones the HBM roofline figure is quoted on -- from the in-step ones, which
@@ -57,10 +52,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mdct_long_x2p(PacxTables T
 {
     __shared__ __attribute__((aligned(16))) cplx tiles[WAVES][WFFT_TILE_N];
     __shared__ __attribute__((aligned(16))) short raws[WAVES][2][PACX_N_LONG];
-    __shared__ __attribute__((aligned(16))) cplx twl[512];
-    __shared__ __attribute__((aligned(16))) double wsin[1024];
-    __shared__ __attribute__((aligned(16))) cplx w64[7][8];        /* W64^(r k2), k2 = 1..7 */
-    __shared__ __attribute__((aligned(16))) cplx w1s[7][64];       /* W512^(lane k1), k1 = 1..7 */
+    __shared__ __attribute__((aligned(16))) MdctLongTables tb;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     cplx *tile = tiles[wv];
@@ -80,99 +72,20 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mdct_long_x2p(PacxTables T
                      "global_load_lds_dwordx4 %0, off offset:3072"
                      :: "v"(src + lane), "s"(lds) : "memory", "m0");
     };
-    /* XCD-aware frame order: workgroups are handed to the 8 XCDs round-robin, so workgroup b
-       runs on XCD b % 8.  Consecutive frames share a hop of PCM; giving every XCD a CONTIGUOUS
-       run of workgroups' worth of frames keeps that shared hop in one XCD's L2 instead of
-       fetching it from HBM once per XCD (a quarter of the hops were read twice) */
-    const unsigned vb = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const unsigned vb = pacx_xcd_block(blockIdx.x, gridDim.x);    /* XCD-aware frame order (pacx_dev.h) */
     const unsigned g = vb * WAVES + wv;
     unsigned cfa = g, cfb = g + n_waves;
     if (cfa < total)
         stage(cfa, 0);
     if (cfb < total)
         stage(cfb, 1);
-    for (int i = tid; i < 512; i += 64 * WAVES)
-        twl[i] = T.tw_long[i];
-    const double kscale = (2.0 / 65535.0) * (2.0 / PACX_N_LONG);
-    for (int i = tid; i < 1024; i += 64 * WAVES)
-        wsin[i] = T.win_long[i] * kscale;
-    if (tid < 56)
-        w64[tid >> 3][tid & 7] = T.w512[8 * (tid & 7) * ((tid >> 3) + 1)];
-    for (int i = tid; i < 7 * 64; i += 64 * WAVES)
-        w1s[i >> 6][i & 63] = T.w512[(i & 63) * ((i >> 6) + 1)];
+    tb.stage<64 * WAVES>(T, tid);
     __syncthreads();
 
-    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
-    const int g8 = lane >> 3, r8 = lane & 7;
-    auto wr1 = [&](const cplx *v) {
-#pragma unroll
-        for (int k1 = 0; k1 < 8; ++k1)
-            tile[64 * k1 + (lane ^ (8 * k1))] = v[k1];
-    };
-    auto rd1 = [&](cplx *v) {
-#pragma unroll
-        for (int n2 = 0; n2 < 8; ++n2)
-            v[n2] = tile[64 * g8 + 8 * (n2 ^ g8) + r8];
-    };
-    auto wr2 = [&](const cplx *v) {
-#pragma unroll
-        for (int k2 = 0; k2 < 8; ++k2)
-            tile[64 * g8 + 8 * k2 + (r8 ^ g8)] = v[k2];
-    };
-    auto rd2 = [&](cplx *v) {
-#pragma unroll
-        for (int n3 = 0; n3 < 8; ++n3)
-            v[n3] = tile[64 * r8 + 8 * g8 + (n3 ^ r8)];
-    };
-    auto tw1 = [&](cplx *v) {
-#pragma unroll
-        for (int k1 = 1; k1 < 8; ++k1)
-            v[k1] = c_mul(v[k1], w1s[k1 - 1][lane]);
-    };
-    auto tw2 = [&](cplx *v) {
-#pragma unroll
-        for (int k2 = 1; k2 < 8; ++k2)
-            v[k2] = c_mul(v[k2], w64[k2 - 1][r8]);
-    };
+    const cplx *w1 = tb.w1(lane), *w2 = tb.w2(lane);
     auto epilogue = [&](const cplx *v, unsigned cf) {
-        double a[8], b[8];
-        double mx = 0.0;
-#pragma unroll
-        for (int k3 = 0; k3 < 8; ++k3) {
-            const cplx d = twl[lane + 64 * k3];
-            a[k3] = fma(v[k3].x, d.x, -(v[k3].y * d.y));      /* Re y = X[2k] */
-            b[k3] = -fma(v[k3].x, d.y, v[k3].y * d.x);        /* -Im y = X[1023 - 2k] */
-            mx = fmax(mx, fmax(fabs(a[k3]), fabs(b[k3])));
-        }
-        double odd[8];
-#pragma unroll
-        for (int k3 = 0; k3 < 8; ++k3)
-            odd[k3] = __shfl(b[7 - k3], 63 - lane, 64);
-        /* overall scale: ScaleFactor is non-increasing in its argument, so the scale of
-           the block maximum is the minimum of the lanes' own scales -- a few-bit integer,
-           found by bisection with one ballot per bit while the lane reversal above is in
-           flight (a 64-bit max over the wave would be six dependent LDS round trips) */
-        int lo = 0;
-        bool guard = false;
-        if (scale_out) {
-            const int s = pacx_scale_factor(mx, T.n_scale_bits, 5);
-            for (int bit = T.n_scale_bits - 1; bit >= 0; --bit)
-                if (!__builtin_amdgcn_ballot_w64(s < lo + (1 << bit)))
-                    lo += 1 << bit;
-            /* PACX_ST_GUARD: the lanes that decide the minimum hold a maximum within a factor
-               two of the block's; theirs sitting at a boundary of ScaleFactor flags the frame
-               (line error bound relative to the block maximum, pacx_exact.h) */
-            guard = STEP && T.guard && status_init && s == lo && pacx_scale_guard(mx, T.n_scale_bits, 5, 2.0 * PACX_GUARD_LINE_ERR * mx);
-        }
-        double2 *__restrict__ out = (double2 *)(lines + (long long)cf * PACX_M_LONG);
-        static_assert(EPI_STORES * 64 * 2 == PACX_M_LONG, "one epilogue = EPI_STORES 16-byte stores per lane");
-#pragma unroll
-        for (int k3 = 0; k3 < EPI_STORES; ++k3)
-            out[lane + 64 * k3] = make_double2(a[k3], odd[k3]);
-        if (scale_out && lane == 0)
-            scale_out[(long long)cf * scale_stride] = lo;
-        if (__builtin_amdgcn_ballot_w64(guard) && lane == 0)
-            status_init[cf] = 16u;                 /* after this lane's own zero-store of the same word */
+        mdct_long_epilogue(T, v, [&](int k3) { return tb.twl[lane + 64 * k3]; }, cf, lane, lines, scale_out,
+                           scale_stride, STEP ? status_init : nullptr);
     };
 #ifdef PACX_MDCT_DEBUG
     const bool dbg_on = blockIdx.x == 7;
@@ -201,47 +114,24 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mdct_long_x2p(PacxTables T
 #pragma unroll
             for (int n1 = 0; n1 < 8; ++n1) {
                 const int n = lane + 64 * n1;
-                int i0, i1, i2, i3;
-                double wa, wb;
-                if (n1 < 4) {
-                    i0 = 3 * Q - 1 - 2 * n; i1 = 3 * Q + 2 * n; i2 = Q - 1 - 2 * n; i3 = Q + 2 * n;
-                    wa = wsin[i3]; wb = wsin[i2];                    /* = w[i0], w[i1] */
-                } else {
-                    const int m = 2 * n - Q;
-                    i0 = m; i1 = M - 1 - m; i2 = 2 * Q + m; i3 = 4 * Q - 1 - m;
-                    wa = wsin[i0]; wb = wsin[i1];                    /* = w[i3], w[i2] */
-                }
-                const cplx tw = twl[n];
+                int i0, i1, i2, i3, ia, ib;
+                mdct_fold_index<PACX_N_LONG>(n1, n, i0, i1, i2, i3);
+                mdct_fold_sym_index(n1, i0, i1, i2, i3, ia, ib);
+                const double wa = tb.wsin[ia], wb = tb.wsin[ib];     /* every table value serves both frames */
+                const cplx tw = tb.twl[n];
 #pragma unroll
                 for (int f = 0; f < 2; ++f) {
-                    const short *raw = raws[wv][f];
-                    int c0 = raw[i0], c1 = raw[i1], c2 = raw[i2], c3 = raw[i3];
-                    asm("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
-                    lowest[f] = min(lowest[f], min(min(c0, c1), min(c2, c3)));
-                    double re, im;
-                    if (n1 < 4) {
-                        re = -fma(wb, (double)c1, wa * (double)c0);
-                        im = fma(wb, (double)c2, -(wa * (double)c3));
-                    } else {
-                        re = fma(wa, (double)c0, -(wb * (double)c1));
-                        im = -fma(wb, (double)c2, wa * (double)c3);
-                    }
-                    v[f][n1] = c_mul(make_double2(re, im), tw);
+                    double c0, c1, c2, c3;
+                    mdct_fold_codes<true>(raws[wv][f], i0, i1, i2, i3, c0, c1, c2, c3, lowest[f]);
+                    v[f][n1] = c_mul(mdct_fold_sym(n1, wa, wb, c0, c1, c2, c3), tw);
                 }
             }
             if (pass || !__builtin_amdgcn_ballot_w64(lowest[0] == -32768 || lowest[1] == -32768))
                 break;
             wave_lds_fence();
 #pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                unsigned *rw = (unsigned *)raws[wv][f];
-                for (int j = 0; j < 16; ++j) {
-                    unsigned x = rw[lane + 64 * j];
-                    if ((x & 0xFFFFu) == 0x8000u) x &= 0xFFFF0000u;
-                    if ((x >> 16) == 0x8000u) x &= 0x0000FFFFu;
-                    rw[lane + 64 * j] = x;
-                }
-            }
+            for (int f = 0; f < 2; ++f)
+                mdct_zero_min_codes((unsigned *)raws[wv][f], lane);
             wave_lds_fence();
         }
         wave_lds_fence();
@@ -269,15 +159,15 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_mdct_long_x2p(PacxTables T
         DBG_T(2);
 
         /* 512-point FFTs (wave_fft.h fft512n), the two frames alternating on the tile */
-        dft8(v[0]); tw1(v[0]); wr1(v[0]);
-        dft8(v[1]); tw1(v[1]);
-        wave_lds_fence(); rd1(v[0]); wr1(v[1]);
-        dft8(v[0]); tw2(v[0]);
-        wave_lds_fence(); rd1(v[1]); wr2(v[0]);
-        dft8(v[1]); tw2(v[1]);
-        wave_lds_fence(); rd2(v[0]); wr2(v[1]);
+        dft8(v[0]); fft512n_twiddle(v[0], w1, 64); fft512n_x1_write(tile, v[0], lane);
+        dft8(v[1]); fft512n_twiddle(v[1], w1, 64);
+        wave_lds_fence(); fft512n_x1_read(tile, v[0], lane); fft512n_x1_write(tile, v[1], lane);
+        dft8(v[0]); fft512n_twiddle(v[0], w2, 8);
+        wave_lds_fence(); fft512n_x1_read(tile, v[1], lane); fft512n_x2_write(tile, v[0], lane);
+        dft8(v[1]); fft512n_twiddle(v[1], w2, 8);
+        wave_lds_fence(); fft512n_x2_read(tile, v[0], lane); fft512n_x2_write(tile, v[1], lane);
         dft8(v[0]);
-        wave_lds_fence(); rd2(v[1]);
+        wave_lds_fence(); fft512n_x2_read(tile, v[1], lane);
         DBG_T(3);
         epilogue(v[0], cfa);
         DBG_T(4);

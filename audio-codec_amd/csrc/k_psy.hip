@@ -25,7 +25,7 @@
  *   X[k] = (Z[k] + conj Z[N/2-k])/2 - (j/2) W_N^k (Z[k] - conj Z[N/2-k]).
  */
 #include "pacx_launch.h"
-#include "wave_fft.h"
+#include "mdct_dev.h"
 #include "pcm_stage.h"
 #include "wave_np_sum.h"
 #include "quant_dev.h"
@@ -94,22 +94,18 @@ __device__ __forceinline__ PacxPeak make_peak(double left, double centre, int f,
 /* LDS of one wave.  The three users of it follow one another in time: raw samples (until
  * the FFT inputs are in registers), the FFT exchange tile (until the spectrum is in
  * registers), then the intensities together with the peak lists.
- *   COMPACT (no SBR): 9.1 KB for int16 input
+ * 9.1 KB for int16 input:
  *     region B (8.06 KB): raw, then the tile, then inten -- whose low slots the maskers'
  *       Bark values and SPLs overwrite one round of 64 at a time (masker p comes from bins
  *       i_p - 1, i_p with i_p >= 2 p + 1, so slots 2p, 2p + 1 are never read again)
  *     region A (1 KB): peak bin numbers
- *   (COMPACT false, 17.5 KB, region A holding the tile: the layout of the time when the maskers'
- *    Bark values and SPLs were kept in LDS; no launcher uses it any more -- SBR handles, whose epilogue
- *    needs the intensities to the end, run the compact kernel too)
  * The packed spectrum Z never goes to LDS: the real-FFT split needs Z[k] with
  * Z[N/2-k], and with natural-order FFT output (wave_fft.h fft512n) that
  * partner sits in the mirrored lane's mirrored register, one ds_bpermute away. */
-template <int DT, bool COMPACT> struct SideLongLds {
+template <int DT> struct SideLongLds {
     typedef typename PcmStage<DT>::elem E;
     static constexpr int RAW_BYTES = (int)sizeof(E) * PACX_N_LONG;
-    static constexpr int A_BYTES = COMPACT ? 1024
-                                           : 1024 + 2 * PACX_MAX_PEAKS * 8;   /* >= 512 * sizeof(cplx) */
+    static constexpr int A_BYTES = 1024;
     static constexpr int B_BYTES = RAW_BYTES > 1032 * 8 ? RAW_BYTES : 1032 * 8;
     static constexpr int BYTES = A_BYTES + B_BYTES;
 };
@@ -123,7 +119,6 @@ template <int DT, bool COMPACT> struct SideLongLds {
 __device__ __forceinline__ void fft512n_g2(cplx a[8], cplx b[8], cplx *tile, const cplx tw1[7], const cplx tw2[7],
                                            int lane)
 {
-    const int g = lane >> 3, r = lane & 7;
     dft8(a);
     dft8(b);
 #pragma unroll
@@ -132,21 +127,13 @@ __device__ __forceinline__ void fft512n_g2(cplx a[8], cplx b[8], cplx *tile, con
         a[k1] = c_mul(a[k1], w);
         b[k1] = c_mul(b[k1], w);
     }
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1)
-        tile[64 * k1 + (lane ^ (8 * k1))] = a[k1];
+    fft512n_x1_write(tile, a, lane);
     wave_lds_fence();
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2)
-        a[n2] = tile[64 * g + 8 * (n2 ^ g) + r];
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1)
-        tile[64 * k1 + (lane ^ (8 * k1))] = b[k1];
+    fft512n_x1_read(tile, a, lane);
+    fft512n_x1_write(tile, b, lane);
     dft8(a);
     wave_lds_fence();
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2)
-        b[n2] = tile[64 * g + 8 * (n2 ^ g) + r];
+    fft512n_x1_read(tile, b, lane);
     dft8(b);
 #pragma unroll
     for (int k2 = 1; k2 < 8; ++k2) {
@@ -154,21 +141,13 @@ __device__ __forceinline__ void fft512n_g2(cplx a[8], cplx b[8], cplx *tile, con
         a[k2] = c_mul(a[k2], w);
         b[k2] = c_mul(b[k2], w);
     }
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2)
-        tile[64 * g + 8 * k2 + (r ^ g)] = a[k2];
+    fft512n_x2_write(tile, a, lane);
     wave_lds_fence();
-#pragma unroll
-    for (int n3 = 0; n3 < 8; ++n3)
-        a[n3] = tile[64 * r + 8 * g + (n3 ^ r)];
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2)
-        tile[64 * g + 8 * k2 + (r ^ g)] = b[k2];
+    fft512n_x2_read(tile, a, lane);
+    fft512n_x2_write(tile, b, lane);
     dft8(a);
     wave_lds_fence();
-#pragma unroll
-    for (int n3 = 0; n3 < 8; ++n3)
-        b[n3] = tile[64 * r + 8 * g + (n3 ^ r)];
+    fft512n_x2_read(tile, b, lane);
     wave_lds_fence();
     dft8(b);
 }
@@ -202,9 +181,8 @@ __device__ __forceinline__ void load_lane_twiddles(const PacxTables &T, int lane
 
 /* ------------------------------------------------- long: fused front end */
 /* The MDCT of one long sine-window frame by the wave that runs the frame's side chain (k_front_long): the
- * arithmetic of k_mdct_long_x2p (k_mdct3.hip) for one frame, operation by operation -- window value
- * win_long[i] * kscale, the fold's fma forms, c_mul with tw_long[n], fft512n, the post-twiddle, the lane reversal
- * and the ballot-bisected overall scale -- so the lines and the scale are the same bits.  What differs is where the
+ * arithmetic of k_mdct_long_x2p (k_mdct3.hip) for one frame, built from the same pieces (mdct_dev.h), so the lines
+ * and the scale are the same bits.  What differs is where the
  * operands come from: window and pre/post twiddles are read from the global tables (L2), not from a workgroup's LDS
  * copy, the FFT's per-lane twiddles from the global W512 table as the side chain's are, and the PCM goes through
  * registers to LDS (plain loads and stores) for the fold's scattered 16-bit reads.
@@ -226,7 +204,6 @@ struct MdctOperands {
 __device__ __forceinline__ void mdct_fetch(const PacxTables &T, const short *__restrict__ src, int lane,
                                            MdctOperands &m)
 {
-    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
     const double *__restrict__ win = T.win_long;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -235,15 +212,11 @@ __device__ __forceinline__ void mdct_fetch(const PacxTables &T, const short *__r
     }
 #pragma unroll
     for (int n1 = 0; n1 < 8; ++n1) {
-        const int n = lane + 64 * n1;
-        if (n1 < 4) {
-            m.w[2 * n1] = win[Q + 2 * n];                 /* w[i3] = w[i0] */
-            m.w[2 * n1 + 1] = win[Q - 1 - 2 * n];         /* w[i2] = w[i1] */
-        } else {
-            const int mm = 2 * n - Q;
-            m.w[2 * n1] = win[mm];                        /* w[i0] = w[i3] */
-            m.w[2 * n1 + 1] = win[M - 1 - mm];            /* w[i1] = w[i2] */
-        }
+        int i0, i1, i2, i3, ia, ib;
+        mdct_fold_index<PACX_N_LONG>(n1, lane + 64 * n1, i0, i1, i2, i3);
+        mdct_fold_sym_index(n1, i0, i1, i2, i3, ia, ib);
+        m.w[2 * n1] = win[ia];
+        m.w[2 * n1 + 1] = win[ib];
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k)
@@ -263,47 +236,23 @@ __device__ __forceinline__ void mdct_long_one(const PacxTables &T, long long cf,
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         *(int4 *)(raw + 8 * (lane + 64 * j)) = make_int4(m.q[4 * j], m.q[4 * j + 1], m.q[4 * j + 2], m.q[4 * j + 3]);
-    const int Q = PACX_N_LONG / 4, M = PACX_M_LONG;
-    const double kscale = (2.0 / 65535.0) * (2.0 / PACX_N_LONG);
     wave_lds_fence();
     cplx v[8];
     for (int pass = 0;; ++pass) {
         int lowest = 0;
 #pragma unroll
         for (int n1 = 0; n1 < 8; ++n1) {
-            const int n = lane + 64 * n1;
             int i0, i1, i2, i3;
-            const double wa = m.w[2 * n1] * kscale, wb = m.w[2 * n1 + 1] * kscale;
-            if (n1 < 4) {
-                i0 = 3 * Q - 1 - 2 * n; i1 = 3 * Q + 2 * n; i2 = Q - 1 - 2 * n; i3 = Q + 2 * n;
-            } else {
-                const int mm = 2 * n - Q;
-                i0 = mm; i1 = M - 1 - mm; i2 = 2 * Q + mm; i3 = 4 * Q - 1 - mm;
-            }
-            int c0 = raw[i0], c1 = raw[i1], c2 = raw[i2], c3 = raw[i3];
-            lowest = min(lowest, min(min(c0, c1), min(c2, c3)));
-            double re, im;
-            if (n1 < 4) {
-                re = -fma(wb, (double)c1, wa * (double)c0);
-                im = fma(wb, (double)c2, -(wa * (double)c3));
-            } else {
-                re = fma(wa, (double)c0, -(wb * (double)c1));
-                im = -fma(wb, (double)c2, wa * (double)c3);
-            }
-            v[n1] = c_mul(make_double2(re, im), m.twl[n1]);
+            mdct_fold_index<PACX_N_LONG>(n1, lane + 64 * n1, i0, i1, i2, i3);
+            double c0, c1, c2, c3;
+            mdct_fold_codes<false>(raw, i0, i1, i2, i3, c0, c1, c2, c3, lowest);
+            const double wa = m.w[2 * n1] * MDCT_LONG_KSCALE, wb = m.w[2 * n1 + 1] * MDCT_LONG_KSCALE;
+            v[n1] = c_mul(mdct_fold_sym(n1, wa, wb, c0, c1, c2, c3), m.twl[n1]);
         }
         if (pass || !__builtin_amdgcn_ballot_w64(lowest == -32768))
             break;
-        /* the code -32768 counts as 0 (coder/pcmfile.py:93-97): rewrite the staged codes of such a frame
-           and fold again */
         wave_lds_fence();
-        unsigned *rw = (unsigned *)raw;
-        for (int j = 0; j < 16; ++j) {
-            unsigned x = rw[lane + 64 * j];
-            if ((x & 0xFFFFu) == 0x8000u) x &= 0xFFFF0000u;
-            if ((x >> 16) == 0x8000u) x &= 0x0000FFFFu;
-            rw[lane + 64 * j] = x;
-        }
+        mdct_zero_min_codes((unsigned *)raw, lane);
         wave_lds_fence();
     }
     /* the second exchange's twiddles: fetched here and not with the first's, where they would be 28 more registers
@@ -313,39 +262,12 @@ __device__ __forceinline__ void mdct_long_one(const PacxTables &T, long long cf,
         tw2[k - 1] = T.w512[(8 * (lane & 7) * k) & 511];
     wave_lds_fence();                  /* raw is consumed: region B becomes the FFT tile */
     fft512n(v, tile, tw1, 1, tw2, 1, lane);
-    /* post-twiddle, lane reversal, overall scale and guard: k_mdct_long_x2p's epilogue */
-    double a[8], b[8];
-    double mx = 0.0;
-#pragma unroll
-    for (int k3 = 0; k3 < 8; ++k3) {
-        const cplx d = m.twl[k3];
-        a[k3] = fma(v[k3].x, d.x, -(v[k3].y * d.y));      /* Re y = X[2k] */
-        b[k3] = -fma(v[k3].x, d.y, v[k3].y * d.x);        /* -Im y = X[1023 - 2k] */
-        mx = fmax(mx, fmax(fabs(a[k3]), fabs(b[k3])));
-    }
-    double odd[8];
-#pragma unroll
-    for (int k3 = 0; k3 < 8; ++k3)
-        odd[k3] = __shfl(b[7 - k3], 63 - lane, 64);
-    int lo = 0;
-    const int s = pacx_scale_factor(mx, T.n_scale_bits, 5);
-    for (int bit = T.n_scale_bits - 1; bit >= 0; --bit)
-        if (!__builtin_amdgcn_ballot_w64(s < lo + (1 << bit)))
-            lo += 1 << bit;
-    const bool guard = T.guard && s == lo && pacx_scale_guard(mx, T.n_scale_bits, 5, 2.0 * PACX_GUARD_LINE_ERR * mx);
-    double2 *__restrict__ out = (double2 *)(lines + cf * PACX_M_LONG);
-#pragma unroll
-    for (int k3 = 0; k3 < 8; ++k3)
-        out[lane + 64 * k3] = make_double2(a[k3], odd[k3]);
-    if (lane == 0)
-        scale_out[cf * PACX_SUB] = lo;
-    if (__builtin_amdgcn_ballot_w64(guard) && lane == 0)
-        status[cf] = 16u;                          /* PACX_ST_GUARD, after this lane's own zero store */
+    mdct_long_epilogue(T, v, [&](int k3) { return m.twl[k3]; }, cf, lane, lines, scale_out, PACX_SUB, status);
 }
 
 /* one long channel-frame by one wave; every barrier is wave-local (the wave
  * owns its LDS slice).  FRONT: the frame's MDCT as well (k_front_long, *fa) */
-template <int DT, bool FAST, bool COMPACT, bool FRONT = false>
+template <int DT, bool FAST, bool FRONT = false>
 __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcmView &in, long long cf,
                                               char *regA, char *regB, int lane,
                                               PacxPeak *__restrict__ peaks, int32_t *__restrict__ n_peaks,
@@ -355,7 +277,7 @@ __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcm
                                               const FrontArgs *fa = nullptr)
 {
     typedef typename PcmStage<DT>::elem E;
-    cplx *tile = (cplx *)(COMPACT ? regB : regA);
+    cplx *tile = (cplx *)regB;
     double *inten = (double *)regB;
     E *raw = (E *)regB;
 
@@ -634,7 +556,7 @@ __device__ __forceinline__ void side_long_one(const PacxTables &T, const PacxPcm
     }
 }
 
-template <int DT, bool FAST, bool COMPACT>
+template <int DT, bool FAST>
 __global__ __launch_bounds__(64, DT == 0 ? 3 : 2) void k_side_long(PacxTables T, PacxPcmView in,
                                                  const uint8_t *__restrict__ flags, long long n_cf,
                                                  int skip_cur, PacxPeak *__restrict__ peaks,
@@ -643,27 +565,19 @@ __global__ __launch_bounds__(64, DT == 0 ? 3 : 2) void k_side_long(PacxTables T,
                                                  double *__restrict__ sbr_mean,
                                                  int32_t *__restrict__ sbr_overall)
 {
-    __shared__ __attribute__((aligned(16))) char regA[SideLongLds<DT, COMPACT>::A_BYTES];
-    __shared__ __attribute__((aligned(16))) char regB[SideLongLds<DT, COMPACT>::B_BYTES];
-    /* XCD-aware block order: block b runs on XCD b % 8, and the MDCT kernel, which reads the
-       same PCM at the same time on the other stream, gives XCD x the frames with
-       (cf / 256) % 8 == x (k_mdct3.hip): the same assignment here, so that the hop is in
-       this XCD's L2 whichever of the two kernels asks first */
-    long long cf = blockIdx.x;
-    if ((n_cf & 2047) == 0 && gridDim.x == (unsigned)n_cf) {
-        const unsigned b = blockIdx.x, idx = b >> 3;
-        cf = (long long)(idx >> 8) * 2048 + (b & 7u) * 256 + (idx & 255u);
-    }
+    __shared__ __attribute__((aligned(16))) char regA[SideLongLds<DT>::A_BYTES];
+    __shared__ __attribute__((aligned(16))) char regB[SideLongLds<DT>::B_BYTES];
+    const long long cf = pacx_xcd_frame(blockIdx.x, gridDim.x, n_cf);      /* XCD-aware frame order (pacx_dev.h) */
     if (cf >= n_cf)
         return;
     const unsigned fl = flags ? flags[cf / in.n_ch] : 0u;
     if (skip_cur && (fl & 2u))
         return;
-    side_long_one<DT, FAST, COMPACT>(T, in, cf, regA, regB, threadIdx.x, peaks, n_peaks, n_kept_out, sbr_mean,
-                                     sbr_overall);
+    side_long_one<DT, FAST>(T, in, cf, regA, regB, threadIdx.x, peaks, n_peaks, n_kept_out, sbr_mean,
+                            sbr_overall);
 }
 
-/* k_side_long<0, true, true> with the frame's MDCT in the same wave (all-long batches of aligned unit-stride int16
+/* k_side_long<0, true> with the frame's MDCT in the same wave (all-long batches of aligned unit-stride int16
  * PCM, no per-frame flags, no SBR): one kernel where the step had the side chain and, behind it on the same
  * hardware queue, the one kernel that holds a whole CU's LDS.  Same grid, same XCD-aware frame order, same LDS as
  * k_side_long.  Side jobs of k_mdct_long_x2p<.., true>: the status word (0 here, PACX_ST_GUARD later from the same
@@ -673,14 +587,10 @@ __global__ __launch_bounds__(64, 3) void k_front_long(PacxTables T, PacxPcmView 
                                                       uint32_t *__restrict__ status, PacxPeak *__restrict__ peaks,
                                                       int32_t *__restrict__ n_peaks, int32_t *__restrict__ n_kept_out)
 {
-    __shared__ __attribute__((aligned(16))) char regA[SideLongLds<0, true>::A_BYTES];
-    __shared__ __attribute__((aligned(16))) char regB[SideLongLds<0, true>::B_BYTES];
-    static_assert(SideLongLds<0, true>::B_BYTES >= (int)sizeof(cplx) * WFFT_TILE_N, "region B holds the FFT tile");
-    long long cf = blockIdx.x;
-    if ((n_cf & 2047) == 0 && gridDim.x == (unsigned)n_cf) {          /* as in k_side_long */
-        const unsigned b = blockIdx.x, idx = b >> 3;
-        cf = (long long)(idx >> 8) * 2048 + (b & 7u) * 256 + (idx & 255u);
-    }
+    __shared__ __attribute__((aligned(16))) char regA[SideLongLds<0>::A_BYTES];
+    __shared__ __attribute__((aligned(16))) char regB[SideLongLds<0>::B_BYTES];
+    static_assert(SideLongLds<0>::B_BYTES >= (int)sizeof(cplx) * WFFT_TILE_N, "region B holds the FFT tile");
+    const long long cf = pacx_xcd_frame(blockIdx.x, gridDim.x, n_cf);      /* as in k_side_long */
     if (cf >= n_cf)
         return;
     const int lane = threadIdx.x;
@@ -695,8 +605,8 @@ __global__ __launch_bounds__(64, 3) void k_front_long(PacxTables T, PacxPcmView 
     fa.lines = lines;
     fa.scale_out = scale_out;
     fa.status = status;
-    side_long_one<0, true, true, true>(T, in, cf, regA, regB, lane, peaks, n_peaks, n_kept_out, nullptr, nullptr,
-                                       &fa);
+    side_long_one<0, true, true>(T, in, cf, regA, regB, lane, peaks, n_peaks, n_kept_out, nullptr, nullptr,
+                                 &fa);
 }
 
 /* ----------------------------------------------------------------- short */
@@ -1468,7 +1378,7 @@ static void launch_side(const PacxTables &T, const PacxPcmView &in, const uint8_
        are intact when the SBR epilogue wants them (the 17.5 KB layout it used to need cost a quarter of
        the occupancy: 88 against 53 us) */
     if (do_long)
-        hipLaunchKernelGGL((k_side_long<DT, FAST, true>), grid, block, 0, st, T, in, flags, n_cf, mixed, peaks,
+        hipLaunchKernelGGL((k_side_long<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed, peaks,
                            n_peaks, n_kept, sbr_mean, sbr_overall);
     if (do_short)
         hipLaunchKernelGGL((k_side_short<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed, peaks, n_peaks, n_kept);

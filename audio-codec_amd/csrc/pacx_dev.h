@@ -91,6 +91,28 @@ struct MaskTail {
     int payload_stride;
 };
 
+/* XCD-aware order.  Workgroups are handed to the 8 XCDs round-robin, so workgroup b runs on XCD b % 8.
+   Consecutive channel-frames share a hop of PCM; giving every XCD a CONTIGUOUS run of frames keeps that
+   shared hop in one XCD's L2 instead of fetching it from HBM once per XCD (a quarter of the hops were read
+   twice).  Two remaps, which must give the same answer to "which XCD reads frame cf":
+     - the persistent MDCT kernels (k_mdct_long_v2, k_mdct_long_x2p) run workgroup b as virtual workgroup
+       pacx_xcd_block(b): XCD x takes the x-th eighth of the workgroups.  On the headline shape (256 workgroups of
+       8 waves, n_cf a multiple of 2048) that is the frames with (cf / 256) % 8 == x;
+     - the one-frame-per-workgroup kernels of the side chain (k_side_long, k_front_long), which read the same
+       PCM at the same time on another stream, run block b on frame pacx_xcd_frame(b): the same assignment, so
+       that the hop is in this XCD's L2 whichever kernel asks first. */
+__device__ __forceinline__ unsigned pacx_xcd_block(unsigned b, unsigned n_blocks)
+{
+    return (n_blocks & 7u) ? b : (b & 7u) * (n_blocks >> 3) + (b >> 3);
+}
+__device__ __forceinline__ long long pacx_xcd_frame(unsigned b, unsigned n_blocks, long long n_cf)
+{
+    if ((n_cf & 2047) != 0 || n_blocks != (unsigned)n_cf)
+        return b;
+    const unsigned idx = b >> 3;
+    return (long long)(idx >> 8) * 2048 + (b & 7u) * 256 + (idx & 255u);
+}
+
 /* workspace of pacx_index_body (k_index.hip, body_index.h): byte offsets into one allocation of the handle,
    sized by the call (pacx_index_ws_bytes) */
 struct PacxIndexWs {

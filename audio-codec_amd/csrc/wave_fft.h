@@ -152,35 +152,60 @@ __device__ __forceinline__ void fft512(cplx v[8], cplx *tile, const cplx *__rest
  *   X2 write  row g,  col 8 k2 + (r ^ g)     X2 read  row lane&7, col 8 (lane>>3) + (n3 ^ (lane&7))
  * w1[(k-1) w1_stride] = W512^(lane k), w2[(k-1) w2_stride] = W64^((lane&7) k),
  * k = 1..7: per-lane twiddles, normally LDS tables shared by the workgroup.
+ * The stages are functions of their own for the kernels that interleave two transforms on one
+ * tile (k_mdct_long_x2p, k_psy.hip fft512n_g2): a write and the read that follows it are
+ * separated by a wave_lds_fence(), a transform's reads may be followed by another's writes
+ * without one (the DS instructions of a wave execute in issue order).
  */
 #define WFFT_TILE_N 512
-__device__ __forceinline__ void fft512n(cplx v[8], cplx *tile, const cplx *w1, int w1_stride, const cplx *w2,
-                                        int w2_stride, int lane)
+__device__ __forceinline__ void fft512n_x1_write(cplx *tile, const cplx v[8], int lane)
 {
-    const int g = lane >> 3, r = lane & 7;
-    dft8(v);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; ++k1)
-        v[k1] = c_mul(v[k1], w1[(k1 - 1) * w1_stride]);
 #pragma unroll
     for (int k1 = 0; k1 < 8; ++k1)
         tile[64 * k1 + (lane ^ (8 * k1))] = v[k1];
-    wave_lds_fence();
+}
+__device__ __forceinline__ void fft512n_x1_read(const cplx *tile, cplx v[8], int lane)
+{
+    const int g = lane >> 3, r = lane & 7;
 #pragma unroll
     for (int n2 = 0; n2 < 8; ++n2)
         v[n2] = tile[64 * g + 8 * (n2 ^ g) + r];
-    wave_lds_fence();
-    dft8(v);
-#pragma unroll
-    for (int k2 = 1; k2 < 8; ++k2)
-        v[k2] = c_mul(v[k2], w2[(k2 - 1) * w2_stride]);
+}
+__device__ __forceinline__ void fft512n_x2_write(cplx *tile, const cplx v[8], int lane)
+{
+    const int g = lane >> 3, r = lane & 7;
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2)
         tile[64 * g + 8 * k2 + (r ^ g)] = v[k2];
-    wave_lds_fence();
+}
+__device__ __forceinline__ void fft512n_x2_read(const cplx *tile, cplx v[8], int lane)
+{
+    const int g = lane >> 3, r = lane & 7;
 #pragma unroll
     for (int n3 = 0; n3 < 8; ++n3)
         v[n3] = tile[64 * r + 8 * g + (n3 ^ r)];
+}
+/* v[k] *= w[(k-1) stride], k = 1..7: the twiddles between two radix-8 passes */
+__device__ __forceinline__ void fft512n_twiddle(cplx v[8], const cplx *w, int stride)
+{
+#pragma unroll
+    for (int k = 1; k < 8; ++k)
+        v[k] = c_mul(v[k], w[(k - 1) * stride]);
+}
+__device__ __forceinline__ void fft512n(cplx v[8], cplx *tile, const cplx *w1, int w1_stride, const cplx *w2,
+                                        int w2_stride, int lane)
+{
+    dft8(v);
+    fft512n_twiddle(v, w1, w1_stride);
+    fft512n_x1_write(tile, v, lane);
+    wave_lds_fence();
+    fft512n_x1_read(tile, v, lane);
+    wave_lds_fence();
+    dft8(v);
+    fft512n_twiddle(v, w2, w2_stride);
+    fft512n_x2_write(tile, v, lane);
+    wave_lds_fence();
+    fft512n_x2_read(tile, v, lane);
     wave_lds_fence();
     dft8(v);
 }

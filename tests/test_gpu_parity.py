@@ -181,6 +181,40 @@ def test_mdct_pipelined_kernel_equals_one_frame_kernel(A, torch):
     assert torch.equal(a.view(torch.int64), b.view(torch.int64))
 
 
+@pytest.mark.parametrize("n_ch", [1, 2])
+@pytest.mark.parametrize("n_frames", [3, 17, 33])
+def test_mdct_refold_equals_cleaned_input(A, torch, n_ch, n_frames):
+    """"The code -32768 counts as 0" (coder/pcmfile.py:93-97), kernel by kernel: a long kernel that meets the code
+    rewrites the frame's staged samples and folds again (csrc/mdct_dev.h mdct_zero_min_codes), and must then give,
+    bit for bit, the lines and overall scales it gives for the same PCM with those codes replaced by 0 -- without
+    flags (k_mdct_long_x2p), with zero flags (k_mdct_long_v2, sine window) and with flags that select the start,
+    stop and start-stop windows (k_mdct_long_v2, window kinds 1, 2, 3: the packed last / cur / next bytes of the
+    golden long_flags, which itself holds 0 and 1 only).  Mono batches of 3, 17 and 33 channel-frames are fewer than
+    a pair per wave and one past one and two workgroups' worth of pairs; a stereo batch has two per frame.
+    The code sits at the ends and the middles of the four quarters of a block, in the low half, the high half and
+    both halves of a 32-bit word.  Not a tautology: -32767 at the same places gives other lines."""
+    enc = enc_for(A, 48000)
+    rng = np.random.default_rng(100 * n_ch + n_frames)
+    clean = rng.integers(-20000, 20000, (n_frames, n_ch, 2048)).astype(np.int16)
+    hit = np.zeros(clean.shape, bool)
+    hit[0, 0, [0, 511, 512, 1023, 1024, 1535, 1536, 2047]] = True
+    hit[1, n_ch - 1, [100, 101]] = True                    # both halves of one word
+    hit[1, n_ch - 1, [777, 1300]] = True                   # a high half and a low half alone
+    hit[n_frames - 1, n_ch - 1, [0, 2047]] = True          # the batch's last channel-frame
+    hit[n_frames // 2, 0, 1024] = True
+    clean[hit] = 0
+    dirty, near = clean.copy(), clean.copy()
+    dirty[hit] = -32768
+    near[hit] = -32767
+    views = [A.engine.PcmView.frames(torch.as_tensor(x, device=enc.device)) for x in (clean, dirty, near)]
+    kinds = np.resize(np.array([4, 1, 5], np.uint8), n_frames)          # window kinds 1, 2, 3, frame after frame
+    for flags in (None, np.zeros(n_frames, np.uint8), kinds):
+        (want, want_scale), (got, got_scale), (other, _) = [enc.mdct(v, flags=flags, want_scale=True) for v in views]
+        assert torch.equal(got.view(torch.int64), want.view(torch.int64))
+        assert torch.equal(got_scale, want_scale)
+        assert not torch.equal(other[0], got[0])      # channel-frame 0: codes where no window is zero
+
+
 # ------------------------------------------------------------ psychoacoustics
 @pytest.mark.parametrize("kind", ["long", "short"])
 def test_threshold_and_smr_golden(A, torch, stages, kind):
