@@ -14,6 +14,7 @@ ST_REF_RAISES = 64
 ST_RATE_CAP = 128
 RATE_STEP = 32             # PACX_RATE_STEP: budgets of the constant-quality mode are multiples of this many bits
 RATE_TARGET_GRID = 64      # PACX_RATE_TARGET_GRID: targets of pacx_rate_solve are multiples of 1 / 64 dB
+BAND_CAND = 16             # PACX_BAND_CAND: mantissa sizes on a band curve, candidate i = 0 bits for i = 0, else i + 1
 E_ARG, E_UNSUPPORTED = -1, -2
 # what the reference raises where PACX_ST_REF_RAISES is set (coder/quantize.py:74, see include/pacx.h)
 REF_SCALAR_SBR_ERROR = "'numpy.int64' object does not support item assignment"
@@ -154,6 +155,12 @@ SIGNATURES = {
                                              _P]),
     "pacx_rate_solve": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64,
                                        ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
+    "pacx_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_band_pick": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_band_solve": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                       _P, _P, _P, _P, _P]),
+    "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                    _P]),
 }
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320

@@ -1,0 +1,364 @@
+/*
+ * k_band.hip -- bits handed to the bands one by one against a noise-to-mask target (pacx_band_curve_batch /
+ * pacx_band_pick / pacx_band_solve / pacx_encode_pack_alloc_batch, include/pacx.h).  In this coder the noise of a
+ * band depends on that band's own mantissa size and on nothing else, so the smallest stream that keeps every band at
+ * or below a target is found band by band on a stored curve of PACX_BAND_CAND sizes.
+ *
+ *   k_band_curve<M>   one wave per unit (M = 1024: a long block, M = 128: a short sub-block), k_rate_search's units and
+ *                     preamble (rate_unit, rate_dev.h).  Candidate 0 (no bits) is the lines' own energy; for each of the
+ *                     other sizes one pass over the lines in LDS with every band at that size: scale factor of the
+ *                     stored maximum, mantissa -> the decoder's dequantiser -> n[k] = 4 (x - xh)^2, then the band sums
+ *                     in k_nmr's order (lanes stride over the band, butterfly of shuffles).  One BitAlloc at the cap
+ *                     budget 32 J (bitalloc_half, the encoder's own) gives the allocation of a unit that cannot have
+ *                     what its bands ask for.
+ *   k_band_pick       works on the arrays alone: one wave per channel-frame, a lane per (unit, band) pair scans the
+ *                     band's sizes in ascending order for the first at or below the target; the unit sums go through
+ *                     LDS, the frame's bits through the wave.  For a solve it adds the body total: integer sums, one
+ *                     64-bit atomicAdd per workgroup, and k_rate.hip's k_solve_init / k_solve_step decide on it.
+ *   k_band_sanitize   a caller's allocation made representable (below 2 -> 0, above maxMantBits -> maxMantBits), and
+ *                     an all-zero allocation for a channel-frame whose record would leave PACX_PAYLOAD_STRIDE.
+ *
+ * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
+ */
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "pacx_launch.h"
+#include "wave_fft.h"   /* wave_lds_fence */
+#include "quant_dev.h"
+#include "rate_dev.h"
+
+using namespace pacx_k;
+
+namespace {
+
+constexpr int BAND_CAND = PACX_BAND_CAND;
+constexpr int PICK_THREADS = 256;                  /* four channel-frames per workgroup, one per wave */
+
+__device__ __forceinline__ int cand_bits(int i) { return i ? i + 1 : 0; }
+
+/* NMR_b of every band from the n[k] in S.v: lane b keeps band b's value (k_nmr's order of additions) */
+template <int M>
+__device__ __forceinline__ double band_nmr(const RateLds<M> &S, int nb, int lane)
+{
+    double mine = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        double sn = 0.0;
+        for (int k = lane; k < S.cnt[b]; k += 64)
+            sn += S.v[S.lower[b] + k];
+        sn = wave_sum(sn);
+        const double r = 10.0 * log10((sn / (double)S.cnt[b] + PACX_EPS) / S.mm[b]);
+        if (lane == b)
+            mine = r;
+    }
+    return mine;
+}
+
+template <int M>
+__global__ __launch_bounds__(64) void k_band_curve(PacxTables T, const uint8_t *__restrict__ flags, int n_ch,
+                                                  long long n_units, double max_bps,
+                                                  const double *__restrict__ lines, const double *__restrict__ thr,
+                                                  const double *__restrict__ smr, const int32_t *__restrict__ overall,
+                                                  uint32_t *__restrict__ status, double *__restrict__ nmr,
+                                                  int32_t *__restrict__ cap, int32_t *__restrict__ cap_alloc)
+{
+    constexpr bool SHORT = (M == PACX_M_SHORT);
+    constexpr int PER = M / 64;
+    __shared__ RateLds<M> S;
+    const int lane = threadIdx.x, half = lane >> 5, l = lane & 31;
+    const long long unit = blockIdx.x;
+    if (unit >= n_units)
+        return;
+    const long long cf = SHORT ? unit / PACX_SUB : unit;
+    const int sb = SHORT ? (int)(unit % PACX_SUB) : 0;
+    const long long frame = cf / n_ch;
+    const unsigned fl = flags ? flags[frame] : 0u;
+    if (SHORT != ((fl & 2u) != 0))
+        return;                                    /* the other instance's */
+    const int nb = SHORT ? T.nb_short : T.nb_long;
+    const long long boff = cf * T.band_stride + sb * nb;
+    /* slots of the row no band of this frame uses: no allocation */
+    if (!SHORT || sb == PACX_SUB - 1)
+        for (int s = (SHORT ? PACX_SUB * nb : nb) + lane; s < T.band_stride; s += 64)
+            cap_alloc[cf * T.band_stride + s] = 0;
+    if (!SHORT && lane < PACX_SUB)
+        cap[cf * PACX_SUB + lane] = -1;            /* long frames use [0], written below by lane 0 again */
+    if (SHORT) {
+        unsigned st = 0;                           /* a hop the reference drops, as in k_rate_search */
+        for (int c = 0; c < n_ch; ++c)
+            st |= status[frame * n_ch + c];
+        if (st & 2u) {
+            if (lane < nb)
+                cap_alloc[boff + lane] = 0;
+            if (lane == 0)
+                cap[cf * PACX_SUB + sb] = -1;
+            return;
+        }
+    }
+    const RateUnit u = rate_unit<M>(T, S, cf, sb, fl, max_bps, lines, thr, smr, overall);
+    const double up = u.up, inv = u.inv;
+    const int n_cand = u.max_mant;                 /* sizes 0, 2, 3, ..., maxMantBits */
+    double *__restrict__ out = nmr + (boff + lane) * BAND_CAND;      /* lane b: the row of band b */
+
+    /* ---- candidate 0: nothing is coded, the noise is the lines themselves */
+#pragma unroll 1
+    for (int j = 0; j < PER; ++j) {
+        const int k = lane + 64 * j;
+        const double e = S.x[k];
+        S.v[k] = (e * e) * 4.0;
+    }
+    wave_lds_fence();
+    {
+        const double r = band_nmr<M>(S, nb, lane);
+        if (lane < nb)
+            out[0] = r;
+    }
+    wave_lds_fence();
+    /* ---- candidates 1 ... n_cand - 1: every band with i + 1 bits */
+    for (int i = 1; i < n_cand; ++i) {
+        const int bits = i + 1;
+        if (lane < nb)
+            S.sf[lane] = pacx_scale_factor(__longlong_as_double((long long)S.bmax[lane]), T.n_scale_bits, bits);
+        wave_lds_fence();
+#pragma unroll 1
+        for (int j = 0; j < PER; ++j) {
+            const int k = lane + 64 * j;
+            const int b = S.band[k];
+            const double xv = S.x[k];
+            double d = 0.0;
+            if (b < nb)                            /* lines no band covers are not coded */
+                d = pacx_dequantize(pacx_mantissa(xv * up, S.sf[b], T.n_scale_bits, bits), S.sf[b], T.n_scale_bits, bits);
+            const double e = xv - d * inv;
+            S.v[k] = (e * e) * 4.0;
+        }
+        wave_lds_fence();
+        const double r = band_nmr<M>(S, nb, lane);
+        if (lane < nb)
+            out[i] = r;
+        wave_lds_fence();                          /* v, sf free for the next size */
+    }
+    if (lane < nb)
+        for (int i = n_cand; i < BAND_CAND; ++i)
+            out[i] = INFINITY;
+
+    /* ---- the allocation of a unit that cannot have what its bands ask for: BitAlloc at the cap budget */
+    int bits = 0, acap = 0;
+    bitalloc_half(half == 0, u.has, u.sv, u.nl, (double)(32 * u.J), u.max_mant, S.cp[half], half, l, bits, acap,
+                  T.guard != 0, nb);
+    if (u.has)
+        cap_alloc[boff + l] = bits;
+    if (lane == 0) {
+        cap[cf * PACX_SUB + sb] = 32 * u.J;
+        const unsigned st = ((acap & 1) ? 4u : 0u) | ((acap & 2) ? 16u : 0u);
+        if (st)
+            atomicOr(&status[cf], st);             /* PACX_ST_ALLOC_CAP, _GUARD */
+    }
+}
+
+/* pick(unit, T) of include/pacx.h for every unit of one channel-frame per wave.  s == nullptr: pacx_band_pick at
+   `target`, the outputs are written.  Else a pick of the solve at the target in flight; final: the last launch, at
+   the target found, which also writes the outputs. */
+__global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveState *__restrict__ s, long long n_cf,
+                                                           double target, const double *__restrict__ nmr,
+                                                           const int32_t *__restrict__ cap,
+                                                           const int32_t *__restrict__ cap_alloc, int final,
+                                                           int32_t *__restrict__ bit_alloc, int32_t *__restrict__ n_bytes,
+                                                           uint8_t *__restrict__ capped)
+{
+    constexpr int WAVES = PICK_THREADS / 64;
+    constexpr int SLOTS = PACX_SUB * PACX_MAX_BANDS / 64;          /* band slots of a row per lane, at most */
+    __shared__ int unit_sum[WAVES][PACX_SUB], unit_miss[WAVES][PACX_SUB];
+    __shared__ unsigned long long part[WAVES];
+    if (s) {
+        if (s->done && !final)
+            return;                                /* the answer is known: this launch does nothing */
+        target = (double)s->mid / 64.0;
+    }
+    const bool write = !s || final;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long cf = (long long)blockIdx.x * WAVES + w;
+    unsigned long long mine = 0ull;
+    if (lane < PACX_SUB) {
+        unit_sum[w][lane] = 0;
+        unit_miss[w][lane] = 0;
+    }
+    wave_lds_fence();
+    if (cf < n_cf) {                               /* wave-uniform */
+        const int32_t *__restrict__ cp = cap + cf * PACX_SUB;
+        const bool is_short = cp[1] >= 0;          /* a long frame's slots 1-7 and a dropped hop's eight hold -1 */
+        const int nb = is_short ? T.nb_short : T.nb_long;
+        const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
+        int n_cand = 1 << T.n_mant_size_bits;
+        if (n_cand > BAND_CAND)
+            n_cand = BAND_CAND;
+        const long long row = cf * T.band_stride;
+        int a[SLOTS], nl[SLOTS], sbs[SLOTS];
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) {
+            const int slot = lane + 64 * q;
+            const int sb = is_short ? slot / nb : (slot < nb ? 0 : PACX_SUB);
+            const int b = is_short ? slot - sb * nb : slot;
+            a[q] = 0;
+            nl[q] = 0;
+            sbs[q] = -1;
+            if (slot < T.band_stride && sb < PACX_SUB && cp[sb] >= 0) {
+                const double *__restrict__ r = nmr + (row + slot) * BAND_CAND;
+                int pick = -1;
+                for (int i = n_cand - 1; i >= 0; --i)          /* the ascending scan's first pass = the lowest passing i */
+                    if (r[i] <= target)
+                        pick = i;
+                sbs[q] = sb;
+                nl[q] = count[b];
+                a[q] = cand_bits(pick < 0 ? n_cand - 1 : pick);
+                atomicAdd(&unit_sum[w][sb], a[q] * nl[q]);
+                if (pick < 0)
+                    atomicOr(&unit_miss[w][sb], 1);
+            }
+        }
+        wave_lds_fence();
+        int sum = 0;
+        bool any_cap = false;
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) {
+            const int slot = lane + 64 * q;
+            if (sbs[q] >= 0) {
+                const bool over = unit_sum[w][sbs[q]] > cp[sbs[q]];
+                if (over)
+                    a[q] = cap_alloc[row + slot];
+                any_cap = any_cap || over || unit_miss[w][sbs[q]] != 0;
+                sum += T.n_mant_size_bits + T.n_scale_bits + a[q] * nl[q];
+            }
+            if (write && slot < T.band_stride)
+                bit_alloc[row + slot] = a[q];
+        }
+        int units = 0;
+        for (int sb = 0; sb < PACX_SUB; ++sb)
+            units += cp[sb] >= 0 ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            sum += __shfl_xor(sum, off, 64);
+        const bool cap_cf = __builtin_amdgcn_ballot_w64(any_cap) != 0ull;
+        const int nby = units ? (sum + units * T.n_scale_bits + 4 + 7) >> 3 : 0;
+        if (nby > 0)
+            mine = (unsigned long long)nby + 4ull;
+        if (write && lane == 0) {
+            n_bytes[cf] = nby;
+            capped[cf] = cap_cf ? 1 : 0;
+        }
+    }
+    if (!s)
+        return;
+    if (lane == 0)
+        part[w] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0ull;
+        for (int i = 0; i < WAVES; ++i)
+            all += part[i];
+        if (all)
+            atomicAdd(&s->total, all);
+    }
+}
+
+/* a caller's allocation as k_quantize and k_pack may read it: one wave per channel-frame */
+__global__ __launch_bounds__(64) void k_band_sanitize(PacxTables T, const uint8_t *__restrict__ flags, int n_ch,
+                                                     long long n_cf, const int32_t *in, int32_t *out,
+                                                     uint32_t *__restrict__ status,
+                                                     int payload_stride)
+{
+    constexpr int SLOTS = PACX_SUB * PACX_MAX_BANDS / 64;
+    const int lane = threadIdx.x;
+    const long long cf = blockIdx.x;
+    if (cf >= n_cf)
+        return;
+    const bool is_short = flags && (flags[cf / n_ch] & 2u) != 0;
+    const int nb = is_short ? T.nb_short : T.nb_long;
+    const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
+    const int n_slots = is_short ? PACX_SUB * nb : nb;
+    int max_mant = 1 << T.n_mant_size_bits;
+    if (max_mant > 16)
+        max_mant = 16;
+    const long long row = cf * T.band_stride;
+    int a[SLOTS];
+    int sum = 0;
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+        const int slot = lane + 64 * q;
+        a[q] = 0;
+        if (slot < n_slots && slot < T.band_stride) {
+            const int v = in[row + slot];
+            a[q] = v < 2 ? 0 : (v > max_mant ? max_mant : v);
+            sum += T.n_mant_size_bits + T.n_scale_bits + a[q] * count[is_short ? slot % nb : slot];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        sum += __shfl_xor(sum, off, 64);
+    /* k_pack's size rule; a record that would leave its slot is coded without bits and flagged */
+    const int nby = (sum + (is_short ? PACX_SUB : 1) * T.n_scale_bits + 4 + 7) >> 3;
+    const bool fits = nby <= payload_stride;
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+        const int slot = lane + 64 * q;
+        if (slot < T.band_stride)
+            out[row + slot] = fits ? a[q] : 0;
+    }
+    if (!fits && lane == 0)
+        atomicOr(&status[cf], 128u);               /* PACX_ST_RATE_CAP */
+}
+
+}  // namespace
+
+void pacx_k::pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                                    double max_bits_per_sample, const double *lines, const double *thr,
+                                    const double *smr, const int32_t *overall, uint32_t *status, double *nmr,
+                                    int32_t *cap, int32_t *cap_alloc, hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    hipLaunchKernelGGL((k_band_curve<PACX_M_LONG>), dim3((unsigned)n_cf), dim3(64), 0, st, T, flags, n_ch, n_cf,
+                       max_bits_per_sample, lines, thr, smr, overall, status, nmr, cap, cap_alloc);
+    if (flags)
+        hipLaunchKernelGGL((k_band_curve<PACX_M_SHORT>), dim3((unsigned)(n_cf * PACX_SUB)), dim3(64), 0, st, T, flags,
+                           n_ch, n_cf * PACX_SUB, max_bits_per_sample, lines, thr, smr, overall, status, nmr, cap,
+                           cap_alloc);
+}
+
+void pacx_k::pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, const double *nmr,
+                                   const int32_t *cap, const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes,
+                                   uint8_t *capped, hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    const unsigned grid = (unsigned)((n_cf + PICK_THREADS / 64 - 1) / (PICK_THREADS / 64));
+    hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)nullptr, n_cf, target, nmr,
+                       cap, cap_alloc, 1, bit_alloc, n_bytes, capped);
+}
+
+void pacx_k::pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_cf, const double *nmr, const int32_t *cap,
+                                    const int32_t *cap_alloc, long long limit, int t_lo, int t_hi, int32_t *bit_alloc,
+                                    int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, hipStream_t st)
+{
+    SolveState *s = (SolveState *)ws;
+    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi);
+    const unsigned grid = (unsigned)((n_cf + PICK_THREADS / 64 - 1) / (PICK_THREADS / 64));
+    pacx_launch_solve_init(ws, t_lo, t_hi, st);
+    for (int p = 0; p < pairs; ++p) {
+        const int final = p == pairs - 1;
+        if (grid)
+            hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, s, n_cf, 0.0, nmr, cap, cap_alloc,
+                               final, bit_alloc, n_bytes, capped);
+        pacx_launch_solve_step(ws, limit, final, result, st);
+    }
+}
+
+void pacx_k::pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                                       const int32_t *in, int32_t *out, uint32_t *status, int payload_stride,
+                                       hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    hipLaunchKernelGGL(k_band_sanitize, dim3((unsigned)n_cf), dim3(64), 0, st, T, flags, n_ch, n_cf, in, out, status,
+                       payload_stride);
+}

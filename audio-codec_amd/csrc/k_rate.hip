@@ -20,6 +20,7 @@
  *                      curve at the target in flight, sums the frame's bytes; one 64-bit atomicAdd per workgroup.
  *   k_solve_step       one thread: the bisection's decision on that total.  The host enqueues a fixed number of
  *                      pick / step pairs and waits for none; pairs after the answer is known do nothing.
+ * RateLds, RateUnit, rate_unit, wave_sum and SolveState live in rate_dev.h: k_band.hip shares them.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
  */
@@ -30,112 +31,13 @@
 #include "pacx_launch.h"
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "quant_dev.h"
+#include "rate_dev.h"   /* RateLds, RateUnit, rate_unit, wave_sum, SolveState */
 
 using namespace pacx_k;
 
 namespace {
 
 constexpr int RATE_MAX_EVAL = 12;                  /* 1 + ceil(log2(J + 1)) for J < 2048; the entry point keeps J <= 512 */
-constexpr int RATE_SLOTS = PACX_MAX_BANDS + 1;     /* the bands and the dummy band of the lines no band covers */
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-/* what a unit's evaluations share, in LDS */
-template <int M>
-struct RateLds {
-    double v[M];                                   /* m[k] while the band means are taken, then n[k] of an evaluation */
-    double x[M];                                   /* the unit's lines */
-    uint8_t band[M];                               /* band of every line (nb: none) */
-    double cp[2][32];
-    double mm[PACX_MAX_BANDS];                     /* M_b */
-    unsigned long long bmax[RATE_SLOTS];
-    int ba[RATE_SLOTS], sf[RATE_SLOTS], lower[PACX_MAX_BANDS], cnt[PACX_MAX_BANDS];
-};
-
-/* and in registers */
-struct RateUnit {
-    int nb, nl, max_mant, J;
-    bool has;                                      /* BitAlloc's lanes: band l on the first half wave */
-    double sv, up, inv;
-};
-
-/* the preamble of k_rate_search and k_rate_curve: lines, line bands, band maxima and the band means of the mask into
-   LDS, the unit's SMRs and J into registers.  Called by the whole wave. */
-template <int M>
-__device__ __forceinline__ RateUnit rate_unit(const PacxTables &T, RateLds<M> &S, long long cf, int sb, unsigned fl,
-                                              double max_bps, const double *__restrict__ lines,
-                                              const double *__restrict__ thr, const double *__restrict__ smr,
-                                              const int32_t *__restrict__ overall)
-{
-    constexpr bool SHORT = (M == PACX_M_SHORT);
-    constexpr int PER = M / 64;                    /* lines per lane */
-    const int lane = threadIdx.x, half = lane >> 5, l = lane & 31;
-    RateUnit u;
-    u.nb = SHORT ? T.nb_short : T.nb_long;
-    const int nb = u.nb;
-    const long long boff = cf * T.band_stride + sb * nb;
-    u.has = half == 0 && l < nb;
-    /* ---- what every evaluation shares: line lane + 64 j belongs to lane `lane` (coalesced, and LDS without bank
-       conflicts); the lines stay in LDS, so the evaluations' line loop need not be unrolled */
-    const long long loff = cf * PACX_M_LONG + sb * PACX_M_SHORT;
-    const uint8_t *__restrict__ band_of = SHORT ? T.line_band_short : T.line_band_long;
-    const int ov = overall[cf * PACX_SUB + sb];
-    u.up = (double)(1 << ov);                      /* mdctLines *= (1 << overallScale) */
-    u.inv = ldexp(1.0, -ov);                       /* the decoder's division: a power of two, exact */
-    const double up = u.up;
-    if (lane < RATE_SLOTS) {
-        S.bmax[lane] = 0ull;
-        S.ba[lane] = 0;
-        S.sf[lane] = 0;
-    }
-    const int32_t *__restrict__ lower = SHORT ? T.band_lower_short : T.band_lower_long;
-    const int32_t *__restrict__ count = SHORT ? T.band_lines_short : T.band_lines_long;
-    if (lane < nb) {
-        int cnt = count[lane];
-        if (lower[lane] + cnt > M)                 /* a table that runs past the block (build_bands refuses it) */
-            cnt = M - lower[lane];
-        S.lower[lane] = lower[lane];
-        S.cnt[lane] = cnt;
-    }
-    wave_lds_fence();
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int k = lane + 64 * j;
-        const double xv = lines[loff + k];
-        S.x[k] = xv;
-        S.band[k] = band_of[k];
-        /* 10^y by exp2(y log2 10), as k_nmr */
-        S.v[k] = exp2(((thr[loff + k] - 96.0) / 10.0) * 3.32192809488736234787);
-        /* band maxima of |x 2^overall| on the bit pattern (quant_dev.h, long_scale_factors): they do not depend on the
-           allocation, only the scale factor taken from them does */
-        atomicMax(&S.bmax[band_of[k]], (unsigned long long)__double_as_longlong(fabs(xv * up)));
-    }
-    wave_lds_fence();
-    for (int b = 0; b < nb; ++b) {
-        double sm = 0.0;
-        for (int k = lane; k < S.cnt[b]; k += 64)
-            sm += S.v[S.lower[b] + k];
-        sm = wave_sum(sm);
-        if (lane == 0)
-            S.mm[b] = sm / (double)S.cnt[b];
-    }
-    wave_lds_fence();
-
-    u.sv = u.has ? smr[boff + l] : 0.0;
-    u.nl = u.has ? count[l] : 0;
-    u.max_mant = 1 << T.n_mant_size_bits;
-    if (u.max_mant > 16)
-        u.max_mant = 16;
-    /* the existing rule with the cap rate in place of the handle's */
-    u.J = pacx_rate_steps(max_bps, M, SHORT ? 1 : 0, (fl & 5u) != 0, T.n_scale_bits, T.n_mant_size_bits, nb);
-    return u;
-}
 
 /* One evaluation, the only one: the unit coded with BitAlloc budget 32 step -> max_b NMR_b, the allocation of band l
    in `bits` (lanes with u.has) and BitAlloc's guard bits in `acap`.  ok(B) of include/pacx.h is lane 0's
@@ -357,14 +259,6 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
 constexpr int SOLVE_THREADS = 256;
 constexpr int SOLVE_MAX_LOOKUP = 12;               /* 1 + ceil(log2(J + 1)) for J < 2048, as RATE_MAX_EVAL */
 
-/* lo / hi / mid on the target grid, t = 64 T */
-struct SolveState {
-    int lo, hi, mid;
-    int phase;                                     /* 0: total(t_hi) is being taken, 1: the bisection */
-    int done, met;
-    unsigned long long total;                      /* of the pick in flight */
-};
-
 __device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either sign */
 {
     return (a - (a < 0 ? 1 : 0)) / 2;
@@ -497,6 +391,17 @@ int pacx_k::pacx_rate_solve_pairs(int t_lo, int t_hi)
     while ((1ll << n) < (long long)t_hi - t_lo + 2)
         ++n;
     return 2 + n;
+}
+
+/* the solve's two one-thread kernels for a solve whose pick lives elsewhere (k_band.hip) */
+void pacx_k::pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_solve_init, dim3(1), dim3(1), 0, st, (SolveState *)ws, t_lo, t_hi);
+}
+
+void pacx_k::pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, (SolveState *)ws, limit, final, result);
 }
 
 void pacx_k::pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,

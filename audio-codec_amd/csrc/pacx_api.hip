@@ -1699,10 +1699,12 @@ extern "C" int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t 
 
 /* ---- coding to a target noise-to-mask ratio ---- */
 /* the front end of pacx_nmr_batch on one stream (lines, SMRs and, for the search, the threshold of every line), the
-   allocation by k_rate_search or from the caller's budgets, then the separate-kernel chain k_quantize -> k_pack */
-static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, bool search,
+   allocation by k_rate_search or from the caller's budgets, then the separate-kernel chain k_quantize -> k_pack.
+   With the caller's allocation (ALLOC_GIVEN) the front end is the MDCT alone: nothing here reads SMRs or maskers. */
+enum { BUDGET_SEARCH, BUDGET_GIVEN, ALLOC_GIVEN };
+static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, int mode,
                            double target_nmr_db, double max_bits_per_sample, const int32_t *budget_in,
-                           int32_t *overall_scale, int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa,
+                           const int32_t *alloc_in, int32_t *overall_scale, int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa,
                            uint32_t *status, uint8_t *payload, int32_t *n_bytes, int32_t *budget_out, void *stream,
                            const char *what)
 {
@@ -1710,6 +1712,7 @@ static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *fr
         return PACX_E_ARG;
     if (h->T.use_vq || h->T.use_sbr)
         return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    const bool search = mode == BUDGET_SEARCH, given = mode == ALLOC_GIVEN;
     if (search && !std::isfinite(target_nmr_db))
         return fail(h, PACX_E_ARG, std::string(what) + ": target_nmr_db is not finite");
     if (search && !(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
@@ -1721,7 +1724,7 @@ static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *fr
     if (rc)
         return rc;
     if (!overall_scale || !scale_factor || !bit_alloc || !status || !payload || !n_bytes ||
-        (search ? !budget_out : !budget_in))
+        (search ? !budget_out : given ? !alloc_in : !budget_in))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
     if (n_cf == 0)
         return PACX_OK;
@@ -1742,10 +1745,14 @@ static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *fr
     if (s.mixed)
         s.lists(st);
     s.mdct(st);
-    s.side(0, false, st);
-    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                     search ? h->ws_thr : nullptr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
-    if (search)
+    if (!given) {
+        s.side(0, false, st);
+        pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                         search ? h->ws_thr : nullptr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    }
+    if (given)
+        pacx_launch_band_sanitize(h->T, frame_flags, s.n_ch, n_cf, alloc_in, bit_alloc, status, PACX_PAYLOAD_STRIDE, st);
+    else if (search)
         pacx_launch_rate_search(h->T, frame_flags, s.n_ch, n_cf, target_nmr_db, max_bits_per_sample, h->ws_lines,
                                 h->ws_thr, h->ws_smr, overall_scale, budget_out, bit_alloc, status, st);
     else
@@ -1762,7 +1769,7 @@ extern "C" int pacx_encode_pack_nmr_batch(pacx_handle *h, const pacx_pcm *in, co
                                           int32_t *scale_factor, int32_t *bit_alloc, int32_t *mantissa, uint32_t *status,
                                           uint8_t *payload, int32_t *n_bytes, int32_t *budget, void *stream)
 {
-    return encode_budgeted(h, in, frame_flags, true, target_nmr_db, max_bits_per_sample, nullptr, overall_scale,
+    return encode_budgeted(h, in, frame_flags, BUDGET_SEARCH, target_nmr_db, max_bits_per_sample, nullptr, nullptr, overall_scale,
                            scale_factor, bit_alloc, mantissa, status, payload, n_bytes, budget, stream,
                            "pacx_encode_pack_nmr_batch");
 }
@@ -1772,8 +1779,17 @@ extern "C" int pacx_encode_pack_budget_batch(pacx_handle *h, const pacx_pcm *in,
                                              int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
                                              int32_t *n_bytes, void *stream)
 {
-    return encode_budgeted(h, in, frame_flags, false, 0.0, 0.0, budget, overall_scale, scale_factor, bit_alloc, mantissa,
-                           status, payload, n_bytes, nullptr, stream, "pacx_encode_pack_budget_batch");
+    return encode_budgeted(h, in, frame_flags, BUDGET_GIVEN, 0.0, 0.0, budget, nullptr, overall_scale, scale_factor, bit_alloc,
+                           mantissa, status, payload, n_bytes, nullptr, stream, "pacx_encode_pack_budget_batch");
+}
+
+extern "C" int pacx_encode_pack_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                            const int32_t *bit_alloc_in, int32_t *overall_scale, int32_t *scale_factor,
+                                            int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
+                                            int32_t *n_bytes, void *stream)
+{
+    return encode_budgeted(h, in, frame_flags, ALLOC_GIVEN, 0.0, 0.0, nullptr, bit_alloc_in, overall_scale, scale_factor,
+                           bit_alloc, mantissa, status, payload, n_bytes, nullptr, stream, "pacx_encode_pack_alloc_batch");
 }
 
 /* ---- coding to an average bit rate: the curve of every unit, then one target for the stream ---- */
@@ -1886,6 +1902,123 @@ extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_
         return rc;
     pacx_launch_rate_solve(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, limit_bytes, (int)lo64, (int)hi64,
                            budget, n_bytes, capped, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+/* ---- bits handed to the bands one by one ---- */
+/* the longest record a pick can give at this cap rate, in bytes: per unit the header bits and at most
+   min(32 J, maxMantBits x lines) mantissa bits (a unit within its cap, or BitAlloc's at that budget) */
+static long long band_record_bound(const PacxTables &T, double max_bps)
+{
+    int max_mant = 1 << T.n_mant_size_bits;
+    if (max_mant > 16)
+        max_mant = 16;
+    long long worst = 0;
+    for (int sh = 0; sh < 2; ++sh)
+        for (int lon = 0; lon < 2; ++lon) {
+            const int nb = sh ? T.nb_short : T.nb_long, m = sh ? PACX_M_SHORT : PACX_M_LONG;
+            const long long all = (long long)max_mant * m;
+            const long long j = pacx_rate_steps(max_bps, m, sh, lon, T.n_scale_bits, T.n_mant_size_bits, nb);
+            const long long mant = 32 * j < all ? 32 * j : all;
+            const long long unit = T.n_scale_bits + (long long)nb * (T.n_mant_size_bits + T.n_scale_bits) + mant;
+            const long long bytes = ((sh ? PACX_SUB : 1) * unit + 4 + 7) >> 3;
+            worst = bytes > worst ? bytes : worst;
+        }
+    return worst;
+}
+
+extern "C" int pacx_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                     double max_bits_per_sample, double *nmr, int32_t *cap, int32_t *cap_alloc,
+                                     void *stream)
+{
+    const char *what = "pacx_band_curve_batch";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (!nmr || !cap || !cap_alloc)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (band_record_bound(h->T, max_bits_per_sample) > PACX_PAYLOAD_STRIDE)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": a record at this cap rate would not fit pacx_payload_stride");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    /* the front end of pacx_rate_curve_batch; overall scales and status words stay in the workspace */
+    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
+    }
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
+    if (s.mixed)
+        s.lists(st);
+    s.mdct(st);
+    s.side(0, false, st);
+    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    pacx_launch_band_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_lines, h->ws_thr, h->ws_smr,
+                           h->ws_overall, h->ws_rate_status, nmr, cap, cap_alloc, st);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_pick(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                              double target_nmr_db, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, void *stream)
+{
+    const char *what = "pacx_band_pick";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (!std::isfinite(target_nmr_db))
+        return fail(h, PACX_E_ARG, std::string(what) + ": target_nmr_db is not finite");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_pick(h->T, n_cf, target_nmr_db, nmr, cap, cap_alloc, bit_alloc, n_bytes, capped, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                               int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc,
+                               int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream)
+{
+    const char *what = "pacx_band_solve";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (!result || (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    const double bound = 1048576.0;
+    if (!std::isfinite(nmr_lo_db) || !std::isfinite(nmr_hi_db) || fabs(nmr_lo_db) > bound || fabs(nmr_hi_db) > bound)
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be finite (at most 2^20 dB in magnitude)");
+    const double lo64 = nmr_lo_db * PACX_RATE_TARGET_GRID, hi64 = nmr_hi_db * PACX_RATE_TARGET_GRID;
+    if (lo64 != floor(lo64) || hi64 != floor(hi64))
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be multiples of 1/64 dB");
+    if (lo64 > hi64)
+        return fail(h, PACX_E_ARG, std::string(what) + ": nmr_lo_db is above nmr_hi_db");
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = grow(h, GROW_SOLVE, 1);
+    if (rc)
+        return rc;
+    pacx_launch_band_solve(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, limit_bytes, (int)lo64, (int)hi64, bit_alloc,
+                           n_bytes, capped, result, (hipStream_t)stream);
     return post_launch(h, what);
 }
 

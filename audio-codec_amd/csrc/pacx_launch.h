@@ -141,6 +141,26 @@ void pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, c
                             int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
                             hipStream_t st);
 
+/* the two one-thread kernels of that solve, for a solve with a pick of its own (k_band.hip) */
+void pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st);
+void pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st);
+
+/* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve (nmr float64
+   [n_cf][band_stride][PACX_BAND_CAND], cap int32 [n_cf][8], cap_alloc int32 [n_cf][band_stride]; the solve uses
+   pacx_rate_solve's state and number of pairs) and the sanitised copy of a caller's allocation (in == out allowed) */
+void pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                            double max_bits_per_sample, const double *lines, const double *thr, const double *smr,
+                            const int32_t *overall, uint32_t *status, double *nmr, int32_t *cap, int32_t *cap_alloc,
+                            hipStream_t st);
+void pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, const double *nmr, const int32_t *cap,
+                           const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                           hipStream_t st);
+void pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_cf, const double *nmr, const int32_t *cap,
+                            const int32_t *cap_alloc, long long limit, int t_lo, int t_hi, int32_t *bit_alloc,
+                            int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, hipStream_t st);
+void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
+                               int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);
+
 /* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,

@@ -371,6 +371,83 @@ class Encoder:
         return {"target_nmr_db": t / float(_lib.RATE_TARGET_GRID), "met": met, "total_bytes": total, "budget": budget,
                 "n_bytes": n_bytes, "capped": capped.bool()}
 
+    def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
+        """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
+        [n_cf, band_stride, 16] float64, candidate i = 0 bits for i = 0, else i + 1 (+inf beyond maxMantBits), band
+        slots as bit_alloc; cap [n_cf, 8] int32, the cap budget 32 J of every long block / short sub-block, -1 where
+        there is none; cap_alloc [n_cf, band_stride] int32, BitAlloc's allocation at that budget.  Slots no band uses
+        are not written (they keep what `out` held; NaN in a dict made here).  -> dict nmr, cap, cap_alloc."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        if out is None:
+            out = {"nmr": torch.full((n_cf, self.band_stride, _lib.BAND_CAND), float("nan"), dtype=torch.float64,
+                                     device=self.device),
+                   "cap": torch.full((n_cf, _lib.SUB), -1, dtype=torch.int32, device=self.device),
+                   "cap_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device)}
+        if tuple(out["nmr"].shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or \
+                tuple(out["cap"].shape) != (n_cf, _lib.SUB) or tuple(out["cap_alloc"].shape) != (n_cf, self.band_stride):
+            raise ValueError(f"band curve: nmr [{n_cf}, {self.band_stride}, {_lib.BAND_CAND}], cap [{n_cf}, {_lib.SUB}], "
+                             f"cap_alloc [{n_cf}, {self.band_stride}]")
+        self._call_rate("pacx_band_curve_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(max_bits_per_sample),
+                        _ptr(out["nmr"]), _ptr(out["cap"]), _ptr(out["cap_alloc"]), self._stream())
+        out["flags"] = fl
+        return out
+
+    def _band_arrays(self, curve, what):
+        nmr, cap, cap_alloc = (curve[k].contiguous() for k in ("nmr", "cap", "cap_alloc"))
+        n_cf = nmr.shape[0]
+        if nmr.dtype != torch.float64 or cap.dtype != torch.int32 or cap_alloc.dtype != torch.int32 or \
+                tuple(nmr.shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or tuple(cap.shape) != (n_cf, _lib.SUB) or \
+                tuple(cap_alloc.shape) != (n_cf, self.band_stride):
+            raise ValueError(f"{what}: a curve as band_curve returns it")
+        out = {"bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
+               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+        return nmr, cap, cap_alloc, n_cf, out
+
+    def band_pick(self, curve, target_nmr_db):
+        """Per band the smallest mantissa size whose NMR on the curve is at or below target_nmr_db (pacx_band_pick,
+        include/pacx.h); a unit whose bands ask for more than its cap gets cap_alloc.  -> dict bit_alloc
+        [n_cf, band_stride] int32 for encode_pack_alloc, n_bytes [n_cf] int32 (predicted), capped [n_cf] bool."""
+        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_pick")
+        self._call_rate("pacx_band_pick", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_double(target_nmr_db), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
+                        self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def band_solve(self, curve, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """rate_solve on a band curve (pacx_band_solve, include/pacx.h): the lowest target on the grid of 1/64 dB in
+        [nmr_lo_db, nmr_hi_db] whose body, every band at band_pick's size, stays within limit_bytes.  -> dict
+        target_nmr_db, met, total_bytes and band_pick's bit_alloc, n_bytes, capped at that target."""
+        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_solve")
+        result = torch.zeros((4,), dtype=torch.int32, device=self.device)        # pacx_rate_result: t, met, total (int64)
+        self._call_rate("pacx_band_solve", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_int64(int(limit_bytes)), ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
+                        _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]), _ptr(result), self._stream())
+        res = result.cpu().numpy()
+        out.update({"target_nmr_db": int(res[0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[1]),
+                    "total_bytes": int(res.view(np.int64)[1]), "capped": out["capped"].bool()})
+        return out
+
+    def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
+        """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):
+        bit_alloc int32 [n_cf, band_stride]; values below 2 count as 0, values above maxMantBits as maxMantBits, and
+        out["bit_alloc"] holds what was coded."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        bit_alloc = torch.as_tensor(bit_alloc, device=self.device).to(torch.int32).contiguous()
+        if tuple(bit_alloc.shape) != (n_cf, self.band_stride):
+            raise ValueError(f"bit_alloc: int32 [{n_cf}, {self.band_stride}]")
+        if out is None:
+            out = self.alloc_outputs(n_cf, with_payload=True)
+        self._call_rate("pacx_encode_pack_alloc_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(bit_alloc),
+                        _ptr(out["overall"]), _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
+                        _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]), _ptr(out["payload"]),
+                        _ptr(out["n_bytes"]), self._stream())
+        out["flags"] = fl
+        return out
+
     def encode_vq(self, pcm, flags=None, out=None, want_entries=False, entries_per_band=160):
         """The shipped configuration (gain-shape PVQ, SBR if the handle has it) from
         PCM to finished payloads.  Returns dict: overall [n_cf,8], bit_alloc

@@ -439,16 +439,34 @@ def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, 
     return cp, enc, view, flags
 
 
-def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples):
-    """(.pac bytes, the outputs of Encoder.encode_pack_nmr for the n + 2 blocks the driver writes, the encoder)"""
+def _check_allocation(allocation):
+    if allocation not in ("budget", "band"):
+        raise ValueError(f"allocation = {allocation!r}: 'budget' (BitAlloc with a budget per block) or 'band' (the "
+                         f"smallest mantissa size per band)")
+    return allocation == "band"
+
+
+def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
+                       allocation="budget"):
+    """(.pac bytes, the outputs of Encoder.encode_pack_nmr -- allocation "band": of Encoder.encode_pack_alloc, with the
+    pick's capped mask as out["capped"] -- for the n + 2 blocks the driver writes, the encoder)"""
+    band = _check_allocation(allocation)
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
-    out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
+    if band:
+        if not np.isfinite(float(target_nmr_db)):
+            raise ValueError("target_nmr_db must be finite")
+        pick = enc.band_pick(enc.band_curve(view, flags, cp.targetBitsPerSample), float(target_nmr_db))
+        out = enc.encode_pack_alloc(view, flags, pick["bit_alloc"])
+        out["capped"] = pick["capped"]
+    else:
+        out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
     body, total = enc.gather_body(out["payload"], out["n_bytes"])
     return header_bytes(cp) + body[:int(total.item())].cpu().numpy().tobytes(), out, enc
 
 
 def encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
-                      header_samples=None, use_vq=False, use_sbr=False, chunk_hops=None, n_lines=1024):
+                      header_samples=None, use_vq=False, use_sbr=False, chunk_hops=None, n_lines=1024,
+                      allocation="budget"):
     """Whole-stream encode at constant quality instead of constant rate -> .pac bytes: the smallest stream (by the
     bisection of include/pacx.h, pacx_encode_pack_nmr_batch) whose predicted noise stays at or below target_nmr_db
     of the masked threshold in every band of every block, no block above the budget of max_kbps_per_channel.  An
@@ -456,12 +474,18 @@ def encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320,
     batch: gain-shape / SBR streams, other block sizes and the chunked host-to-host encoder are not covered.
     The cap is at most 16 bits per sample (the widest mantissa; it bounds the search, include/pacx.h): with the
     default 320 kb/s that needs a sample rate of 20 kHz or more, below it pass a smaller max_kbps_per_channel
-    (ValueError otherwise)."""
+    (ValueError otherwise).
+    allocation="budget" hands the bits to the bands by BitAlloc with the budget the bisection finds per block;
+    "band" gives every band the smallest mantissa size that keeps it at or below the target (pacx_band_curve_batch,
+    pacx_band_pick, pacx_encode_pack_alloc_batch): the same guarantee in fewer bits, a true minimum wherever the cap
+    is not reached."""
     # use_vq, use_sbr, chunk_hops, n_lines: encode_stream's keywords, taken here only so that a caller who switches
     # from encode_stream gets NotImplementedError for what this mode does not cover, not a TypeError
+    _check_allocation(allocation)
     if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
         raise NotImplementedError("constant-quality streams: scalar mantissas, nMDCTLines 1024, one batch")
-    return _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples)[0]
+    return _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
+                              allocation)[0]
 
 
 def _abr_limit(cp, view, head, kbps_per_channel, max_bytes):
@@ -492,22 +516,27 @@ def _abr_range(nmr_range_db):
     return lo, hi
 
 
-def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db):
+def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db,
+                       allocation="budget"):
     """One curve, one solve + second pass per size.  sizes: list of (kbps_per_channel, max_bytes).
-    -> list of (.pac bytes, solve dict, outputs of encode_pack_budget, body limit), the encoder"""
+    -> list of (.pac bytes, solve dict, outputs of encode_pack_budget -- allocation "band": of encode_pack_alloc --,
+    body limit), the encoder"""
+    band = _check_allocation(allocation)
     lo, hi = _abr_range(nmr_range_db)
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
     head = header_bytes(cp)
     limits = [_abr_limit(cp, view, head, k, b) for k, b in sizes]
-    curve = enc.rate_curve(view, flags, cp.targetBitsPerSample)
+    curve = enc.band_curve(view, flags, cp.targetBitsPerSample) if band else \
+        enc.rate_curve(view, flags, cp.targetBitsPerSample)
     done = []
     for limit in limits:
-        sol = enc.rate_solve(curve, flags, limit, lo, hi)
+        sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
         if not sol["met"]:
             raise ValueError(f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
                              f"{sol['total_bytes']} bytes ({len(head) + sol['total_bytes']} with the header), the "
                              f"smallest size this range of targets gives")
-        out = enc.encode_pack_budget(view, flags, sol["budget"])
+        out = enc.encode_pack_alloc(view, flags, sol["bit_alloc"]) if band else \
+            enc.encode_pack_budget(view, flags, sol["budget"])
         body, total = enc.gather_body(out["payload"], out["n_bytes"])
         done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, limit))
     return done, enc
@@ -515,7 +544,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
 
 def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
                       block_switching=False, header_samples=None, nmr_range_db=(-30, 30), use_vq=False, use_sbr=False,
-                      chunk_hops=None, n_lines=1024):
+                      chunk_hops=None, n_lines=1024, allocation="budget"):
     """Whole-stream encode to an average bit rate -> .pac bytes: the best constant quality that fits a size.  One
     target NMR for the whole stream, the smallest on the grid of 1/64 dB in nmr_range_db (by the bisection of
     include/pacx.h, pacx_rate_solve) at which the stream of encode_stream_nmr(target) stays within the size; the
@@ -528,11 +557,15 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
     range does not fit; the message names the smallest size reachable.  The rate-distortion curve of every block is
     taken once (Encoder.rate_curve), the solve reads only that (Encoder.rate_solve), the second pass is
     Encoder.encode_pack_budget: quality.rate_curve gives the curve for several sizes.  Scalar mantissas, 1024 lines,
-    one batch, as encode_stream_nmr."""
+    one batch, as encode_stream_nmr.
+    allocation="band": the stream of encode_stream_nmr(target, allocation="band") instead, on Encoder.band_curve,
+    band_solve and encode_pack_alloc; wherever no block reaches its cap the target found is the lowest on the grid
+    that fits (include/pacx.h)."""
+    _check_allocation(allocation)
     if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
         raise NotImplementedError("average-bit-rate streams: scalar mantissas, nMDCTLines 1024, one batch")
     done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
-                                 block_switching, header_samples, nmr_range_db)
+                                 block_switching, header_samples, nmr_range_db, allocation)
     return done[0][0]
 
 

@@ -305,35 +305,42 @@ def encode_stream_report(pcm, sample_rate, kbps_per_channel, block_switching=Fal
 
 
 def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
-                         header_samples=None):
+                         header_samples=None, allocation="budget"):
     """pacfile.encode_stream_nmr with a Report: -> (.pac bytes, Report, info).  The report is nmr_of_file's of the
     finished bytes.  info, for the n + 2 blocks the driver submits:
-      budget   int32 [blocks, nCh, 8]: the BitAlloc budget of every long block ([..., 0]) / short sub-block, bits;
+      budget   int32 [blocks, nCh, 8]: the BitAlloc budget of every long block ([..., 0]) / short sub-block, bits
+               (allocation "budget" only);
+      bit_alloc int32 [blocks, nCh, band_stride]: the mantissa size of every band as coded;
       capped   bool  [blocks, nCh]: some unit of the block reached the cap (PACX_ST_RATE_CAP) and may miss the target;
       written  bool  [blocks]: the block is in the file (a dropped short-coded hop is not);
       kbps_per_channel: the records of the file, their length prefixes included, over the duration of the blocks
-                        submitted."""
+                        submitted;
+      allocation: "budget" or "band", as given (pacfile.encode_stream_nmr)."""
     from . import pacfile
     data, out, enc = pacfile._encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching,
-                                                header_samples)
+                                                header_samples, allocation)
     n_ch = np.asarray(pcm).shape[1]
     n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
     n_blocks = len(n_bytes)
     body = int(np.sum(n_bytes[n_bytes > 0] + 4))
     info = {
-        "budget": out["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB),
-        "capped": (out["status"].cpu().numpy().reshape(n_blocks, n_ch) & _lib.ST_RATE_CAP) != 0,
+        "allocation": allocation,
+        "bit_alloc": out["bit_alloc"].cpu().numpy().reshape(n_blocks, n_ch, -1),
+        "capped": out["capped"].cpu().numpy().reshape(n_blocks, n_ch) if "capped" in out else
+        (out["status"].cpu().numpy().reshape(n_blocks, n_ch) & _lib.ST_RATE_CAP) != 0,
         "written": n_bytes[:, 0] > 0,
         "kbps_per_channel": 8.0 * body / (n_blocks * HOP / float(sample_rate)) / n_ch / 1000.0,
     }
+    if "budget" in out:
+        info["budget"] = out["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB)
     return data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info
 
 
 def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
-                          block_switching=False, header_samples=None, nmr_range_db=(-30, 30)):
+                          block_switching=False, header_samples=None, nmr_range_db=(-30, 30), allocation="budget"):
     """pacfile.encode_stream_abr with a Report: -> (.pac bytes, Report, info).  A list for kbps_per_channel or for
     max_bytes gives a list of such triples, all solved from one rate curve.  info, for the n + 2 blocks the driver
-    submits, is encode_stream_to_nmr's (budget, capped, written, kbps_per_channel: achieved) and
+    submits, is encode_stream_to_nmr's (budget, bit_alloc, capped, written, kbps_per_channel: achieved, allocation) and
       target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
       n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written)."""
     from . import pacfile
@@ -345,23 +352,26 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
     else:
         sizes = [(kbps_per_channel, max_bytes)]
     done, enc = pacfile._encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching,
-                                           header_samples, nmr_range_db)
+                                           header_samples, nmr_range_db, allocation)
     n_ch = np.asarray(pcm).shape[1]
     res = []
     for data, sol, out, limit in done:
         n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
         n_blocks = len(n_bytes)
         info = {
+            "allocation": allocation,
             "target_nmr_db": sol["target_nmr_db"],
             "limit_bytes": limit,
             "total_bytes": sol["total_bytes"],
             "n_bytes": sol["n_bytes"].cpu().numpy().reshape(n_blocks, n_ch),
-            "budget": sol["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB),
+            "bit_alloc": out["bit_alloc"].cpu().numpy().reshape(n_blocks, n_ch, -1),
             "capped": sol["capped"].cpu().numpy().reshape(n_blocks, n_ch),
             "written": n_bytes[:, 0] > 0,
             "kbps_per_channel": 8.0 * int(np.sum(n_bytes[n_bytes > 0] + 4)) / (n_blocks * HOP / float(sample_rate)) /
             n_ch / 1000.0,
         }
+        if "budget" in sol:
+            info["budget"] = sol["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB)
         res.append((data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info))
     return res if many else res[0]
 
@@ -381,6 +391,23 @@ def rate_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False
     return {"worst": c["worst"].cpu().numpy().reshape(-1, n_ch, c["row"]),
             "bits": c["bits"].cpu().numpy().reshape(-1, n_ch, c["row"]),
             "steps": c["steps"].cpu().numpy().reshape(-1, n_ch, _lib.SUB), "row": c["row"], "sub_stride": c["sub_stride"]}
+
+
+def band_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False):
+    """The noise-to-mask ratio of every band of a stream at every mantissa size, for plotting: -> dict of NumPy
+    arrays for the n + 2 blocks the driver submits,
+      nmr        float64 [blocks, nCh, band_stride, 16]: NMR_b (dB) with candidate i = 0 bits for i = 0, else i + 1;
+                 sub-block sb of a short-coded block at [sb * nBandsShort + b]; NaN where there is no band, +inf
+                 beyond the widest mantissa;
+      cap        int32 [blocks, nCh, 8]: the mantissa bits the cap rate allows every unit, -1 where there is none;
+      cap_alloc  int32 [blocks, nCh, band_stride]: BitAlloc's allocation at that budget."""
+    from . import pacfile
+    cp, enc, view, flags = pacfile._rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, None)
+    c = enc.band_curve(view, flags, cp.targetBitsPerSample)
+    n_ch = cp.nChannels
+    return {"nmr": c["nmr"].cpu().numpy().reshape(-1, n_ch, enc.band_stride, _lib.BAND_CAND),
+            "cap": c["cap"].cpu().numpy().reshape(-1, n_ch, _lib.SUB),
+            "cap_alloc": c["cap_alloc"].cpu().numpy().reshape(-1, n_ch, enc.band_stride)}
 
 
 def nmr_of_file(pcm, pac_bytes, block_switching=None, chunk_hops=4096):

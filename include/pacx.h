@@ -803,6 +803,98 @@ int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_strid
                     const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
                     int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream);
 
+/* ---- bits handed to the bands one by one: the minimum for a target NMR ------- */
+
+#define PACX_BAND_CAND 16         /* mantissa sizes on a band curve: candidate i means bits(i) = 0 for i = 0, else i + 1 */
+
+/*
+ * The search and the curve above hand the bits to the bands by the reference's BitAlloc, which works from the
+ * psychoacoustic model's SMRs: the worst band dictates the budget and every other band is coded finer than the
+ * target asks.  In this coder the noise of a band depends on that band's own mantissa size and on nothing else (the
+ * overall scale is fixed before the allocation, the scale factor comes from the band's own maximum, mantissas and
+ * dequantiser are per line), and a record carries every band's allocation (0, 2, 3, ..., maxMantBits are the
+ * representable sizes).  So the smallest stream that keeps every band at or below a target is found band by band:
+ * one curve of PACX_BAND_CAND values per band (pacx_band_curve_batch), a pick or a solve on it (pacx_band_pick,
+ * pacx_band_solve), and a second pass that codes with the allocation found (pacx_encode_pack_alloc_batch), whose
+ * n_bytes equal the ones predicted.  Scalar coder, 1024 lines, one batch, as pacx_encode_pack_nmr_batch.
+ *
+ * Per unit, on the quantities of pacx_encode_pack_nmr_batch -- lines X, the overall scale, the masked threshold
+ * T[k], the band maxima max_b of |X 2^overall|:
+ *
+ *   n_cand = maxMantBits = min(2^nMantSizeBits, 16)
+ *   nmr[b][i], i < n_cand: NMR_b as pacx_nmr_batch defines it when band b is coded with bits(i): the scale factor
+ *          pacx_scale_factor(max_b, nScaleBits, bits), per line pacx_mantissa -> pacx_dequantize -> / 2^overall
+ *          (Xh = 0 for 0 bits), n = 4 (X - Xh)^2, band means, eps = 2^-52, m = 10^((T - 96) / 10)
+ *   nmr[b][i], i >= n_cand: +inf
+ *   cap       = 32 J, J exactly as the search takes it (pacx_rate_steps with max_bits_per_sample, same flags and
+ *               short-block handling)
+ *   cap_alloc = BitAlloc(double(32 J), maxMantBits, bands, SMR), the encoder's own; the status bits it raises
+ *               (PACX_ST_ALLOC_CAP, PACX_ST_GUARD) are kept per cf in the handle beside the front end's, as
+ *               pacx_rate_curve_batch keeps its front end's
+ *
+ *   pick(unit, T): per band a_b = bits(i*), i* the smallest i, scanning in ascending order, with nmr[b][i] <= T
+ *          (some bands' NMR rises somewhere along the sizes, so the scan visits them all and does not bisect);
+ *          a NaN or a miss at every i gives a_b = bits(n_cand - 1) and marks the band missed.
+ *          If any band missed, or sum_b a_b lines_b > cap, the unit is capped and its channel-frame marked in
+ *          `capped` (what PACX_ST_RATE_CAP marks for the search).  A capped unit whose sum exceeds cap is coded with
+ *          cap_alloc -- exactly as the search codes a unit it flags PACX_ST_RATE_CAP; one whose sum fits keeps its a_b.
+ *   bits(unit)   = nScaleBits + sum_b (nMantSizeBits + nScaleBits + a_b lines_b)
+ *   bytes(cf, T) = 0 for a dropped hop, else ((sum over its units of bits(unit)) + 4 + 7) >> 3
+ *   total(T)     = sum over cf with bytes > 0 of (bytes + 4)
+ *
+ * Wherever no unit is capped, a_b is the minimum over all representable sizes that keeps band b at or below T.
+ * There a_b and total(T) are non-increasing in T (the set of passing sizes only grows with T), so the solve below
+ * returns the lowest grid target that fits, not merely the bisection's answer.  Where a unit moves from capped to
+ * uncapped as T rises, total may rise.  A unit capped for size spends at most cap mantissa bits -- the bound of the
+ * existing capped path; pacx_band_curve_batch checks that this keeps every record within pacx_payload_stride for
+ * the cap rate given (an allocation of maxMantBits everywhere need not fit for a short-coded frame, which is why
+ * the cap is not optional) and returns PACX_E_UNSUPPORTED otherwise.  A short-coded hop the reference drops
+ * (PACX_ST_ZERO_SUBBLOCK) stays dropped.
+ *
+ *   nmr (out):       float64 [n_cf][band_stride][PACX_BAND_CAND], band slots as bit_alloc: cf band_stride + sb nb + b;
+ *                    slots no band of the frame uses are not written
+ *   cap (out):       int32 [n_cf][8], 32 J of every unit and -1 where there is none: slots 1-7 of a long frame, every
+ *                    slot of a dropped hop -- the later steps need no flags
+ *   cap_alloc (out): int32 [n_cf][band_stride], 0 where there is no band
+ * Runs MDCT -> side chain -> masked threshold -> k_band_curve on `stream` (maxMantBits passes over a unit's lines
+ * instead of a BitAlloc and a pass per budget).  PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr;
+ * PACX_E_ARG for a null output, a cap rate outside (0, 16].
+ */
+int pacx_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, double max_bits_per_sample,
+                          double *nmr, int32_t *cap, int32_t *cap_alloc, void *stream);
+
+/*
+ * pick(unit, T) for every unit at T = target_nmr_db (finite), on the arrays alone: one wave per channel-frame, a
+ * lane per (unit, band) pair.
+ *   bit_alloc (out): int32 [n_cf][band_stride], 0 where there is no unit
+ *   n_bytes (out):   int32 [n_cf], bytes(cf, T);  capped (out): uint8 [n_cf]
+ */
+int pacx_band_pick(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                   double target_nmr_db, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, void *stream);
+
+/*
+ * pacx_rate_solve with this pick in place of the curve look-up: the same grid (PACX_RATE_TARGET_GRID), the same
+ * decision, state, fixed number of pick / step pairs without a host wait, and the same pacx_rate_result.  Argument
+ * rules are pacx_rate_solve's; the outputs are those of pacx_band_pick at the t returned.
+ */
+int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                    int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc, int32_t *n_bytes,
+                    uint8_t *capped, pacx_rate_result *result, void *stream);
+
+/*
+ * The second pass: pacx_encode_pack_budget_batch with the allocation of every band given by the caller instead of a
+ * budget per unit.  bit_alloc_in: int32 [n_cf][band_stride] (may be the bit_alloc output itself); a value below 2
+ * is taken as 0 and one above maxMantBits as maxMantBits, slots no band uses are ignored, and bit_alloc receives
+ * what was coded.  With the allocation of a pick it writes records of exactly the predicted lengths.  A
+ * channel-frame whose record would not fit pacx_payload_stride with the allocation asked for (no pick gives one)
+ * is coded without mantissa bits and flagged PACX_ST_RATE_CAP.  status carries the front end's bits and that one
+ * only: no BitAlloc runs here.  Runs MDCT -> k_band_sanitize -> scale factors + mantissas -> pack on `stream`.
+ */
+int pacx_encode_pack_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                 const int32_t *bit_alloc_in, int32_t *overall_scale, int32_t *scale_factor,
+                                 int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
+                                 int32_t *n_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
