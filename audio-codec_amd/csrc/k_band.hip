@@ -15,6 +15,9 @@
  *                     band's sizes in ascending order for the first at or below the target; the unit sums go through
  *                     LDS, the frame's bits through the wave.  For a solve it adds the body total: integer sums, one
  *                     64-bit atomicAdd per workgroup, and k_rate.hip's k_solve_init / k_solve_step decide on it.
+ *   k_band_pick_seg   pacx_band_solve_segments: the same frame work (band_frame) with one SolveState per stretch of
+ *                     consecutive channel-frames; the wave finds its frame's segment in the uploaded boundaries
+ *                     (segment_of, rate_dev.h), k_rate.hip's k_solve_init_seg / k_solve_step_seg decide per segment.
  *   k_band_sanitize   a caller's allocation made representable (below 2 -> 0, above maxMantBits -> maxMantBits), and
  *                     an all-zero allocation for a channel-frame whose record would leave PACX_PAYLOAD_STRIDE.
  *
@@ -156,9 +159,91 @@ __global__ __launch_bounds__(64) void k_band_curve(PacxTables T, const uint8_t *
     }
 }
 
-/* pick(unit, T) of include/pacx.h for every unit of one channel-frame per wave.  s == nullptr: pacx_band_pick at
-   `target`, the outputs are written.  Else a pick of the solve at the target in flight; final: the last launch, at
-   the target found, which also writes the outputs. */
+constexpr int PICK_WAVES = PICK_THREADS / 64;
+
+/* pick(unit, T) of include/pacx.h for every unit of one channel-frame, by one wave, the only one: a lane per (unit,
+   band) pair scans the band's sizes in ascending order, the unit sums go through the wave's LDS row (unit_sum,
+   unit_miss: zeroed here), the cap rule, the frame's bits through the wave.  write: the outputs are written.
+   -> what the frame adds to the body: its bytes and their length prefix (every lane holds it) */
+__device__ __forceinline__ unsigned long long band_frame(const PacxTables &T, long long cf, double target,
+                                                         const double *__restrict__ nmr,
+                                                         const int32_t *__restrict__ cap,
+                                                         const int32_t *__restrict__ cap_alloc, bool write,
+                                                         int32_t *__restrict__ bit_alloc, int32_t *__restrict__ n_bytes,
+                                                         uint8_t *__restrict__ capped, int *unit_sum, int *unit_miss)
+{
+    constexpr int SLOTS = PACX_SUB * PACX_MAX_BANDS / 64;          /* band slots of a row per lane, at most */
+    const int lane = threadIdx.x & 63;
+    if (lane < PACX_SUB) {
+        unit_sum[lane] = 0;
+        unit_miss[lane] = 0;
+    }
+    wave_lds_fence();
+    const int32_t *__restrict__ cp = cap + cf * PACX_SUB;
+    const bool is_short = cp[1] >= 0;              /* a long frame's slots 1-7 and a dropped hop's eight hold -1 */
+    const int nb = is_short ? T.nb_short : T.nb_long;
+    const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
+    int n_cand = 1 << T.n_mant_size_bits;
+    if (n_cand > BAND_CAND)
+        n_cand = BAND_CAND;
+    const long long row = cf * T.band_stride;
+    int a[SLOTS], nl[SLOTS], sbs[SLOTS];
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+        const int slot = lane + 64 * q;
+        const int sb = is_short ? slot / nb : (slot < nb ? 0 : PACX_SUB);
+        const int b = is_short ? slot - sb * nb : slot;
+        a[q] = 0;
+        nl[q] = 0;
+        sbs[q] = -1;
+        if (slot < T.band_stride && sb < PACX_SUB && cp[sb] >= 0) {
+            const double *__restrict__ r = nmr + (row + slot) * BAND_CAND;
+            int pick = -1;
+            for (int i = n_cand - 1; i >= 0; --i)              /* the ascending scan's first pass = the lowest passing i */
+                if (r[i] <= target)
+                    pick = i;
+            sbs[q] = sb;
+            nl[q] = count[b];
+            a[q] = cand_bits(pick < 0 ? n_cand - 1 : pick);
+            atomicAdd(&unit_sum[sb], a[q] * nl[q]);
+            if (pick < 0)
+                atomicOr(&unit_miss[sb], 1);
+        }
+    }
+    wave_lds_fence();
+    int sum = 0;
+    bool any_cap = false;
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+        const int slot = lane + 64 * q;
+        if (sbs[q] >= 0) {
+            const bool over = unit_sum[sbs[q]] > cp[sbs[q]];
+            if (over)
+                a[q] = cap_alloc[row + slot];
+            any_cap = any_cap || over || unit_miss[sbs[q]] != 0;
+            sum += T.n_mant_size_bits + T.n_scale_bits + a[q] * nl[q];
+        }
+        if (write && slot < T.band_stride)
+            bit_alloc[row + slot] = a[q];
+    }
+    int units = 0;
+    for (int sb = 0; sb < PACX_SUB; ++sb)
+        units += cp[sb] >= 0 ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        sum += __shfl_xor(sum, off, 64);
+    const bool cap_cf = __builtin_amdgcn_ballot_w64(any_cap) != 0ull;
+    const int nby = units ? (sum + units * T.n_scale_bits + 4 + 7) >> 3 : 0;
+    if (write && lane == 0) {
+        n_bytes[cf] = nby;
+        capped[cf] = cap_cf ? 1 : 0;
+    }
+    return nby > 0 ? (unsigned long long)nby + 4ull : 0ull;
+}
+
+/* band_frame for one channel-frame per wave.  s == nullptr: pacx_band_pick at `target`, the outputs are written.
+   Else a pick of the solve at the target in flight; final: the last launch, at the target found, which also writes
+   the outputs. */
 __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveState *__restrict__ s, long long n_cf,
                                                            double target, const double *__restrict__ nmr,
                                                            const int32_t *__restrict__ cap,
@@ -166,10 +251,8 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveS
                                                            int32_t *__restrict__ bit_alloc, int32_t *__restrict__ n_bytes,
                                                            uint8_t *__restrict__ capped)
 {
-    constexpr int WAVES = PICK_THREADS / 64;
-    constexpr int SLOTS = PACX_SUB * PACX_MAX_BANDS / 64;          /* band slots of a row per lane, at most */
-    __shared__ int unit_sum[WAVES][PACX_SUB], unit_miss[WAVES][PACX_SUB];
-    __shared__ unsigned long long part[WAVES];
+    __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
+    __shared__ unsigned long long part[PICK_WAVES];
     if (s) {
         if (s->done && !final)
             return;                                /* the answer is known: this launch does nothing */
@@ -177,76 +260,11 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveS
     }
     const bool write = !s || final;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long long cf = (long long)blockIdx.x * WAVES + w;
+    const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
     unsigned long long mine = 0ull;
-    if (lane < PACX_SUB) {
-        unit_sum[w][lane] = 0;
-        unit_miss[w][lane] = 0;
-    }
-    wave_lds_fence();
-    if (cf < n_cf) {                               /* wave-uniform */
-        const int32_t *__restrict__ cp = cap + cf * PACX_SUB;
-        const bool is_short = cp[1] >= 0;          /* a long frame's slots 1-7 and a dropped hop's eight hold -1 */
-        const int nb = is_short ? T.nb_short : T.nb_long;
-        const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
-        int n_cand = 1 << T.n_mant_size_bits;
-        if (n_cand > BAND_CAND)
-            n_cand = BAND_CAND;
-        const long long row = cf * T.band_stride;
-        int a[SLOTS], nl[SLOTS], sbs[SLOTS];
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q) {
-            const int slot = lane + 64 * q;
-            const int sb = is_short ? slot / nb : (slot < nb ? 0 : PACX_SUB);
-            const int b = is_short ? slot - sb * nb : slot;
-            a[q] = 0;
-            nl[q] = 0;
-            sbs[q] = -1;
-            if (slot < T.band_stride && sb < PACX_SUB && cp[sb] >= 0) {
-                const double *__restrict__ r = nmr + (row + slot) * BAND_CAND;
-                int pick = -1;
-                for (int i = n_cand - 1; i >= 0; --i)          /* the ascending scan's first pass = the lowest passing i */
-                    if (r[i] <= target)
-                        pick = i;
-                sbs[q] = sb;
-                nl[q] = count[b];
-                a[q] = cand_bits(pick < 0 ? n_cand - 1 : pick);
-                atomicAdd(&unit_sum[w][sb], a[q] * nl[q]);
-                if (pick < 0)
-                    atomicOr(&unit_miss[w][sb], 1);
-            }
-        }
-        wave_lds_fence();
-        int sum = 0;
-        bool any_cap = false;
-#pragma unroll
-        for (int q = 0; q < SLOTS; ++q) {
-            const int slot = lane + 64 * q;
-            if (sbs[q] >= 0) {
-                const bool over = unit_sum[w][sbs[q]] > cp[sbs[q]];
-                if (over)
-                    a[q] = cap_alloc[row + slot];
-                any_cap = any_cap || over || unit_miss[w][sbs[q]] != 0;
-                sum += T.n_mant_size_bits + T.n_scale_bits + a[q] * nl[q];
-            }
-            if (write && slot < T.band_stride)
-                bit_alloc[row + slot] = a[q];
-        }
-        int units = 0;
-        for (int sb = 0; sb < PACX_SUB; ++sb)
-            units += cp[sb] >= 0 ? 1 : 0;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-            sum += __shfl_xor(sum, off, 64);
-        const bool cap_cf = __builtin_amdgcn_ballot_w64(any_cap) != 0ull;
-        const int nby = units ? (sum + units * T.n_scale_bits + 4 + 7) >> 3 : 0;
-        if (nby > 0)
-            mine = (unsigned long long)nby + 4ull;
-        if (write && lane == 0) {
-            n_bytes[cf] = nby;
-            capped[cf] = cap_cf ? 1 : 0;
-        }
-    }
+    if (cf < n_cf)                                 /* wave-uniform */
+        mine = band_frame(T, cf, target, nmr, cap, cap_alloc, write, bit_alloc, n_bytes, capped, unit_sum[w],
+                          unit_miss[w]);
     if (!s)
         return;
     if (lane == 0)
@@ -254,10 +272,57 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveS
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long all = 0ull;
-        for (int i = 0; i < WAVES; ++i)
+        for (int i = 0; i < PICK_WAVES; ++i)
             all += part[i];
         if (all)
             atomicAdd(&s->total, all);
+    }
+}
+
+/* k_band_pick with a state per segment (pacx_band_solve_segments): the wave takes the target of its frame's segment
+   and adds to that segment's total; a frame whose segment is done is not scanned before the last launch.  A
+   workgroup whose four frames lie in one segment adds once, one that straddles a boundary once per wave. */
+__global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, SolveState *__restrict__ s,
+                                                               const long long *__restrict__ seg_first, int n_seg,
+                                                               int search_steps, long long n_cf,
+                                                               const double *__restrict__ nmr,
+                                                               const int32_t *__restrict__ cap,
+                                                               const int32_t *__restrict__ cap_alloc, int final,
+                                                               int32_t *__restrict__ bit_alloc,
+                                                               int32_t *__restrict__ n_bytes,
+                                                               uint8_t *__restrict__ capped)
+{
+    __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
+    __shared__ unsigned long long part[PICK_WAVES];
+    __shared__ int seg_of[PICK_WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
+    int seg = -1;                                  /* past the end: no segment, nothing to add */
+    unsigned long long mine = 0ull;
+    if (cf < n_cf) {                               /* wave-uniform, and so is everything read through seg */
+        seg = segment_of(seg_first, n_seg, search_steps, cf);
+        const SolveState *mystate = s + seg;
+        if (final || !mystate->done)
+            mine = band_frame(T, cf, (double)mystate->mid / 64.0, nmr, cap, cap_alloc, final != 0, bit_alloc, n_bytes,
+                              capped, unit_sum[w], unit_miss[w]);
+    }
+    if (lane == 0) {
+        part[w] = mine;
+        seg_of[w] = seg;
+    }
+    __syncthreads();
+    const long long left = n_cf - (long long)blockIdx.x * PICK_WAVES;             /* >= 1: frames of this workgroup */
+    const int last = left < PICK_WAVES ? (int)left - 1 : PICK_WAVES - 1;
+    if (seg_of[0] == seg_of[last]) {               /* workgroup-uniform: one segment */
+        if (threadIdx.x == 0) {
+            unsigned long long all = 0ull;
+            for (int i = 0; i < PICK_WAVES; ++i)
+                all += part[i];
+            if (all)
+                atomicAdd(&s[seg_of[0]].total, all);
+        }
+    } else if (lane == 0 && seg >= 0 && mine) {
+        atomicAdd(&s[seg].total, mine);
     }
 }
 
@@ -350,6 +415,25 @@ void pacx_k::pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_c
             hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, s, n_cf, 0.0, nmr, cap, cap_alloc,
                                final, bit_alloc, n_bytes, capped);
         pacx_launch_solve_step(ws, limit, final, result, st);
+    }
+}
+
+void pacx_k::pacx_launch_band_solve_segments(const PacxTables &T, void *ws, long long n_cf, const double *nmr,
+                                             const int32_t *cap, const int32_t *cap_alloc, int n_seg,
+                                             const long long *seg_first, const long long *limit, int t_lo, int t_hi,
+                                             int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                                             pacx_rate_result *result, hipStream_t st)
+{
+    SolveState *s = (SolveState *)ws;
+    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi), search = pacx_segment_search_steps(n_seg);
+    const unsigned grid = (unsigned)((n_cf + PICK_WAVES - 1) / PICK_WAVES);
+    pacx_launch_solve_init_segments(ws, n_seg, t_lo, t_hi, st);
+    for (int p = 0; p < pairs; ++p) {
+        const int final = p == pairs - 1;
+        if (grid)
+            hipLaunchKernelGGL(k_band_pick_seg, dim3(grid), dim3(PICK_THREADS), 0, st, T, s, seg_first, n_seg, search,
+                               n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
+        pacx_launch_solve_step_segments(ws, n_seg, limit, final, result, st);
     }
 }
 

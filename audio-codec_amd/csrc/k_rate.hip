@@ -20,6 +20,10 @@
  *                      curve at the target in flight, sums the frame's bytes; one 64-bit atomicAdd per workgroup.
  *   k_solve_step       one thread: the bisection's decision on that total.  The host enqueues a fixed number of
  *                      pick / step pairs and waits for none; pairs after the answer is known do nothing.
+ *   k_solve_pick_seg, k_solve_init_seg, k_solve_step_seg
+ *                      pacx_rate_solve_segments: the same frame work (solve_frame) and the same decision (solve_step)
+ *                      with one SolveState per segment; a frame finds its segment in the uploaded boundaries
+ *                      (segment_of, rate_dev.h) and adds to that segment's total.
  * RateLds, RateUnit, rate_unit, wave_sum and SolveState live in rate_dev.h: k_band.hip shares them.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
@@ -255,7 +259,8 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
         atomicOr(&status[cf], ((cap & 1) ? 4u : 0u) | ((cap & 2) ? 16u : 0u));   /* ALLOC_CAP, GUARD */
 }
 
-/* ---- the solve of pacx_rate_solve (include/pacx.h): one target for the whole stream, on the stored curves ---- */
+/* ---- the solve of pacx_rate_solve (include/pacx.h): one target for the whole stream, on the stored curves; and of
+   pacx_rate_solve_segments: one target per stretch of consecutive channel-frames, a SolveState each ---- */
 constexpr int SOLVE_THREADS = 256;
 constexpr int SOLVE_MAX_LOOKUP = 12;               /* 1 + ceil(log2(J + 1)) for J < 2048, as RATE_MAX_EVAL */
 
@@ -264,7 +269,8 @@ __device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either 
     return (a - (a < 0 ? 1 : 0)) / 2;
 }
 
-__global__ void k_solve_init(SolveState *s, int t_lo, int t_hi)
+/* the state of a solve before its first pick */
+__device__ __forceinline__ void solve_init(SolveState *s, int t_lo, int t_hi)
 {
     s->lo = t_lo - 1;
     s->hi = t_hi;
@@ -275,79 +281,9 @@ __global__ void k_solve_init(SolveState *s, int t_lo, int t_hi)
     s->total = 0ull;
 }
 
-/* pick(unit, T) of every unit of one channel-frame per thread, the frame's bytes, their sum over the workgroup and
-   one atomicAdd.  final: the last launch, at the target found, which also writes the outputs. */
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s, long long n_cf, int row,
-                                                             int sub_stride, const double *__restrict__ worst,
-                                                             const int32_t *__restrict__ bits,
-                                                             const int32_t *__restrict__ steps, int final,
-                                                             int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
-                                                             uint8_t *__restrict__ capped)
-{
-    __shared__ unsigned long long part[SOLVE_THREADS / 64];
-    if (s->done && !final)
-        return;                                    /* the answer is known: this launch does nothing */
-    const double target = (double)s->mid / 64.0;
-    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
-    unsigned long long mine = 0ull;
-    if (cf < n_cf) {
-        int sum = 0, units = 0;
-        bool cap = false;
-        for (int sb = 0; sb < PACX_SUB; ++sb) {
-            int J = steps[cf * PACX_SUB + sb];
-            int b = 0;
-            if (J >= 0) {
-                const int base = sb * sub_stride;
-                if (base + J >= row)               /* never read past the row */
-                    J = row - 1 - base;
-            }
-            if (J >= 0) {
-                const long long at = cf * (long long)row + sb * sub_stride;
-                int hi = J;
-                if (!(worst[at + J] <= target)) {
-                    cap = true;
-                } else {
-                    int lo = -1;
-                    for (int it = 0; it < SOLVE_MAX_LOOKUP && hi - lo > 1; ++it) {
-                        const int mid = (lo + hi) / 2;
-                        if (worst[at + mid] <= target)
-                            hi = mid;
-                        else
-                            lo = mid;
-                    }
-                }
-                sum += bits[at + hi];
-                b = 32 * hi;
-                ++units;
-            }
-            if (final)
-                budget[cf * PACX_SUB + sb] = b;
-        }
-        const int nby = units ? (sum + 4 + 7) >> 3 : 0;
-        if (nby > 0)
-            mine = (unsigned long long)nby + 4ull;
-        if (final) {
-            n_bytes[cf] = nby;
-            capped[cf] = cap ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        mine += __shfl_xor(mine, off, 64);
-    if ((threadIdx.x & 63) == 0)
-        part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0ull;
-        for (int w = 0; w < SOLVE_THREADS / 64; ++w)
-            all += part[w];
-        if (all)
-            atomicAdd(&s->total, all);
-    }
-}
-
-/* one thread: the decision of include/pacx.h on the total the pick before it left.  final: write the result */
-__global__ void k_solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
+/* the decision of include/pacx.h on the total the pick before it left, the only one: k_solve_step takes it for the
+   stream, k_solve_step_seg for every segment.  final: write the result */
+__device__ __forceinline__ void solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
 {
     const unsigned long long total = s->total;
     s->total = 0ull;
@@ -380,6 +316,177 @@ __global__ void k_solve_step(SolveState *s, long long limit, int final, pacx_rat
     }
 }
 
+__global__ void k_solve_init(SolveState *s, int t_lo, int t_hi)
+{
+    solve_init(s, t_lo, t_hi);
+}
+
+/* one thread per segment */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_init_seg(SolveState *s, int n_seg, int t_lo, int t_hi)
+{
+    const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    if (i < n_seg)
+        solve_init(s + i, t_lo, t_hi);
+}
+
+/* pick(unit, T) of every unit of one channel-frame, the only one: the look-ups in the curve, the frame's bytes and,
+   in the launch that writes, its outputs.  -> what the frame adds to the body: its bytes and their length prefix */
+__device__ __forceinline__ unsigned long long solve_frame(long long cf, double target, int row, int sub_stride,
+                                                          const double *__restrict__ worst,
+                                                          const int32_t *__restrict__ bits,
+                                                          const int32_t *__restrict__ steps, int final,
+                                                          int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
+                                                          uint8_t *__restrict__ capped)
+{
+    int sum = 0, units = 0;
+    bool cap = false;
+    for (int sb = 0; sb < PACX_SUB; ++sb) {
+        int J = steps[cf * PACX_SUB + sb];
+        int b = 0;
+        if (J >= 0) {
+            const int base = sb * sub_stride;
+            if (base + J >= row)                   /* never read past the row */
+                J = row - 1 - base;
+        }
+        if (J >= 0) {
+            const long long at = cf * (long long)row + sb * sub_stride;
+            int hi = J;
+            if (!(worst[at + J] <= target)) {
+                cap = true;
+            } else {
+                int lo = -1;
+                for (int it = 0; it < SOLVE_MAX_LOOKUP && hi - lo > 1; ++it) {
+                    const int mid = (lo + hi) / 2;
+                    if (worst[at + mid] <= target)
+                        hi = mid;
+                    else
+                        lo = mid;
+                }
+            }
+            sum += bits[at + hi];
+            b = 32 * hi;
+            ++units;
+        }
+        if (final)
+            budget[cf * PACX_SUB + sb] = b;
+    }
+    const int nby = units ? (sum + 4 + 7) >> 3 : 0;
+    if (final) {
+        n_bytes[cf] = nby;
+        capped[cf] = cap ? 1 : 0;
+    }
+    return nby > 0 ? (unsigned long long)nby + 4ull : 0ull;
+}
+
+/* the sum of a workgroup's frames: through the waves, then LDS; thread 0 holds it */
+__device__ __forceinline__ unsigned long long solve_block_sum(unsigned long long mine, unsigned long long *part)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0)
+        part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    unsigned long long all = 0ull;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < SOLVE_THREADS / 64; ++w)
+            all += part[w];
+    return all;
+}
+
+/* one channel-frame per thread (solve_frame), the sum of the frames' bytes over the workgroup and one atomicAdd.
+   final: the last launch, at the target found, which also writes the outputs. */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s, long long n_cf, int row,
+                                                             int sub_stride, const double *__restrict__ worst,
+                                                             const int32_t *__restrict__ bits,
+                                                             const int32_t *__restrict__ steps, int final,
+                                                             int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
+                                                             uint8_t *__restrict__ capped)
+{
+    __shared__ unsigned long long part[SOLVE_THREADS / 64];
+    if (s->done && !final)
+        return;                                    /* the answer is known: this launch does nothing */
+    const double target = (double)s->mid / 64.0;
+    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    unsigned long long mine = 0ull;
+    if (cf < n_cf)
+        mine = solve_frame(cf, target, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
+    const unsigned long long all = solve_block_sum(mine, part);
+    if (threadIdx.x == 0 && all)
+        atomicAdd(&s->total, all);
+}
+
+/* k_solve_pick with a state per segment (pacx_rate_solve_segments): every frame takes the target of its segment's
+   state and adds to that segment's total.  A frame whose segment is done does no look-ups before the last launch.
+   A workgroup whose frames lie in one segment adds once, as k_solve_pick; one that straddles boundaries sums the
+   runs of equal segments in LDS (the frames of a segment are consecutive) and adds once per segment present. */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick_seg(SolveState *__restrict__ s,
+                                                                 const long long *__restrict__ seg_first, int n_seg,
+                                                                 int search_steps, long long n_cf, int row,
+                                                                 int sub_stride, const double *__restrict__ worst,
+                                                                 const int32_t *__restrict__ bits,
+                                                                 const int32_t *__restrict__ steps, int final,
+                                                                 int32_t *__restrict__ budget,
+                                                                 int32_t *__restrict__ n_bytes,
+                                                                 uint8_t *__restrict__ capped)
+{
+    __shared__ unsigned long long part[SOLVE_THREADS / 64];
+    __shared__ unsigned long long run[SOLVE_THREADS];
+    __shared__ int seg_of[SOLVE_THREADS];
+    const int t = threadIdx.x;
+    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + t;
+    int seg = -1;                                  /* past the end: no segment, nothing to add */
+    unsigned long long mine = 0ull;
+    if (cf < n_cf) {
+        seg = segment_of(seg_first, n_seg, search_steps, cf);
+        const SolveState *mystate = s + seg;
+        if (final || !mystate->done)
+            mine = solve_frame(cf, (double)mystate->mid / 64.0, row, sub_stride, worst, bits, steps, final, budget,
+                               n_bytes, capped);
+    }
+    seg_of[t] = seg;
+    __syncthreads();
+    const long long left = n_cf - (long long)blockIdx.x * SOLVE_THREADS;          /* >= 1: frames of this workgroup */
+    const int last = left < SOLVE_THREADS ? (int)left - 1 : SOLVE_THREADS - 1;
+    const int first_seg = seg_of[0];
+    if (first_seg == seg_of[last]) {               /* workgroup-uniform: one segment */
+        const unsigned long long all = solve_block_sum(mine, part);
+        if (t == 0 && all)
+            atomicAdd(&s[first_seg].total, all);
+        return;
+    }
+    /* segmented sum: after the step of stride off, run[t] holds the frames [t, t + 2 off) of t's own run */
+    run[t] = mine;
+    __syncthreads();
+#pragma unroll 1
+    for (int off = 1; off < SOLVE_THREADS; off <<= 1) {
+        const bool same = t + off < SOLVE_THREADS && seg_of[t + off] == seg;
+        const unsigned long long add = same ? run[t + off] : 0ull;
+        __syncthreads();
+        mine += add;
+        run[t] = mine;
+        __syncthreads();
+    }
+    if (seg >= 0 && mine && (t == 0 || seg_of[t - 1] != seg))
+        atomicAdd(&s[seg].total, mine);
+}
+
+/* one thread: solve_step on the total the pick before it left */
+__global__ void k_solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
+{
+    solve_step(s, limit, final, result);
+}
+
+/* one thread per segment: solve_step with the segment's limit; final: result[seg] */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_step_seg(SolveState *s, int n_seg,
+                                                                 const long long *__restrict__ limit, int final,
+                                                                 pacx_rate_result *result)
+{
+    const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    if (i < n_seg)
+        solve_step(s + i, limit[i], final, result + i);
+}
+
 }  // namespace
 
 size_t pacx_k::pacx_rate_solve_ws_bytes(void) { return sizeof(SolveState); }
@@ -402,6 +509,28 @@ void pacx_k::pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st
 void pacx_k::pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st)
 {
     hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, (SolveState *)ws, limit, final, result);
+}
+
+/* and the same pair with a state per segment: one thread per segment */
+void pacx_k::pacx_launch_solve_init_segments(void *ws, int n_seg, int t_lo, int t_hi, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_solve_init_seg, dim3((unsigned)((n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)),
+                       dim3(SOLVE_THREADS), 0, st, (SolveState *)ws, n_seg, t_lo, t_hi);
+}
+
+void pacx_k::pacx_launch_solve_step_segments(void *ws, int n_seg, const long long *limit, int final,
+                                             pacx_rate_result *result, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_solve_step_seg, dim3((unsigned)((n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)),
+                       dim3(SOLVE_THREADS), 0, st, (SolveState *)ws, n_seg, limit, final, result);
+}
+
+int pacx_k::pacx_segment_search_steps(int n_seg)
+{
+    int n = 0;                                     /* ceil(log2(n_seg)): halvings of [0, n_seg) down to one segment */
+    while ((1ll << n) < (long long)n_seg)
+        ++n;
+    return n;
 }
 
 void pacx_k::pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
@@ -436,7 +565,24 @@ void pacx_k::pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_s
         hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, s, limit, final, result);
     }
 }
-
+void pacx_k::pacx_launch_rate_solve_segments(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
+                                             const int32_t *bits, const int32_t *steps, int n_seg,
+                                             const long long *seg_first, const long long *limit, int t_lo, int t_hi,
+                                             int32_t *budget, int32_t *n_bytes, uint8_t *capped,
+                                             pacx_rate_result *result, hipStream_t st)
+{
+    SolveState *s = (SolveState *)ws;
+    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi), search = pacx_segment_search_steps(n_seg);
+    const unsigned grid = (unsigned)((n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
+    pacx_launch_solve_init_segments(ws, n_seg, t_lo, t_hi, st);
+    for (int p = 0; p < pairs; ++p) {
+        const int final = p == pairs - 1;
+        if (grid)
+            hipLaunchKernelGGL(k_solve_pick_seg, dim3(grid), dim3(SOLVE_THREADS), 0, st, s, seg_first, n_seg, search,
+                               n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
+        pacx_launch_solve_step_segments(ws, n_seg, limit, final, result, st);
+    }
+}
 
 void pacx_k::pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                                      double target_nmr_db, double max_bits_per_sample, const double *lines,

@@ -108,8 +108,12 @@ struct pacx_handle {
     long long ws_thr_cf;              /* capacity of ws_thr (0 until the first pacx_nmr_batch) */
     double *ws_thr;                   /* [cf][1024] masked threshold, dB SPL     */
     uint32_t *ws_rate_status;         /* [cf] status words of pacx_rate_curve_batch's front end (capacity ws_thr_cf) */
-    long long ws_solve_n;             /* 1 once ws_solve exists                  */
-    char *ws_solve;                   /* pacx_rate_solve's state                 */
+    long long ws_solve_n;             /* states ws_solve holds: 1 for the plain solves, n_seg for the segmented */
+    char *ws_solve;                   /* [ws_solve_n] pacx_rate_solve's state    */
+    long long *ws_seg;                /* [3 ws_solve_n] a segmented solve's boundaries [n_seg + 1], then its limits [n_seg] */
+    long long seg_host_n;             /* segments the pinned staging copy holds  */
+    long long *seg_host;              /* [2 seg_host_n + 1] pinned: what ws_seg is uploaded from */
+    hipEvent_t ev_seg;                /* the last upload from seg_host           */
     std::string err;
 };
 
@@ -324,6 +328,10 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->ws_rate_status = nullptr;
     h->ws_solve_n = 0;
     h->ws_solve = nullptr;
+    h->ws_seg = nullptr;
+    h->seg_host_n = 0;
+    h->seg_host = nullptr;
+    h->ev_seg = nullptr;
     h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
     h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
     h->ws_lists = nullptr;
@@ -641,7 +649,8 @@ static GrowGroup grow_group(pacx_handle *h, int which)
         return {&h->ws_thr_cf, {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)},
                                 {(void **)&h->ws_rate_status, sizeof(uint32_t)}}};
     case GROW_SOLVE:
-        return {&h->ws_solve_n, {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()}}};
+        return {&h->ws_solve_n, {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()},
+                                 {(void **)&h->ws_seg, 3 * sizeof(long long)}}};
     default:
         return {&h->ws_index_bytes, {{(void **)&h->ws_index, 1}}};
     }
@@ -707,6 +716,12 @@ extern "C" void pacx_destroy(pacx_handle *h)
     free_ws(h);
     for (int which = 0; which < GROW_N; ++which)
         free_group(grow_group(h, which));
+    if (h->ev_seg) {
+        (void)hipEventSynchronize(h->ev_seg);
+        (void)hipEventDestroy(h->ev_seg);
+    }
+    if (h->seg_host)
+        (void)hipHostFree(h->seg_host);
     for (void *p : h->owned)
         (void)hipFree(p);
     delete h;
@@ -1870,6 +1885,70 @@ extern "C" int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const u
     return post_launch(h, what);
 }
 
+/* ---- what the solves share: the target range on the grid, and the segments of the segmented ones ---- */
+static int solve_range(pacx_handle *h, const char *what, double nmr_lo_db, double nmr_hi_db, int *t_lo, int *t_hi)
+{
+    const double bound = 1048576.0;
+    if (!std::isfinite(nmr_lo_db) || !std::isfinite(nmr_hi_db) || fabs(nmr_lo_db) > bound || fabs(nmr_hi_db) > bound)
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be finite (at most 2^20 dB in magnitude)");
+    const double lo64 = nmr_lo_db * PACX_RATE_TARGET_GRID, hi64 = nmr_hi_db * PACX_RATE_TARGET_GRID;
+    if (lo64 != floor(lo64) || hi64 != floor(hi64))
+        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be multiples of 1/64 dB");
+    if (lo64 > hi64)
+        return fail(h, PACX_E_ARG, std::string(what) + ": nmr_lo_db is above nmr_hi_db");
+    *t_lo = (int)lo64;
+    *t_hi = (int)hi64;
+    return PACX_OK;
+}
+
+/* the host arrays of a segmented solve (include/pacx.h, pacx_rate_solve_segments) */
+static int check_segments(pacx_handle *h, const char *what, int64_t n_cf, int64_t n_seg, const int64_t *seg_first,
+                          const int64_t *limit_bytes)
+{
+    if (n_seg < 1 || n_seg > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad segment count");
+    if (!seg_first || !limit_bytes)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (seg_first[0] != 0 || seg_first[n_seg] != n_cf)
+        return fail(h, PACX_E_ARG, std::string(what) + ": seg_first must run from 0 to n_cf");
+    for (int64_t s = 0; s < n_seg; ++s) {
+        if (seg_first[s + 1] < seg_first[s])
+            return fail(h, PACX_E_ARG, std::string(what) + ": seg_first decreases at segment " + std::to_string(s));
+        if (limit_bytes[s] < 0)
+            return fail(h, PACX_E_ARG, std::string(what) + ": negative limit for segment " + std::to_string(s));
+    }
+    return PACX_OK;
+}
+
+/* room for n_seg states, and the boundaries and limits in ws_seg: copied to the pinned staging buffer before this
+   returns (the caller's arrays are free again), from there on `st`.  The staging buffer is the handle's one, so the
+   upload before this one is waited for first; it has long run unless the caller queues segmented solves back to
+   back. */
+static int upload_segments(pacx_handle *h, int64_t n_seg, const int64_t *seg_first, const int64_t *limit_bytes,
+                           hipStream_t st)
+{
+    int rc = grow(h, GROW_SOLVE, n_seg);
+    if (rc)
+        return rc;
+    if (!h->ev_seg)
+        HIP_TRY(h, hipEventCreateWithFlags(&h->ev_seg, hipEventDisableTiming));
+    else
+        HIP_TRY(h, hipEventSynchronize(h->ev_seg));
+    if (n_seg > h->seg_host_n) {
+        if (h->seg_host)
+            HIP_TRY(h, hipHostFree(h->seg_host));
+        h->seg_host = nullptr;
+        h->seg_host_n = 0;
+        HIP_TRY(h, hipHostMalloc((void **)&h->seg_host, (size_t)(2 * n_seg + 1) * sizeof(long long), hipHostMallocDefault));
+        h->seg_host_n = n_seg;
+    }
+    memcpy(h->seg_host, seg_first, (size_t)(n_seg + 1) * sizeof(int64_t));
+    memcpy(h->seg_host + n_seg + 1, limit_bytes, (size_t)n_seg * sizeof(int64_t));
+    HIP_TRY(h, hipMemcpyAsync(h->ws_seg, h->seg_host, (size_t)(2 * n_seg + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipEventRecord(h->ev_seg, st));
+    return PACX_OK;
+}
+
 extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
                                const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db,
                                double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
@@ -1888,20 +1967,45 @@ extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_
         return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
     if (limit_bytes < 0)
         return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
-    const double bound = 1048576.0;
-    if (!std::isfinite(nmr_lo_db) || !std::isfinite(nmr_hi_db) || fabs(nmr_lo_db) > bound || fabs(nmr_hi_db) > bound)
-        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be finite (at most 2^20 dB in magnitude)");
-    const double lo64 = nmr_lo_db * PACX_RATE_TARGET_GRID, hi64 = nmr_hi_db * PACX_RATE_TARGET_GRID;
-    if (lo64 != floor(lo64) || hi64 != floor(hi64))
-        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be multiples of 1/64 dB");
-    if (lo64 > hi64)
-        return fail(h, PACX_E_ARG, std::string(what) + ": nmr_lo_db is above nmr_hi_db");
+    int t_lo, t_hi;
+    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = grow(h, GROW_SOLVE, 1);
     if (rc)
         return rc;
-    pacx_launch_rate_solve(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, limit_bytes, (int)lo64, (int)hi64,
+    pacx_launch_rate_solve(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, limit_bytes, t_lo, t_hi,
                            budget, n_bytes, capped, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_solve_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride,
+                                        const double *worst, const int32_t *bits, const int32_t *steps, int64_t n_seg,
+                                        const int64_t *seg_first, const int64_t *limit_bytes, double nmr_lo_db,
+                                        double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
+                                        pacx_rate_result *result, void *stream)
+{
+    const char *what = "pacx_rate_solve_segments";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (!result || (n_cf > 0 && (!worst || !bits || !steps || !budget || !n_bytes || !capped)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1)
+        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
+    int t_lo, t_hi;
+    int rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
+    if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = upload_segments(h, n_seg, seg_first, limit_bytes, (hipStream_t)stream)))
+        return rc;
+    pacx_launch_rate_solve_segments(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, (int)n_seg, h->ws_seg,
+                                    h->ws_seg + n_seg + 1, t_lo, t_hi, budget, n_bytes, capped, result,
+                                    (hipStream_t)stream);
     return post_launch(h, what);
 }
 
@@ -2005,20 +2109,43 @@ extern "C" int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, 
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
     if (limit_bytes < 0)
         return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
-    const double bound = 1048576.0;
-    if (!std::isfinite(nmr_lo_db) || !std::isfinite(nmr_hi_db) || fabs(nmr_lo_db) > bound || fabs(nmr_hi_db) > bound)
-        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be finite (at most 2^20 dB in magnitude)");
-    const double lo64 = nmr_lo_db * PACX_RATE_TARGET_GRID, hi64 = nmr_hi_db * PACX_RATE_TARGET_GRID;
-    if (lo64 != floor(lo64) || hi64 != floor(hi64))
-        return fail(h, PACX_E_ARG, std::string(what) + ": target bounds must be multiples of 1/64 dB");
-    if (lo64 > hi64)
-        return fail(h, PACX_E_ARG, std::string(what) + ": nmr_lo_db is above nmr_hi_db");
+    int t_lo, t_hi;
+    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     int rc = grow(h, GROW_SOLVE, 1);
     if (rc)
         return rc;
-    pacx_launch_band_solve(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, limit_bytes, (int)lo64, (int)hi64, bit_alloc,
+    pacx_launch_band_solve(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, limit_bytes, t_lo, t_hi, bit_alloc,
                            n_bytes, capped, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                        const int32_t *cap_alloc, int64_t n_seg, const int64_t *seg_first,
+                                        const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                                        int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+                                        void *stream)
+{
+    const char *what = "pacx_band_solve_segments";
+    if (!h)
+        return PACX_E_ARG;
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (!result || (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    int t_lo, t_hi;
+    int rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
+    if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if ((rc = upload_segments(h, n_seg, seg_first, limit_bytes, (hipStream_t)stream)))
+        return rc;
+    pacx_launch_band_solve_segments(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, (int)n_seg, h->ws_seg,
+                                    h->ws_seg + n_seg + 1, t_lo, t_hi, bit_alloc, n_bytes, capped, result,
+                                    (hipStream_t)stream);
     return post_launch(h, what);
 }
 

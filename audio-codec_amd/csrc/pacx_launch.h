@@ -145,6 +145,19 @@ void pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, c
 void pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st);
 void pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st);
 
+/* pacx_rate_solve_segments / pacx_band_solve_segments: one state per segment (ws holds n_seg times
+   pacx_rate_solve_ws_bytes()), seg_first int64 [n_seg + 1] and limit int64 [n_seg] in device memory, result [n_seg].
+   Init and step run one thread per segment; a pick finds a frame's segment in pacx_segment_search_steps(n_seg)
+   halvings.  The pairs are pacx_rate_solve's. */
+int pacx_segment_search_steps(int n_seg);
+void pacx_launch_solve_init_segments(void *ws, int n_seg, int t_lo, int t_hi, hipStream_t st);
+void pacx_launch_solve_step_segments(void *ws, int n_seg, const long long *limit, int final, pacx_rate_result *result,
+                                     hipStream_t st);
+void pacx_launch_rate_solve_segments(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
+                                     const int32_t *bits, const int32_t *steps, int n_seg, const long long *seg_first,
+                                     const long long *limit, int t_lo, int t_hi, int32_t *budget, int32_t *n_bytes,
+                                     uint8_t *capped, pacx_rate_result *result, hipStream_t st);
+
 /* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve (nmr float64
    [n_cf][band_stride][PACX_BAND_CAND], cap int32 [n_cf][8], cap_alloc int32 [n_cf][band_stride]; the solve uses
    pacx_rate_solve's state and number of pairs) and the sanitised copy of a caller's allocation (in == out allowed) */
@@ -158,6 +171,11 @@ void pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, c
 void pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_cf, const double *nmr, const int32_t *cap,
                             const int32_t *cap_alloc, long long limit, int t_lo, int t_hi, int32_t *bit_alloc,
                             int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, hipStream_t st);
+void pacx_launch_band_solve_segments(const PacxTables &T, void *ws, long long n_cf, const double *nmr,
+                                     const int32_t *cap, const int32_t *cap_alloc, int n_seg,
+                                     const long long *seg_first, const long long *limit, int t_lo, int t_hi,
+                                     int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+                                     hipStream_t st);
 void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
                                int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);
 

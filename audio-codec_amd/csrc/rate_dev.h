@@ -121,4 +121,22 @@ struct SolveState {
     unsigned long long total;                      /* of the pick in flight */
 };
 
+/* the segment of channel-frame cf, 0 <= cf < first[n_seg]: the s with first[s] <= cf < first[s + 1] (first[0] = 0,
+   non-decreasing, so an empty segment is never the answer).  `steps` halvings, pacx_segment_search_steps(n_seg) of
+   them: the trip count is the caller's argument, not the data's. */
+__device__ __forceinline__ int segment_of(const long long *__restrict__ first, int n_seg, int steps, long long cf)
+{
+    int lo = 0, hi = n_seg;                        /* first[lo] <= cf < first[hi] */
+    for (int it = 0; it < steps; ++it) {
+        const int mid = lo + (hi - lo) / 2;
+        if (hi - lo > 1) {
+            if (first[mid] <= cf)
+                lo = mid;
+            else
+                hi = mid;
+        }
+    }
+    return lo;
+}
+
 #endif

@@ -371,6 +371,52 @@ class Encoder:
         return {"target_nmr_db": t / float(_lib.RATE_TARGET_GRID), "met": met, "total_bytes": total, "budget": budget,
                 "n_bytes": n_bytes, "capped": capped.bool()}
 
+    @staticmethod
+    def _segments(what, seg_first, limit_bytes, n_cf):
+        """the host arrays of a segmented solve as int64, checked as the C side checks them"""
+        try:
+            first = np.ascontiguousarray(np.asarray(seg_first).astype(np.int64, casting="same_kind"))
+            limit = np.ascontiguousarray(np.asarray(limit_bytes).astype(np.int64, casting="same_kind"))
+        except TypeError:
+            raise ValueError(f"{what}: seg_first and limit_bytes are sequences of integers") from None
+        if first.ndim != 1 or limit.ndim != 1 or len(limit) < 1 or len(first) != len(limit) + 1:
+            raise ValueError(f"{what}: seg_first [n_seg + 1] and limit_bytes [n_seg], n_seg >= 1")
+        if first[0] != 0 or first[-1] != n_cf or (np.diff(first) < 0).any():
+            raise ValueError(f"{what}: seg_first starts at 0, never decreases and ends at n_cf = {n_cf}")
+        if (limit < 0).any():
+            raise ValueError(f"{what}: negative limit for segment {int(np.argmax(limit < 0))}")
+        return first, limit
+
+    def _segment_results(self, result):
+        """pacx_rate_result [n_seg] on the device -> target_nmr_db float64, met bool, total_bytes int64"""
+        res = result.cpu().numpy()
+        return {"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID),
+                "met": res[:, 1] != 0, "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]}
+
+    def rate_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """rate_solve with one limit and one target per stretch of consecutive channel-frames
+        (pacx_rate_solve_segments, include/pacx.h): segment s holds the channel-frames seg_first[s] ... seg_first[s + 1]
+        - 1 (it may be empty) and gets what rate_solve gives on that slice of the curve with limit_bytes[s].
+        seg_first [n_seg + 1] and limit_bytes [n_seg]: any integer sequences.  -> dict budget, n_bytes, capped as
+        rate_solve, and NumPy arrays target_nmr_db [n_seg] float64, met [n_seg] bool, total_bytes [n_seg] int64."""
+        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
+        n_cf, row = worst.shape
+        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
+                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
+            raise ValueError("rate_solve_segments: a curve as rate_curve returns it")
+        first, limit = self._segments("rate_solve_segments", seg_first, limit_bytes, n_cf)
+        budget = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
+        n_bytes = torch.zeros((n_cf,), dtype=torch.int32, device=self.device)
+        capped = torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)
+        result = torch.zeros((len(limit), 4), dtype=torch.int32, device=self.device)
+        self._call_rate("pacx_rate_solve_segments", ctypes.c_int64(n_cf), int(row), int(curve["sub_stride"]),
+                        _ptr(worst), _ptr(bits), _ptr(steps), ctypes.c_int64(len(limit)), first.ctypes.data,
+                        limit.ctypes.data, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(budget),
+                        _ptr(n_bytes), _ptr(capped), _ptr(result), self._stream())
+        out = {"budget": budget, "n_bytes": n_bytes, "capped": capped.bool()}
+        out.update(self._segment_results(result))
+        return out
+
     def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
         [n_cf, band_stride, 16] float64, candidate i = 0 bits for i = 0, else i + 1 (+inf beyond maxMantBits), band
@@ -428,6 +474,21 @@ class Encoder:
         res = result.cpu().numpy()
         out.update({"target_nmr_db": int(res[0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[1]),
                     "total_bytes": int(res.view(np.int64)[1]), "capped": out["capped"].bool()})
+        return out
+
+    def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """band_solve with one limit and one target per stretch of consecutive channel-frames
+        (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,
+        n_bytes, capped as band_solve, and NumPy arrays target_nmr_db, met, total_bytes [n_seg]."""
+        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_solve_segments")
+        first, limit = self._segments("band_solve_segments", seg_first, limit_bytes, n_cf)
+        result = torch.zeros((len(limit), 4), dtype=torch.int32, device=self.device)
+        self._call_rate("pacx_band_solve_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data, ctypes.c_double(nmr_lo_db),
+                        ctypes.c_double(nmr_hi_db), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
+                        _ptr(result), self._stream())
+        out["capped"] = out["capped"].bool()
+        out.update(self._segment_results(result))
         return out
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):

@@ -504,6 +504,23 @@ def _abr_limit(cp, view, head, kbps_per_channel, max_bytes):
     return limit
 
 
+def segment_limits(kbps_per_channel, n_channels, sample_rate, blocks, segment_hops):
+    """The segments of encode_stream_abr(segment_hops=...): `blocks` blocks cut into consecutive stretches of
+    segment_hops blocks, the last may be shorter.  -> int64 arrays (first_block, blocks, limit_bytes) per segment,
+    limit = floor(kbps * 1000 * nCh * blocks_in_segment * 1024 / sampleRate / 8): the whole-stream convention per
+    segment, so the limits sum to at most the whole-stream limit.  Pure arithmetic."""
+    hops, blocks = int(segment_hops), int(blocks)
+    if hops != segment_hops or hops < 1:
+        raise ValueError(f"segment_hops = {segment_hops!r}: a whole number of blocks, at least 1")
+    if not kbps_per_channel > 0:
+        raise ValueError("kbps_per_channel must be positive")
+    first = np.arange(0, max(blocks, 1), hops, dtype=np.int64)
+    count = np.minimum(first + hops, blocks) - first
+    limit = np.array([int(np.floor(kbps_per_channel * 1000.0 * n_channels * int(c) * 1024 / sample_rate / 8.0))
+                      for c in count], np.int64)
+    return first, count.astype(np.int64), limit
+
+
 def _abr_range(nmr_range_db):
     try:
         lo, hi = (float(v) for v in nmr_range_db)
@@ -517,18 +534,45 @@ def _abr_range(nmr_range_db):
 
 
 def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db,
-                       allocation="budget"):
+                       allocation="budget", segment_hops=None):
     """One curve, one solve + second pass per size.  sizes: list of (kbps_per_channel, max_bytes).
     -> list of (.pac bytes, solve dict, outputs of encode_pack_budget -- allocation "band": of encode_pack_alloc --,
-    body limit), the encoder"""
+    body limit), the encoder.  segment_hops: one segmented solve per size instead; the solve dict is
+    Encoder.rate_solve_segments' / band_solve_segments' plus "segments" (first_block, blocks, limit_bytes per segment),
+    the body limit the sum of the segments'."""
     band = _check_allocation(allocation)
     lo, hi = _abr_range(nmr_range_db)
+    if segment_hops is not None:
+        if any(b is not None for _, b in sizes):
+            raise ValueError("segment_hops goes with kbps_per_channel: max_bytes is the size of a file, not of a segment")
+        if any(k is None for k, _ in sizes):
+            raise ValueError("give exactly one of kbps_per_channel and max_bytes")
+        segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
     head = header_bytes(cp)
-    limits = [_abr_limit(cp, view, head, k, b) for k, b in sizes]
+    limits = [] if segment_hops is not None else [_abr_limit(cp, view, head, k, b) for k, b in sizes]
     curve = enc.band_curve(view, flags, cp.targetBitsPerSample) if band else \
         enc.rate_curve(view, flags, cp.targetBitsPerSample)
     done = []
+    if segment_hops is not None:
+        n_ch = cp.nChannels
+        for kbps, _ in sizes:
+            first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
+            seg_first = np.append(first, view.n_frames) * n_ch
+            sol = enc.band_solve_segments(curve, seg_first, seg_limit, lo, hi) if band else \
+                enc.rate_solve_segments(curve, seg_first, seg_limit, lo, hi)
+            if not sol["met"].all():
+                s = int(np.argmin(sol["met"]))
+                raise ValueError(f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) cannot be reached: "
+                                 f"its limit is {int(seg_limit[s])} bytes and at the highest target, {hi:g} dB, it "
+                                 f"takes {int(sol['total_bytes'][s])} bytes, the smallest size this range of targets "
+                                 f"gives")
+            sol["segments"] = {"first_block": first, "blocks": count, "limit_bytes": seg_limit}
+            out = enc.encode_pack_alloc(view, flags, sol["bit_alloc"]) if band else \
+                enc.encode_pack_budget(view, flags, sol["budget"])
+            body, total = enc.gather_body(out["payload"], out["n_bytes"])
+            done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, int(seg_limit.sum())))
+        return done, enc
     for limit in limits:
         sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
         if not sol["met"]:
@@ -544,7 +588,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
 
 def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
                       block_switching=False, header_samples=None, nmr_range_db=(-30, 30), use_vq=False, use_sbr=False,
-                      chunk_hops=None, n_lines=1024, allocation="budget"):
+                      chunk_hops=None, n_lines=1024, allocation="budget", segment_hops=None):
     """Whole-stream encode to an average bit rate -> .pac bytes: the best constant quality that fits a size.  One
     target NMR for the whole stream, the smallest on the grid of 1/64 dB in nmr_range_db (by the bisection of
     include/pacx.h, pacx_rate_solve) at which the stream of encode_stream_nmr(target) stays within the size; the
@@ -560,12 +604,19 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
     one batch, as encode_stream_nmr.
     allocation="band": the stream of encode_stream_nmr(target, allocation="band") instead, on Encoder.band_curve,
     band_solve and encode_pack_alloc; wherever no block reaches its cap the target found is the lowest on the grid
-    that fits (include/pacx.h)."""
+    that fits (include/pacx.h).
+    segment_hops=S (S >= 1, with kbps_per_channel only): an average bit rate per segment instead of per stream.  The
+    n + 2 blocks the driver writes are cut into consecutive segments of S blocks (the last may be shorter), every
+    segment gets the limit of segment_limits() -- the convention above for its own blocks -- and the lowest target on
+    the grid at which its own records fit (pacx_rate_solve_segments / pacx_band_solve_segments: one curve, one solve
+    for all segments, one second pass).  The records of a segment are those of encode_stream_nmr at that segment's
+    target.  ValueError when a segment cannot be reached; the message names the first such segment, its first block,
+    its limit and the bytes it takes at the highest target."""
     _check_allocation(allocation)
     if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
         raise NotImplementedError("average-bit-rate streams: scalar mantissas, nMDCTLines 1024, one batch")
     done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
-                                 block_switching, header_samples, nmr_range_db, allocation)
+                                 block_switching, header_samples, nmr_range_db, allocation, segment_hops)
     return done[0][0]
 
 

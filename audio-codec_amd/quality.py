@@ -337,12 +337,17 @@ def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=3
 
 
 def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
-                          block_switching=False, header_samples=None, nmr_range_db=(-30, 30), allocation="budget"):
+                          block_switching=False, header_samples=None, nmr_range_db=(-30, 30), allocation="budget",
+                          segment_hops=None):
     """pacfile.encode_stream_abr with a Report: -> (.pac bytes, Report, info).  A list for kbps_per_channel or for
     max_bytes gives a list of such triples, all solved from one rate curve.  info, for the n + 2 blocks the driver
     submits, is encode_stream_to_nmr's (budget, bit_alloc, capped, written, kbps_per_channel: achieved, allocation) and
       target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
-      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written)."""
+      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written).
+    segment_hops (pacfile.encode_stream_abr; with a list of rates: one curve, one segmented solve per rate): info gains
+      segments       dict of arrays per segment: first_block, blocks, limit_bytes, total_bytes, target_nmr_db;
+    target_nmr_db becomes float64 [blocks], every block's segment's target, limit_bytes and total_bytes the sums over
+    the segments."""
     from . import pacfile
     many = isinstance(kbps_per_channel, (list, tuple)) or isinstance(max_bytes, (list, tuple))
     if many:
@@ -352,17 +357,21 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
     else:
         sizes = [(kbps_per_channel, max_bytes)]
     done, enc = pacfile._encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching,
-                                           header_samples, nmr_range_db, allocation)
+                                           header_samples, nmr_range_db, allocation, segment_hops)
     n_ch = np.asarray(pcm).shape[1]
     res = []
     for data, sol, out, limit in done:
         n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
         n_blocks = len(n_bytes)
+        target, total, segments = sol["target_nmr_db"], sol["total_bytes"], sol.get("segments")
+        if segments is not None:
+            segments = dict(segments, total_bytes=total, target_nmr_db=target)
+            target, total = np.repeat(target, segments["blocks"]), int(total.sum())
         info = {
             "allocation": allocation,
-            "target_nmr_db": sol["target_nmr_db"],
+            "target_nmr_db": target,
             "limit_bytes": limit,
-            "total_bytes": sol["total_bytes"],
+            "total_bytes": total,
             "n_bytes": sol["n_bytes"].cpu().numpy().reshape(n_blocks, n_ch),
             "bit_alloc": out["bit_alloc"].cpu().numpy().reshape(n_blocks, n_ch, -1),
             "capped": sol["capped"].cpu().numpy().reshape(n_blocks, n_ch),
@@ -372,6 +381,8 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
         }
         if "budget" in sol:
             info["budget"] = sol["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB)
+        if segments is not None:
+            info["segments"] = segments
         res.append((data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info))
     return res if many else res[0]
 

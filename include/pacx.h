@@ -881,6 +881,52 @@ int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, const int32
                     int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc, int32_t *n_bytes,
                     uint8_t *capped, pacx_rate_result *result, void *stream);
 
+/* ---- one target per stretch of a stream: the two solves, segment by segment ---- */
+
+/*
+ * pacx_rate_solve and pacx_band_solve know one size constraint: the whole batch within limit_bytes at one target.
+ * These two take one limit per segment -- the segments of a stream that must each fit a size, or the items of a
+ * batch that must not pay for one another -- and find one target per segment, in the same number of launches.
+ *
+ * Segments are stretches of consecutive channel-frames (cf = block * nCh + ch as everywhere; a caller who means
+ * blocks multiplies by the channel count):
+ *
+ *   n_seg:        >= 1, bounded like n_cf
+ *   seg_first:    int64 [n_seg + 1] in HOST memory: seg_first[0] = 0, non-decreasing, seg_first[n_seg] = n_cf;
+ *                 segment s holds the channel-frames [seg_first[s], seg_first[s + 1]) and may be empty
+ *   limit_bytes:  int64 [n_seg] in HOST memory, each >= 0 (the plain solves take their limit by value too)
+ *   result (out): pacx_rate_result [n_seg] in device memory
+ *
+ * The contract: result[s] and the per-cf outputs in [seg_first[s], seg_first[s + 1]) are those of pacx_rate_solve /
+ * pacx_band_solve called with that slice of every array and limit_bytes[s] -- grid, bounds (all segments share
+ * nmr_lo_db and nmr_hi_db), decision, the met = 0 rule and the caveats about totals that are not monotone are the
+ * plain solves', per segment.  An empty segment gives t = t_lo, met = 1, total = 0, as a plain solve with n_cf = 0.
+ *
+ * Both host arrays are checked on the host, copied before the call returns (the caller may free them at once) and
+ * uploaded on `stream` through a pinned buffer of the handle's; a call waits for the upload of the segmented solve
+ * before it on the same handle, and for nothing else.  The call is therefore not meant for stream capture into a
+ * graph; its callers read the result back anyway.  On the device one state per segment lives in the handle beside
+ * the boundaries: init and step kernels run one thread per segment, the pick kernels are the plain solves' per-frame
+ * work with the target taken from the frame's segment (found in at most ceil(log2(n_seg + 1)) halvings of the
+ * boundaries) and the frame's bytes added to that segment's total: reduced on chip, then one 64-bit integer
+ * atomicAdd per workgroup whose frames lie in one segment, one per segment present (pacx_band_solve_segments: per
+ * wave) in a workgroup that straddles a boundary.  Frames of a segment whose answer is known are skipped until the
+ * last pick, which writes the outputs.  2 + ceil(log2(t_hi - t_lo + 2)) pairs whatever the data, no host wait.
+ * A plain solve on the same handle afterwards behaves as before.
+ *
+ * Other arguments, PACX_E_UNSUPPORTED and PACX_E_ARG: as pacx_rate_solve / pacx_band_solve; PACX_E_ARG also for
+ * n_seg < 1, a null seg_first or limit_bytes, boundaries that do not start at 0, decrease or do not end at n_cf, and
+ * a negative limit.
+ */
+int pacx_rate_solve_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                             const int32_t *bits, const int32_t *steps, int64_t n_seg, const int64_t *seg_first,
+                             const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *budget,
+                             int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream);
+int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                             const int32_t *cap_alloc, int64_t n_seg, const int64_t *seg_first,
+                             const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc,
+                             int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream);
+
 /*
  * The second pass: pacx_encode_pack_budget_batch with the allocation of every band given by the caller instead of a
  * budget per unit.  bit_alloc_in: int32 [n_cf][band_stride] (may be the bit_alloc output itself); a value below 2
