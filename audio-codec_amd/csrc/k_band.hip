@@ -13,11 +13,12 @@
  *                     what its bands ask for.
  *   k_band_pick       works on the arrays alone: one wave per channel-frame, a lane per (unit, band) pair scans the
  *                     band's sizes in ascending order for the first at or below the target; the unit sums go through
- *                     LDS, the frame's bits through the wave.  For a solve it adds the body total: integer sums, one
- *                     64-bit atomicAdd per workgroup, and k_rate.hip's k_solve_init / k_solve_step decide on it.
- *   k_band_pick_seg   pacx_band_solve_segments: the same frame work (band_frame) with one SolveState per stretch of
- *                     consecutive channel-frames; the wave finds its frame's segment in the uploaded boundaries
- *                     (segment_of, rate_dev.h), k_rate.hip's k_solve_init_seg / k_solve_step_seg decide per segment.
+ *                     LDS, the frame's bits through the wave (band_frame).
+ *   k_band_pick_seg   pacx_band_solve / pacx_band_solve_segments: the same frame work with one SolveState per stretch of
+ *                     consecutive channel-frames (the whole stream is one stretch); the wave finds its frame's segment
+ *                     in the boundaries (segment_of, rate_dev.h) and adds the frame's bytes to that segment's total:
+ *                     integer sums, one 64-bit atomicAdd per workgroup and segment present.  k_rate.hip's k_solve_init /
+ *                     k_solve_step decide per segment.
  *   k_band_sanitize   a caller's allocation made representable (below 2 -> 0, above maxMantBits -> maxMantBits), and
  *                     an all-zero allocation for a channel-frame whose record would leave PACX_PAYLOAD_STRIDE.
  *
@@ -241,47 +242,25 @@ __device__ __forceinline__ unsigned long long band_frame(const PacxTables &T, lo
     return nby > 0 ? (unsigned long long)nby + 4ull : 0ull;
 }
 
-/* band_frame for one channel-frame per wave.  s == nullptr: pacx_band_pick at `target`, the outputs are written.
-   Else a pick of the solve at the target in flight; final: the last launch, at the target found, which also writes
-   the outputs. */
-__global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, SolveState *__restrict__ s, long long n_cf,
-                                                           double target, const double *__restrict__ nmr,
+/* band_frame for one channel-frame per wave at `target` (pacx_band_pick): the outputs are written */
+__global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, long long n_cf, double target,
+                                                           const double *__restrict__ nmr,
                                                            const int32_t *__restrict__ cap,
-                                                           const int32_t *__restrict__ cap_alloc, int final,
+                                                           const int32_t *__restrict__ cap_alloc,
                                                            int32_t *__restrict__ bit_alloc, int32_t *__restrict__ n_bytes,
                                                            uint8_t *__restrict__ capped)
 {
     __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
-    __shared__ unsigned long long part[PICK_WAVES];
-    if (s) {
-        if (s->done && !final)
-            return;                                /* the answer is known: this launch does nothing */
-        target = (double)s->mid / 64.0;
-    }
-    const bool write = !s || final;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int w = threadIdx.x >> 6;
     const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
-    unsigned long long mine = 0ull;
     if (cf < n_cf)                                 /* wave-uniform */
-        mine = band_frame(T, cf, target, nmr, cap, cap_alloc, write, bit_alloc, n_bytes, capped, unit_sum[w],
-                          unit_miss[w]);
-    if (!s)
-        return;
-    if (lane == 0)
-        part[w] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long all = 0ull;
-        for (int i = 0; i < PICK_WAVES; ++i)
-            all += part[i];
-        if (all)
-            atomicAdd(&s->total, all);
-    }
+        band_frame(T, cf, target, nmr, cap, cap_alloc, true, bit_alloc, n_bytes, capped, unit_sum[w], unit_miss[w]);
 }
 
-/* k_band_pick with a state per segment (pacx_band_solve_segments): the wave takes the target of its frame's segment
-   and adds to that segment's total; a frame whose segment is done is not scanned before the last launch.  A
-   workgroup whose four frames lie in one segment adds once, one that straddles a boundary once per wave. */
+/* k_band_pick as a pick of the solve, with a state per segment: the wave takes the target its frame's segment has in
+   flight and adds to that segment's total; a frame whose segment is done is not scanned before the last launch.
+   final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose four frames lie in
+   one segment (every workgroup of a whole-stream solve) adds once, one that straddles a boundary once per wave. */
 __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, SolveState *__restrict__ s,
                                                                const long long *__restrict__ seg_first, int n_seg,
                                                                int search_steps, long long n_cf,
@@ -295,7 +274,9 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, So
     __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
     __shared__ unsigned long long part[PICK_WAVES];
     __shared__ int seg_of[PICK_WAVES];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    /* the wave's index in a scalar register: its frame, the boundaries searched and its segment's state are then read
+       once per wave through the scalar cache, not by every lane (two vector loads less at the head of every wave) */
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
     int seg = -1;                                  /* past the end: no segment, nothing to add */
     unsigned long long mine = 0ull;
@@ -396,45 +377,20 @@ void pacx_k::pacx_launch_band_pick(const PacxTables &T, long long n_cf, double t
 {
     if (n_cf <= 0)
         return;
-    const unsigned grid = (unsigned)((n_cf + PICK_THREADS / 64 - 1) / (PICK_THREADS / 64));
-    hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)nullptr, n_cf, target, nmr,
-                       cap, cap_alloc, 1, bit_alloc, n_bytes, capped);
-}
-
-void pacx_k::pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_cf, const double *nmr, const int32_t *cap,
-                                    const int32_t *cap_alloc, long long limit, int t_lo, int t_hi, int32_t *bit_alloc,
-                                    int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, hipStream_t st)
-{
-    SolveState *s = (SolveState *)ws;
-    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi);
-    const unsigned grid = (unsigned)((n_cf + PICK_THREADS / 64 - 1) / (PICK_THREADS / 64));
-    pacx_launch_solve_init(ws, t_lo, t_hi, st);
-    for (int p = 0; p < pairs; ++p) {
-        const int final = p == pairs - 1;
-        if (grid)
-            hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, s, n_cf, 0.0, nmr, cap, cap_alloc,
-                               final, bit_alloc, n_bytes, capped);
-        pacx_launch_solve_step(ws, limit, final, result, st);
-    }
-}
-
-void pacx_k::pacx_launch_band_solve_segments(const PacxTables &T, void *ws, long long n_cf, const double *nmr,
-                                             const int32_t *cap, const int32_t *cap_alloc, int n_seg,
-                                             const long long *seg_first, const long long *limit, int t_lo, int t_hi,
-                                             int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
-                                             pacx_rate_result *result, hipStream_t st)
-{
-    SolveState *s = (SolveState *)ws;
-    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi), search = pacx_segment_search_steps(n_seg);
     const unsigned grid = (unsigned)((n_cf + PICK_WAVES - 1) / PICK_WAVES);
-    pacx_launch_solve_init_segments(ws, n_seg, t_lo, t_hi, st);
-    for (int p = 0; p < pairs; ++p) {
-        const int final = p == pairs - 1;
-        if (grid)
-            hipLaunchKernelGGL(k_band_pick_seg, dim3(grid), dim3(PICK_THREADS), 0, st, T, s, seg_first, n_seg, search,
-                               n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
-        pacx_launch_solve_step_segments(ws, n_seg, limit, final, result, st);
-    }
+    hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, n_cf, target, nmr, cap, cap_alloc, bit_alloc,
+                       n_bytes, capped);
+}
+
+void pacx_k::pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolve &v, const double *nmr,
+                                             const int32_t *cap, const int32_t *cap_alloc, int32_t *bit_alloc,
+                                             int32_t *n_bytes, uint8_t *capped, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((v.n_cf + PICK_WAVES - 1) / PICK_WAVES);
+    pacx_solve_drive(v, st, [&](int search, int final) {
+        hipLaunchKernelGGL(k_band_pick_seg, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)v.ws, v.seg, v.n_seg,
+                           search, v.n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
+    });
 }
 
 void pacx_k::pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,

@@ -16,14 +16,15 @@
  *   k_rate_curve<M>    k_rate_search's units, preamble (rate_unit) and evaluation (rate_eval), every step j = 0 ... J
  *                      instead of a bisection: worst[j] = max_b NMR_b and bits[j] = what pack_body writes for the
  *                      allocation of budget 32 j (pacx_rate_curve_batch).
- *   k_solve_pick       pacx_rate_solve: one channel-frame per thread picks the budget of each of its units from the
- *                      curve at the target in flight, sums the frame's bytes; one 64-bit atomicAdd per workgroup.
- *   k_solve_step       one thread: the bisection's decision on that total.  The host enqueues a fixed number of
- *                      pick / step pairs and waits for none; pairs after the answer is known do nothing.
- *   k_solve_pick_seg, k_solve_init_seg, k_solve_step_seg
- *                      pacx_rate_solve_segments: the same frame work (solve_frame) and the same decision (solve_step)
- *                      with one SolveState per segment; a frame finds its segment in the uploaded boundaries
- *                      (segment_of, rate_dev.h) and adds to that segment's total.
+ *   k_solve_pick       pacx_rate_solve / pacx_rate_solve_segments: one channel-frame per thread finds its segment in
+ *                      the boundaries (segment_of, rate_dev.h), picks the budget of each of its units from the curve
+ *                      at the target its segment has in flight and sums the frame's bytes; one 64-bit atomicAdd per
+ *                      workgroup and segment present.
+ *   k_solve_init, k_solve_step
+ *                      one thread per segment: a SolveState each, and the bisection's decision on the segment's total.
+ *                      The host enqueues a fixed number of pick / step pairs and waits for none; pairs after a
+ *                      segment's answer is known do nothing for it.  The whole-stream solve is the one-segment case:
+ *                      its table {0, n_cf, limit} is written by k_solve_init, not uploaded.
  * RateLds, RateUnit, rate_unit, wave_sum and SolveState live in rate_dev.h: k_band.hip shares them.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
@@ -259,8 +260,8 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
         atomicOr(&status[cf], ((cap & 1) ? 4u : 0u) | ((cap & 2) ? 16u : 0u));   /* ALLOC_CAP, GUARD */
 }
 
-/* ---- the solve of pacx_rate_solve (include/pacx.h): one target for the whole stream, on the stored curves; and of
-   pacx_rate_solve_segments: one target per stretch of consecutive channel-frames, a SolveState each ---- */
+/* ---- the solve of pacx_rate_solve_segments (include/pacx.h): one target per stretch of consecutive channel-frames,
+   on the stored curves, a SolveState each; pacx_rate_solve's whole stream is one such stretch ---- */
 constexpr int SOLVE_THREADS = 256;
 constexpr int SOLVE_MAX_LOOKUP = 12;               /* 1 + ceil(log2(J + 1)) for J < 2048, as RATE_MAX_EVAL */
 
@@ -269,20 +270,8 @@ __device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either 
     return (a - (a < 0 ? 1 : 0)) / 2;
 }
 
-/* the state of a solve before its first pick */
-__device__ __forceinline__ void solve_init(SolveState *s, int t_lo, int t_hi)
-{
-    s->lo = t_lo - 1;
-    s->hi = t_hi;
-    s->mid = t_hi;
-    s->phase = 0;
-    s->done = 0;
-    s->met = 0;
-    s->total = 0ull;
-}
-
-/* the decision of include/pacx.h on the total the pick before it left, the only one: k_solve_step takes it for the
-   stream, k_solve_step_seg for every segment.  final: write the result */
+/* the decision of include/pacx.h on the total the pick before it left, the only one: k_solve_step takes it for every
+   segment.  final: write the result */
 __device__ __forceinline__ void solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
 {
     const unsigned long long total = s->total;
@@ -316,17 +305,19 @@ __device__ __forceinline__ void solve_step(SolveState *s, long long limit, int f
     }
 }
 
-__global__ void k_solve_init(SolveState *s, int t_lo, int t_hi)
-{
-    solve_init(s, t_lo, t_hi);
-}
-
-/* one thread per segment */
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_init_seg(SolveState *s, int n_seg, int t_lo, int t_hi)
+/* one thread per segment: the state of a solve before its first pick.  one: the whole-stream solve's table, seg_first
+   {0, n_cf} and its limit, written here on the stream instead of uploaded (n_seg == 1); nullptr: the table is in place */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_init(SolveState *s, int n_seg, int t_lo, int t_hi,
+                                                             long long *one, long long n_cf, long long limit)
 {
     const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
     if (i < n_seg)
-        solve_init(s + i, t_lo, t_hi);
+        s[i] = SolveState{t_lo - 1, t_hi, t_hi, 0, 0, 0, 0ull};      /* lo, hi, mid, phase, done, met, total */
+    if (one && i == 0) {
+        one[0] = 0;
+        one[1] = n_cf;
+        one[2] = limit;
+    }
 }
 
 /* pick(unit, T) of every unit of one channel-frame, the only one: the look-ups in the curve, the frame's bytes and,
@@ -394,41 +385,20 @@ __device__ __forceinline__ unsigned long long solve_block_sum(unsigned long long
     return all;
 }
 
-/* one channel-frame per thread (solve_frame), the sum of the frames' bytes over the workgroup and one atomicAdd.
-   final: the last launch, at the target found, which also writes the outputs. */
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s, long long n_cf, int row,
-                                                             int sub_stride, const double *__restrict__ worst,
+/* one channel-frame per thread (solve_frame) with a state per segment: every frame takes the target of its segment's
+   state and adds to that segment's total.  A frame whose segment is done does no look-ups before the last launch.
+   final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose frames lie in one
+   segment (every workgroup of a whole-stream solve) sums them through the waves and adds once; one that straddles
+   boundaries sums the runs of equal segments in LDS (the frames of a segment are consecutive) and adds once per
+   segment present. */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s,
+                                                             const long long *__restrict__ seg_first, int n_seg,
+                                                             int search_steps, long long n_cf, int row, int sub_stride,
+                                                             const double *__restrict__ worst,
                                                              const int32_t *__restrict__ bits,
                                                              const int32_t *__restrict__ steps, int final,
                                                              int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
                                                              uint8_t *__restrict__ capped)
-{
-    __shared__ unsigned long long part[SOLVE_THREADS / 64];
-    if (s->done && !final)
-        return;                                    /* the answer is known: this launch does nothing */
-    const double target = (double)s->mid / 64.0;
-    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
-    unsigned long long mine = 0ull;
-    if (cf < n_cf)
-        mine = solve_frame(cf, target, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
-    const unsigned long long all = solve_block_sum(mine, part);
-    if (threadIdx.x == 0 && all)
-        atomicAdd(&s->total, all);
-}
-
-/* k_solve_pick with a state per segment (pacx_rate_solve_segments): every frame takes the target of its segment's
-   state and adds to that segment's total.  A frame whose segment is done does no look-ups before the last launch.
-   A workgroup whose frames lie in one segment adds once, as k_solve_pick; one that straddles boundaries sums the
-   runs of equal segments in LDS (the frames of a segment are consecutive) and adds once per segment present. */
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick_seg(SolveState *__restrict__ s,
-                                                                 const long long *__restrict__ seg_first, int n_seg,
-                                                                 int search_steps, long long n_cf, int row,
-                                                                 int sub_stride, const double *__restrict__ worst,
-                                                                 const int32_t *__restrict__ bits,
-                                                                 const int32_t *__restrict__ steps, int final,
-                                                                 int32_t *__restrict__ budget,
-                                                                 int32_t *__restrict__ n_bytes,
-                                                                 uint8_t *__restrict__ capped)
 {
     __shared__ unsigned long long part[SOLVE_THREADS / 64];
     __shared__ unsigned long long run[SOLVE_THREADS];
@@ -471,16 +441,10 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick_seg(SolveState *__
         atomicAdd(&s[seg].total, mine);
 }
 
-/* one thread: solve_step on the total the pick before it left */
-__global__ void k_solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
-{
-    solve_step(s, limit, final, result);
-}
-
 /* one thread per segment: solve_step with the segment's limit; final: result[seg] */
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_step_seg(SolveState *s, int n_seg,
-                                                                 const long long *__restrict__ limit, int final,
-                                                                 pacx_rate_result *result)
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_step(SolveState *s, int n_seg,
+                                                             const long long *__restrict__ limit, int final,
+                                                             pacx_rate_result *result)
 {
     const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
     if (i < n_seg)
@@ -500,29 +464,18 @@ int pacx_k::pacx_rate_solve_pairs(int t_lo, int t_hi)
     return 2 + n;
 }
 
-/* the solve's two one-thread kernels for a solve whose pick lives elsewhere (k_band.hip) */
-void pacx_k::pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st)
+/* the solve's init and step, one thread per segment, for pacx_solve_drive (pacx_launch.h) */
+void pacx_k::pacx_launch_solve_init_segments(const PacxSolve &v, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_solve_init, dim3(1), dim3(1), 0, st, (SolveState *)ws, t_lo, t_hi);
+    hipLaunchKernelGGL(k_solve_init, dim3((unsigned)((v.n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)), dim3(SOLVE_THREADS),
+                       0, st, (SolveState *)v.ws, v.n_seg, v.t_lo, v.t_hi, v.one_limit ? v.seg : nullptr, v.n_cf,
+                       v.one_limit ? *v.one_limit : 0ll);
 }
 
-void pacx_k::pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st)
+void pacx_k::pacx_launch_solve_step_segments(const PacxSolve &v, int final, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, (SolveState *)ws, limit, final, result);
-}
-
-/* and the same pair with a state per segment: one thread per segment */
-void pacx_k::pacx_launch_solve_init_segments(void *ws, int n_seg, int t_lo, int t_hi, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_solve_init_seg, dim3((unsigned)((n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)),
-                       dim3(SOLVE_THREADS), 0, st, (SolveState *)ws, n_seg, t_lo, t_hi);
-}
-
-void pacx_k::pacx_launch_solve_step_segments(void *ws, int n_seg, const long long *limit, int final,
-                                             pacx_rate_result *result, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_solve_step_seg, dim3((unsigned)((n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)),
-                       dim3(SOLVE_THREADS), 0, st, (SolveState *)ws, n_seg, limit, final, result);
+    hipLaunchKernelGGL(k_solve_step, dim3((unsigned)((v.n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)), dim3(SOLVE_THREADS),
+                       0, st, (SolveState *)v.ws, v.n_seg, v.seg + v.n_seg + 1, final, v.result);
 }
 
 int pacx_k::pacx_segment_search_steps(int n_seg)
@@ -548,40 +501,15 @@ void pacx_k::pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, i
                            worst, bits, steps);
 }
 
-void pacx_k::pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
-                                    const int32_t *bits, const int32_t *steps, long long limit, int t_lo, int t_hi,
-                                    int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
-                                    hipStream_t st)
+void pacx_k::pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int sub_stride, const double *worst,
+                                             const int32_t *bits, const int32_t *steps, int32_t *budget,
+                                             int32_t *n_bytes, uint8_t *capped, hipStream_t st)
 {
-    SolveState *s = (SolveState *)ws;
-    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi);
-    const unsigned grid = (unsigned)((n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
-    hipLaunchKernelGGL(k_solve_init, dim3(1), dim3(1), 0, st, s, t_lo, t_hi);
-    for (int p = 0; p < pairs; ++p) {
-        const int final = p == pairs - 1;
-        if (grid)
-            hipLaunchKernelGGL(k_solve_pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, s, n_cf, row, sub_stride, worst,
-                               bits, steps, final, budget, n_bytes, capped);
-        hipLaunchKernelGGL(k_solve_step, dim3(1), dim3(1), 0, st, s, limit, final, result);
-    }
-}
-void pacx_k::pacx_launch_rate_solve_segments(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
-                                             const int32_t *bits, const int32_t *steps, int n_seg,
-                                             const long long *seg_first, const long long *limit, int t_lo, int t_hi,
-                                             int32_t *budget, int32_t *n_bytes, uint8_t *capped,
-                                             pacx_rate_result *result, hipStream_t st)
-{
-    SolveState *s = (SolveState *)ws;
-    const int pairs = pacx_rate_solve_pairs(t_lo, t_hi), search = pacx_segment_search_steps(n_seg);
-    const unsigned grid = (unsigned)((n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
-    pacx_launch_solve_init_segments(ws, n_seg, t_lo, t_hi, st);
-    for (int p = 0; p < pairs; ++p) {
-        const int final = p == pairs - 1;
-        if (grid)
-            hipLaunchKernelGGL(k_solve_pick_seg, dim3(grid), dim3(SOLVE_THREADS), 0, st, s, seg_first, n_seg, search,
-                               n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
-        pacx_launch_solve_step_segments(ws, n_seg, limit, final, result, st);
-    }
+    const unsigned grid = (unsigned)((v.n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
+    pacx_solve_drive(v, st, [&](int search, int final) {
+        hipLaunchKernelGGL(k_solve_pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.seg, v.n_seg,
+                           search, v.n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
+    });
 }
 
 void pacx_k::pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,

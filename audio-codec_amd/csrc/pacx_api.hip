@@ -109,8 +109,9 @@ struct pacx_handle {
     double *ws_thr;                   /* [cf][1024] masked threshold, dB SPL     */
     uint32_t *ws_rate_status;         /* [cf] status words of pacx_rate_curve_batch's front end (capacity ws_thr_cf) */
     long long ws_solve_n;             /* states ws_solve holds: 1 for the plain solves, n_seg for the segmented */
-    char *ws_solve;                   /* [ws_solve_n] pacx_rate_solve's state    */
-    long long *ws_seg;                /* [3 ws_solve_n] a segmented solve's boundaries [n_seg + 1], then its limits [n_seg] */
+    char *ws_solve;                   /* [ws_solve_n] the solve's state per segment */
+    long long *ws_seg;                /* [3 ws_solve_n] a solve's boundaries [n_seg + 1], then its limits [n_seg]: uploaded by
+                                         the segmented solves, written by the init kernel for the plain ones */
     long long seg_host_n;             /* segments the pinned staging copy holds  */
     long long *seg_host;              /* [2 seg_host_n + 1] pinned: what ws_seg is uploaded from */
     hipEvent_t ev_seg;                /* the last upload from seg_host           */
@@ -996,6 +997,17 @@ struct EncodeStep {
         pacx_launch_front_long(h->T, v, n_cf, h->ws_lines, overall_scale, status, h->ws_peaks, h->ws_npeaks,
                                h->ws_nkept, st);
     }
+    /* lines, SMRs and, with thr, the masked threshold of every line, all on one stream: frame lists, MDCT, side
+       chain, mask */
+    void front(double *thr, hipStream_t st) const
+    {
+        if (mixed)
+            lists(st);
+        mdct(st);
+        side(0, false, st);
+        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr, thr,
+                         h->n_cu, list_long, list_short, counts, nullptr, st);
+    }
     /* tail: the outputs of the work fused into the long mask kernel, or nullptr */
     void mask(int part, const MaskTail *tail, hipStream_t st) const
     {
@@ -1701,12 +1713,7 @@ extern "C" int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t 
        workspace and are not used: the noise is taken against the scales the decoder read), the maskers, then the
        masked threshold of every line */
     const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, nullptr);
-    if (s.mixed)
-        s.lists(st);
-    s.mdct(st);
-    s.side(0, false, st);
-    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    s.front(h->ws_thr, st);
     pacx_launch_nmr(h->T, frame_flags, s.n_ch, n_cf, h->ws_lines, dec_lines, overall_scale, h->ws_thr, status, noise, mask,
                     nmr_db, st);
     return post_launch(h, "pacx_nmr_batch");
@@ -1757,13 +1764,12 @@ static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *fr
         HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
     }
     const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
-    if (s.mixed)
-        s.lists(st);
-    s.mdct(st);
-    if (!given) {
-        s.side(0, false, st);
-        pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                         search ? h->ws_thr : nullptr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
+    if (given) {
+        if (s.mixed)
+            s.lists(st);
+        s.mdct(st);
+    } else {
+        s.front(search ? h->ws_thr : nullptr, st);
     }
     if (given)
         pacx_launch_band_sanitize(h->T, frame_flags, s.n_ch, n_cf, alloc_in, bit_alloc, status, PACX_PAYLOAD_STRIDE, st);
@@ -1838,11 +1844,33 @@ extern "C" int pacx_rate_curve_layout(const pacx_handle *h, double max_bits_per_
     return PACX_OK;
 }
 
-extern "C" int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
-                                     double max_bits_per_sample, int32_t row, double *worst, int32_t *bits,
-                                     int32_t *steps, void *stream)
+/* the longest record a pick can give at this cap rate, in bytes: per unit the header bits and at most
+   min(32 J, maxMantBits x lines) mantissa bits (a unit within its cap, or BitAlloc's at that budget) */
+static long long band_record_bound(const PacxTables &T, double max_bps)
 {
-    const char *what = "pacx_rate_curve_batch";
+    int max_mant = 1 << T.n_mant_size_bits;
+    if (max_mant > 16)
+        max_mant = 16;
+    long long worst = 0;
+    for (int sh = 0; sh < 2; ++sh)
+        for (int lon = 0; lon < 2; ++lon) {
+            const int nb = sh ? T.nb_short : T.nb_long, m = sh ? PACX_M_SHORT : PACX_M_LONG;
+            const long long all = (long long)max_mant * m;
+            const long long j = pacx_rate_steps(max_bps, m, sh, lon, T.n_scale_bits, T.n_mant_size_bits, nb);
+            const long long mant = 32 * j < all ? 32 * j : all;
+            const long long unit = T.n_scale_bits + (long long)nb * (T.n_mant_size_bits + T.n_scale_bits) + mant;
+            const long long bytes = ((sh ? PACX_SUB : 1) * unit + 4 + 7) >> 3;
+            worst = bytes > worst ? bytes : worst;
+        }
+    return worst;
+}
+
+/* pacx_rate_curve_batch and pacx_band_curve_batch: the checks and the front end of pacx_encode_pack_nmr_batch (overall
+   scales and status words stay in the workspace), then the curve kernel of one of them.  band: nmr, cap, cap_alloc;
+   else worst, bits, steps with rows of `row` */
+static int curve_batch(pacx_handle *h, bool band, const char *what, const pacx_pcm *in, const uint8_t *frame_flags,
+                       double max_bits_per_sample, int32_t row, double *curve, int32_t *a, int32_t *b, void *stream)
+{
     if (!h)
         return PACX_E_ARG;
     if (h->T.use_vq || h->T.use_sbr)
@@ -1855,37 +1883,56 @@ extern "C" int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const u
     int rc = check_pcm(h, in, &v, &fast, &n_cf);
     if (rc)
         return rc;
-    if (!worst || !bits || !steps)
+    if (!curve || !a || !b)
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    int need, sub_stride;
-    rate_curve_layout(h->T, max_bits_per_sample, &need, &sub_stride);
-    if (row < need)
-        return fail(h, PACX_E_ARG, std::string(what) + ": row is smaller than pacx_rate_curve_layout's (" +
-                                       std::to_string(need) + ")");
+    int need = 0, sub_stride = 0;
+    if (band) {
+        if (band_record_bound(h->T, max_bits_per_sample) > PACX_PAYLOAD_STRIDE)
+            return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": a record at this cap rate would not fit pacx_payload_stride");
+    } else {
+        rate_curve_layout(h->T, max_bits_per_sample, &need, &sub_stride);
+        if (row < need)
+            return fail(h, PACX_E_ARG, std::string(what) + ": row is smaller than pacx_rate_curve_layout's (" +
+                                           std::to_string(need) + ")");
+    }
     if (n_cf == 0)
         return PACX_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
         return rc;
     hipStream_t st = (hipStream_t)stream;
-    /* the front end of pacx_encode_pack_nmr_batch; overall scales and status words stay in the workspace */
     if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
         HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
         HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
     }
     const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
-    if (s.mixed)
-        s.lists(st);
-    s.mdct(st);
-    s.side(0, false, st);
-    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
-    pacx_launch_rate_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, row, sub_stride, h->ws_lines, h->ws_thr,
-                           h->ws_smr, h->ws_overall, h->ws_rate_status, worst, bits, steps, st);
+    s.front(h->ws_thr, st);
+    if (band)
+        pacx_launch_band_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_lines, h->ws_thr, h->ws_smr,
+                               h->ws_overall, h->ws_rate_status, curve, a, b, st);
+    else
+        pacx_launch_rate_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, row, sub_stride, h->ws_lines,
+                               h->ws_thr, h->ws_smr, h->ws_overall, h->ws_rate_status, curve, a, b, st);
     return post_launch(h, what);
 }
 
-/* ---- what the solves share: the target range on the grid, and the segments of the segmented ones ---- */
+extern "C" int pacx_rate_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                     double max_bits_per_sample, int32_t row, double *worst, int32_t *bits,
+                                     int32_t *steps, void *stream)
+{
+    return curve_batch(h, false, "pacx_rate_curve_batch", in, frame_flags, max_bits_per_sample, row, worst, bits, steps,
+                       stream);
+}
+
+extern "C" int pacx_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                     double max_bits_per_sample, double *nmr, int32_t *cap, int32_t *cap_alloc,
+                                     void *stream)
+{
+    return curve_batch(h, true, "pacx_band_curve_batch", in, frame_flags, max_bits_per_sample, 0, nmr, cap, cap_alloc,
+                       stream);
+}
+
+/* ---- the solves: the target range on the grid, the segments of the segmented ones, the one checked path ---- */
 static int solve_range(pacx_handle *h, const char *what, double nmr_lo_db, double nmr_hi_db, int *t_lo, int *t_hi)
 {
     const double bound = 1048576.0;
@@ -1949,34 +1996,54 @@ static int upload_segments(pacx_handle *h, int64_t n_seg, const int64_t *seg_fir
     return PACX_OK;
 }
 
-extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
-                               const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db,
-                               double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
-                               pacx_rate_result *result, void *stream)
+/* The four solves, checked and launched in one place.  kind: SOLVE_RATE on a rate curve (curve, a, b = worst, bits,
+   steps with rows of `row`; per_cf = budget) or SOLVE_BAND on a band curve (nmr, cap, cap_alloc; bit_alloc).
+   segmented: n_seg segments from the host arrays seg_first and limit_bytes, uploaded.  Else the whole stream as one
+   segment: seg_first is not given, limit_bytes points at the one limit, which reaches the device as an argument of
+   the init kernel -- no staging buffer, no event, nothing the host waits for -- and the workspace grows to one state. */
+enum { SOLVE_RATE, SOLVE_BAND };
+static int solve(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t row, int32_t sub_stride,
+                 const double *curve, const int32_t *a, const int32_t *b, bool segmented, int64_t n_seg,
+                 const int64_t *seg_first, const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                 int32_t *per_cf, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream)
 {
-    const char *what = "pacx_rate_solve";
     if (!h)
         return PACX_E_ARG;
     if (h->T.use_vq || h->T.use_sbr)
         return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
     if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (!result || (n_cf > 0 && (!worst || !bits || !steps || !budget || !n_bytes || !capped)))
+    if (!result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1)
+    if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
         return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
-    if (limit_bytes < 0)
-        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
-    int t_lo, t_hi;
-    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+    int rc = PACX_OK, t_lo, t_hi;
+    if (segmented)
+        rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
+    else if (*limit_bytes < 0)
+        rc = fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
         return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = grow(h, GROW_SOLVE, 1);
-    if (rc)
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = segmented ? upload_segments(h, n_seg, seg_first, limit_bytes, st) : grow(h, GROW_SOLVE, 1)))
         return rc;
-    pacx_launch_rate_solve(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, limit_bytes, t_lo, t_hi,
-                           budget, n_bytes, capped, result, (hipStream_t)stream);
+    const PacxSolve v = {h->ws_solve, h->ws_seg, (int)n_seg, segmented ? nullptr : (const long long *)limit_bytes,
+                         n_cf, t_lo, t_hi, result};
+    if (kind == SOLVE_RATE)
+        pacx_launch_rate_solve_segments(v, row, sub_stride, curve, a, b, per_cf, n_bytes, capped, st);
+    else
+        pacx_launch_band_solve_segments(h->T, v, curve, a, b, per_cf, n_bytes, capped, st);
     return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_solve(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                               const int32_t *bits, const int32_t *steps, int64_t limit_bytes, double nmr_lo_db,
+                               double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
+                               pacx_rate_result *result, void *stream)
+{
+    return solve(h, SOLVE_RATE, "pacx_rate_solve", n_cf, row, sub_stride, worst, bits, steps, false, 1, nullptr,
+                 &limit_bytes, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, stream);
 }
 
 extern "C" int pacx_rate_solve_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride,
@@ -1985,96 +2052,11 @@ extern "C" int pacx_rate_solve_segments(pacx_handle *h, int64_t n_cf, int32_t ro
                                         double nmr_hi_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
                                         pacx_rate_result *result, void *stream)
 {
-    const char *what = "pacx_rate_solve_segments";
-    if (!h)
-        return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
-    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
-        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (!result || (n_cf > 0 && (!worst || !bits || !steps || !budget || !n_bytes || !capped)))
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1)
-        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
-    int t_lo, t_hi;
-    int rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
-    if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
-        return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = upload_segments(h, n_seg, seg_first, limit_bytes, (hipStream_t)stream)))
-        return rc;
-    pacx_launch_rate_solve_segments(h->ws_solve, n_cf, row, sub_stride, worst, bits, steps, (int)n_seg, h->ws_seg,
-                                    h->ws_seg + n_seg + 1, t_lo, t_hi, budget, n_bytes, capped, result,
-                                    (hipStream_t)stream);
-    return post_launch(h, what);
+    return solve(h, SOLVE_RATE, "pacx_rate_solve_segments", n_cf, row, sub_stride, worst, bits, steps, true, n_seg,
+                 seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, stream);
 }
 
 /* ---- bits handed to the bands one by one ---- */
-/* the longest record a pick can give at this cap rate, in bytes: per unit the header bits and at most
-   min(32 J, maxMantBits x lines) mantissa bits (a unit within its cap, or BitAlloc's at that budget) */
-static long long band_record_bound(const PacxTables &T, double max_bps)
-{
-    int max_mant = 1 << T.n_mant_size_bits;
-    if (max_mant > 16)
-        max_mant = 16;
-    long long worst = 0;
-    for (int sh = 0; sh < 2; ++sh)
-        for (int lon = 0; lon < 2; ++lon) {
-            const int nb = sh ? T.nb_short : T.nb_long, m = sh ? PACX_M_SHORT : PACX_M_LONG;
-            const long long all = (long long)max_mant * m;
-            const long long j = pacx_rate_steps(max_bps, m, sh, lon, T.n_scale_bits, T.n_mant_size_bits, nb);
-            const long long mant = 32 * j < all ? 32 * j : all;
-            const long long unit = T.n_scale_bits + (long long)nb * (T.n_mant_size_bits + T.n_scale_bits) + mant;
-            const long long bytes = ((sh ? PACX_SUB : 1) * unit + 4 + 7) >> 3;
-            worst = bytes > worst ? bytes : worst;
-        }
-    return worst;
-}
-
-extern "C" int pacx_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
-                                     double max_bits_per_sample, double *nmr, int32_t *cap, int32_t *cap_alloc,
-                                     void *stream)
-{
-    const char *what = "pacx_band_curve_batch";
-    if (!h)
-        return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
-    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
-        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
-        return rc;
-    if (!nmr || !cap || !cap_alloc)
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (band_record_bound(h->T, max_bits_per_sample) > PACX_PAYLOAD_STRIDE)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": a record at this cap rate would not fit pacx_payload_stride");
-    if (n_cf == 0)
-        return PACX_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    /* the front end of pacx_rate_curve_batch; overall scales and status words stay in the workspace */
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
-    if (s.mixed)
-        s.lists(st);
-    s.mdct(st);
-    s.side(0, false, st);
-    pacx_launch_mask(h->T, frame_flags, s.n_ch, n_cf, 0, s.mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                     h->ws_thr, h->n_cu, s.list_long, s.list_short, s.counts, nullptr, st);
-    pacx_launch_band_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_lines, h->ws_thr, h->ws_smr,
-                           h->ws_overall, h->ws_rate_status, nmr, cap, cap_alloc, st);
-    return post_launch(h, what);
-}
-
 extern "C" int pacx_band_pick(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
                               double target_nmr_db, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, void *stream)
 {
@@ -2098,27 +2080,8 @@ extern "C" int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, 
                                int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc,
                                int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream)
 {
-    const char *what = "pacx_band_solve";
-    if (!h)
-        return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
-    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
-        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (!result || (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped)))
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (limit_bytes < 0)
-        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
-    int t_lo, t_hi;
-    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
-        return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    int rc = grow(h, GROW_SOLVE, 1);
-    if (rc)
-        return rc;
-    pacx_launch_band_solve(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, limit_bytes, t_lo, t_hi, bit_alloc,
-                           n_bytes, capped, result, (hipStream_t)stream);
-    return post_launch(h, what);
+    return solve(h, SOLVE_BAND, "pacx_band_solve", n_cf, 0, 0, nmr, cap, cap_alloc, false, 1, nullptr, &limit_bytes,
+                 nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream);
 }
 
 extern "C" int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
@@ -2127,26 +2090,8 @@ extern "C" int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const doub
                                         int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
                                         void *stream)
 {
-    const char *what = "pacx_band_solve_segments";
-    if (!h)
-        return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
-    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
-        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (!result || (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped)))
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    int t_lo, t_hi;
-    int rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
-    if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
-        return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = upload_segments(h, n_seg, seg_first, limit_bytes, (hipStream_t)stream)))
-        return rc;
-    pacx_launch_band_solve_segments(h->T, h->ws_solve, n_cf, nmr, cap, cap_alloc, (int)n_seg, h->ws_seg,
-                                    h->ws_seg + n_seg + 1, t_lo, t_hi, bit_alloc, n_bytes, capped, result,
-                                    (hipStream_t)stream);
-    return post_launch(h, what);
+    return solve(h, SOLVE_BAND, "pacx_band_solve_segments", n_cf, 0, 0, nmr, cap, cap_alloc, true, n_seg, seg_first,
+                 limit_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream);
 }
 
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,

@@ -127,40 +127,55 @@ void pacx_launch_rate_search(const PacxTables &T, const uint8_t *flags, int n_ch
 void pacx_launch_bitalloc_budget(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                                  const int32_t *budget, const double *smr, int32_t *bit_alloc, uint32_t *status,
                                  hipStream_t st);
-/* the rate curve of pacx_rate_curve_batch (k_rate_search's units and evaluation, every step j = 0 ... J) and the
-   solve of pacx_rate_solve on it: ws holds pacx_rate_solve_ws_bytes() bytes, the solve enqueues
-   pacx_rate_solve_pairs(t_lo, t_hi) pick / step pairs and never waits for one */
+/* the rate curve of pacx_rate_curve_batch (k_rate_search's units and evaluation, every step j = 0 ... J) */
 void pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                             double max_bits_per_sample, int row, int sub_stride, const double *lines,
                             const double *thr, const double *smr, const int32_t *overall, const uint32_t *status,
                             double *worst, int32_t *bits, int32_t *steps, hipStream_t st);
+
+/* The solve, the only one: one target per segment of consecutive channel-frames, found on stored curves.  A whole-
+   stream solve (pacx_rate_solve, pacx_band_solve) is the solve of one segment.  Nothing here waits for the device. */
+struct PacxSolve {
+    void *ws;                         /* n_seg states of pacx_rate_solve_ws_bytes() bytes */
+    long long *seg;                   /* device: seg_first [n_seg + 1], then limit [n_seg] */
+    int n_seg;
+    const long long *one_limit;       /* nullptr: seg is uploaded.  Else n_seg == 1, and the init kernel writes
+                                         {0, n_cf, *one_limit} into seg itself: no copy from the host */
+    long long n_cf;
+    int t_lo, t_hi;                   /* the target range on the grid */
+    pacx_rate_result *result;         /* [n_seg] */
+};
 size_t pacx_rate_solve_ws_bytes(void);
 int pacx_rate_solve_pairs(int t_lo, int t_hi);
-void pacx_launch_rate_solve(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
-                            const int32_t *bits, const int32_t *steps, long long limit, int t_lo, int t_hi,
-                            int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
-                            hipStream_t st);
-
-/* the two one-thread kernels of that solve, for a solve with a pick of its own (k_band.hip) */
-void pacx_launch_solve_init(void *ws, int t_lo, int t_hi, hipStream_t st);
-void pacx_launch_solve_step(void *ws, long long limit, int final, pacx_rate_result *result, hipStream_t st);
-
-/* pacx_rate_solve_segments / pacx_band_solve_segments: one state per segment (ws holds n_seg times
-   pacx_rate_solve_ws_bytes()), seg_first int64 [n_seg + 1] and limit int64 [n_seg] in device memory, result [n_seg].
-   Init and step run one thread per segment; a pick finds a frame's segment in pacx_segment_search_steps(n_seg)
-   halvings.  The pairs are pacx_rate_solve's. */
 int pacx_segment_search_steps(int n_seg);
-void pacx_launch_solve_init_segments(void *ws, int n_seg, int t_lo, int t_hi, hipStream_t st);
-void pacx_launch_solve_step_segments(void *ws, int n_seg, const long long *limit, int final, pacx_rate_result *result,
-                                     hipStream_t st);
-void pacx_launch_rate_solve_segments(void *ws, long long n_cf, int row, int sub_stride, const double *worst,
-                                     const int32_t *bits, const int32_t *steps, int n_seg, const long long *seg_first,
-                                     const long long *limit, int t_lo, int t_hi, int32_t *budget, int32_t *n_bytes,
-                                     uint8_t *capped, pacx_rate_result *result, hipStream_t st);
+/* init and step: one thread per segment (k_rate.hip) */
+void pacx_launch_solve_init_segments(const PacxSolve &v, hipStream_t st);
+void pacx_launch_solve_step_segments(const PacxSolve &v, int final, hipStream_t st);
 
-/* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve (nmr float64
-   [n_cf][band_stride][PACX_BAND_CAND], cap int32 [n_cf][8], cap_alloc int32 [n_cf][band_stride]; the solve uses
-   pacx_rate_solve's state and number of pairs) and the sanitised copy of a caller's allocation (in == out allowed) */
+/* the driver: init, then pacx_rate_solve_pairs(t_lo, t_hi) pick / step pairs, the last of which writes the outputs.
+   pick(search_steps, final) launches the solve's own pick kernel, which finds a frame's segment in
+   pacx_segment_search_steps(n_seg) halvings (none for one segment: seg_first is not read); without frames no pick */
+template <class Pick>
+inline void pacx_solve_drive(const PacxSolve &v, hipStream_t st, Pick pick)
+{
+    const int pairs = pacx_rate_solve_pairs(v.t_lo, v.t_hi), search = pacx_segment_search_steps(v.n_seg);
+    pacx_launch_solve_init_segments(v, st);
+    for (int p = 0; p < pairs; ++p) {
+        const int final = p == pairs - 1;
+        if (v.n_cf > 0)
+            pick(search, final);
+        pacx_launch_solve_step_segments(v, final, st);
+    }
+}
+
+/* the solve on a rate curve: a frame's units at the budgets the curve gives at its segment's target */
+void pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int sub_stride, const double *worst,
+                                     const int32_t *bits, const int32_t *steps, int32_t *budget, int32_t *n_bytes,
+                                     uint8_t *capped, hipStream_t st);
+
+/* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve_segments (nmr
+   float64 [n_cf][band_stride][PACX_BAND_CAND], cap int32 [n_cf][8], cap_alloc int32 [n_cf][band_stride]; the solve is
+   the one above with a pick of its own) and the sanitised copy of a caller's allocation (in == out allowed) */
 void pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
                             double max_bits_per_sample, const double *lines, const double *thr, const double *smr,
                             const int32_t *overall, uint32_t *status, double *nmr, int32_t *cap, int32_t *cap_alloc,
@@ -168,13 +183,8 @@ void pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch,
 void pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, const double *nmr, const int32_t *cap,
                            const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
                            hipStream_t st);
-void pacx_launch_band_solve(const PacxTables &T, void *ws, long long n_cf, const double *nmr, const int32_t *cap,
-                            const int32_t *cap_alloc, long long limit, int t_lo, int t_hi, int32_t *bit_alloc,
-                            int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, hipStream_t st);
-void pacx_launch_band_solve_segments(const PacxTables &T, void *ws, long long n_cf, const double *nmr,
-                                     const int32_t *cap, const int32_t *cap_alloc, int n_seg,
-                                     const long long *seg_first, const long long *limit, int t_lo, int t_hi,
-                                     int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+void pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolve &v, const double *nmr, const int32_t *cap,
+                                     const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
                                      hipStream_t st);
 void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
                                int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);

@@ -346,6 +346,43 @@ class Encoder:
         out["row"], out["sub_stride"], out["flags"] = row, sub, fl
         return out
 
+    def _solve(self, what, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db):
+        """The four solves: `what` names the method, band_* on a band curve and rate_* on a rate curve, *_segments with
+        seg_first and one limit per segment, else the whole stream with its one limit (the plain C entry point).  Checks
+        the curve, makes the outputs, calls pacx_<what> and decodes the pacx_rate_result of every segment: t, met,
+        total (int64) in four int32."""
+        band, segmented = what.startswith("band"), what.endswith("_segments")
+        if band:
+            *arrays, n_cf, out = self._band_arrays(curve, what)
+            head, per_cf = [], "bit_alloc"
+        else:
+            arrays = worst, bits, steps = tuple(curve[k].contiguous() for k in ("worst", "bits", "steps"))
+            n_cf, row = worst.shape
+            if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
+                    tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
+                raise ValueError(f"{what}: a curve as rate_curve returns it")
+            head, per_cf = [int(row), int(curve["sub_stride"])], "budget"
+            out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
+                   "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+                   "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+        if segmented:
+            first, limit = self._segments(what, seg_first, limit_bytes, n_cf)
+            limits = [ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data]
+        else:
+            limits = [ctypes.c_int64(int(limit_bytes))]
+        result = torch.zeros((len(limit) if segmented else 1, 4), dtype=torch.int32, device=self.device)
+        self._call_rate("pacx_" + what, ctypes.c_int64(n_cf), *head, *(_ptr(t) for t in arrays), *limits,
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(out[per_cf]), _ptr(out["n_bytes"]),
+                        _ptr(out["capped"]), _ptr(result), self._stream())
+        res = result.cpu().numpy()
+        out["capped"] = out["capped"].bool()
+        out.update({"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID), "met": res[:, 1] != 0,
+                    "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]})
+        if not segmented:
+            out.update({"target_nmr_db": float(out["target_nmr_db"][0]), "met": bool(out["met"][0]),
+                        "total_bytes": int(out["total_bytes"][0])})
+        return out
+
     def rate_solve(self, curve, flags, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """One target NMR for the whole stream (pacx_rate_solve, include/pacx.h): the bisection over the grid of
         1/64 dB in [nmr_lo_db, nmr_hi_db] for the smallest target whose body -- every unit at the budget
@@ -353,23 +390,7 @@ class Encoder:
         given to rate_curve (the curve's steps already carry what the solve needs of them).  -> dict
         target_nmr_db, met (False: not even nmr_hi_db fits; the outputs are then that target's), total_bytes,
         budget [n_cf, 8] int32 for encode_pack_budget, n_bytes [n_cf] int32 (predicted), capped [n_cf] bool."""
-        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
-        n_cf, row = worst.shape
-        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
-                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
-            raise ValueError("rate_solve: a curve as rate_curve returns it")
-        budget = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
-        n_bytes = torch.zeros((n_cf,), dtype=torch.int32, device=self.device)
-        capped = torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)
-        result = torch.zeros((4,), dtype=torch.int32, device=self.device)        # pacx_rate_result: t, met, total (int64)
-        self._call_rate("pacx_rate_solve", ctypes.c_int64(n_cf), int(row), int(curve["sub_stride"]), _ptr(worst),
-                        _ptr(bits), _ptr(steps), ctypes.c_int64(int(limit_bytes)), ctypes.c_double(nmr_lo_db),
-                        ctypes.c_double(nmr_hi_db), _ptr(budget), _ptr(n_bytes), _ptr(capped), _ptr(result),
-                        self._stream())
-        res = result.cpu().numpy()
-        t, met, total = int(res[0]), bool(res[1]), int(res.view(np.int64)[1])
-        return {"target_nmr_db": t / float(_lib.RATE_TARGET_GRID), "met": met, "total_bytes": total, "budget": budget,
-                "n_bytes": n_bytes, "capped": capped.bool()}
+        return self._solve("rate_solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     @staticmethod
     def _segments(what, seg_first, limit_bytes, n_cf):
@@ -387,35 +408,14 @@ class Encoder:
             raise ValueError(f"{what}: negative limit for segment {int(np.argmax(limit < 0))}")
         return first, limit
 
-    def _segment_results(self, result):
-        """pacx_rate_result [n_seg] on the device -> target_nmr_db float64, met bool, total_bytes int64"""
-        res = result.cpu().numpy()
-        return {"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID),
-                "met": res[:, 1] != 0, "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]}
-
     def rate_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """rate_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_rate_solve_segments, include/pacx.h): segment s holds the channel-frames seg_first[s] ... seg_first[s + 1]
-        - 1 (it may be empty) and gets what rate_solve gives on that slice of the curve with limit_bytes[s].
-        seg_first [n_seg + 1] and limit_bytes [n_seg]: any integer sequences.  -> dict budget, n_bytes, capped as
-        rate_solve, and NumPy arrays target_nmr_db [n_seg] float64, met [n_seg] bool, total_bytes [n_seg] int64."""
-        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
-        n_cf, row = worst.shape
-        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
-                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
-            raise ValueError("rate_solve_segments: a curve as rate_curve returns it")
-        first, limit = self._segments("rate_solve_segments", seg_first, limit_bytes, n_cf)
-        budget = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
-        n_bytes = torch.zeros((n_cf,), dtype=torch.int32, device=self.device)
-        capped = torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)
-        result = torch.zeros((len(limit), 4), dtype=torch.int32, device=self.device)
-        self._call_rate("pacx_rate_solve_segments", ctypes.c_int64(n_cf), int(row), int(curve["sub_stride"]),
-                        _ptr(worst), _ptr(bits), _ptr(steps), ctypes.c_int64(len(limit)), first.ctypes.data,
-                        limit.ctypes.data, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(budget),
-                        _ptr(n_bytes), _ptr(capped), _ptr(result), self._stream())
-        out = {"budget": budget, "n_bytes": n_bytes, "capped": capped.bool()}
-        out.update(self._segment_results(result))
-        return out
+        - 1 (it may be empty) and gets what rate_solve gives on that slice of the curve with limit_bytes[s]: rate_solve
+        is the same solve with the one segment [0, n_cf].  seg_first [n_seg + 1] and limit_bytes [n_seg]: any integer
+        sequences.  -> dict budget, n_bytes, capped as rate_solve, and NumPy arrays target_nmr_db [n_seg] float64, met
+        [n_seg] bool, total_bytes [n_seg] int64."""
+        return self._solve("rate_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
@@ -466,30 +466,13 @@ class Encoder:
         """rate_solve on a band curve (pacx_band_solve, include/pacx.h): the lowest target on the grid of 1/64 dB in
         [nmr_lo_db, nmr_hi_db] whose body, every band at band_pick's size, stays within limit_bytes.  -> dict
         target_nmr_db, met, total_bytes and band_pick's bit_alloc, n_bytes, capped at that target."""
-        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_solve")
-        result = torch.zeros((4,), dtype=torch.int32, device=self.device)        # pacx_rate_result: t, met, total (int64)
-        self._call_rate("pacx_band_solve", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_int64(int(limit_bytes)), ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
-                        _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]), _ptr(result), self._stream())
-        res = result.cpu().numpy()
-        out.update({"target_nmr_db": int(res[0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[1]),
-                    "total_bytes": int(res.view(np.int64)[1]), "capped": out["capped"].bool()})
-        return out
+        return self._solve("band_solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,
         n_bytes, capped as band_solve, and NumPy arrays target_nmr_db, met, total_bytes [n_seg]."""
-        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_solve_segments")
-        first, limit = self._segments("band_solve_segments", seg_first, limit_bytes, n_cf)
-        result = torch.zeros((len(limit), 4), dtype=torch.int32, device=self.device)
-        self._call_rate("pacx_band_solve_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data, ctypes.c_double(nmr_lo_db),
-                        ctypes.c_double(nmr_hi_db), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
-                        _ptr(result), self._stream())
-        out["capped"] = out["capped"].bool()
-        out.update(self._segment_results(result))
-        return out
+        return self._solve("band_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

@@ -550,35 +550,33 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
         segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
     head = header_bytes(cp)
-    limits = [] if segment_hops is not None else [_abr_limit(cp, view, head, k, b) for k, b in sizes]
+    limits = [None] * len(sizes) if segment_hops is not None else [_abr_limit(cp, view, head, k, b) for k, b in sizes]
     curve = enc.band_curve(view, flags, cp.targetBitsPerSample) if band else \
         enc.rate_curve(view, flags, cp.targetBitsPerSample)
+    n_ch = cp.nChannels
     done = []
-    if segment_hops is not None:
-        n_ch = cp.nChannels
-        for kbps, _ in sizes:
+    for (kbps, _), limit in zip(sizes, limits):
+        if segment_hops is None:        # the whole stream: the partition [0, n_cf] with its one limit, the plain method
+            sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
+            unmet = None if sol["met"] else \
+                (f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
+                 f"{sol['total_bytes']} bytes ({len(head) + sol['total_bytes']} with the header), the "
+                 f"smallest size this range of targets gives")
+        else:
             first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
             sol = enc.band_solve_segments(curve, seg_first, seg_limit, lo, hi) if band else \
                 enc.rate_solve_segments(curve, seg_first, seg_limit, lo, hi)
-            if not sol["met"].all():
-                s = int(np.argmin(sol["met"]))
-                raise ValueError(f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) cannot be reached: "
-                                 f"its limit is {int(seg_limit[s])} bytes and at the highest target, {hi:g} dB, it "
-                                 f"takes {int(sol['total_bytes'][s])} bytes, the smallest size this range of targets "
-                                 f"gives")
+            s = int(np.argmin(sol["met"]))
+            unmet = None if sol["met"].all() else \
+                (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) cannot be reached: "
+                 f"its limit is {int(seg_limit[s])} bytes and at the highest target, {hi:g} dB, it "
+                 f"takes {int(sol['total_bytes'][s])} bytes, the smallest size this range of targets "
+                 f"gives")
             sol["segments"] = {"first_block": first, "blocks": count, "limit_bytes": seg_limit}
-            out = enc.encode_pack_alloc(view, flags, sol["bit_alloc"]) if band else \
-                enc.encode_pack_budget(view, flags, sol["budget"])
-            body, total = enc.gather_body(out["payload"], out["n_bytes"])
-            done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, int(seg_limit.sum())))
-        return done, enc
-    for limit in limits:
-        sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
-        if not sol["met"]:
-            raise ValueError(f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
-                             f"{sol['total_bytes']} bytes ({len(head) + sol['total_bytes']} with the header), the "
-                             f"smallest size this range of targets gives")
+            limit = int(seg_limit.sum())
+        if unmet:
+            raise ValueError(unmet)
         out = enc.encode_pack_alloc(view, flags, sol["bit_alloc"]) if band else \
             enc.encode_pack_budget(view, flags, sol["budget"])
         body, total = enc.gather_body(out["payload"], out["n_bytes"])

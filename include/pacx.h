@@ -782,11 +782,13 @@ typedef struct pacx_rate_result {
  *
  * worst[j] is not monotone in j (see the search above) and total need not be monotone in t, so the result is this
  * bisection's, not a global optimum: total(t) <= limit_bytes holds at the t returned and failed at the last t
- * tried below it.  On the device: a pick kernel (one channel-frame per thread, at most 8 x 11 look-ups, a
- * workgroup reduction, one 64-bit integer atomicAdd per workgroup) and a one-thread step kernel, enqueued as
+ * tried below it.  On the device this is pacx_rate_solve_segments' solve with the whole batch as its one segment
+ * (there is one implementation; see below): a pick kernel (one channel-frame per thread, at most 8 x 11 look-ups, a
+ * workgroup reduction, one 64-bit integer atomicAdd per workgroup) and a step kernel, enqueued as
  * 2 + ceil(log2(t_hi - t_lo + 2)) pairs whatever the data; pairs after the answer is known do nothing, and the
- * host waits for none.  Integer sums: the result does not depend on the order of execution.  The solve's few
- * words of state live in the handle: solves of one handle belong on one stream, as all its calls do.
+ * host waits for none: the limit travels as a kernel argument, nothing is copied from the host.  Integer sums: the
+ * result does not depend on the order of execution.  The solve's few words of state live in the handle: solves of
+ * one handle belong on one stream, as all its calls do.
  *
  *   worst, bits, steps, row, sub_stride: a curve as pacx_rate_curve_batch writes it (row >= 7 sub_stride + 1); a
  *                  J that would leave its row is cut to the row
@@ -906,13 +908,15 @@ int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, const int32
  * uploaded on `stream` through a pinned buffer of the handle's; a call waits for the upload of the segmented solve
  * before it on the same handle, and for nothing else.  The call is therefore not meant for stream capture into a
  * graph; its callers read the result back anyway.  On the device one state per segment lives in the handle beside
- * the boundaries: init and step kernels run one thread per segment, the pick kernels are the plain solves' per-frame
- * work with the target taken from the frame's segment (found in at most ceil(log2(n_seg + 1)) halvings of the
+ * the boundaries: init and step kernels run one thread per segment, the pick kernels do the per-frame work described
+ * above with the target taken from the frame's segment (found in at most ceil(log2(n_seg + 1)) halvings of the
  * boundaries) and the frame's bytes added to that segment's total: reduced on chip, then one 64-bit integer
  * atomicAdd per workgroup whose frames lie in one segment, one per segment present (pacx_band_solve_segments: per
  * wave) in a workgroup that straddles a boundary.  Frames of a segment whose answer is known are skipped until the
  * last pick, which writes the outputs.  2 + ceil(log2(t_hi - t_lo + 2)) pairs whatever the data, no host wait.
- * A plain solve on the same handle afterwards behaves as before.
+ * These kernels are the only solve there is: pacx_rate_solve and pacx_band_solve run them with n_seg = 1 and the
+ * table {0, n_cf, limit_bytes} written on the device, so the contract above holds by construction.  Plain and
+ * segmented solves may follow one another on a handle's stream in any order.
  *
  * Other arguments, PACX_E_UNSUPPORTED and PACX_E_ARG: as pacx_rate_solve / pacx_band_solve; PACX_E_ARG also for
  * n_seg < 1, a null seg_first or limit_bytes, boundaries that do not start at 0, decrease or do not end at n_cf, and

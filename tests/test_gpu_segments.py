@@ -80,7 +80,7 @@ def material(kind):
 
 
 # boundaries one frame before, at and after 64 and 256 (a wave and a workgroup of k_solve_pick; every one of them
-# inside some 4-frame workgroup of k_band_pick), with empty segments between
+# inside some 4-frame workgroup of k_band_pick_seg), with empty segments between
 EDGES = np.array([0, 63, 64, 65, 65, 255, 256, 257, 257, 257, 511, 513, 1023, 1024, 1025, 1279, 1281, 1281, 2999, 3000],
                  np.int64)
 
@@ -108,19 +108,115 @@ def test_other_ranges(A, kind, lo_db, hi_db):
 
 
 # ------------------------------------------------------------------ 2. one segment is the plain solve
+def plain_solve(enc, kind, dev, limit, lo_db=-30, hi_db=30):
+    return enc.band_solve(dev, limit, lo_db, hi_db) if kind == "band" else enc.rate_solve(dev, None, limit, lo_db, hi_db)
+
+
+def assert_plain_equals_model(kind, one, ref, what):
+    """a plain solve's dict against the model's one-segment result: everything equal"""
+    assert isinstance(one["target_nmr_db"], float) and isinstance(one["met"], bool) and isinstance(one["total_bytes"], int)
+    got = (round(one["target_nmr_db"] * 64), one["met"], one["total_bytes"])
+    want = (int(ref["t"][0]), bool(ref["met"][0]), int(ref["total"][0]))
+    print(f"{what} {kind}: gpu {got}, model {want}")
+    assert one["target_nmr_db"] * 64 == got[0] and got == want, (what, kind)
+    for k in sm.PER_CF[kind]:
+        assert np.array_equal(one[k].cpu().numpy(), ref[k]), (what, kind, k)
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_one_segment_equals_the_plain_solve(A, kind):
+    """both routes to the one solve -- the plain entry point, whose table the init kernel writes, and the segmented
+    one with an uploaded one-segment table -- against each other and against the model"""
     c, _, _ = material(kind)
     enc = encoder(A, kind)
     dev = on_device(enc, kind, c)
+    n_cf = sm.n_cf_of(kind, c)
     small, big = sm.total(kind, c, 30 * 64), sm.total(kind, c, -30 * 64)
     for limit in ((small + big) // 2, small - 1, small, 10 ** 12):
-        seg = gpu_solve(enc, kind, dev, [0, len(c["cap" if kind == "band" else "steps"])], [limit])
-        one = enc.band_solve(dev, limit) if kind == "band" else enc.rate_solve(dev, None, limit)
+        seg = gpu_solve(enc, kind, dev, [0, n_cf], [limit])
+        one = plain_solve(enc, kind, dev, limit)
         assert (seg["target_nmr_db"][0], bool(seg["met"][0]), int(seg["total_bytes"][0])) == \
             (one["target_nmr_db"], one["met"], one["total_bytes"]), limit
         for k in sm.PER_CF[kind]:
             assert np.array_equal(seg[k].cpu().numpy(), one[k].cpu().numpy()), (limit, k)
+        ref = sm.solve_segments(kind, c, [0, n_cf], [limit])
+        assert_plain_equals_model(kind, one, ref, f"limit {limit}")
+        assert (round(seg["target_nmr_db"][0] * 64), int(seg["met"][0]), int(seg["total_bytes"][0])) == \
+            (ref["t"][0], ref["met"][0], ref["total"][0]), limit
+        for k in sm.PER_CF[kind]:
+            assert np.array_equal(seg[k].cpu().numpy(), ref[k]), (limit, k)
+
+
+@pytest.mark.parametrize("n_cf", [0, 1, 3, 4, 5, 255, 256, 257])
+@pytest.mark.parametrize("kind", KINDS)
+def test_plain_solves_at_the_workgroup_edges(A, kind, n_cf):
+    """the plain solves with no, one and a few frames and one frame before, at and after the band pick's 4-frame and
+    the rate pick's 256-frame workgroup, at four limits: one byte less than the highest target takes, exactly that,
+    the midpoint of the smallest and the largest body, and more than anything takes.  Without frames the first of
+    them is -1, which is no limit: the call refuses it, as every negative limit."""
+    c = sm.synthetic(kind, n_cf, 11)
+    enc = encoder(A, kind)
+    dev = on_device(enc, kind, c)
+    small, big = sm.total(kind, c, 30 * 64), sm.total(kind, c, -30 * 64)
+    for limit in (small - 1, small, (small + big) // 2, 10 ** 12):
+        if limit < 0:
+            assert n_cf == 0
+            with pytest.raises(A._lib.PacxError, match="negative limit"):
+                plain_solve(enc, kind, dev, limit)
+            continue
+        ref = sm.solve_segments(kind, c, [0, n_cf], [limit])
+        assert_plain_equals_model(kind, plain_solve(enc, kind, dev, limit), ref, f"{n_cf} frames, limit {limit}")
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_plain_and_segmented_solves_interleaved(A, kind):
+    """a plain solve, a segmented one and a second plain one with another limit, queued on one handle and one stream
+    through the C entry points and read back only after the third: they share the handle's states and its segment
+    table, which the plain solves' init kernel writes and the segmented solve uploads"""
+    import torch
+    c, _, _ = material(kind)
+    enc = encoder(A, kind)
+    dev = on_device(enc, kind, c)
+    n_cf = sm.n_cf_of(kind, c)
+    first, limits = EDGES, sm.limits_for(kind, c, EDGES)
+    small, big = sm.total(kind, c, 30 * 64), sm.total(kind, c, -30 * 64)
+    plain_limits = ((small + big) // 2, small + (big - small) // 5)
+    check(enc, kind, dev, c, first, limits, what="before")          # the handle's states are grown: no wait below
+    ptr = A.engine._ptr
+    arrays = [ptr(dev[k]) for k in (("nmr", "cap", "cap_alloc") if kind == "band" else ("worst", "bits", "steps"))]
+    head = [] if kind == "band" else [int(dev["row"]), int(dev["sub_stride"])]
+    width = enc.band_stride if kind == "band" else 8
+    seg_first, seg_limit = np.ascontiguousarray(first, np.int64), np.ascontiguousarray(limits, np.int64)
+
+    def queue(n_seg):
+        """one solve queued, nothing read: n_seg None is the plain entry point -> its outputs on the device"""
+        out = [torch.zeros((n_cf, width), dtype=torch.int32, device=enc.device),
+               torch.zeros((n_cf,), dtype=torch.int32, device=enc.device),
+               torch.zeros((n_cf,), dtype=torch.uint8, device=enc.device),
+               torch.zeros((n_seg or 1, 4), dtype=torch.int32, device=enc.device)]
+        name = f"pacx_{kind}_solve" + ("_segments" if n_seg else "")
+        size = [ctypes.c_int64(n_seg), seg_first.ctypes.data, seg_limit.ctypes.data] if n_seg else \
+            [ctypes.c_int64(int(plain_limits[len(queued) // 2]))]
+        rc = getattr(enc.lib, name)(enc.h, ctypes.c_int64(n_cf), *head, *arrays, *size, ctypes.c_double(-30.0),
+                                    ctypes.c_double(30.0), *(ptr(t) for t in out), enc._stream())
+        assert rc == 0, (name, enc.lib.pacx_last_error(enc.h))
+        queued.append(out)
+
+    queued = []
+    for n_seg in (None, len(limits), None):
+        queue(n_seg)
+    torch.cuda.synchronize()
+    refs = [sm.solve_segments(kind, c, [0, n_cf], [plain_limits[0]]), sm.solve_segments(kind, c, first, limits),
+            sm.solve_segments(kind, c, [0, n_cf], [plain_limits[1]])]
+    assert refs[0]["t"][0] != refs[2]["t"][0]                        # the two plain solves have answers of their own
+    for i, (out, ref) in enumerate(zip(queued, refs)):
+        res = out[3].cpu().numpy()
+        got = (res[:, 0].astype(np.int64), res[:, 1].astype(np.int64), res[:, 2:].copy().view(np.int64)[:, 0])
+        print(f"{kind} solve {i}: {len(got[0])} segments, {int(got[1].sum())} met")
+        for g, k in zip(got, ("t", "met", "total")):
+            assert np.array_equal(g, ref[k]), (kind, i, k)
+        for t, k in zip(out, sm.PER_CF[kind]):
+            assert np.array_equal(t.cpu().numpy().astype(ref[k].dtype), ref[k]), (kind, i, k)
 
 
 # ------------------------------------------------------------------ 3. as many segments as frames, and more

@@ -134,10 +134,10 @@ def test_library_exports_the_entry_points():
 
 
 def test_segment_kernels_use_no_scratch():
-    """the compiler's resource report of the new kernels: no scratch, no spilled registers"""
+    """the compiler's resource report of the solve's kernels: no scratch, no spilled registers"""
     import importlib
     res = importlib.import_module("audio_codec_amd.build").resources()
-    want = {"k_solve_pick_seg", "k_solve_init_seg", "k_solve_step_seg", "k_band_pick_seg"}
+    want = {"k_solve_pick", "k_solve_init", "k_solve_step", "k_band_pick_seg"}
     mine = {k: v for k, v in res.items() if any(n in k for n in want)}
     assert {n for n in want if any(n in k for k in mine)} == want
     for name, r in mine.items():
