@@ -28,7 +28,8 @@ template <int DT, bool FAST>
 __global__ __launch_bounds__(64) void k_mdct_long(PacxTables T, PacxPcmView in,
                                                  const uint8_t *__restrict__ flags, long long n_cf,
                                                  int skip_cur, int prewin, double *__restrict__ lines,
-                                                 int32_t *__restrict__ scale_out, int scale_stride)
+                                                 int32_t *__restrict__ scale_out, int scale_stride,
+                                                 uint32_t *__restrict__ status)
 {
     typedef typename PcmStage<DT>::elem E;
     __shared__ __attribute__((aligned(16))) cplx tile[WFFT_TILE];
@@ -81,9 +82,15 @@ __global__ __launch_bounds__(64) void k_mdct_long(PacxTables T, PacxPcmView in,
         mx = fmax(mx, fmax(fabs(a), fabs(b)));
     }
     if (scale_out) {
-        mx = wave_max(mx);
+        /* the fast kernels' decision (mdct_dev.h); the caller zeroed status, and in a block-switched batch
+           k_mdct_short owns the words of the CUR frames this kernel skips */
+        int sc;
+        const int lo = mdct_long_scale(T, mx, sc);
+        const bool guard = T.guard && status && mdct_long_guard(T, mx, sc, lo);
         if (lane == 0)
-            scale_out[cf * scale_stride] = pacx_scale_factor(mx, T.n_scale_bits, 5);
+            scale_out[cf * scale_stride] = lo;
+        if (__builtin_amdgcn_ballot_w64(guard) && lane == 0)
+            atomicOr(&status[cf], 16u);
     }
 }
 
@@ -221,7 +228,7 @@ static void launch_mdct(const PacxTables &T, const PacxPcmView &in, const uint8_
     }
     if (!short_blocks || mixed)
         hipLaunchKernelGGL((k_mdct_long<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed,
-                           prewin, lines, scale_out, scale_stride);
+                           prewin, lines, scale_out, scale_stride, status);
     if (short_blocks || mixed)
         hipLaunchKernelGGL((k_mdct_short<DT, FAST>), grid, block, 0, st, T, in, flags, n_cf, mixed ? 1 : 0,
                            prewin, lines, scale_out, status);

@@ -35,6 +35,15 @@ class PcmView:
             raise ValueError("PCM tensor must live on the GPU")
         self.tensor = tensor                      # keeps the memory alive
         self.n_channels, self.n_frames = int(n_channels), int(n_frames)
+        # the C side cannot see the allocation: the last element the view addresses, counted from the tensor's place
+        # in its storage, has to lie inside that storage (negative strides are left to the library, which refuses them)
+        if self.n_frames > 0 and self.n_channels > 0:
+            last = (self.n_frames - 1) * max(int(frame_stride), 0) + (self.n_channels - 1) * max(int(channel_stride), 0) \
+                + (2 * N_LONG - 1) * max(int(sample_stride), 0)
+            have = tensor.untyped_storage().nbytes() // tensor.element_size() - tensor.storage_offset()
+            if last >= have:
+                raise ValueError(f"PCM view leaves its storage: its last element is {last} past the tensor's first, "
+                                 f"the storage holds {have} from there")
         self.c = _lib.PacxPcm(tensor.data_ptr(), dt, self.n_channels, self.n_frames,
                               int(frame_stride), int(channel_stride), int(sample_stride))
 

@@ -102,11 +102,13 @@ def excerpt_case(name):
     return pcm, sr, rm.analysis(pcm, sr, True)
 
 
-def gpu_curve(A, pcm, sr, bs, cap, sentinel=True):
+def gpu_curve(A, pcm, sr, bs, cap, sentinel=True, view_of=None):
     """Encoder.rate_curve on the stream's blocks, into arrays that hold a sentinel -> (dict of NumPy arrays, encoder
-    state for further calls)"""
+    state for further calls).  view_of(enc, pcm): another view of the same blocks (tests/test_gpu_pcm_views.py)"""
     import torch
     cp, enc, view, flags = A.pacfile._rate_stream_setup(pcm, sr, cap, bs, None)
+    if view_of is not None:
+        view = view_of(enc, pcm)
     row, sub = enc.rate_curve_layout(cp.targetBitsPerSample)
     out = None
     if sentinel:
@@ -143,14 +145,8 @@ def check_solve(A, enc, dev_curve, host_curve, limit, lo_db, hi_db, what):
     return sol, ref
 
 
-# ------------------------------------------------------------------ 1. the curve, 2. the solve on it
-@pytest.mark.parametrize("name", sorted(SHAPES))
-def test_curve_and_solve_on_shapes(A, name):
-    """1, 2 and 3 channels (odd numbers of channel-frames), one hop, no flags, every window kind (start / stop flags
-    change J), digital silence and a dropped hop, the 32 and 96 kHz band layouts (the dummy band), a cap at which
-    short sub-blocks have a tiny J, the default cap"""
-    pcm, sr, bs, cap, a, model = shape_case(name)
-    host, dev, enc, view, flags = gpu_curve(A, pcm, sr, bs, cap)
+def compare_curve(name, a, cap, model, host, flags):
+    """the curve of the GPU (host arrays made with the sentinels) against the model's, with this file's bars"""
     assert (host["row"], host["sub_stride"]) == (model["row"], model["sub_stride"]) == am.layout(a, cap)
     if flags is not None:
         want = np.array([l * 1 + c * 2 + n * 4 for (l, c, n) in a["flags"]], np.uint8)
@@ -168,6 +164,17 @@ def test_curve_and_solve_on_shapes(A, name):
           f"max |worst - model| {err:.3g} dB")
     assert err <= WORST_TOL
     assert (host["worst"][~used] == SENTINEL_W).all() and (host["bits"][~used] == SENTINEL_B).all()
+
+
+# ------------------------------------------------------------------ 1. the curve, 2. the solve on it
+@pytest.mark.parametrize("name", sorted(SHAPES))
+def test_curve_and_solve_on_shapes(A, name):
+    """1, 2 and 3 channels (odd numbers of channel-frames), one hop, no flags, every window kind (start / stop flags
+    change J), digital silence and a dropped hop, the 32 and 96 kHz band layouts (the dummy band), a cap at which
+    short sub-blocks have a tiny J, the default cap"""
+    pcm, sr, bs, cap, a, model = shape_case(name)
+    host, dev, enc, view, flags = gpu_curve(A, pcm, sr, bs, cap)
+    compare_curve(name, a, cap, model, host, flags)
     kinds = {(bool(l), bool(c), bool(n)) for (l, c, n) in a["flags"]}
     if name == "windows":
         assert {(False, False, True), (True, False, False), (True, False, True), (False, True, False)} <= kinds

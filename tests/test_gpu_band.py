@@ -100,11 +100,14 @@ def excerpt_case(name):
 _GPU = {}
 
 
-def gpu_curve(A, key, pcm, sr, bs, cap):
+def gpu_curve(A, key, pcm, sr, bs, cap, view_of=None):
     """Encoder.band_curve on the stream's blocks, once per case -> dict: host arrays, device curve, enc, view, flags,
-    status (the words of a search that caps every unit: BitAlloc at the cap budget, as the curve runs it)"""
+    status (the words of a search that caps every unit: BitAlloc at the cap budget, as the curve runs it).
+    view_of(enc, pcm): another view of the same blocks (tests/test_gpu_pcm_views.py; its key must be its own)"""
     if key not in _GPU:
         cp, enc, view, flags = A.pacfile._rate_stream_setup(pcm, sr, cap, bs, None)
+        if view_of is not None:
+            view = view_of(enc, pcm)
         dev = enc.band_curve(view, flags, cp.targetBitsPerSample)
         host = {k: dev[k].cpu().numpy() for k in ("nmr", "cap", "cap_alloc")}
         status = enc.encode_pack_nmr(view, flags, -1000.0, cp.targetBitsPerSample)["status"].cpu().numpy()
