@@ -167,6 +167,12 @@ SIGNATURES = {
                                                 _P]),
     "pacx_band_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_double,
                                                 ctypes.c_double, _P, _P, _P, _P, _P]),
+    # seg_first, peak_bytes: int64 arrays in host memory; limit_bytes by value; floor, result [n_seg], result_stream
+    "pacx_rate_solve_peak": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                            ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                            _P, _P, _P, _P, _P, _P, _P]),
+    "pacx_band_solve_peak": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64,
+                                            ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
 }
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320

@@ -18,7 +18,8 @@
  *                     consecutive channel-frames (the whole stream is one stretch); the wave finds its frame's segment
  *                     in the boundaries (segment_of, rate_dev.h) and adds the frame's bytes to that segment's total:
  *                     integer sums, one 64-bit atomicAdd per workgroup and segment present.  k_rate.hip's k_solve_init /
- *                     k_solve_step decide per segment.
+ *                     k_solve_step decide per segment.  <true>: pacx_band_solve_peak's picks at max(stream target,
+ *                     segment floor), see there.
  *   k_band_sanitize   a caller's allocation made representable (below 2 -> 0, above maxMantBits -> maxMantBits), and
  *                     an all-zero allocation for a channel-frame whose record would leave PACX_PAYLOAD_STRIDE.
  *
@@ -260,7 +261,12 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, long l
 /* k_band_pick as a pick of the solve, with a state per segment: the wave takes the target its frame's segment has in
    flight and adds to that segment's total; a frame whose segment is done is not scanned before the last launch.
    final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose four frames lie in
-   one segment (every workgroup of a whole-stream solve) adds once, one that straddles a boundary once per wave. */
+   one segment (every workgroup of a whole-stream solve) adds once, one that straddles a boundary once per wave.
+   PEAK (pacx_band_solve_peak, stage B; k_rate.hip, k_solve_pick): the segments' states rest with their floor in mid,
+   the state in flight is the stream's, s[n_seg], and the wave's target is max(stream target, its segment's floor) --
+   two more words through the scalar cache.  Before the last launch a workgroup adds its frames to the stream's total,
+   once; the last launch adds per segment as above.  The instance without PEAK is the kernel as it was. */
+template <bool PEAK>
 __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, SolveState *__restrict__ s,
                                                                const long long *__restrict__ seg_first, int n_seg,
                                                                int search_steps, long long n_cf,
@@ -282,10 +288,14 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, So
     unsigned long long mine = 0ull;
     if (cf < n_cf) {                               /* wave-uniform, and so is everything read through seg */
         seg = segment_of(seg_first, n_seg, search_steps, cf);
-        const SolveState *mystate = s + seg;
-        if (final || !mystate->done)
-            mine = band_frame(T, cf, (double)mystate->mid / 64.0, nmr, cap, cap_alloc, final != 0, bit_alloc, n_bytes,
-                              capped, unit_sum[w], unit_miss[w]);
+        const SolveState *mystate = s + seg, *flying = PEAK ? s + n_seg : mystate;
+        if (final || !flying->done) {
+            int mid = flying->mid;
+            if (PEAK && mystate->mid > mid)
+                mid = mystate->mid;                /* the segment's floor */
+            mine = band_frame(T, cf, (double)mid / 64.0, nmr, cap, cap_alloc, final != 0, bit_alloc, n_bytes, capped,
+                              unit_sum[w], unit_miss[w]);
+        }
     }
     if (lane == 0) {
         part[w] = mine;
@@ -294,13 +304,14 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, So
     __syncthreads();
     const long long left = n_cf - (long long)blockIdx.x * PICK_WAVES;             /* >= 1: frames of this workgroup */
     const int last = left < PICK_WAVES ? (int)left - 1 : PICK_WAVES - 1;
-    if (seg_of[0] == seg_of[last]) {               /* workgroup-uniform: one segment */
+    const bool whole = PEAK && !final;             /* the stream's total takes the workgroup as it is */
+    if (whole || seg_of[0] == seg_of[last]) {      /* workgroup-uniform: one total */
         if (threadIdx.x == 0) {
             unsigned long long all = 0ull;
             for (int i = 0; i < PICK_WAVES; ++i)
                 all += part[i];
             if (all)
-                atomicAdd(&s[seg_of[0]].total, all);
+                atomicAdd(&s[whole ? n_seg : seg_of[0]].total, all);
         }
     } else if (lane == 0 && seg >= 0 && mine) {
         atomicAdd(&s[seg].total, mine);
@@ -388,8 +399,20 @@ void pacx_k::pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolv
 {
     const unsigned grid = (unsigned)((v.n_cf + PICK_WAVES - 1) / PICK_WAVES);
     pacx_solve_drive(v, st, [&](int search, int final) {
-        hipLaunchKernelGGL(k_band_pick_seg, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)v.ws, v.seg, v.n_seg,
-                           search, v.n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
+        hipLaunchKernelGGL(k_band_pick_seg<false>, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)v.ws, v.seg,
+                           v.n_seg, search, v.n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
+    });
+}
+
+void pacx_k::pacx_launch_band_solve_peak(const PacxTables &T, const PacxSolve &v, const PacxSolveStream &p,
+                                         const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                                         int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((v.n_cf + PICK_WAVES - 1) / PICK_WAVES);
+    pacx_peak_drive(v, p, st, [&](int search, int final, bool peak) {
+        const auto pick = peak ? k_band_pick_seg<true> : k_band_pick_seg<false>;
+        hipLaunchKernelGGL(pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, (SolveState *)v.ws, v.seg, v.n_seg, search,
+                           v.n_cf, nmr, cap, cap_alloc, final, bit_alloc, n_bytes, capped);
     });
 }
 

@@ -25,6 +25,11 @@
  *                      The host enqueues a fixed number of pick / step pairs and waits for none; pairs after a
  *                      segment's answer is known do nothing for it.  The whole-stream solve is the one-segment case:
  *                      its table {0, n_cf, limit} is written by k_solve_init, not uploaded.
+ *   k_peak_init, k_peak_step, k_peak_finish
+ *                      pacx_rate_solve_peak / pacx_band_solve_peak: the second level of the solve.  The segments' states
+ *                      hold their floors after the drive above without its last pick; one more state, the stream's,
+ *                      is driven by the same solve_step on picks at max(stream target, floor of the frame's segment)
+ *                      (k_solve_pick<true>, k_band_pick_seg<true>).
  * RateLds, RateUnit, rate_unit, wave_sum and SolveState live in rate_dev.h: k_band.hip shares them.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
@@ -390,7 +395,12 @@ __device__ __forceinline__ unsigned long long solve_block_sum(unsigned long long
    final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose frames lie in one
    segment (every workgroup of a whole-stream solve) sums them through the waves and adds once; one that straddles
    boundaries sums the runs of equal segments in LDS (the frames of a segment are consecutive) and adds once per
-   segment present. */
+   segment present.
+   PEAK (pacx_rate_solve_peak, stage B): the segments' states rest, their mid is the segment's floor, and the state in
+   flight is the stream's, s[n_seg]: every frame takes max(stream target, its segment's floor).  Before the last
+   launch a workgroup adds all its frames to the stream's total, once, whatever their segments; the last launch adds
+   per segment exactly as above.  The instance without PEAK is the kernel as it was. */
+template <bool PEAK>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__restrict__ s,
                                                              const long long *__restrict__ seg_first, int n_seg,
                                                              int search_steps, long long n_cf, int row, int sub_stride,
@@ -409,17 +419,22 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__rest
     unsigned long long mine = 0ull;
     if (cf < n_cf) {
         seg = segment_of(seg_first, n_seg, search_steps, cf);
-        const SolveState *mystate = s + seg;
-        if (final || !mystate->done)
-            mine = solve_frame(cf, (double)mystate->mid / 64.0, row, sub_stride, worst, bits, steps, final, budget,
-                               n_bytes, capped);
+        const SolveState *mystate = s + seg, *flying = PEAK ? s + n_seg : mystate;
+        if (final || !flying->done) {
+            int mid = flying->mid;
+            if (PEAK && mystate->mid > mid)
+                mid = mystate->mid;                /* the segment's floor */
+            mine = solve_frame(cf, (double)mid / 64.0, row, sub_stride, worst, bits, steps, final, budget, n_bytes,
+                               capped);
+        }
     }
     seg_of[t] = seg;
     __syncthreads();
     const long long left = n_cf - (long long)blockIdx.x * SOLVE_THREADS;          /* >= 1: frames of this workgroup */
     const int last = left < SOLVE_THREADS ? (int)left - 1 : SOLVE_THREADS - 1;
-    const int first_seg = seg_of[0];
-    if (first_seg == seg_of[last]) {               /* workgroup-uniform: one segment */
+    const bool whole = PEAK && !final;             /* the stream's total takes the workgroup as it is */
+    const int first_seg = whole ? n_seg : seg_of[0];
+    if (whole || first_seg == seg_of[last]) {      /* workgroup-uniform: one total */
         const unsigned long long all = solve_block_sum(mine, part);
         if (t == 0 && all)
             atomicAdd(&s[first_seg].total, all);
@@ -449,6 +464,50 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_step(SolveState *s, int
     const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
     if (i < n_seg)
         solve_step(s + i, limit[i], final, result + i);
+}
+
+/* ---- the second level (pacx_rate_solve_peak / pacx_band_solve_peak): the stream's state is s[n_seg] ---- */
+
+/* one thread per segment, after stage A: the state's mid is the segment's floor u_s.  Writes it out, clears the
+   segment's total and starts the stream's state */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_peak_init(SolveState *s, int n_seg, int t_lo, int t_hi,
+                                                            int32_t *__restrict__ floor)
+{
+    const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    if (i < n_seg) {
+        floor[i] = s[i].mid;
+        s[i].total = 0ull;
+    }
+    if (i == 0)
+        s[n_seg] = SolveState{t_lo - 1, t_hi, t_hi, 0, 0, 0, 0ull};
+}
+
+/* one thread: solve_step on the stream's total against the stream's limit; final: result_stream */
+__global__ void k_peak_step(SolveState *stream, long long limit, int final, pacx_rate_result *result)
+{
+    solve_step(stream, limit, final, result);
+}
+
+/* one thread per segment, after the last pick: result[seg] at T_s = max(t*, u_s), met measured there against the
+   segment's peak; the segments' totals summed into the stream's (integers: in any order) for k_peak_step's final */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_peak_finish(SolveState *s, int n_seg,
+                                                              const long long *__restrict__ peak,
+                                                              pacx_rate_result *__restrict__ result)
+{
+    __shared__ unsigned long long part[SOLVE_THREADS / 64];
+    const long long i = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    const SolveState *stream = s + n_seg;
+    unsigned long long total = 0ull;
+    if (i < n_seg) {
+        total = s[i].total;
+        s[i].total = 0ull;
+        result[i].t = stream->mid > s[i].mid ? stream->mid : s[i].mid;
+        result[i].met = total <= (unsigned long long)peak[i] ? 1 : 0;
+        result[i].total = (int64_t)total;
+    }
+    const unsigned long long all = solve_block_sum(total, part);
+    if (threadIdx.x == 0 && all)
+        atomicAdd(&s[n_seg].total, all);
 }
 
 }  // namespace
@@ -507,8 +566,35 @@ void pacx_k::pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int su
 {
     const unsigned grid = (unsigned)((v.n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
     pacx_solve_drive(v, st, [&](int search, int final) {
-        hipLaunchKernelGGL(k_solve_pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.seg, v.n_seg,
-                           search, v.n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
+        hipLaunchKernelGGL(k_solve_pick<false>, dim3(grid), dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.seg,
+                           v.n_seg, search, v.n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
+    });
+}
+
+/* the second level's init, step and finish for pacx_peak_drive (pacx_launch.h) */
+void pacx_k::pacx_launch_peak_init(const PacxSolve &v, const PacxSolveStream &p, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_peak_init, dim3((unsigned)((v.n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)), dim3(SOLVE_THREADS),
+                       0, st, (SolveState *)v.ws, v.n_seg, v.t_lo, v.t_hi, p.floor);
+}
+
+void pacx_k::pacx_launch_peak_step(const PacxSolve &v, const PacxSolveStream &p, int final, hipStream_t st)
+{
+    if (final)
+        hipLaunchKernelGGL(k_peak_finish, dim3((unsigned)((v.n_seg + SOLVE_THREADS - 1) / SOLVE_THREADS)),
+                           dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.n_seg, v.seg + v.n_seg + 1, v.result);
+    hipLaunchKernelGGL(k_peak_step, dim3(1), dim3(1), 0, st, (SolveState *)v.ws + v.n_seg, p.limit, final, p.result);
+}
+
+void pacx_k::pacx_launch_rate_solve_peak(const PacxSolve &v, const PacxSolveStream &p, int row, int sub_stride,
+                                         const double *worst, const int32_t *bits, const int32_t *steps,
+                                         int32_t *budget, int32_t *n_bytes, uint8_t *capped, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((v.n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
+    pacx_peak_drive(v, p, st, [&](int search, int final, bool peak) {
+        const auto pick = peak ? k_solve_pick<true> : k_solve_pick<false>;
+        hipLaunchKernelGGL(pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.seg, v.n_seg, search,
+                           v.n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
     });
 }
 

@@ -108,7 +108,8 @@ struct pacx_handle {
     long long ws_thr_cf;              /* capacity of ws_thr (0 until the first pacx_nmr_batch) */
     double *ws_thr;                   /* [cf][1024] masked threshold, dB SPL     */
     uint32_t *ws_rate_status;         /* [cf] status words of pacx_rate_curve_batch's front end (capacity ws_thr_cf) */
-    long long ws_solve_n;             /* states ws_solve holds: 1 for the plain solves, n_seg for the segmented */
+    long long ws_solve_n;             /* states ws_solve holds: 1 for the plain solves, n_seg for the segmented, n_seg + 1
+                                         for the peak solves (the stream's state behind the segments') */
     char *ws_solve;                   /* [ws_solve_n] the solve's state per segment */
     long long *ws_seg;                /* [3 ws_solve_n] a solve's boundaries [n_seg + 1], then its limits [n_seg]: uploaded by
                                          the segmented solves, written by the init kernel for the plain ones */
@@ -1967,14 +1968,14 @@ static int check_segments(pacx_handle *h, const char *what, int64_t n_cf, int64_
     return PACX_OK;
 }
 
-/* room for n_seg states, and the boundaries and limits in ws_seg: copied to the pinned staging buffer before this
-   returns (the caller's arrays are free again), from there on `st`.  The staging buffer is the handle's one, so the
-   upload before this one is waited for first; it has long run unless the caller queues segmented solves back to
-   back. */
+/* room for n_seg + more_states states, and the boundaries and limits in ws_seg: copied to the pinned staging buffer
+   before this returns (the caller's arrays are free again), from there on `st`.  The staging buffer is the handle's
+   one, so the upload before this one is waited for first; it has long run unless the caller queues segmented solves
+   back to back. */
 static int upload_segments(pacx_handle *h, int64_t n_seg, const int64_t *seg_first, const int64_t *limit_bytes,
-                           hipStream_t st)
+                           int64_t more_states, hipStream_t st)
 {
-    int rc = grow(h, GROW_SOLVE, n_seg);
+    int rc = grow(h, GROW_SOLVE, n_seg + more_states);
     if (rc)
         return rc;
     if (!h->ev_seg)
@@ -1996,16 +1997,19 @@ static int upload_segments(pacx_handle *h, int64_t n_seg, const int64_t *seg_fir
     return PACX_OK;
 }
 
-/* The four solves, checked and launched in one place.  kind: SOLVE_RATE on a rate curve (curve, a, b = worst, bits,
+/* The six solves, checked and launched in one place.  kind: SOLVE_RATE on a rate curve (curve, a, b = worst, bits,
    steps with rows of `row`; per_cf = budget) or SOLVE_BAND on a band curve (nmr, cap, cap_alloc; bit_alloc).
    segmented: n_seg segments from the host arrays seg_first and limit_bytes, uploaded.  Else the whole stream as one
    segment: seg_first is not given, limit_bytes points at the one limit, which reaches the device as an argument of
-   the init kernel -- no staging buffer, no event, nothing the host waits for -- and the workspace grows to one state. */
+   the init kernel -- no staging buffer, no event, nothing the host waits for -- and the workspace grows to one state.
+   peak (include/pacx.h, pacx_rate_solve_peak): a segmented solve whose limits are the peaks, with the stream's limit,
+   the floors and the stream's result beside it and one more state, the stream's, behind the segments'. */
 enum { SOLVE_RATE, SOLVE_BAND };
 static int solve(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t row, int32_t sub_stride,
                  const double *curve, const int32_t *a, const int32_t *b, bool segmented, int64_t n_seg,
                  const int64_t *seg_first, const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db,
-                 int32_t *per_cf, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream)
+                 int32_t *per_cf, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream,
+                 const PacxSolveStream *peak = nullptr)
 {
     if (!h)
         return PACX_E_ARG;
@@ -2013,7 +2017,8 @@ static int solve(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32
         return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
     if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (!result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)))
+    if (!result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)) ||
+        (peak && (!peak->floor || !peak->result)))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
     if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
         return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
@@ -2022,15 +2027,21 @@ static int solve(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32
         rc = check_segments(h, what, n_cf, n_seg, seg_first, limit_bytes);
     else if (*limit_bytes < 0)
         rc = fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    if (!rc && peak && peak->limit < 0)
+        rc = fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
     if (rc || (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
         return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = segmented ? upload_segments(h, n_seg, seg_first, limit_bytes, st) : grow(h, GROW_SOLVE, 1)))
+    if ((rc = segmented ? upload_segments(h, n_seg, seg_first, limit_bytes, peak ? 1 : 0, st) : grow(h, GROW_SOLVE, 1)))
         return rc;
     const PacxSolve v = {h->ws_solve, h->ws_seg, (int)n_seg, segmented ? nullptr : (const long long *)limit_bytes,
                          n_cf, t_lo, t_hi, result};
-    if (kind == SOLVE_RATE)
+    if (peak && kind == SOLVE_RATE)
+        pacx_launch_rate_solve_peak(v, *peak, row, sub_stride, curve, a, b, per_cf, n_bytes, capped, st);
+    else if (peak)
+        pacx_launch_band_solve_peak(h->T, v, *peak, curve, a, b, per_cf, n_bytes, capped, st);
+    else if (kind == SOLVE_RATE)
         pacx_launch_rate_solve_segments(v, row, sub_stride, curve, a, b, per_cf, n_bytes, capped, st);
     else
         pacx_launch_band_solve_segments(h->T, v, curve, a, b, per_cf, n_bytes, capped, st);
@@ -2054,6 +2065,17 @@ extern "C" int pacx_rate_solve_segments(pacx_handle *h, int64_t n_cf, int32_t ro
 {
     return solve(h, SOLVE_RATE, "pacx_rate_solve_segments", n_cf, row, sub_stride, worst, bits, steps, true, n_seg,
                  seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, stream);
+}
+
+extern "C" int pacx_rate_solve_peak(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                                    const int32_t *bits, const int32_t *steps, int64_t n_seg, const int64_t *seg_first,
+                                    const int64_t *peak_bytes, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                                    int32_t *budget, int32_t *n_bytes, uint8_t *capped, int32_t *floor,
+                                    pacx_rate_result *result, pacx_rate_result *result_stream, void *stream)
+{
+    const PacxSolveStream peak = {limit_bytes, floor, result_stream};
+    return solve(h, SOLVE_RATE, "pacx_rate_solve_peak", n_cf, row, sub_stride, worst, bits, steps, true, n_seg,
+                 seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, stream, &peak);
 }
 
 /* ---- bits handed to the bands one by one ---- */
@@ -2092,6 +2114,17 @@ extern "C" int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const doub
 {
     return solve(h, SOLVE_BAND, "pacx_band_solve_segments", n_cf, 0, 0, nmr, cap, cap_alloc, true, n_seg, seg_first,
                  limit_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream);
+}
+
+extern "C" int pacx_band_solve_peak(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                    const int32_t *cap_alloc, int64_t n_seg, const int64_t *seg_first,
+                                    const int64_t *peak_bytes, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                                    int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, int32_t *floor,
+                                    pacx_rate_result *result, pacx_rate_result *result_stream, void *stream)
+{
+    const PacxSolveStream peak = {limit_bytes, floor, result_stream};
+    return solve(h, SOLVE_BAND, "pacx_band_solve_peak", n_cf, 0, 0, nmr, cap, cap_alloc, true, n_seg, seg_first,
+                 peak_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream, &peak);
 }
 
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,

@@ -136,7 +136,7 @@ void pacx_launch_rate_curve(const PacxTables &T, const uint8_t *flags, int n_ch,
 /* The solve, the only one: one target per segment of consecutive channel-frames, found on stored curves.  A whole-
    stream solve (pacx_rate_solve, pacx_band_solve) is the solve of one segment.  Nothing here waits for the device. */
 struct PacxSolve {
-    void *ws;                         /* n_seg states of pacx_rate_solve_ws_bytes() bytes */
+    void *ws;                         /* n_seg states of pacx_rate_solve_ws_bytes() bytes (a peak solve: one more) */
     long long *seg;                   /* device: seg_first [n_seg + 1], then limit [n_seg] */
     int n_seg;
     const long long *one_limit;       /* nullptr: seg is uploaded.  Else n_seg == 1, and the init kernel writes
@@ -173,7 +173,46 @@ void pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int sub_stride
                                      const int32_t *bits, const int32_t *steps, int32_t *budget, int32_t *n_bytes,
                                      uint8_t *capped, hipStream_t st);
 
-/* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve_segments (nmr
+/* The second level (pacx_rate_solve_peak / pacx_band_solve_peak): a limit for the whole batch above the segments'
+   peaks.  v is a segmented solve with the peaks as its limits and ws holding n_seg + 1 states: the last one is the
+   stream's. */
+struct PacxSolveStream {
+    long long limit;                  /* for the whole batch: a kernel argument */
+    int32_t *floor;                   /* [n_seg] */
+    pacx_rate_result *result;         /* the stream's, one entry */
+};
+void pacx_launch_peak_init(const PacxSolve &v, const PacxSolveStream &p, hipStream_t st);
+void pacx_launch_peak_step(const PacxSolve &v, const PacxSolveStream &p, int final, hipStream_t st);
+
+/* the driver.  Stage A: pacx_solve_drive without its last pair -- after pacx_rate_solve_pairs - 1 pairs every
+   segment's answer is in its state, and nothing needs the outputs at it.  Then the init of the second level (floors
+   out, the stream's state started) and stage B: the same number of pairs as a solve, on the stream's state, with
+   pick(search_steps, final, true) taking every frame at max(stream target, its segment's floor); the last step
+   writes result[n_seg] (one launch) and the stream's (one more).  With P = pacx_rate_solve_pairs(t_lo, t_hi):
+   4 P + 1 launches, 2 P + 2 without frames, whatever the data; nothing waits for the device. */
+template <class Pick>
+inline void pacx_peak_drive(const PacxSolve &v, const PacxSolveStream &p, hipStream_t st, Pick pick)
+{
+    const int pairs = pacx_rate_solve_pairs(v.t_lo, v.t_hi), search = pacx_segment_search_steps(v.n_seg);
+    pacx_launch_solve_init_segments(v, st);
+    for (int q = 0; q < pairs - 1; ++q) {
+        if (v.n_cf > 0)
+            pick(search, 0, false);
+        pacx_launch_solve_step_segments(v, 0, st);
+    }
+    pacx_launch_peak_init(v, p, st);
+    for (int q = 0; q < pairs; ++q) {
+        const int final = q == pairs - 1;
+        if (v.n_cf > 0)
+            pick(search, final, true);
+        pacx_launch_peak_step(v, p, final, st);
+    }
+}
+void pacx_launch_rate_solve_peak(const PacxSolve &v, const PacxSolveStream &p, int row, int sub_stride,
+                                 const double *worst, const int32_t *bits, const int32_t *steps, int32_t *budget,
+                                 int32_t *n_bytes, uint8_t *capped, hipStream_t st);
+
+/* k_band.hip: the band-by-band allocation of pacx_band_curve_batch / pacx_band_pick / pacx_band_solve_segments / _peak (nmr
    float64 [n_cf][band_stride][PACX_BAND_CAND], cap int32 [n_cf][8], cap_alloc int32 [n_cf][band_stride]; the solve is
    the one above with a pick of its own) and the sanitised copy of a caller's allocation (in == out allowed) */
 void pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
@@ -186,6 +225,9 @@ void pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, c
 void pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolve &v, const double *nmr, const int32_t *cap,
                                      const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
                                      hipStream_t st);
+void pacx_launch_band_solve_peak(const PacxTables &T, const PacxSolve &v, const PacxSolveStream &p, const double *nmr,
+                                 const int32_t *cap, const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes,
+                                 uint8_t *capped, hipStream_t st);
 void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
                                int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);
 

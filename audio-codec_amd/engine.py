@@ -355,12 +355,14 @@ class Encoder:
         out["row"], out["sub_stride"], out["flags"] = row, sub, fl
         return out
 
-    def _solve(self, what, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db):
-        """The four solves: `what` names the method, band_* on a band curve and rate_* on a rate curve, *_segments with
-        seg_first and one limit per segment, else the whole stream with its one limit (the plain C entry point).  Checks
-        the curve, makes the outputs, calls pacx_<what> and decodes the pacx_rate_result of every segment: t, met,
-        total (int64) in four int32."""
-        band, segmented = what.startswith("band"), what.endswith("_segments")
+    def _solve(self, what, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None):
+        """The six solves: `what` names the method, band_* on a band curve and rate_* on a rate curve, *_segments with
+        seg_first and one limit per segment, *_peak with those (the limits are then the peaks) and stream_limit for the
+        whole batch, else the whole stream with its one limit (the plain C entry point).  Checks the curve, makes the
+        outputs, calls pacx_<what> and decodes the pacx_rate_result of every segment: t, met, total (int64) in four
+        int32."""
+        band, peak = what.startswith("band"), what.endswith("_peak")
+        segmented = peak or what.endswith("_segments")
         if band:
             *arrays, n_cf, out = self._band_arrays(curve, what)
             head, per_cf = [], "bit_alloc"
@@ -379,14 +381,30 @@ class Encoder:
             limits = [ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data]
         else:
             limits = [ctypes.c_int64(int(limit_bytes))]
-        result = torch.zeros((len(limit) if segmented else 1, 4), dtype=torch.int32, device=self.device)
+        n_seg = len(limit) if segmented else 1
+        # a peak solve's floors and the stream's result ride behind the segments' results: one tensor, one copy back
+        result = torch.zeros((n_seg + (n_seg + 3) // 4 + 1 if peak else n_seg, 4), dtype=torch.int32, device=self.device)
+        more = []
+        if peak:
+            if int(stream_limit) != stream_limit or stream_limit < 0:
+                raise ValueError(f"{what}: limit_bytes = {stream_limit!r}: a whole number of bytes, not negative")
+            limits.append(ctypes.c_int64(int(stream_limit)))
+            more = [_ptr(result[n_seg + 1:]), _ptr(result), _ptr(result[n_seg:])]       # floor, result, result_stream
+        else:
+            more = [_ptr(result)]
         self._call_rate("pacx_" + what, ctypes.c_int64(n_cf), *head, *(_ptr(t) for t in arrays), *limits,
                         ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(out[per_cf]), _ptr(out["n_bytes"]),
-                        _ptr(out["capped"]), _ptr(result), self._stream())
+                        _ptr(out["capped"]), *more, self._stream())
+        grid = float(_lib.RATE_TARGET_GRID)
         res = result.cpu().numpy()
         out["capped"] = out["capped"].bool()
-        out.update({"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID), "met": res[:, 1] != 0,
-                    "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]})
+        out.update({"target_nmr_db": res[:n_seg, 0].astype(np.float64) / grid, "met": res[:n_seg, 1] != 0,
+                    "total_bytes": res[:n_seg, 2:].copy().view(np.int64)[:, 0]})
+        if peak:
+            out.update({"floor_nmr_db": res[n_seg + 1:].reshape(-1)[:n_seg].astype(np.float64) / grid,
+                        "stream_target_nmr_db": float(res[n_seg, 0]) / grid, "stream_met": bool(res[n_seg, 1]),
+                        "stream_total_bytes": int(res[n_seg:n_seg + 1, 2:].copy().view(np.int64)[0, 0])})
+            out["pinned"] = out["target_nmr_db"] > out["stream_target_nmr_db"]
         if not segmented:
             out.update({"target_nmr_db": float(out["target_nmr_db"][0]), "met": bool(out["met"][0]),
                         "total_bytes": int(out["total_bytes"][0])})
@@ -425,6 +443,15 @@ class Encoder:
         sequences.  -> dict budget, n_bytes, capped as rate_solve, and NumPy arrays target_nmr_db [n_seg] float64, met
         [n_seg] bool, total_bytes [n_seg] int64."""
         return self._solve("rate_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
+
+    def rate_solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """An average for the stream and a peak for every segment (pacx_rate_solve_peak, include/pacx.h): one target for
+        the whole curve within limit_bytes, and for a segment that would exceed its peak_bytes[s] there the lowest
+        target at which it fits, its floor.  Segments as rate_solve_segments.  -> dict budget, n_bytes, capped as
+        rate_solve; NumPy arrays per segment target_nmr_db (max of the stream's target and the floor), met (the bytes at
+        that target against the peak), total_bytes, floor_nmr_db, pinned (target above the stream's); and
+        stream_target_nmr_db, stream_met, stream_total_bytes for the whole."""
+        return self._solve("rate_solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
 
     def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
@@ -482,6 +509,11 @@ class Encoder:
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,
         n_bytes, capped as band_solve, and NumPy arrays target_nmr_db, met, total_bytes [n_seg]."""
         return self._solve("band_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
+
+    def band_solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """rate_solve_peak on a band curve (pacx_band_solve_peak, include/pacx.h).  -> dict bit_alloc, n_bytes, capped as
+        band_solve and rate_solve_peak's results per segment and for the stream."""
+        return self._solve("band_solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

@@ -533,35 +533,71 @@ def _abr_range(nmr_range_db):
     return lo, hi
 
 
+def _check_peak(peak_kbps_per_channel, segment_hops):
+    """the peak_kbps_per_channel keyword, before any GPU work"""
+    if peak_kbps_per_channel is None:
+        return
+    if segment_hops is None:
+        raise ValueError("peak_kbps_per_channel goes with segment_hops: a peak is the rate of a segment")
+    if not peak_kbps_per_channel > 0:
+        raise ValueError("peak_kbps_per_channel must be positive")
+
+
 def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db,
-                       allocation="budget", segment_hops=None):
+                       allocation="budget", segment_hops=None, peak_kbps_per_channel=None):
     """One curve, one solve + second pass per size.  sizes: list of (kbps_per_channel, max_bytes).
     -> list of (.pac bytes, solve dict, outputs of encode_pack_budget -- allocation "band": of encode_pack_alloc --,
     body limit), the encoder.  segment_hops: one segmented solve per size instead; the solve dict is
     Encoder.rate_solve_segments' / band_solve_segments' plus "segments" (first_block, blocks, limit_bytes per segment),
-    the body limit the sum of the segments'."""
+    the body limit the sum of the segments'.  peak_kbps_per_channel: one peak solve per size (Encoder.rate_solve_peak /
+    band_solve_peak): the size is the stream's and the body limit, the segments' limit_bytes are the peaks."""
     band = _check_allocation(allocation)
     lo, hi = _abr_range(nmr_range_db)
+    peak = peak_kbps_per_channel is not None
+    _check_peak(peak_kbps_per_channel, segment_hops)
     if segment_hops is not None:
-        if any(b is not None for _, b in sizes):
+        if not peak and any(b is not None for _, b in sizes):
             raise ValueError("segment_hops goes with kbps_per_channel: max_bytes is the size of a file, not of a segment")
-        if any(k is None for k, _ in sizes):
+        if not peak and any(k is None for k, _ in sizes):
             raise ValueError("give exactly one of kbps_per_channel and max_bytes")
         segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
     head = header_bytes(cp)
-    limits = [None] * len(sizes) if segment_hops is not None else [_abr_limit(cp, view, head, k, b) for k, b in sizes]
+    limits = [None] * len(sizes) if segment_hops is not None and not peak else \
+        [_abr_limit(cp, view, head, k, b) for k, b in sizes]
     curve = enc.band_curve(view, flags, cp.targetBitsPerSample) if band else \
         enc.rate_curve(view, flags, cp.targetBitsPerSample)
     n_ch = cp.nChannels
+
+    def unreachable(limit, total):
+        return (f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
+                f"{total} bytes ({len(head) + total} with the header), the "
+                f"smallest size this range of targets gives")
+
     done = []
     for (kbps, _), limit in zip(sizes, limits):
         if segment_hops is None:        # the whole stream: the partition [0, n_cf] with its one limit, the plain method
             sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
-            unmet = None if sol["met"] else \
-                (f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
-                 f"{sol['total_bytes']} bytes ({len(head) + sol['total_bytes']} with the header), the "
-                 f"smallest size this range of targets gives")
+            unmet = None if sol["met"] else unreachable(limit, sol["total_bytes"])
+        elif peak:                      # the stream's limit above the segments' peaks
+            first, count, seg_limit = segment_limits(peak_kbps_per_channel, n_ch, cp.sampleRate, view.n_frames,
+                                                     segment_hops)
+            seg_first = np.append(first, view.n_frames) * n_ch
+            sol = enc.band_solve_peak(curve, seg_first, seg_limit, limit, lo, hi) if band else \
+                enc.rate_solve_peak(curve, seg_first, seg_limit, limit, lo, hi)
+            s = int(np.argmin(sol["met"]))
+            if not sol["stream_met"]:
+                unmet = unreachable(limit, sol["stream_total_bytes"])
+            elif sol["met"].all():
+                unmet = None
+            else:
+                unmet = (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) exceeds its peak of "
+                         f"{int(seg_limit[s])} bytes: it takes {int(sol['total_bytes'][s])} bytes; ")
+                unmet += (f"it cannot be reached at all: its floor is the highest target, {hi:g} dB, the smallest size "
+                          f"this range of targets gives") if sol["floor_nmr_db"][s] == hi else \
+                    (f"it fits at its own floor, {sol['floor_nmr_db'][s]:g} dB, but not at the stream's target, "
+                     f"{sol['stream_target_nmr_db']:g} dB (its bytes rise with the target there)")
+            sol["segments"] = {"first_block": first, "blocks": count, "limit_bytes": seg_limit}
         else:
             first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
@@ -586,7 +622,8 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
 
 def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
                       block_switching=False, header_samples=None, nmr_range_db=(-30, 30), use_vq=False, use_sbr=False,
-                      chunk_hops=None, n_lines=1024, allocation="budget", segment_hops=None):
+                      chunk_hops=None, n_lines=1024, allocation="budget", segment_hops=None,
+                      peak_kbps_per_channel=None):
     """Whole-stream encode to an average bit rate -> .pac bytes: the best constant quality that fits a size.  One
     target NMR for the whole stream, the smallest on the grid of 1/64 dB in nmr_range_db (by the bisection of
     include/pacx.h, pacx_rate_solve) at which the stream of encode_stream_nmr(target) stays within the size; the
@@ -609,12 +646,21 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
     the grid at which its own records fit (pacx_rate_solve_segments / pacx_band_solve_segments: one curve, one solve
     for all segments, one second pass).  The records of a segment are those of encode_stream_nmr at that segment's
     target.  ValueError when a segment cannot be reached; the message names the first such segment, its first block,
-    its limit and the bytes it takes at the highest target."""
+    its limit and the bytes it takes at the highest target.
+    peak_kbps_per_channel=P (P > 0, with segment_hops=S): constrained VBR -- the size, kbps_per_channel or max_bytes
+    (a file size is meaningful here), is the whole stream's as without segments, and segment_limits(P, ...) gives every
+    segment a peak.  Every segment that fits its peak at the stream's target takes the stream's target; one that does
+    not is pinned to its floor, the lowest target at which it fits, and what it gives up the others spend
+    (pacx_rate_solve_peak / pacx_band_solve_peak: one curve, one solve, one second pass).  ValueError when the stream's
+    size cannot be reached (the message above) or a segment exceeds its peak at its final target; the message names
+    the first such segment, its first block, its peak and its bytes, and says whether the segment cannot be reached at
+    all or fits at its own floor but not at the stream's target (where its bytes are not monotone in the target)."""
     _check_allocation(allocation)
     if use_vq or use_sbr or chunk_hops or int(n_lines) != 1024:
         raise NotImplementedError("average-bit-rate streams: scalar mantissas, nMDCTLines 1024, one batch")
     done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
-                                 block_switching, header_samples, nmr_range_db, allocation, segment_hops)
+                                 block_switching, header_samples, nmr_range_db, allocation, segment_hops,
+                                 peak_kbps_per_channel)
     return done[0][0]
 
 

@@ -338,7 +338,7 @@ def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=3
 
 def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
                           block_switching=False, header_samples=None, nmr_range_db=(-30, 30), allocation="budget",
-                          segment_hops=None):
+                          segment_hops=None, peak_kbps_per_channel=None):
     """pacfile.encode_stream_abr with a Report: -> (.pac bytes, Report, info).  A list for kbps_per_channel or for
     max_bytes gives a list of such triples, all solved from one rate curve.  info, for the n + 2 blocks the driver
     submits, is encode_stream_to_nmr's (budget, bit_alloc, capped, written, kbps_per_channel: achieved, allocation) and
@@ -347,7 +347,12 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
     segment_hops (pacfile.encode_stream_abr; with a list of rates: one curve, one segmented solve per rate): info gains
       segments       dict of arrays per segment: first_block, blocks, limit_bytes, total_bytes, target_nmr_db;
     target_nmr_db becomes float64 [blocks], every block's segment's target, limit_bytes and total_bytes the sums over
-    the segments."""
+    the segments.
+    peak_kbps_per_channel (with segment_hops; pacfile.encode_stream_abr): the size is the stream's again, limit_bytes
+    and total_bytes are the stream's, segments["limit_bytes"] holds the peaks, and
+      segments       gains floor_nmr_db (the lowest target at which the segment fits its peak) and pinned (bool: its
+                     target is above the stream's);
+      stream_target_nmr_db  the one target of every segment that is not pinned."""
     from . import pacfile
     many = isinstance(kbps_per_channel, (list, tuple)) or isinstance(max_bytes, (list, tuple))
     if many:
@@ -357,7 +362,8 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
     else:
         sizes = [(kbps_per_channel, max_bytes)]
     done, enc = pacfile._encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching,
-                                           header_samples, nmr_range_db, allocation, segment_hops)
+                                           header_samples, nmr_range_db, allocation, segment_hops,
+                                           peak_kbps_per_channel)
     n_ch = np.asarray(pcm).shape[1]
     res = []
     for data, sol, out, limit in done:
@@ -367,6 +373,8 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
         if segments is not None:
             segments = dict(segments, total_bytes=total, target_nmr_db=target)
             target, total = np.repeat(target, segments["blocks"]), int(total.sum())
+            if "pinned" in sol:
+                segments.update(floor_nmr_db=sol["floor_nmr_db"], pinned=sol["pinned"])
         info = {
             "allocation": allocation,
             "target_nmr_db": target,
@@ -383,6 +391,8 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
             info["budget"] = sol["budget"].cpu().numpy().reshape(n_blocks, n_ch, _lib.SUB)
         if segments is not None:
             info["segments"] = segments
+        if "stream_target_nmr_db" in sol:
+            info["stream_target_nmr_db"] = sol["stream_target_nmr_db"]
         res.append((data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info))
     return res if many else res[0]
 

@@ -931,6 +931,74 @@ int pacx_band_solve_segments(pacx_handle *h, int64_t n_cf, const double *nmr, co
                              const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc,
                              int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result, void *stream);
 
+/* ---- an average for the stream, a peak for every stretch of it: the two solves on two levels ---- */
+
+/*
+ * The whole-stream solves spend the bytes best, but a loud passage may take several times the nominal rate; the
+ * segmented solves bound every segment, but a quiet segment cannot pass on what it does not need.  These two hold both
+ * constraints: one target for the stream within limit_bytes, and a higher one only for a segment that would exceed
+ * its peak at the stream's.
+ *
+ * Arguments as pacx_rate_solve_segments / pacx_band_solve_segments -- n_seg, seg_first and the bounds under the same
+ * rules and the same host-side checks; the per-segment array of limits is here called peak_bytes -- and:
+ *
+ *   limit_bytes:         >= 0, by value, for the whole batch (a kernel argument, as the plain solves')
+ *   floor (out):         int32 [n_seg] in device memory, u_s on the grid
+ *   result (out):        pacx_rate_result [n_seg] in device memory
+ *   result_stream (out): one pacx_rate_result in device memory
+ *
+ *   stage A   u_s      = the t that pacx_*_solve_segments(seg_first, peak_bytes) finds for segment s
+ *                        (t_hi where the segment cannot be reached);   floor[s] = u_s
+ *   stage B   T_s(t)   = max(t, u_s)
+ *             total*(t) = sum over s of total_s(T_s(t)),  total_s = the plain solve's total over the frames of s
+ *             the plain solve's decision, unchanged, on total* against limit_bytes: the probe of t_hi, met* = 0 and
+ *             t* = t_hi if it does not fit, else the same bisection with lo = t_lo - 1, hi = t_hi  ->  t*, met*
+ *   outputs   per cf: the pick's outputs at T_seg(cf)(t*)
+ *             result_stream = { t*, met*, total*(t*) }
+ *             result[s]     = { t: T_s(t*),  met: total_s(T_s(t*)) <= peak_bytes[s],  total: total_s(T_s(t*)) }
+ *
+ * What follows from it:
+ *   - With peaks that never bind every u_s = t_lo, and every output is pacx_rate_solve's / pacx_band_solve's with
+ *     limit_bytes (result[s] then carries t* and the segment's share of the total).
+ *   - With a limit_bytes that never binds t* = t_lo, and every output is pacx_*_solve_segments' with peak_bytes.
+ *   - A segment is pinned iff result[s].t > result_stream.t.
+ *   - An empty segment gives floor = t_lo, met = 1, total = 0 (and t = t*).  n_cf = 0 gives t* = t_lo, met* = 1.
+ *   - result[s].met is measured at the final target, not inherited from stage A.  Where total_s is non-increasing in
+ *     the target, a segment that stage A could reach stays within its peak at any T_s >= u_s; band allocation with
+ *     no capped unit in the segment is such a case (see pacx_band_curve_batch).  Elsewhere a unit leaves its cap as
+ *     the target rises, or the budget curve's worst[j] is not monotone: the total may then rise, and met = 0 reports
+ *     it.  This is the bisection's answer, as for the existing solves.  Nothing re-pins such a segment.
+ *
+ * On the device there stays one solve.  Stage A is the segmented solve's init and its pick / step pairs without the
+ * last pair: after P - 1 pairs, P = 2 + ceil(log2(t_hi - t_lo + 2)), every segment's state holds u_s, and nothing
+ * needs the outputs at it.  One kernel, a thread per segment, writes floor, clears the segments' totals and starts one
+ * more state, the stream's, kept in the handle behind the segments'.  Stage B drives that state through P pairs with
+ * the plain decision: its picks are the same two pick kernels in a second instance that takes every frame at
+ * max(stream target, floor of its segment) -- before the last pick a workgroup adds all its frames to the stream's
+ * total in one 64-bit integer atomicAdd, the last pick writes the per-cf outputs and adds per segment exactly as the
+ * segmented solve's.  A last kernel with a thread per segment writes result[s] and sums the segments' totals into the
+ * stream's, and one with a single thread writes result_stream.  In all
+ *
+ *     4 P + 1 kernel launches (2 P + 2 when n_cf = 0) and the one upload of seg_first and peak_bytes,
+ *
+ * fixed by t_lo, t_hi and whether there are frames; a segmented solve takes 2 P + 1.  No host wait between the
+ * stages; the upload goes through the handle's pinned buffer under pacx_rate_solve_segments' rule.  All sums are
+ * 64-bit integers: no result depends on the order of execution.  Plain, segmented and peak solves may follow one
+ * another on a handle's stream in any order.
+ *
+ * PACX_E_UNSUPPORTED and PACX_E_ARG as pacx_*_solve_segments; PACX_E_ARG also for a negative limit_bytes and a null
+ * floor or result_stream.
+ */
+int pacx_rate_solve_peak(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                         const int32_t *bits, const int32_t *steps, int64_t n_seg, const int64_t *seg_first,
+                         const int64_t *peak_bytes, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                         int32_t *budget, int32_t *n_bytes, uint8_t *capped, int32_t *floor, pacx_rate_result *result,
+                         pacx_rate_result *result_stream, void *stream);
+int pacx_band_solve_peak(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                         int64_t n_seg, const int64_t *seg_first, const int64_t *peak_bytes, int64_t limit_bytes,
+                         double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                         int32_t *floor, pacx_rate_result *result, pacx_rate_result *result_stream, void *stream);
+
 /*
  * The second pass: pacx_encode_pack_budget_batch with the allocation of every band given by the caller instead of a
  * budget per unit.  bit_alloc_in: int32 [n_cf][band_stride] (may be the bit_alloc output itself); a value below 2
