@@ -277,6 +277,14 @@ static int build_bands(pacx_handle *h, const int32_t *lines, int nb, int total,
     return upload(h, map.data(), total, d_map);
 }
 
+/* bytes of one record (coder/pacfile.py:342-361, 552-565): per (sub-)block the overall scale, a size and a scale
+   factor per band and mant_bits of mantissas; eight of them in a short frame; plus 4 bits, rounded up */
+static long long record_bytes(int n_scale_bits, int n_mant_size_bits, int nb, long long mant_bits, bool is_short)
+{
+    const long long unit = n_scale_bits + (long long)nb * (n_mant_size_bits + n_scale_bits) + mant_bits;
+    return ((is_short ? PACX_SUB : 1) * unit + 4 + 7) >> 3;
+}
+
 extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
 {
     if (!cfg || !out)
@@ -513,6 +521,22 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     T.n_scale_bits = cfg->n_scale_bits;
     T.n_mant_size_bits = cfg->n_mant_size_bits;
     T.target_bps = cfg->target_bits_per_sample;
+    {
+        /* the packers build a record in PACX_PAYLOAD_WORDS LDS words and copy it to a slot of PACX_PAYLOAD_STRIDE
+           bytes: the longest record of these layouts and widths (every band at maxMantBits) has to fit */
+        const int max_mant = T.n_mant_size_bits < 4 ? 1 << T.n_mant_size_bits : 16;
+        const int ns = T.n_scale_bits, nm = T.n_mant_size_bits;
+        const long long lon = record_bytes(ns, nm, T.nb_long, (long long)max_mant * covered_long, false);
+        const long long sht = record_bytes(ns, nm, T.nb_short, (long long)max_mant * covered_short, true);
+        const long long longest = lon > sht ? lon : sht;
+        if (longest > PACX_PAYLOAD_STRIDE) {
+            g_create_err = "pacx_create: the longest record of these band layouts at nScaleBits " + std::to_string(ns) +
+                           ", nMantSizeBits " + std::to_string(nm) + " takes " + std::to_string(longest) +
+                           " bytes, a payload slot holds " + std::to_string(PACX_PAYLOAD_STRIDE);
+            pacx_destroy(h);
+            return PACX_E_UNSUPPORTED;
+        }
+    }
 
     /* coding variant */
     T.guard = cfg->guard ? 1 : 0;
@@ -1859,8 +1883,7 @@ static long long band_record_bound(const PacxTables &T, double max_bps)
             const long long all = (long long)max_mant * m;
             const long long j = pacx_rate_steps(max_bps, m, sh, lon, T.n_scale_bits, T.n_mant_size_bits, nb);
             const long long mant = 32 * j < all ? 32 * j : all;
-            const long long unit = T.n_scale_bits + (long long)nb * (T.n_mant_size_bits + T.n_scale_bits) + mant;
-            const long long bytes = ((sh ? PACX_SUB : 1) * unit + 4 + 7) >> 3;
+            const long long bytes = record_bytes(T.n_scale_bits, T.n_mant_size_bits, nb, mant, sh != 0);
             worst = bytes > worst ? bytes : worst;
         }
     return worst;

@@ -16,8 +16,12 @@
 #define PACX_SUB 8            /* short sub-blocks per frame                   */
 #define PACX_SHORT_FIRST 448  /* first sub-block starts here (long/2-short/2) */
 #define PACX_MAX_PEAKS 512    /* strict local maxima of 1025 bins             */
-/* payload slot of one channel-block, bytes and 32-bit words: >= 3 + 8*(4+8*16) + 1024*16 bits.  The packers
-   build a record in this many LDS words, pacx_payload_stride() reports it and no record is longer */
+/* payload slot of one channel-block, bytes and 32-bit words.  A record is 3 flag bits and, per (sub-)block,
+   nScaleBits + nBands * (nMantSizeBits + nScaleBits) header bits and up to 16 bits per covered line, rounded up with
+   the size rule's extra bit: at the widths 4 / 12 at most 2181 bytes (8 short bands), but 2193 with 16-bit size fields
+   and 7 short bands.  The packers build a record in this many LDS words and copy it whole, so pacx_create refuses a
+   handle whose longest record (its layouts and widths, every band at 16 bits) is longer; pacx_payload_stride()
+   reports the slot */
 #define PACX_PAYLOAD_STRIDE 2192
 #define PACX_PAYLOAD_WORDS (PACX_PAYLOAD_STRIDE / 4)
 

@@ -231,7 +231,10 @@ int  pacx_abi_version(void);
 /* ints per cf in the scale_factor / bit_alloc outputs:
    max(n_bands_long, 8*n_bands_short) */
 int  pacx_band_stride(const pacx_handle *h);
-/* bytes per cf slot in the packed-payload output of pacx_pack_batch */
+/* bytes per cf slot in the packed-payload output of pacx_pack_batch.  No record of the handle is longer: pacx_create
+   returns PACX_E_UNSUPPORTED (pacx_last_error names the size) for band layouts and widths whose longest record --
+   every band at the largest mantissa size the widths allow, a short frame counting eight sub-blocks -- would not fit,
+   e.g. nMantSizeBits 16 with seven or eight short bands (sample rates of 32 kHz and below) */
 int  pacx_payload_stride(const pacx_handle *h);
 /* pre-size the device workspace for batches of up to n_cf channel-frames */
 int  pacx_reserve(pacx_handle *h, int64_t n_cf);
