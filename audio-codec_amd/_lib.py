@@ -161,6 +161,8 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P]),
     "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                     _P]),
+    "pacx_vq_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_encode_vq_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P]),
     # seg_first, limit_bytes: int64 arrays in host memory
     "pacx_rate_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
                                                 ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P,

@@ -25,6 +25,16 @@ def encoder(sample_rate, target_bits_per_sample, n_scale_bits=4, n_mant_size_bit
     return enc
 
 
+def scalar_sibling(enc):
+    """The scalar encoder beside a gain-shape one: same device, sample rate, widths and band tables, without use_vq
+    and use_sbr.  The band pick and the solves read nothing else of a handle, and the C side serves them on scalar
+    handles only (include/pacx.h, pacx_vq_band_curve_batch).  Cached like every encoder here."""
+    if enc.device.index != engine.torch.cuda.current_device():
+        raise ValueError("scalar_sibling: the encoder lives on another device than the current one")
+    return encoder(enc.sample_rate, enc.target_bits_per_sample, enc.n_scale_bits, enc.n_mant_size_bits,
+                   enc.sfBands, enc.sfBandsShort)
+
+
 def encoder_for_params(cp):
     """From a reference-style CodingParams bag (coder/pacfile.py:699-707,323-330)."""
     return encoder(cp.sampleRate, cp.targetBitsPerSample, cp.nScaleBits, cp.nMantSizeBits,

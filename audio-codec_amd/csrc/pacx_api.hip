@@ -116,6 +116,9 @@ struct pacx_handle {
     long long seg_host_n;             /* segments the pinned staging copy holds  */
     long long *seg_host;              /* [2 seg_host_n + 1] pinned: what ws_seg is uploaded from */
     hipEvent_t ev_seg;                /* the last upload from seg_host           */
+    long long ws_vqb_cf;              /* capacity of ws_vqb (0 until the first pacx_vq_band_curve_batch) */
+    char *ws_vqb;                     /* one pass of the gain-shape band curve: payload slots, the pass's allocation and
+                                         status words, what the decoder reads back, k_nmr's rows (vq_band_ws) */
     std::string err;
 };
 
@@ -342,6 +345,8 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     h->seg_host_n = 0;
     h->seg_host = nullptr;
     h->ev_seg = nullptr;
+    h->ws_vqb_cf = 0;
+    h->ws_vqb = nullptr;
     h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
     h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
     h->ws_lists = nullptr;
@@ -649,15 +654,48 @@ static int post_launch_forked(pacx_handle *h, const char *what)
 
 /* The buffers outside pacx_reserve's workspace: each group has a capacity of its own (channel-frames; bytes for
    the index) and only ever grows, on the first call that needs more. */
-enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_SOLVE, GROW_N };
+enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_SOLVE, GROW_VQ_BAND, GROW_N };
 struct GrowGroup {
     long long *cap;
     struct { void **p; size_t unit; } buf[3];       /* unit: bytes per unit of capacity; p == nullptr ends the group */
 };
 
+/* pacx_vq_band_curve_batch's buffers of one pass, carved out of one allocation: n entries of every array, each
+   entry a multiple of 16 bytes */
+struct VqBandWs {
+    uint8_t *payload;                 /* [n][PACX_PAYLOAD_STRIDE] what the coder wrote */
+    double *noise, *mask, *nmr;       /* [n][band_stride] k_nmr's rows */
+    int32_t *alloc, *dec_alloc;       /* [n][band_stride] the pass's allocation (in and out), the decoder's copy */
+    int32_t *dec_overall, *budget;    /* [n][8] the overall scales the decoder read; the cap budgets */
+    int32_t *n_bytes;                 /* [n] */
+    uint32_t *status;                 /* [n] the pass's own status words */
+    uint8_t *cf_flags;                /* [n] the flags the decoder read */
+};
+
+static size_t vq_band_ws(const PacxTables &T, char *base, long long n, VqBandWs *ws)
+{
+    const size_t rows = ((size_t)T.band_stride * sizeof(double) + 15) & ~(size_t)15;
+    const size_t ints = ((size_t)T.band_stride * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t unit[] = {PACX_PAYLOAD_STRIDE, rows, rows, rows, ints, ints, PACX_SUB * sizeof(int32_t),
+                           PACX_SUB * sizeof(int32_t), 16, 16, 16};
+    static_assert(PACX_PAYLOAD_STRIDE % 16 == 0, "every array of the carve starts 16-byte aligned");
+    char *at[sizeof(unit) / sizeof(unit[0])];
+    size_t total = 0;
+    for (size_t i = 0; i < sizeof(unit) / sizeof(unit[0]); ++i) {
+        at[i] = base + (size_t)n * total;
+        total += unit[i];
+    }
+    if (ws)
+        *ws = {(uint8_t *)at[0], (double *)at[1], (double *)at[2], (double *)at[3], (int32_t *)at[4], (int32_t *)at[5],
+               (int32_t *)at[6], (int32_t *)at[7], (int32_t *)at[8], (uint32_t *)at[9], (uint8_t *)at[10]};
+    return total;                                  /* bytes per channel-frame */
+}
+
 static GrowGroup grow_group(pacx_handle *h, int which)
 {
     switch (which) {
+    case GROW_VQ_BAND:
+        return {&h->ws_vqb_cf, {{(void **)&h->ws_vqb, vq_band_ws(h->T, nullptr, 0, nullptr)}}};
     case GROW_MANT:
         return {&h->ws_mant_cf, {{(void **)&h->ws_mant, PACX_M_LONG * sizeof(int32_t)}}};
     case GROW_VQ_UNITS:
@@ -763,6 +801,15 @@ extern "C" int pacx_reserve(pacx_handle *h, int64_t n_cf)
     if (h->ws_thr_cf > 0 && n_cf > h->ws_thr_cf) {
         HIP_TRY(h, hipSetDevice(h->device));
         int rc = grow(h, GROW_NMR, n_cf);
+        if (rc)
+            return rc;
+    }
+    /* and one that has served pacx_vq_band_curve_batch its pass buffers and the decoder's lines */
+    if (h->ws_vqb_cf > 0 && n_cf > h->ws_vqb_cf) {
+        HIP_TRY(h, hipSetDevice(h->device));
+        int rc = grow(h, GROW_VQ_BAND, n_cf);
+        if (!rc)
+            rc = grow(h, GROW_DEC_LINES, n_cf);
         if (rc)
             return rc;
     }
@@ -1954,6 +2001,123 @@ extern "C" int pacx_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const u
 {
     return curve_batch(h, true, "pacx_band_curve_batch", in, frame_flags, max_bits_per_sample, 0, nmr, cap, cap_alloc,
                        stream);
+}
+
+/* ---- the band curve of the gain-shape coder, and its second pass ---- */
+extern "C" int pacx_vq_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                        double max_bits_per_sample, double *nmr, int32_t *cap, int32_t *cap_alloc,
+                                        void *stream)
+{
+    const char *what = "pacx_vq_band_curve_batch";
+    if (!h)
+        return PACX_E_ARG;
+    if (!h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": gain-shape handles without SBR only (created with use_vq, without use_sbr)");
+    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (band_record_bound(h->T, max_bits_per_sample) > PACX_PAYLOAD_STRIDE)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": a record at this cap rate would not fit pacx_payload_stride");
+    if (n_cf == 0)                             /* nothing to write: the outputs may be null, as for pacx_encode_vq_batch */
+        return PACX_OK;
+    if (!nmr || !cap || !cap_alloc)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int mixed = frame_flags ? 1 : 0;
+    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)) || (rc = grow(h, GROW_DEC_LINES, n_cf)) ||
+        (rc = grow(h, GROW_VQ_BAND, n_cf)) || (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf))))
+        return rc;
+    VqBandWs w;
+    vq_band_ws(h->T, h->ws_vqb, h->ws_vqb_cf, &w);
+    hipStream_t st = (hipStream_t)stream;
+    const PacxTables &T = h->T;
+    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
+    }
+    /* the front end once, as pacx_encode_vq_batch runs it up to BitAlloc: lines, SMRs, the threshold of every line; the
+       overall scales and the status words stay in the workspace, as pacx_band_curve_batch keeps them */
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
+    s.front(h->ws_thr, st);
+    /* cap and cap_alloc: BitAlloc at the cap budget of every unit (its status bits beside the front end's) */
+    pacx_launch_vq_band_cap(T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_rate_status, cap, w.budget, st);
+    pacx_launch_bitalloc_budget(T, frame_flags, s.n_ch, n_cf, w.budget, h->ws_smr, cap_alloc, h->ws_rate_status, st);
+    /* a dropped hop keeps n_bytes = 0 through every pass: the coder leaves it alone, the decoder reads nothing */
+    HIP_TRY(h, hipMemsetAsync(w.n_bytes, 0, (size_t)n_cf * sizeof(int32_t), st));
+    /* candidate 0 is the decode of nothing */
+    HIP_TRY(h, hipMemsetAsync(h->ws_dec_lines, 0, (size_t)n_cf * PACX_M_LONG * sizeof(double), st));
+    int n_cand = 1 << T.n_mant_size_bits;
+    if (n_cand > PACX_BAND_CAND)
+        n_cand = PACX_BAND_CAND;
+    for (int i = 1; i < n_cand; ++i) {             /* n_cand >= 2: there is a first pass */
+        pacx_launch_vq_band_fill(T, n_cf, i + 1, h->ws_rate_status, w.alloc, w.status, st);
+        pacx_launch_vq(T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, h->ws_overall, w.alloc, nullptr,
+                       w.status, w.payload, PACX_PAYLOAD_STRIDE, w.n_bytes, h->ws_unit_words, h->ws_unit_bits, nullptr,
+                       nullptr, 0, 0, nullptr, nullptr, h->force.vq_frame, h->force.vq_bfs, st);
+        if (i == 1) {
+            /* the first pass has told which bands code nothing (the coder drops them to 0 bits): candidate 0, with
+               the lines of zeros still in place, and cap_alloc can be finished */
+            pacx_launch_nmr(T, frame_flags, s.n_ch, n_cf, h->ws_lines, h->ws_dec_lines, h->ws_overall, h->ws_thr, nullptr,
+                            w.noise, w.mask, w.nmr, st);
+            pacx_launch_vq_band_store(T, frame_flags, s.n_ch, n_cf, 0, w.nmr, w.alloc, h->ws_rate_status, nullptr, nmr, st);
+            pacx_launch_vq_band_zero(T, frame_flags, s.n_ch, n_cf, w.alloc, h->ws_rate_status, cap_alloc, st);
+        }
+        HIP_TRY(h, hipMemsetAsync(h->ws_dec_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        pacx_launch_vq_dec(T, h->vqdec_view.data(), n_cf, w.payload, PACX_PAYLOAD_STRIDE, nullptr, w.n_bytes, w.cf_flags,
+                           w.dec_overall, w.dec_alloc, h->ws_dec_lines, h->ws_dec_sbr, h->ws_dec_status,
+                           h->force.vq_dec_frame, st);
+        pacx_launch_nmr(T, frame_flags, s.n_ch, n_cf, h->ws_lines, h->ws_dec_lines, w.dec_overall, h->ws_thr, nullptr,
+                        w.noise, w.mask, w.nmr, st);
+        pacx_launch_vq_band_store(T, frame_flags, s.n_ch, n_cf, i, w.nmr, w.alloc, h->ws_rate_status, w.status, nmr, st);
+    }
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                                          const int32_t *bit_alloc_in, int32_t *overall_scale, int32_t *bit_alloc,
+                                          uint8_t *payload, int32_t *n_bytes, uint32_t *status, void *stream)
+{
+    const char *what = "pacx_encode_vq_alloc_batch";
+    if (!h)
+        return PACX_E_ARG;
+    if (!h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": gain-shape handles without SBR only (created with use_vq, without use_sbr)");
+    PacxPcmView v;
+    int fast;
+    long long n_cf;
+    int rc = check_pcm(h, in, &v, &fast, &n_cf);
+    if (rc)
+        return rc;
+    if (n_cf == 0)
+        return PACX_OK;
+    if (!bit_alloc_in || !overall_scale || !bit_alloc || !payload || !n_bytes || !status)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int mixed = frame_flags ? 1 : 0;
+    if ((rc = pacx_reserve(h, n_cf)) || (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf))))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
+        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
+    }
+    if (mixed)                                 /* only dropped short hops keep the zero, as in pacx_encode_vq_batch */
+        HIP_TRY(h, hipMemsetAsync(n_bytes, 0, (size_t)n_cf * sizeof(int32_t), st));
+    /* the MDCT alone: nothing here reads SMRs or maskers */
+    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
+    if (s.mixed)
+        s.lists(st);
+    s.mdct(st);
+    pacx_launch_band_sanitize(h->T, frame_flags, s.n_ch, n_cf, bit_alloc_in, bit_alloc, status, PACX_PAYLOAD_STRIDE, st);
+    pacx_launch_vq(h->T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc, nullptr,
+                   status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words, h->ws_unit_bits, nullptr, nullptr, 0,
+                   0, nullptr, nullptr, h->force.vq_frame, h->force.vq_bfs, st);
+    return post_launch(h, what);
 }
 
 /* ---- the solves: the target range on the grid, the segments of the segmented ones, the one checked path ---- */

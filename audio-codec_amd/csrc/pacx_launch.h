@@ -231,6 +231,21 @@ void pacx_launch_band_solve_peak(const PacxTables &T, const PacxSolve &v, const 
 void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
                                int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);
 
+/* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
+   k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
+   row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr
+   for candidate 0, which no coder ran for) */
+void pacx_launch_vq_band_cap(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf,
+                             double max_bits_per_sample, const uint32_t *status, int32_t *cap, int32_t *budget,
+                             hipStream_t st);
+void pacx_launch_vq_band_fill(const PacxTables &T, long long n_cf, int bits, const uint32_t *status_in, int32_t *alloc,
+                              uint32_t *status_out, hipStream_t st);
+void pacx_launch_vq_band_store(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, int cand,
+                               const double *row, const int32_t *alloc, const uint32_t *status_front,
+                               const uint32_t *status_pass, double *nmr, hipStream_t st);
+void pacx_launch_vq_band_zero(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *alloc,
+                              const uint32_t *status_front, int32_t *cap_alloc, hipStream_t st);
+
 /* k_vq.hip (sizes_long / sizes_short: vector dimension of every band as the coder sees it) */
 void pacx_launch_vq(const PacxTables &T, const void *vq_view, const uint8_t *flags, int n_ch, long long n_cf,
                     const double *lines, const int32_t *overall, int32_t *bit_alloc, const double *sbr_mean,

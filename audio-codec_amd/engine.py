@@ -563,6 +563,51 @@ class Encoder:
             out["entries"], out["entry_count"] = ent, cnt
         return out
 
+    def vq_band_curve(self, pcm, flags, max_bits_per_sample, out=None):
+        """band_curve for a gain-shape handle without SBR (pacx_vq_band_curve_batch, include/pacx.h): the same dict in
+        the same layout, every column taken with the gain-shape coder and its decoder themselves -- candidate i is every
+        band coded with (i + 1) x lines bits.  A band whose lines are all zero holds -inf (it codes nothing at any
+        size).  The pick and the solves run on the scalar sibling of this handle (context.scalar_sibling), the second
+        pass is encode_vq_alloc."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        if out is None:
+            out = {"nmr": torch.full((n_cf, self.band_stride, _lib.BAND_CAND), float("nan"), dtype=torch.float64,
+                                     device=self.device),
+                   "cap": torch.full((n_cf, _lib.SUB), -1, dtype=torch.int32, device=self.device),
+                   "cap_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device)}
+        if tuple(out["nmr"].shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or \
+                tuple(out["cap"].shape) != (n_cf, _lib.SUB) or tuple(out["cap_alloc"].shape) != (n_cf, self.band_stride):
+            raise ValueError(f"band curve: nmr [{n_cf}, {self.band_stride}, {_lib.BAND_CAND}], cap [{n_cf}, {_lib.SUB}], "
+                             f"cap_alloc [{n_cf}, {self.band_stride}]")
+        self._call_rate("pacx_vq_band_curve_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(max_bits_per_sample),
+                        _ptr(out["nmr"]), _ptr(out["cap"]), _ptr(out["cap_alloc"]), self._stream())
+        out["flags"] = fl
+        return out
+
+    def encode_vq_alloc(self, pcm, flags, bit_alloc, out=None):
+        """encode_vq() with the allocation of every band given by the caller (pacx_encode_vq_alloc_batch): bit_alloc
+        int32 [n_cf, band_stride]; values below 2 count as 0, values above maxMantBits as maxMantBits, and
+        out["bit_alloc"] holds what was coded (a band whose lines are all zero drops to 0).  -> encode_vq's dict."""
+        n_cf = pcm.n_cf
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        bit_alloc = torch.as_tensor(bit_alloc, device=self.device).to(torch.int32).contiguous()
+        if tuple(bit_alloc.shape) != (n_cf, self.band_stride):
+            raise ValueError(f"bit_alloc: int32 [{n_cf}, {self.band_stride}]")
+        if out is None:
+            out = {
+                "overall": self._empty((n_cf, _lib.SUB), torch.int32),
+                "bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
+                "status": self._empty((n_cf,), torch.int32),
+                "payload": self._empty((n_cf, self.payload_stride), torch.uint8),
+                "n_bytes": self._empty((n_cf,), torch.int32),
+            }
+        self._call_rate("pacx_encode_vq_alloc_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(bit_alloc),
+                        _ptr(out["overall"]), _ptr(out["bit_alloc"]), _ptr(out["payload"]), _ptr(out["n_bytes"]),
+                        _ptr(out["status"]), self._stream())
+        out["flags"] = fl
+        return out
+
     def alloc_outputs(self, n_cf, with_payload=False):
         o = {
             "overall": self._empty((n_cf, _lib.SUB), torch.int32),

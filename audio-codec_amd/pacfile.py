@@ -413,8 +413,9 @@ def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False, hea
     return head + body[:n].cpu().numpy().tobytes()
 
 
-def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples):
-    """(CodingParams, encoder, PCM view, flags) of the one-batch scalar path with the cap rate as the handle's"""
+def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples, use_vq=False):
+    """(CodingParams, encoder, PCM view, flags) of the one-batch scalar path with the cap rate as the handle's; use_vq:
+    of the gain-shape path without SBR"""
     from .audiofile import CodingParams
     pcm = np.ascontiguousarray(pcm)
     hop = 1024
@@ -431,12 +432,32 @@ def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, 
         raise ValueError(f"max_kbps_per_channel = {max_kbps_per_channel} at {cp.sampleRate} Hz is "
                          f"{cp.targetBitsPerSample:.3g} bits per sample: the cap must lie in (0, 16] bits per sample "
                          f"(at most {16 * cp.sampleRate / 1000:g} kb/s here)")
-    cp.useSBR = cp.useVQ = False
+    cp.useSBR, cp.useVQ = False, bool(use_vq)
     enc = context.encoder_for_params(cp)
     planar = device_stream(enc, pcm, hop)
     view = PcmView.stream(planar, hop)
     flags = enc.transient_flags(planar, len(pcm) // hop, hop)[1] if block_switching else None
     return cp, enc, view, flags
+
+
+class _BandPath:
+    """What the band-by-band streams call, for the scalar coder and for the gain-shape one: the curve and the second
+    pass are the coder's own, the pick and the solves work on the arrays alone and run on a scalar handle -- for a
+    gain-shape encoder its scalar sibling (context.scalar_sibling)."""
+
+    def __init__(self, enc):
+        self.enc = enc
+        self.solver = context.scalar_sibling(enc) if enc.use_vq else enc
+
+    def curve(self, view, flags, max_bits_per_sample):
+        if self.enc.use_vq:
+            return self.enc.vq_band_curve(view, flags, max_bits_per_sample)
+        return self.enc.band_curve(view, flags, max_bits_per_sample)
+
+    def encode(self, view, flags, bit_alloc):
+        if self.enc.use_vq:
+            return self.enc.encode_vq_alloc(view, flags, bit_alloc)
+        return self.enc.encode_pack_alloc(view, flags, bit_alloc)
 
 
 def _check_allocation(allocation):
@@ -447,16 +468,21 @@ def _check_allocation(allocation):
 
 
 def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
-                       allocation="budget"):
+                       allocation="budget", use_vq=False):
     """(.pac bytes, the outputs of Encoder.encode_pack_nmr -- allocation "band": of Encoder.encode_pack_alloc, with the
-    pick's capped mask as out["capped"] -- for the n + 2 blocks the driver writes, the encoder)"""
+    pick's capped mask as out["capped"] -- for the n + 2 blocks the driver writes, the encoder).  use_vq (allocation
+    "band" only): the gain-shape coder, the outputs of Encoder.encode_vq_alloc"""
     band = _check_allocation(allocation)
-    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
+    if use_vq and not band:
+        raise NotImplementedError("gain-shape streams: allocation 'band' only")
+    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples,
+                                              use_vq)
     if band:
         if not np.isfinite(float(target_nmr_db)):
             raise ValueError("target_nmr_db must be finite")
-        pick = enc.band_pick(enc.band_curve(view, flags, cp.targetBitsPerSample), float(target_nmr_db))
-        out = enc.encode_pack_alloc(view, flags, pick["bit_alloc"])
+        path = _BandPath(enc)
+        pick = path.solver.band_pick(path.curve(view, flags, cp.targetBitsPerSample), float(target_nmr_db))
+        out = path.encode(view, flags, pick["bit_alloc"])
         out["capped"] = pick["capped"]
     else:
         out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
@@ -544,14 +570,18 @@ def _check_peak(peak_kbps_per_channel, segment_hops):
 
 
 def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching, header_samples, nmr_range_db,
-                       allocation="budget", segment_hops=None, peak_kbps_per_channel=None):
+                       allocation="budget", segment_hops=None, peak_kbps_per_channel=None, use_vq=False):
     """One curve, one solve + second pass per size.  sizes: list of (kbps_per_channel, max_bytes).
     -> list of (.pac bytes, solve dict, outputs of encode_pack_budget -- allocation "band": of encode_pack_alloc --,
     body limit), the encoder.  segment_hops: one segmented solve per size instead; the solve dict is
     Encoder.rate_solve_segments' / band_solve_segments' plus "segments" (first_block, blocks, limit_bytes per segment),
     the body limit the sum of the segments'.  peak_kbps_per_channel: one peak solve per size (Encoder.rate_solve_peak /
-    band_solve_peak): the size is the stream's and the body limit, the segments' limit_bytes are the peaks."""
+    band_solve_peak): the size is the stream's and the body limit, the segments' limit_bytes are the peaks.
+    use_vq (allocation "band" only): the gain-shape coder -- Encoder.vq_band_curve, the solves on the scalar sibling,
+    the outputs of encode_vq_alloc; the encoder returned is the gain-shape one."""
     band = _check_allocation(allocation)
+    if use_vq and not band:
+        raise NotImplementedError("gain-shape streams: allocation 'band' only")
     lo, hi = _abr_range(nmr_range_db)
     peak = peak_kbps_per_channel is not None
     _check_peak(peak_kbps_per_channel, segment_hops)
@@ -561,11 +591,14 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
         if not peak and any(k is None for k, _ in sizes):
             raise ValueError("give exactly one of kbps_per_channel and max_bytes")
         segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
-    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples)
+    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples,
+                                              use_vq)
     head = header_bytes(cp)
     limits = [None] * len(sizes) if segment_hops is not None and not peak else \
         [_abr_limit(cp, view, head, k, b) for k, b in sizes]
-    curve = enc.band_curve(view, flags, cp.targetBitsPerSample) if band else \
+    path = _BandPath(enc) if band else None
+    solver = path.solver if band else enc
+    curve = path.curve(view, flags, cp.targetBitsPerSample) if band else \
         enc.rate_curve(view, flags, cp.targetBitsPerSample)
     n_ch = cp.nChannels
 
@@ -577,13 +610,13 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
     done = []
     for (kbps, _), limit in zip(sizes, limits):
         if segment_hops is None:        # the whole stream: the partition [0, n_cf] with its one limit, the plain method
-            sol = enc.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
+            sol = solver.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
             unmet = None if sol["met"] else unreachable(limit, sol["total_bytes"])
         elif peak:                      # the stream's limit above the segments' peaks
             first, count, seg_limit = segment_limits(peak_kbps_per_channel, n_ch, cp.sampleRate, view.n_frames,
                                                      segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
-            sol = enc.band_solve_peak(curve, seg_first, seg_limit, limit, lo, hi) if band else \
+            sol = solver.band_solve_peak(curve, seg_first, seg_limit, limit, lo, hi) if band else \
                 enc.rate_solve_peak(curve, seg_first, seg_limit, limit, lo, hi)
             s = int(np.argmin(sol["met"]))
             if not sol["stream_met"]:
@@ -601,7 +634,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
         else:
             first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
-            sol = enc.band_solve_segments(curve, seg_first, seg_limit, lo, hi) if band else \
+            sol = solver.band_solve_segments(curve, seg_first, seg_limit, lo, hi) if band else \
                 enc.rate_solve_segments(curve, seg_first, seg_limit, lo, hi)
             s = int(np.argmin(sol["met"]))
             unmet = None if sol["met"].all() else \
@@ -613,7 +646,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
             limit = int(seg_limit.sum())
         if unmet:
             raise ValueError(unmet)
-        out = enc.encode_pack_alloc(view, flags, sol["bit_alloc"]) if band else \
+        out = path.encode(view, flags, sol["bit_alloc"]) if band else \
             enc.encode_pack_budget(view, flags, sol["budget"])
         body, total = enc.gather_body(out["payload"], out["n_bytes"])
         done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, limit))
@@ -661,6 +694,32 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
     done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
                                  block_switching, header_samples, nmr_range_db, allocation, segment_hops,
                                  peak_kbps_per_channel)
+    return done[0][0]
+
+
+def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
+                         header_samples=None):
+    """encode_stream_nmr(allocation="band") for the gain-shape coder -> .pac bytes with useVQ set and useSBR clear:
+    every band of every block gets the smallest size (0, 2, ..., 16 bits a line) at which the noise of the band AS THE
+    DECODER RECONSTRUCTS IT stays at or below target_nmr_db of the masked threshold, no block above the budget of
+    max_kbps_per_channel.  The curve is taken with the coder and the decoder themselves (Encoder.vq_band_curve,
+    include/pacx.h: pacx_vq_band_curve_batch), the pick runs on the encoder's scalar sibling, the second pass is
+    Encoder.encode_vq_alloc.  Every decoder of encode_stream(use_vq=True) output takes the stream.  Gain-shape without
+    SBR, 1024 lines, one batch; the cap's limits are encode_stream_nmr's."""
+    return _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
+                              "band", use_vq=True)[0]
+
+
+def encode_stream_vq_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
+                         block_switching=False, header_samples=None, nmr_range_db=(-30, 30), segment_hops=None,
+                         peak_kbps_per_channel=None):
+    """encode_stream_abr(allocation="band") for the gain-shape coder: the stream of encode_stream_vq_nmr at the lowest
+    target on the grid that fits the size.  kbps_per_channel / max_bytes, nmr_range_db, segment_hops and
+    peak_kbps_per_channel mean what they mean there, with the same rules, limits and error messages (one
+    implementation serves both); the solves are pacx_band_solve / _segments / _peak on the gain-shape curve."""
+    done, _ = _encode_stream_abr(pcm, sample_rate, [(kbps_per_channel, max_bytes)], max_kbps_per_channel,
+                                 block_switching, header_samples, nmr_range_db, "band", segment_hops,
+                                 peak_kbps_per_channel, use_vq=True)
     return done[0][0]
 
 

@@ -316,9 +316,16 @@ def encode_stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=3
       kbps_per_channel: the records of the file, their length prefixes included, over the duration of the blocks
                         submitted;
       allocation: "budget" or "band", as given (pacfile.encode_stream_nmr)."""
+    return _stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
+                          allocation, False)
+
+
+def _stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples, allocation,
+                   use_vq):
+    """encode_stream_to_nmr, and with use_vq encode_stream_vq_to_nmr"""
     from . import pacfile
     data, out, enc = pacfile._encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching,
-                                                header_samples, allocation)
+                                                header_samples, allocation, use_vq=use_vq)
     n_ch = np.asarray(pcm).shape[1]
     n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
     n_blocks = len(n_bytes)
@@ -353,6 +360,13 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
       segments       gains floor_nmr_db (the lowest target at which the segment fits its peak) and pinned (bool: its
                      target is above the stream's);
       stream_target_nmr_db  the one target of every segment that is not pinned."""
+    return _stream_to_rate(pcm, sample_rate, kbps_per_channel, max_bytes, max_kbps_per_channel, block_switching,
+                           header_samples, nmr_range_db, allocation, segment_hops, peak_kbps_per_channel, False)
+
+
+def _stream_to_rate(pcm, sample_rate, kbps_per_channel, max_bytes, max_kbps_per_channel, block_switching, header_samples,
+                    nmr_range_db, allocation, segment_hops, peak_kbps_per_channel, use_vq):
+    """encode_stream_to_rate, and with use_vq encode_stream_vq_to_rate"""
     from . import pacfile
     many = isinstance(kbps_per_channel, (list, tuple)) or isinstance(max_bytes, (list, tuple))
     if many:
@@ -363,7 +377,7 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
         sizes = [(kbps_per_channel, max_bytes)]
     done, enc = pacfile._encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_switching,
                                            header_samples, nmr_range_db, allocation, segment_hops,
-                                           peak_kbps_per_channel)
+                                           peak_kbps_per_channel, use_vq=use_vq)
     n_ch = np.asarray(pcm).shape[1]
     res = []
     for data, sol, out, limit in done:
@@ -395,6 +409,25 @@ def encode_stream_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=Non
             info["stream_target_nmr_db"] = sol["stream_target_nmr_db"]
         res.append((data, nmr_of_file(pcm, data, block_switching=bool(block_switching)), info))
     return res if many else res[0]
+
+
+def encode_stream_vq_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,
+                            header_samples=None):
+    """pacfile.encode_stream_vq_nmr with a Report: -> (.pac bytes, Report, info).  The report is nmr_of_file's of the
+    finished gain-shape bytes; info is encode_stream_to_nmr's with allocation = "band" (bit_alloc: the final
+    allocation, 0 in a band whose lines are all zero)."""
+    return _stream_to_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, block_switching, header_samples,
+                          "band", True)
+
+
+def encode_stream_vq_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, max_kbps_per_channel=320,
+                             block_switching=False, header_samples=None, nmr_range_db=(-30, 30), segment_hops=None,
+                             peak_kbps_per_channel=None):
+    """pacfile.encode_stream_vq_abr with a Report: -> (.pac bytes, Report, info), or a list of them for a list of
+    sizes (one gain-shape curve, one solve and one second pass per size).  info is encode_stream_to_rate's with
+    allocation = "band"."""
+    return _stream_to_rate(pcm, sample_rate, kbps_per_channel, max_bytes, max_kbps_per_channel, block_switching,
+                           header_samples, nmr_range_db, "band", segment_hops, peak_kbps_per_channel, True)
 
 
 def rate_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False):

@@ -1016,6 +1016,69 @@ int pacx_encode_pack_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8
                                  int32_t *bit_alloc, int32_t *mantissa, uint32_t *status, uint8_t *payload,
                                  int32_t *n_bytes, void *stream);
 
+/* ---- the same for gain-shape streams: a band curve taken with the coder itself ---- */
+
+/*
+ * Without SBR the gain-shape (PVQ) coder is band by band as well: quantize_gain_shape codes a band from that band's
+ * lines and its own allocation a_b (a_b lines_b bits, coder/gain_shape_quantize.py:476-512), the spill of unused bits
+ * into the next band exists only in the SBR encoder (coder/codec.py:522-524), a record carries every band's
+ * allocation, and its length is the scalar formula, nScaleBits + sum_b (nMantSizeBits + nScaleBits + a_b lines_b): the
+ * size rule counts a scale factor per band that is not written (coder/pacfile.py:342-361).  So a band curve in
+ * pacx_band_curve_batch's layout makes the pick and every solve above usable for gain-shape streams as they are.
+ *
+ * pacx_vq_band_curve_batch: outputs, layout, cap rule, dropped hops and -1 slots as pacx_band_curve_batch, for a handle
+ * created with use_vq and without use_sbr (1024 lines, long and short blocks, one batch).  The front end runs once
+ * (MDCT -> side chain -> masked threshold, as pacx_encode_vq_batch up to BitAlloc); then one pass per candidate
+ * i = 1 ... n_cand - 1, n_cand = maxMantBits: every band of every unit at bits(i) = i + 1 through the gain-shape coder
+ * (k_vq*), its payload through the gain-shape decoder to lines (k_vq_dec*), those through k_nmr, the row into column i.
+ * "The decoder's lines" are the decoder's by construction.
+ *
+ *   nmr[b][0]            NMR_b with Xh = 0, as the scalar curve's
+ *   nmr[b][i], i < n_cand   pacx_nmr_batch's NMR_b of the band coded with bits(i) lines_b bits
+ *   a band whose lines are all zero (the coder gives it no bits whatever it is offered, coder/codec.py:352-353):
+ *                        -inf at every candidate below n_cand, so that a pick gives it 0 bits at any target
+ *   a pass that flags the channel-frame PACX_ST_VQ_UNDEFINED: +inf at that candidate for every band of the frame
+ *   nmr[b][i], i >= n_cand  +inf
+ *   cap                  32 J, J by pacx_rate_steps exactly as the scalar curve takes it
+ *   cap_alloc            BitAlloc(double(32 J), maxMantBits, bands, SMR) with the all-zero bands set to 0: a unit coded
+ *                        with it writes exactly the predicted length
+ *
+ * The noise of a gain-shape band is not monotone in its size (the pulse count and the split of the bits between gain
+ * and shape move in steps): the pick's ascending scan is the right one here too.  The status bits the passes raise
+ * stay in the passes' own words; the handle keeps the front end's (and BitAlloc's at the cap budget) as
+ * pacx_band_curve_batch does.  The buffers of one pass -- a payload slot, the decoded lines, one row of k_nmr's three
+ * outputs, the allocation and the status word per channel-frame -- are grow-only workspace of the handle, allocated by
+ * the first call and from then on sized by pacx_reserve too.  The call enqueues a fixed number of launches -- the
+ * front end, BitAlloc, and per pass the same kernels whatever the data -- and the host waits for none.  It is
+ * n_cand - 1 runs of the coder and the decoder, and a run at a large size costs several times one at an ordinary rate:
+ * from about 4 bits a line the frame-level walks (k_vq_frame, k_vq_dec_frame) hand their blocks to the band-by-band
+ * kernels behind them (tools/vq_band_probe.py measures every size; README).
+ *
+ * The pick and the solves -- pacx_band_pick, pacx_band_solve, pacx_band_solve_segments, pacx_band_solve_peak -- read
+ * band tables and header widths only, and they answer a use_vq handle with PACX_E_UNSUPPORTED as before: a C host
+ * creates a second handle with the same sample rate, band tables and widths and without use_vq, and hands it the
+ * arrays (the Python binding keeps that sibling per gain-shape handle, context.scalar_sibling).
+ *
+ * PACX_E_UNSUPPORTED on a handle created without use_vq or with use_sbr (there the bands interact, and the
+ * reconstructed bands have no NMR an allocation controls); the other argument rules are pacx_band_curve_batch's,
+ * except that an empty batch (n_frames = 0) returns at once whatever the output pointers, as pacx_encode_vq_batch does.
+ */
+int pacx_vq_band_curve_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags, double max_bits_per_sample,
+                             double *nmr, int32_t *cap, int32_t *cap_alloc, void *stream);
+
+/*
+ * The second pass: pacx_encode_vq_batch with the allocation of every band given by the caller.  bit_alloc_in: int32
+ * [n_cf][band_stride] (may be the bit_alloc output itself), made representable as pacx_encode_pack_alloc_batch makes
+ * it: below 2 -> 0, above maxMantBits -> maxMantBits, and all zeros with PACX_ST_RATE_CAP for a channel-frame whose
+ * record would not fit pacx_payload_stride.  overall_scale, bit_alloc (the FINAL allocation: a band of zero gain
+ * drops to 0), payload, n_bytes and status as pacx_encode_vq_batch writes them.  With the allocation of a pick on
+ * pacx_vq_band_curve_batch's curve it writes records of exactly the predicted lengths.  Runs MDCT -> k_band_sanitize
+ * -> the gain-shape coder on `stream`: no side chain, no mask, no BitAlloc.  PACX_E_UNSUPPORTED as above.
+ */
+int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
+                               const int32_t *bit_alloc_in, int32_t *overall_scale, int32_t *bit_alloc,
+                               uint8_t *payload, int32_t *n_bytes, uint32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
