@@ -310,46 +310,9 @@ extern "C" int pacx_create(const pacx_config *cfg, pacx_handle **out)
     if (cfg->device < 0 || cfg->device >= n_dev)
         return fail(nullptr, PACX_E_ARG, "pacx_create: device ordinal out of range");
 
-    pacx_handle *h = new pacx_handle();
+    pacx_handle *h = new pacx_handle();      /* every field zero: no workspace, no streams, no events */
     h->device = cfg->device;
     h->force = read_overrides();
-    h->ws_cf = 0;
-    h->ws_blocks_cf = 0;
-    h->ws_blocks = nullptr;
-    h->ws_sbr_mean = nullptr;
-    h->fork_side = 0;
-    h->side_stream = nullptr;
-    h->ev_fork = nullptr;
-    h->ev_join = nullptr;
-    h->short_stream = nullptr;
-    h->spare_stream = nullptr;
-    h->ev_short_done = nullptr;
-    h->ev_lists = nullptr;
-    h->ws_mant_cf = 0;
-    h->ws_mant = nullptr;
-    h->ws_dec_cf = 0;
-    h->ws_dec_lines = nullptr;
-    h->ws_dec_sbr = nullptr;
-    h->ws_dec_status = nullptr;
-    h->ws_vq_cf = 0;
-    h->ws_unit_words = nullptr;
-    h->ws_unit_bits = nullptr;
-    h->ws_index_bytes = 0;
-    h->ws_index = nullptr;
-    h->ws_thr_cf = 0;
-    h->ws_thr = nullptr;
-    h->ws_rate_status = nullptr;
-    h->ws_solve_n = 0;
-    h->ws_solve = nullptr;
-    h->ws_seg = nullptr;
-    h->seg_host_n = 0;
-    h->seg_host = nullptr;
-    h->ev_seg = nullptr;
-    h->ws_vqb_cf = 0;
-    h->ws_vqb = nullptr;
-    h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
-    h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
-    h->ws_lists = nullptr;
     h->tables_exact = 1;
     memset(&h->T, 0, sizeof(h->T));
     int rc = PACX_OK;
@@ -652,12 +615,17 @@ static int post_launch_forked(pacx_handle *h, const char *what)
     return PACX_OK;
 }
 
-/* The buffers outside pacx_reserve's workspace: each group has a capacity of its own (channel-frames; bytes for
-   the index) and only ever grows, on the first call that needs more. */
-enum { GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_SOLVE, GROW_VQ_BAND, GROW_N };
+/* The handle's device buffers, in groups.  Each group has a capacity of its own (channel-frames; bytes for the index,
+   states for the solve) and only ever grows, on the first call that needs more.  The main workspace is what every
+   encode step uses (pacx_reserve); the others belong to the entry points that name them. */
+enum { GROW_NONE = -1, GROW_MANT, GROW_VQ_UNITS, GROW_DEC_BLOCKS, GROW_DEC_LINES, GROW_NMR, GROW_INDEX, GROW_SOLVE,
+       GROW_VQ_BAND, GROW_MAIN, GROW_N };
 struct GrowGroup {
     long long *cap;
-    struct { void **p; size_t unit; } buf[3];       /* unit: bytes per unit of capacity; p == nullptr ends the group */
+    const long long *follows;         /* once this capacity is above zero the group is kept as large as the main workspace
+                                         (reserve); nullptr: it grows only where an entry point asks */
+    /* n units of capacity take unit * (n / div + add) bytes (none: the buffer is not allocated); p == nullptr ends the group */
+    struct { void **p; size_t unit, div = 1, add = 0; } buf[10];
 };
 
 /* pacx_vq_band_curve_batch's buffers of one pass, carved out of one allocation: n entries of every array, each
@@ -694,29 +662,46 @@ static size_t vq_band_ws(const PacxTables &T, char *base, long long n, VqBandWs 
 static GrowGroup grow_group(pacx_handle *h, int which)
 {
     switch (which) {
+    case GROW_MAIN:
+        return {&h->ws_cf, nullptr,
+                {{(void **)&h->ws_lines, PACX_M_LONG * sizeof(double)},
+                 {(void **)&h->ws_smr, h->T.band_stride * sizeof(double)},
+                 {(void **)&h->ws_peaks, PACX_MAX_PEAKS * sizeof(PacxPeak)},
+                 {(void **)&h->ws_npeaks, PACX_SUB * sizeof(int32_t)},
+                 {(void **)&h->ws_nkept, PACX_SUB * sizeof(int32_t)},
+                 {(void **)&h->ws_overall, PACX_SUB * sizeof(int32_t)},
+                 {(void **)&h->ws_chunks, sizeof(long long), 256, 2},                   /* [ws_cf/256 + 2] */
+                 {(void **)&h->ws_offs, sizeof(long long), 1, 1},                       /* [ws_cf + 1] */
+                 {(void **)&h->ws_lists, 2 * sizeof(int32_t), 1, 1},                    /* [2*ws_cf + 2] */
+                 {(void **)&h->ws_sbr_mean, h->T.use_sbr ? PACX_SUB * sizeof(double) : 0}}};
+    /* a handle that has served pacx_vq_band_curve_batch keeps its pass buffers and the decoder's lines as large as the
+       workspace */
     case GROW_VQ_BAND:
-        return {&h->ws_vqb_cf, {{(void **)&h->ws_vqb, vq_band_ws(h->T, nullptr, 0, nullptr)}}};
+        return {&h->ws_vqb_cf, &h->ws_vqb_cf, {{(void **)&h->ws_vqb, vq_band_ws(h->T, nullptr, 0, nullptr)}}};
     case GROW_MANT:
-        return {&h->ws_mant_cf, {{(void **)&h->ws_mant, PACX_M_LONG * sizeof(int32_t)}}};
+        return {&h->ws_mant_cf, nullptr, {{(void **)&h->ws_mant, PACX_M_LONG * sizeof(int32_t)}}};
     case GROW_VQ_UNITS:
-        return {&h->ws_vq_cf, {{(void **)&h->ws_unit_words, PACX_SUB * PACX_PAYLOAD_WORDS * sizeof(unsigned)},
-                               {(void **)&h->ws_unit_bits, PACX_SUB * 2 * sizeof(int32_t)}}};
+        return {&h->ws_vq_cf, nullptr,
+                {{(void **)&h->ws_unit_words, PACX_SUB * PACX_PAYLOAD_WORDS * sizeof(unsigned)},
+                 {(void **)&h->ws_unit_bits, PACX_SUB * 2 * sizeof(int32_t)}}};
     /* the decoders' own workspaces: windowed blocks when the caller wants PCM only; lines + SBR flags (+ status words) */
     case GROW_DEC_BLOCKS:
-        return {&h->ws_blocks_cf, {{(void **)&h->ws_blocks, PACX_N_LONG * sizeof(double)}}};
+        return {&h->ws_blocks_cf, nullptr, {{(void **)&h->ws_blocks, PACX_N_LONG * sizeof(double)}}};
     case GROW_DEC_LINES:
-        return {&h->ws_dec_cf, {{(void **)&h->ws_dec_lines, PACX_M_LONG * sizeof(double)},
-                                {(void **)&h->ws_dec_sbr, 1},
-                                {(void **)&h->ws_dec_status, sizeof(uint32_t)}}};
-    /* pacx_nmr_batch: the masked threshold of every line; pacx_rate_curve_batch: its status words as well */
+        return {&h->ws_dec_cf, &h->ws_vqb_cf,
+                {{(void **)&h->ws_dec_lines, PACX_M_LONG * sizeof(double)},
+                 {(void **)&h->ws_dec_sbr, 1},
+                 {(void **)&h->ws_dec_status, sizeof(uint32_t)}}};
+    /* pacx_nmr_batch: the masked threshold of every line; pacx_rate_curve_batch: its status words as well.  A handle
+       that has served either keeps them as large as the workspace */
     case GROW_NMR:
-        return {&h->ws_thr_cf, {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)},
-                                {(void **)&h->ws_rate_status, sizeof(uint32_t)}}};
+        return {&h->ws_thr_cf, &h->ws_thr_cf,
+                {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)}, {(void **)&h->ws_rate_status, sizeof(uint32_t)}}};
     case GROW_SOLVE:
-        return {&h->ws_solve_n, {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()},
-                                 {(void **)&h->ws_seg, 3 * sizeof(long long)}}};
+        return {&h->ws_solve_n, nullptr,
+                {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()}, {(void **)&h->ws_seg, 3 * sizeof(long long)}}};
     default:
-        return {&h->ws_index_bytes, {{(void **)&h->ws_index, 1}}};
+        return {&h->ws_index_bytes, nullptr, {{(void **)&h->ws_index, 1}}};
     }
 }
 
@@ -730,8 +715,8 @@ static void free_group(const GrowGroup &g)
     *g.cap = 0;
 }
 
-/* room for n units in one group.  A failing hipMalloc leaves the group at capacity 0 (a later call allocates
-   again, and frees what this one got first) */
+/* room for n units in one group, all or nothing: a failing hipMalloc (the main workspace of a 262 144-frame batch is
+   8 GB) leaves the group with NO buffer and capacity 0 -- nothing leaks, and a later, smaller call allocates again */
 static int grow(pacx_handle *h, int which, long long n)
 {
     const GrowGroup g = grow_group(h, which);
@@ -739,25 +724,21 @@ static int grow(pacx_handle *h, int which, long long n)
         return PACX_OK;
     HIP_TRY(h, hipDeviceSynchronize());
     free_group(g);
-    for (const auto &b : g.buf)
-        if (b.p)
-            HIP_TRY(h, hipMalloc(b.p, (size_t)n * b.unit));
+    for (const auto &b : g.buf) {
+        const size_t bytes = b.p ? b.unit * ((size_t)n / b.div + b.add) : 0;
+        if (!bytes)
+            continue;
+        hipError_t e = hipMalloc(b.p, bytes);
+        if (e != hipSuccess) {
+            *b.p = nullptr;
+            free_group(g);
+            (void)hipGetLastError();             /* the failed allocation must not poison the next launch check */
+            return fail(h, PACX_E_HIP, std::string("pacx_reserve: hipMalloc of ") + std::to_string(bytes) +
+                                           " bytes: " + hipGetErrorString(e) + " (workspace released)");
+        }
+    }
     *g.cap = n;
     return PACX_OK;
-}
-
-static void free_ws(pacx_handle *h)
-{
-    void *p[] = {h->ws_lines, h->ws_smr, h->ws_peaks, h->ws_npeaks, h->ws_overall, h->ws_chunks, h->ws_offs,
-                 h->ws_nkept, h->ws_sbr_mean, h->ws_lists};
-    for (void *q : p)
-        if (q)
-            (void)hipFree(q);
-    h->ws_sbr_mean = nullptr;
-    h->ws_lists = nullptr;
-    h->ws_lines = nullptr; h->ws_smr = nullptr; h->ws_peaks = nullptr; h->ws_npeaks = nullptr;
-    h->ws_overall = nullptr; h->ws_chunks = nullptr; h->ws_offs = nullptr; h->ws_nkept = nullptr;
-    h->ws_cf = 0;
 }
 
 extern "C" void pacx_destroy(pacx_handle *h)
@@ -777,7 +758,6 @@ extern "C" void pacx_destroy(pacx_handle *h)
         (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join)
         (void)hipEventDestroy(h->ev_join);
-    free_ws(h);
     for (int which = 0; which < GROW_N; ++which)
         free_group(grow_group(h, which));
     if (h->ev_seg) {
@@ -791,62 +771,26 @@ extern "C" void pacx_destroy(pacx_handle *h)
     delete h;
 }
 
+/* the main workspace for n_cf channel-frames, and the groups that follow it; the device is the handle's already */
+static int reserve(pacx_handle *h, long long n_cf)
+{
+    for (int which = 0; which < GROW_N; ++which) {
+        const long long *follows = grow_group(h, which).follows;
+        int rc;
+        if (follows && *follows > 0 && (rc = grow(h, which, n_cf)))
+            return rc;
+    }
+    return grow(h, GROW_MAIN, n_cf);
+}
+
 extern "C" int pacx_reserve(pacx_handle *h, int64_t n_cf)
 {
     if (!h || n_cf < 0)
         return fail(h, PACX_E_ARG, "pacx_reserve: bad argument");
     if (n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, "pacx_reserve: too many channel-frames for one call");
-    /* a handle that has served pacx_nmr_batch keeps its threshold buffer as large as the workspace */
-    if (h->ws_thr_cf > 0 && n_cf > h->ws_thr_cf) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        int rc = grow(h, GROW_NMR, n_cf);
-        if (rc)
-            return rc;
-    }
-    /* and one that has served pacx_vq_band_curve_batch its pass buffers and the decoder's lines */
-    if (h->ws_vqb_cf > 0 && n_cf > h->ws_vqb_cf) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        int rc = grow(h, GROW_VQ_BAND, n_cf);
-        if (!rc)
-            rc = grow(h, GROW_DEC_LINES, n_cf);
-        if (rc)
-            return rc;
-    }
-    if (n_cf <= h->ws_cf)
-        return PACX_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipDeviceSynchronize());
-    free_ws(h);
-    const size_t n = (size_t)n_cf;
-    /* all or nothing: a failing hipMalloc (the workspace of a 262 144-frame batch is 8 GB) leaves the
-       handle with NO workspace and ws_cf = 0 -- nothing leaks, and a later, smaller call reserves again */
-    struct { void **p; size_t bytes; } want[] = {
-        {(void **)&h->ws_lines, n * PACX_M_LONG * sizeof(double)},
-        {(void **)&h->ws_smr, n * h->T.band_stride * sizeof(double)},
-        {(void **)&h->ws_peaks, n * PACX_MAX_PEAKS * sizeof(PacxPeak)},
-        {(void **)&h->ws_npeaks, n * PACX_SUB * sizeof(int32_t)},
-        {(void **)&h->ws_nkept, n * PACX_SUB * sizeof(int32_t)},
-        {(void **)&h->ws_overall, n * PACX_SUB * sizeof(int32_t)},
-        {(void **)&h->ws_chunks, (n / 256 + 2) * sizeof(long long)},
-        {(void **)&h->ws_offs, (n + 1) * sizeof(long long)},
-        {(void **)&h->ws_lists, (2 * n + 2) * sizeof(int32_t)},
-        {(void **)&h->ws_sbr_mean, h->T.use_sbr ? n * PACX_SUB * sizeof(double) : 0},
-    };
-    for (auto &w : want) {
-        if (!w.bytes)
-            continue;
-        hipError_t e = hipMalloc(w.p, w.bytes);
-        if (e != hipSuccess) {
-            *w.p = nullptr;
-            free_ws(h);
-            (void)hipGetLastError();             /* the failed allocation must not poison the next launch check */
-            return fail(h, PACX_E_HIP, std::string("pacx_reserve: hipMalloc of ") + std::to_string(w.bytes) +
-                                           " bytes: " + hipGetErrorString(e) + " (workspace released)");
-        }
-    }
-    h->ws_cf = n_cf;
-    return PACX_OK;
+    return reserve(h, n_cf);
 }
 
 /* validate a pcm view; fills the device-side view and the fast-path flag */
@@ -880,19 +824,205 @@ static int post_launch(pacx_handle *h, const char *what)
     return PACX_OK;
 }
 
+/* ---- what the entry points refuse, stated once each; PACX_OK: not refused ---- */
+static int scalar_only(pacx_handle *h, const char *what)
+{
+    if (h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    return PACX_OK;
+}
+
+static int vq_plain_only(pacx_handle *h, const char *what)
+{
+    if (!h->T.use_vq || h->T.use_sbr)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": gain-shape handles without SBR only (created with use_vq, without use_sbr)");
+    return PACX_OK;
+}
+
+/* instead: what a gain-shape handle's caller is pointed to */
+static int not_vq(pacx_handle *h, const char *what, const char *instead)
+{
+    if (h->T.use_vq)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": handle was created with use_vq (" + instead + ")");
+    return PACX_OK;
+}
+
+static int vq_only(pacx_handle *h, const char *what)
+{
+    if (!h->T.use_vq)
+        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": handle was created without use_vq");
+    return PACX_OK;
+}
+
+static bool cap_rate_ok(double max_bits_per_sample) { return max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0; }
+
+static int check_cap_rate(pacx_handle *h, const char *what, double max_bits_per_sample)
+{
+    if (!cap_rate_ok(max_bits_per_sample))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
+    return PACX_OK;
+}
+
+/* what one run of the gain-shape coder reads and writes beside the step's lines and overall scales: the allocation (in
+   and out), status words, payload slots and record lengths; the omitted bands' means (SBR handles) and the entry log,
+   or nullptr */
+struct VqCode {
+    int32_t *bit_alloc;
+    uint32_t *status;
+    uint8_t *payload;
+    int32_t *n_bytes;
+    const double *sbr_mean;
+    pacx_vq_entry *log;
+    int32_t *log_count;
+    int log_cap;
+};
+
+/* What a call that takes a pacx_pcm knows about its batch, and what it hands to every launch of an encode's front end
+   (frame lists -> long / short MDCT -> side chain -> mask): the launches below name only what differs between them --
+   the stream, the part of a block-switched batch (0, PACX_PART_LONG, PACX_PART_SHORT), the fused tail.  An entry point
+   strings the pieces together in its own order, view() .. reserve() .. init_outputs(), between its own checks: the
+   order in which the checks answer is part of the interface (include/pacx.h, tests/test_gpu_api_refusals.py).  The
+   schedules themselves (which stream, which order, which events) stay with the entry points: they differ for
+   measured reasons. */
+struct EncodeStep {
+    pacx_handle *h;
+    const uint8_t *frame_flags;
+    int mixed;                        /* per-frame flags (without them every frame is a long sine block) */
+    hipStream_t stream;               /* the caller's */
+    /* view() */
+    PacxPcmView v;
+    int dtype, fast;
+    long long n_frames, n_cf;
+    int n_ch;
+    /* reserve() */
+    int32_t *list_long, *list_short, *counts;       /* h->ws_lists: long cf list, short cf list, the two counts */
+    /* init_outputs() */
+    int32_t *overall_scale;
+    uint32_t *status;
+
+    EncodeStep(pacx_handle *h_, const uint8_t *flags, void *stream_)
+        : h(h_), frame_flags(flags), mixed(flags ? 1 : 0), stream((hipStream_t)stream_), n_cf(0), overall_scale(nullptr),
+          status(nullptr)
+    {
+    }
+
+    int view(const pacx_pcm *in)
+    {
+        const int rc = check_pcm(h, in, &v, &fast, &n_cf);
+        if (rc)
+            return rc;
+        dtype = in->dtype;
+        n_frames = in->n_frames;
+        n_ch = in->n_channels;
+        return PACX_OK;
+    }
+
+    /* the handle's device, its workspace for this batch and the groups the call names (GROW_NONE: none) */
+    int reserve(std::initializer_list<int> groups = {})
+    {
+        HIP_TRY(h, hipSetDevice(h->device));
+        int rc = ::reserve(h, n_cf);
+        for (int which : groups)
+            if (!rc && which != GROW_NONE)
+                rc = grow(h, which, n_cf);
+        if (rc)
+            return rc;
+        list_long = h->ws_lists;
+        list_short = h->ws_lists + n_cf;
+        counts = h->ws_lists + 2 * n_cf;
+        return PACX_OK;
+    }
+
+    /* where the front end leaves its overall scales and status words, zeroed for the generic path */
+    int init_outputs(int32_t *overall, uint32_t *status_)
+    {
+        overall_scale = overall;
+        status = status_;
+        if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
+            HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), stream));
+            HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), stream));
+        }
+        return PACX_OK;
+    }
+
+    void lists(hipStream_t st) const
+    {
+        pacx_launch_frame_lists(frame_flags, n_frames, n_ch, list_long, list_short, counts, st);
+    }
+    /* fast batches.  Long frames: persistent roofline kernel (k_mdct_long_v2; it also initialises status and the
+       overall scales); short (CUR) frames: k_mdct_short */
+    void mdct_long(hipStream_t st) const
+    {
+        pacx_launch_mdct_v2(h->T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
+                            mixed ? list_long : nullptr, mixed ? counts : nullptr, st);
+    }
+    void mdct_short(hipStream_t st) const
+    {
+        pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
+                         st);
+    }
+    /* every frame's MDCT on one stream */
+    void mdct(hipStream_t st) const
+    {
+        if (fast) {
+            mdct_long(st);
+            if (mixed)
+                mdct_short(st);
+        } else {
+            pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale, PACX_SUB,
+                             status, st);
+        }
+    }
+    /* sbr: the side chain also leaves the omitted bands' means and folds max|FFT| into the overall scale the MDCT
+       wrote (so it runs behind the MDCT on that MDCT's stream) */
+    void side(int part, bool sbr, hipStream_t st) const
+    {
+        pacx_launch_side(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed | part, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
+                         sbr ? h->ws_sbr_mean : nullptr, sbr ? overall_scale : nullptr, st);
+    }
+    /* all-long fast batches without SBR: transform and side chain of a frame in one wave (k_front_long), which
+       also initialises status and the overall scales */
+    void front_long(hipStream_t st) const
+    {
+        pacx_launch_front_long(h->T, v, n_cf, h->ws_lines, overall_scale, status, h->ws_peaks, h->ws_npeaks,
+                               h->ws_nkept, st);
+    }
+    /* lines, SMRs and, with thr, the masked threshold of every line, all on one stream: frame lists, MDCT, side
+       chain, mask */
+    void front(double *thr, hipStream_t st) const
+    {
+        if (mixed)
+            lists(st);
+        mdct(st);
+        side(0, false, st);
+        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr, thr,
+                         h->n_cu, list_long, list_short, counts, nullptr, st);
+    }
+    /* tail: the outputs of the work fused into the long mask kernel, or nullptr */
+    void mask(int part, const MaskTail *tail, hipStream_t st) const
+    {
+        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed | part, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
+                         nullptr, h->n_cu, list_long, list_short, counts, tail, st);
+    }
+    /* the gain-shape coder on this batch's lines and overall scales; stage 1: k_vq_frame over the frames of a list, 2:
+       what follows it, 0: both over every frame */
+    void vq(const VqCode &c, int stage, const int32_t *cf_list, const int32_t *cf_count, hipStream_t st) const
+    {
+        pacx_launch_vq(h->T, h->vq_view.data(), frame_flags, n_ch, n_cf, h->ws_lines, overall_scale, c.bit_alloc, c.sbr_mean,
+                       c.status, c.payload, PACX_PAYLOAD_STRIDE, c.n_bytes, h->ws_unit_words, h->ws_unit_bits, c.log,
+                       c.log_count, c.log_cap, stage, cf_list, cf_count, h->force.vq_frame, h->force.vq_bfs, st);
+    }
+};
+
 extern "C" int pacx_mdct_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
                                int mode, double *lines, int32_t *max_scale, void *stream)
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    const int rc = s.view(in);
+    if (rc || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!lines)
         return fail(h, PACX_E_ARG, "pacx_mdct_batch: lines is null");
     if ((mode & PACX_MDCT_KBD) && (frame_flags || (mode & PACX_MDCT_PREWINDOWED)))
@@ -900,18 +1030,18 @@ extern "C" int pacx_mdct_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t
     HIP_TRY(h, hipSetDevice(h->device));
     const int short_blocks = (mode & PACX_MDCT_SHORT) ? 1 : 0;
     if (mode & PACX_MDCT_KBD) {              /* window override 2 = the KBD tables */
-        pacx_launch_mdct(h->T, v, in->dtype, fast, nullptr, n_cf, short_blocks, 0, 2, lines, max_scale,
-                         short_blocks ? PACX_SUB : 1, nullptr, (hipStream_t)stream);
+        pacx_launch_mdct(h->T, s.v, s.dtype, s.fast, nullptr, s.n_cf, short_blocks, 0, 2, lines, max_scale,
+                         short_blocks ? PACX_SUB : 1, nullptr, s.stream);
         return post_launch(h, "pacx_mdct_batch");
     }
-    if (fast && !short_blocks && !(mode & PACX_MDCT_PREWINDOWED)) {
-        pacx_launch_mdct_v2(h->T, v, frame_flags, n_cf, 0, lines, max_scale, 1, nullptr, h->n_cu, nullptr, nullptr,
-                            (hipStream_t)stream);
+    if (s.fast && !short_blocks && !(mode & PACX_MDCT_PREWINDOWED)) {
+        pacx_launch_mdct_v2(h->T, s.v, frame_flags, s.n_cf, 0, lines, max_scale, 1, nullptr, h->n_cu, nullptr, nullptr,
+                            s.stream);
         return post_launch(h, "pacx_mdct_batch");     /* v2 handles all four long windows */
     }
-    pacx_launch_mdct(h->T, v, in->dtype, fast, frame_flags, n_cf, short_blocks, 0,
+    pacx_launch_mdct(h->T, s.v, s.dtype, s.fast, frame_flags, s.n_cf, short_blocks, 0,
                      (mode & PACX_MDCT_PREWINDOWED) ? 1 : 0, lines, max_scale,
-                     short_blocks ? PACX_SUB : 1, nullptr, (hipStream_t)stream);
+                     short_blocks ? PACX_SUB : 1, nullptr, s.stream);
     return post_launch(h, "pacx_mdct_batch");
 }
 
@@ -920,24 +1050,20 @@ extern "C" int pacx_smr_batch(pacx_handle *h, const pacx_pcm *in, const double *
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, nullptr, stream);
+    int rc = s.view(in);
+    if (rc || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!lines || !smr)
         return fail(h, PACX_E_ARG, "pacx_smr_batch: lines or smr is null");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)))
+    if ((rc = s.reserve()))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = s.stream;
+    const long long n_cf = s.n_cf;
     const int sb = short_blocks ? 1 : 0;
-    pacx_launch_side(h->T, v, in->dtype, fast, nullptr, n_cf, sb, 0, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
+    pacx_launch_side(h->T, s.v, s.dtype, s.fast, nullptr, n_cf, sb, 0, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
                      nullptr, nullptr, st);
-    pacx_launch_mask(h->T, nullptr, in->n_channels, n_cf, sb, 0, h->ws_peaks, h->ws_nkept, lines, smr,
+    pacx_launch_mask(h->T, nullptr, s.n_ch, n_cf, sb, 0, h->ws_peaks, h->ws_nkept, lines, smr,
                      threshold, h->n_cu, nullptr, nullptr, nullptr, nullptr, st);
     if (n_peaks) {
         if (sb)
@@ -1004,90 +1130,6 @@ extern "C" int pacx_quantize_batch(pacx_handle *h, int64_t n_cf, const double *l
     return post_launch(h, "pacx_quantize_batch");
 }
 
-/* What one encode call hands to every launch of its front end (frame lists -> long / short MDCT -> side chain ->
-   mask), filled once per call: the launches below name only what differs between them -- the stream, the part
-   of a block-switched batch (0, PACX_PART_LONG, PACX_PART_SHORT), the fused tail.  The schedules themselves (which
-   stream, which order, which events) stay with the two entry points: they differ for measured reasons. */
-struct EncodeStep {
-    pacx_handle *h;
-    PacxPcmView v;
-    int dtype, fast;
-    const uint8_t *frame_flags;
-    long long n_frames, n_cf;
-    int n_ch, mixed;                  /* mixed: per-frame flags (without them every frame is a long sine block) */
-    int32_t *list_long, *list_short, *counts;       /* h->ws_lists: long cf list, short cf list, the two counts */
-    int32_t *overall_scale;
-    uint32_t *status;
-
-    EncodeStep(pacx_handle *h_, const pacx_pcm *in, const PacxPcmView &v_, int fast_, const uint8_t *flags, long long n,
-               int32_t *overall, uint32_t *status_)
-        : h(h_), v(v_), dtype(in->dtype), fast(fast_), frame_flags(flags), n_frames(in->n_frames), n_cf(n),
-          n_ch(in->n_channels), mixed(flags ? 1 : 0), list_long(h_->ws_lists), list_short(h_->ws_lists + n),
-          counts(h_->ws_lists + 2 * n), overall_scale(overall), status(status_)
-    {
-    }
-
-    void lists(hipStream_t st) const
-    {
-        pacx_launch_frame_lists(frame_flags, n_frames, n_ch, list_long, list_short, counts, st);
-    }
-    /* fast batches.  Long frames: persistent roofline kernel (k_mdct_long_v2; it also initialises status and the
-       overall scales); short (CUR) frames: k_mdct_short */
-    void mdct_long(hipStream_t st) const
-    {
-        pacx_launch_mdct_v2(h->T, v, frame_flags, n_cf, mixed, h->ws_lines, overall_scale, PACX_SUB, status, h->n_cu,
-                            mixed ? list_long : nullptr, mixed ? counts : nullptr, st);
-    }
-    void mdct_short(hipStream_t st) const
-    {
-        pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, 4, 0, h->ws_lines, overall_scale, PACX_SUB, status,
-                         st);
-    }
-    /* every frame's MDCT on one stream */
-    void mdct(hipStream_t st) const
-    {
-        if (fast) {
-            mdct_long(st);
-            if (mixed)
-                mdct_short(st);
-        } else {
-            pacx_launch_mdct(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed, 0, h->ws_lines, overall_scale, PACX_SUB,
-                             status, st);
-        }
-    }
-    /* sbr: the side chain also leaves the omitted bands' means and folds max|FFT| into the overall scale the MDCT
-       wrote (so it runs behind the MDCT on that MDCT's stream) */
-    void side(int part, bool sbr, hipStream_t st) const
-    {
-        pacx_launch_side(h->T, v, dtype, fast, frame_flags, n_cf, 0, mixed | part, h->ws_peaks, h->ws_npeaks, h->ws_nkept,
-                         sbr ? h->ws_sbr_mean : nullptr, sbr ? overall_scale : nullptr, st);
-    }
-    /* all-long fast batches without SBR: transform and side chain of a frame in one wave (k_front_long), which
-       also initialises status and the overall scales */
-    void front_long(hipStream_t st) const
-    {
-        pacx_launch_front_long(h->T, v, n_cf, h->ws_lines, overall_scale, status, h->ws_peaks, h->ws_npeaks,
-                               h->ws_nkept, st);
-    }
-    /* lines, SMRs and, with thr, the masked threshold of every line, all on one stream: frame lists, MDCT, side
-       chain, mask */
-    void front(double *thr, hipStream_t st) const
-    {
-        if (mixed)
-            lists(st);
-        mdct(st);
-        side(0, false, st);
-        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr, thr,
-                         h->n_cu, list_long, list_short, counts, nullptr, st);
-    }
-    /* tail: the outputs of the work fused into the long mask kernel, or nullptr */
-    void mask(int part, const MaskTail *tail, hipStream_t st) const
-    {
-        pacx_launch_mask(h->T, frame_flags, n_ch, n_cf, 0, mixed | part, h->ws_peaks, h->ws_nkept, h->ws_lines, h->ws_smr,
-                         nullptr, h->n_cu, list_long, list_short, counts, tail, st);
-    }
-};
-
 static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *frame_flags,
                          int32_t *overall_scale, int32_t *scale_factor, int32_t *bit_alloc,
                          int32_t *mantissa, uint32_t *status, uint8_t *payload, int32_t *n_bytes,
@@ -1095,40 +1137,30 @@ static int encode_scalar(pacx_handle *h, const pacx_pcm *in, const uint8_t *fram
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc = s.view(in);
+    if (rc || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!overall_scale || !scale_factor || !bit_alloc || !status || (!payload && !mantissa) ||
         (payload && !n_bytes))
         return fail(h, PACX_E_ARG, std::string(what) + ": null output pointer");
-    if (h->T.use_vq)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": handle was created with use_vq "
-                                                                "(call pacx_encode_vq_batch)");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)))
+    if ((rc = not_vq(h, what, "call pacx_encode_vq_batch")))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
     const PacxTables &T = h->T;
-    const int mixed = frame_flags ? 1 : 0;     /* without flags every frame is a long sine block */
+    const long long n_cf = s.n_cf;
+    const int fast = s.fast, mixed = s.mixed;
+    hipStream_t st = s.stream;
     /* k_tail_short (and the tails of the long frames) pack from registers; only the separate-kernel fallback for
        layouts with more than 8 short bands (k_quantize<128> -> k_pack) reads the mantissas back from memory.  Round 3:
        the workspace copy is no longer written when nobody asked for mantissas (it was 4 KB per channel-frame of HBM
        writes in every block-switched step) */
-    if (!mantissa && mixed && T.nb_short > 8) {
-        if ((rc = grow(h, GROW_MANT, n_cf)))
-            return rc;
+    const bool own_mant = !mantissa && mixed && T.nb_short > 8;
+    if ((rc = s.reserve({own_mant ? GROW_MANT : GROW_NONE})))
+        return rc;
+    if (own_mant)
         mantissa = h->ws_mant;
-    }
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
+    if ((rc = s.init_outputs(overall_scale, status)))
+        return rc;
     /* mixed streams: compacted lists of the long- and of the short-coded frames -- every
        persistent kernel below walks its own list.  The two-stream schedule forks first: the side
        chains and the short-block MDCT go by the flags alone and start while the lists are made */
@@ -1269,32 +1301,22 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc = s.view(in);
+    if (rc || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!overall_scale || !bit_alloc || !payload || !n_bytes || !status)
         return fail(h, PACX_E_ARG, "pacx_encode_vq_batch: null output pointer");
     if ((entries && (!entry_count || entries_per_band < 1)) || (!entries && entry_count && entries_per_band != 0))
         return fail(h, PACX_E_ARG, "pacx_encode_vq_batch: entries need entry_count and entries_per_band >= 1");
-    if (!h->T.use_vq)
-        return fail(h, PACX_E_UNSUPPORTED, "pacx_encode_vq_batch: handle was created without use_vq");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)))
+    if ((rc = vq_only(h, "pacx_encode_vq_batch")))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
     const PacxTables &T = h->T;
-    const int mixed = frame_flags ? 1 : 0;
-    if (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf)))
+    const long long n_cf = s.n_cf;
+    const int fast = s.fast, mixed = s.mixed;
+    hipStream_t st = s.stream;
+    if ((rc = s.reserve({mixed ? GROW_VQ_UNITS : GROW_NONE})) || (rc = s.init_outputs(overall_scale, status)))
         return rc;
-    if (!fast) {
-        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
     /* every long-coded frame gets its n_bytes from the coder; only dropped short hops keep the zero */
     if (mixed)
         HIP_TRY(h, hipMemsetAsync(n_bytes, 0, (size_t)n_cf * sizeof(int32_t), st));
@@ -1302,17 +1324,14 @@ extern "C" int pacx_encode_vq_batch(pacx_handle *h, const pacx_pcm *in, const ui
     memset(&mt, 0, sizeof(mt));
     mt.bit_alloc = bit_alloc;
     mt.status = status;
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
     /* BitAlloc as a kernel of its own; skip_long: 0 every frame, 1 the short-coded frames only, 2 the long-coded only */
     auto bitalloc = [&](int skip_long, hipStream_t s2) {
         pacx_launch_bitalloc(T, frame_flags, s.n_ch, n_cf, 0, mixed, skip_long, h->ws_smr, bit_alloc, status, s2);
     };
-    /* the gain-shape coder; stage 1: k_vq_frame over the frames of a list, 2: what follows it, 0: both over every frame */
+    const VqCode code = {bit_alloc, status, payload, n_bytes, h->ws_sbr_mean, entries, entry_count,
+                         entries ? entries_per_band : 0};
     auto vq = [&](int stage, const int32_t *cf_list, const int32_t *cf_count, hipStream_t s2) {
-        pacx_launch_vq(T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc,
-                       h->ws_sbr_mean, status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words, h->ws_unit_bits,
-                       entries, entry_count, entries ? entries_per_band : 0, stage, cf_list, cf_count, h->force.vq_frame,
-                       h->force.vq_bfs, s2);
+        s.vq(code, stage, cf_list, cf_count, s2);
     };
     const bool split = mixed && fast && h->force.split_short != 0;
     if (split) {
@@ -1565,10 +1584,8 @@ extern "C" int pacx_transient_flags(pacx_handle *h, const pacx_pcm *hops, uint8_
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, hops, &v, &fast, &n_cf);
+    EncodeStep s(h, nullptr, stream);
+    const int rc = s.view(hops);
     if (rc)
         return rc;
     if (hops->dtype != PACX_PCM_I16 || !transient)
@@ -1576,7 +1593,7 @@ extern "C" int pacx_transient_flags(pacx_handle *h, const pacx_pcm *hops, uint8_
     if (hops->n_channels > 8)
         return fail(h, PACX_E_UNSUPPORTED, "pacx_transient_flags: at most 8 channels");
     HIP_TRY(h, hipSetDevice(h->device));
-    pacx_launch_transient(v, hops->n_frames, PACX_M_LONG, transient, frame_flags, (hipStream_t)stream);
+    pacx_launch_transient(s.v, hops->n_frames, PACX_M_LONG, transient, frame_flags, s.stream);
     return post_launch(h, "pacx_transient_flags");
 }
 
@@ -1615,6 +1632,19 @@ extern "C" int pacx_unpack_batch(pacx_handle *h, int64_t n_cf, const uint8_t *pa
     return post_launch(h, "pacx_unpack_batch");
 }
 
+/* where pacx_launch_decode leaves the windowed blocks: the caller's array, else the handle's when only PCM is wanted */
+static int decode_work(pacx_handle *h, long long n_cf, double *blocks, const int16_t *pcm, double **work)
+{
+    *work = blocks;
+    if (!blocks && pcm && n_cf > 0) {
+        const int rc = grow(h, GROW_DEC_BLOCKS, n_cf);
+        if (rc != PACX_OK)
+            return rc;
+        *work = h->ws_blocks;
+    }
+    return PACX_OK;
+}
+
 static int decode_scalar(pacx_handle *h, const char *what, int64_t n_blocks, int n_channels, const uint8_t *cf_flags,
                          const int32_t *overall_scale, const int32_t *scale_factor, const int32_t *bit_alloc,
                          const int32_t *mantissa, double *lines, double *blocks, int16_t *pcm, uint32_t *status,
@@ -1626,19 +1656,14 @@ static int decode_scalar(pacx_handle *h, const char *what, int64_t n_blocks, int
                                                               !bit_alloc || !mantissa)) ||
         (!blocks && !pcm && !lines))
         return fail(h, PACX_E_ARG, std::string(what) + ": bad argument");
-    if (h->T.use_vq)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": handle was created with use_vq "
-                                           "(pacx_decode_vq_batch reads gain-shape streams)");
+    if (int rc = not_vq(h, what, "pacx_decode_vq_batch reads gain-shape streams"))
+        return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const long long n_cf = n_blocks * n_channels;
-    double *work = blocks;
-    if (!work && pcm && n_cf > 0) {
-        const int rc = grow(h, GROW_DEC_BLOCKS, n_cf);
-        if (rc != PACX_OK)
-            return rc;
-        work = h->ws_blocks;
-    }
+    double *work;
+    if (int rc = decode_work(h, n_cf, blocks, pcm, &work))
+        return rc;
     const double *lines_in = nullptr;
     if (!h->T.use_sbr)
         routing = 0;
@@ -1697,8 +1722,8 @@ extern "C" int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_chan
         (n_blocks > 0 && (!payload || !n_bytes || !cf_flags || !overall_scale || !bit_alloc || !status ||
                           (!offsets && payload_stride <= 0))))
         return fail(h, PACX_E_ARG, "pacx_decode_vq_batch: bad argument");
-    if (!h->T.use_vq)
-        return fail(h, PACX_E_UNSUPPORTED, "pacx_decode_vq_batch: handle was created without use_vq");
+    if (int rc = vq_only(h, "pacx_decode_vq_batch"))
+        return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const long long n_cf = n_blocks * n_channels;
     hipStream_t st = (hipStream_t)stream;
@@ -1708,13 +1733,9 @@ extern "C" int pacx_decode_vq_batch(pacx_handle *h, int64_t n_blocks, int n_chan
             return rc;
     }
     double *ln = lines ? lines : h->ws_dec_lines;
-    double *work = blocks;
-    if (!work && pcm && n_cf > 0) {
-        const int rc = grow(h, GROW_DEC_BLOCKS, n_cf);
-        if (rc != PACX_OK)
-            return rc;
-        work = h->ws_blocks;
-    }
+    double *work;
+    if (int rc = decode_work(h, n_cf, blocks, pcm, &work))
+        return rc;
     if (n_cf > 0) {
         HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
         pacx_launch_vq_dec(h->T, h->vqdec_view.data(), n_cf, payload, payload_stride, (const long long *)offsets,
@@ -1767,26 +1788,21 @@ extern "C" int pacx_nmr_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t 
 {
     if (!h)
         return PACX_E_ARG;
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc = s.view(in);
+    if (rc || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!dec_lines || !overall_scale || !noise || !mask || !nmr_db)
         return fail(h, PACX_E_ARG, "pacx_nmr_batch: null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
+    if ((rc = s.reserve({GROW_NMR})))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = s.stream;
     /* the encoder's own front end on one stream: the original's lines in ws_lines (its overall scales go to the
-       workspace and are not used: the noise is taken against the scales the decoder read), the maskers, then the
-       masked threshold of every line */
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, nullptr);
+       workspace as they come and are not used: the noise is taken against the scales the decoder read; no status
+       words), the maskers, then the masked threshold of every line */
+    s.overall_scale = h->ws_overall;
     s.front(h->ws_thr, st);
-    pacx_launch_nmr(h->T, frame_flags, s.n_ch, n_cf, h->ws_lines, dec_lines, overall_scale, h->ws_thr, status, noise, mask,
+    pacx_launch_nmr(h->T, frame_flags, s.n_ch, s.n_cf, h->ws_lines, dec_lines, overall_scale, h->ws_thr, status, noise, mask,
                     nmr_db, st);
     return post_launch(h, "pacx_nmr_batch");
 }
@@ -1804,38 +1820,29 @@ static int encode_budgeted(pacx_handle *h, const pacx_pcm *in, const uint8_t *fr
 {
     if (!h)
         return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    int rc = scalar_only(h, what);
+    if (rc)
+        return rc;
     const bool search = mode == BUDGET_SEARCH, given = mode == ALLOC_GIVEN;
     if (search && !std::isfinite(target_nmr_db))
         return fail(h, PACX_E_ARG, std::string(what) + ": target_nmr_db is not finite");
-    if (search && !(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
-        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    if ((search && (rc = check_cap_rate(h, what, max_bits_per_sample))) || (rc = s.view(in)))
         return rc;
     if (!overall_scale || !scale_factor || !bit_alloc || !status || !payload || !n_bytes ||
         (search ? !budget_out : given ? !alloc_in : !budget_in))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (n_cf == 0)
+    if (s.n_cf == 0)
         return PACX_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)) || (search && (rc = grow(h, GROW_NMR, n_cf))))
+    /* without the caller's mantissa array the workspace's: k_pack reads the mantissas back from memory */
+    if ((rc = s.reserve({search ? GROW_NMR : GROW_NONE, mantissa ? GROW_NONE : GROW_MANT})))
         return rc;
-    if (!mantissa) {                           /* k_pack reads the mantissas back from memory */
-        if ((rc = grow(h, GROW_MANT, n_cf)))
-            return rc;
+    if (!mantissa)
         mantissa = h->ws_mant;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
+    if ((rc = s.init_outputs(overall_scale, status)))
+        return rc;
+    const long long n_cf = s.n_cf;
+    hipStream_t st = s.stream;
     if (given) {
         if (s.mixed)
             s.lists(st);
@@ -1907,7 +1914,7 @@ extern "C" int pacx_rate_curve_layout(const pacx_handle *h, double max_bits_per_
         return PACX_E_ARG;
     if (h->T.use_vq || h->T.use_sbr)
         return PACX_E_UNSUPPORTED;
-    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
+    if (!cap_rate_ok(max_bits_per_sample))
         return PACX_E_ARG;
     int r, s;
     rate_curve_layout(h->T, max_bits_per_sample, &r, &s);
@@ -1944,15 +1951,9 @@ static int curve_batch(pacx_handle *h, bool band, const char *what, const pacx_p
 {
     if (!h)
         return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
-    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
-        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc;
+    if ((rc = scalar_only(h, what)) || (rc = check_cap_rate(h, what, max_bits_per_sample)) || (rc = s.view(in)))
         return rc;
     if (!curve || !a || !b)
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
@@ -1966,17 +1967,12 @@ static int curve_batch(pacx_handle *h, bool band, const char *what, const pacx_p
             return fail(h, PACX_E_ARG, std::string(what) + ": row is smaller than pacx_rate_curve_layout's (" +
                                            std::to_string(need) + ")");
     }
-    if (n_cf == 0)
+    if (s.n_cf == 0)
         return PACX_OK;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)))
+    if ((rc = s.reserve({GROW_NMR})) || (rc = s.init_outputs(h->ws_overall, h->ws_rate_status)))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
+    const long long n_cf = s.n_cf;
+    hipStream_t st = s.stream;
     s.front(h->ws_thr, st);
     if (band)
         pacx_launch_band_curve(h->T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_lines, h->ws_thr, h->ws_smr,
@@ -2011,38 +2007,27 @@ extern "C" int pacx_vq_band_curve_batch(pacx_handle *h, const pacx_pcm *in, cons
     const char *what = "pacx_vq_band_curve_batch";
     if (!h)
         return PACX_E_ARG;
-    if (!h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": gain-shape handles without SBR only (created with use_vq, without use_sbr)");
-    if (!(max_bits_per_sample > 0.0 && max_bits_per_sample <= 16.0))
-        return fail(h, PACX_E_ARG, std::string(what) + ": max_bits_per_sample must lie in (0, 16]");
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc;
+    if ((rc = vq_plain_only(h, what)) || (rc = check_cap_rate(h, what, max_bits_per_sample)) || (rc = s.view(in)))
         return rc;
     if (band_record_bound(h->T, max_bits_per_sample) > PACX_PAYLOAD_STRIDE)
         return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": a record at this cap rate would not fit pacx_payload_stride");
-    if (n_cf == 0)                             /* nothing to write: the outputs may be null, as for pacx_encode_vq_batch */
+    if (s.n_cf == 0)                           /* nothing to write: the outputs may be null, as for pacx_encode_vq_batch */
         return PACX_OK;
     if (!nmr || !cap || !cap_alloc)
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int mixed = frame_flags ? 1 : 0;
-    if ((rc = pacx_reserve(h, n_cf)) || (rc = grow(h, GROW_NMR, n_cf)) || (rc = grow(h, GROW_DEC_LINES, n_cf)) ||
-        (rc = grow(h, GROW_VQ_BAND, n_cf)) || (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf))))
+    /* the overall scales and the status words of the front end stay in the workspace, as pacx_band_curve_batch keeps
+       them */
+    if ((rc = s.reserve({GROW_NMR, GROW_DEC_LINES, GROW_VQ_BAND, s.mixed ? GROW_VQ_UNITS : GROW_NONE})) ||
+        (rc = s.init_outputs(h->ws_overall, h->ws_rate_status)))
         return rc;
     VqBandWs w;
     vq_band_ws(h->T, h->ws_vqb, h->ws_vqb_cf, &w);
-    hipStream_t st = (hipStream_t)stream;
+    const long long n_cf = s.n_cf;
+    hipStream_t st = s.stream;
     const PacxTables &T = h->T;
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(h->ws_rate_status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(h->ws_overall, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    /* the front end once, as pacx_encode_vq_batch runs it up to BitAlloc: lines, SMRs, the threshold of every line; the
-       overall scales and the status words stay in the workspace, as pacx_band_curve_batch keeps them */
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, h->ws_overall, h->ws_rate_status);
+    /* the front end once, as pacx_encode_vq_batch runs it up to BitAlloc: lines, SMRs, the threshold of every line */
     s.front(h->ws_thr, st);
     /* cap and cap_alloc: BitAlloc at the cap budget of every unit (its status bits beside the front end's) */
     pacx_launch_vq_band_cap(T, frame_flags, s.n_ch, n_cf, max_bits_per_sample, h->ws_rate_status, cap, w.budget, st);
@@ -2054,11 +2039,10 @@ extern "C" int pacx_vq_band_curve_batch(pacx_handle *h, const pacx_pcm *in, cons
     int n_cand = 1 << T.n_mant_size_bits;
     if (n_cand > PACX_BAND_CAND)
         n_cand = PACX_BAND_CAND;
+    const VqCode pass = {w.alloc, w.status, w.payload, w.n_bytes, nullptr, nullptr, nullptr, 0};
     for (int i = 1; i < n_cand; ++i) {             /* n_cand >= 2: there is a first pass */
         pacx_launch_vq_band_fill(T, n_cf, i + 1, h->ws_rate_status, w.alloc, w.status, st);
-        pacx_launch_vq(T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, h->ws_overall, w.alloc, nullptr,
-                       w.status, w.payload, PACX_PAYLOAD_STRIDE, w.n_bytes, h->ws_unit_words, h->ws_unit_bits, nullptr,
-                       nullptr, 0, 0, nullptr, nullptr, h->force.vq_frame, h->force.vq_bfs, st);
+        s.vq(pass, 0, nullptr, nullptr, st);
         if (i == 1) {
             /* the first pass has told which bands code nothing (the coder drops them to 0 bits): candidate 0, with
                the lines of zeros still in place, and cap_alloc can be finished */
@@ -2085,38 +2069,24 @@ extern "C" int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, co
     const char *what = "pacx_encode_vq_alloc_batch";
     if (!h)
         return PACX_E_ARG;
-    if (!h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": gain-shape handles without SBR only (created with use_vq, without use_sbr)");
-    PacxPcmView v;
-    int fast;
-    long long n_cf;
-    int rc = check_pcm(h, in, &v, &fast, &n_cf);
-    if (rc)
+    EncodeStep s(h, frame_flags, stream);
+    int rc;
+    if ((rc = vq_plain_only(h, what)) || (rc = s.view(in)) || s.n_cf == 0)
         return rc;
-    if (n_cf == 0)
-        return PACX_OK;
     if (!bit_alloc_in || !overall_scale || !bit_alloc || !payload || !n_bytes || !status)
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int mixed = frame_flags ? 1 : 0;
-    if ((rc = pacx_reserve(h, n_cf)) || (mixed && (rc = grow(h, GROW_VQ_UNITS, n_cf))))
+    if ((rc = s.reserve({s.mixed ? GROW_VQ_UNITS : GROW_NONE})) || (rc = s.init_outputs(overall_scale, status)))
         return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (!fast) {                               /* fast path: k_mdct_long_v2 initialises both itself */
-        HIP_TRY(h, hipMemsetAsync(status, 0, (size_t)n_cf * sizeof(uint32_t), st));
-        HIP_TRY(h, hipMemsetAsync(overall_scale, 0, (size_t)n_cf * PACX_SUB * sizeof(int32_t), st));
-    }
-    if (mixed)                                 /* only dropped short hops keep the zero, as in pacx_encode_vq_batch */
+    const long long n_cf = s.n_cf;
+    hipStream_t st = s.stream;
+    if (s.mixed)                               /* only dropped short hops keep the zero, as in pacx_encode_vq_batch */
         HIP_TRY(h, hipMemsetAsync(n_bytes, 0, (size_t)n_cf * sizeof(int32_t), st));
     /* the MDCT alone: nothing here reads SMRs or maskers */
-    const EncodeStep s(h, in, v, fast, frame_flags, n_cf, overall_scale, status);
     if (s.mixed)
         s.lists(st);
     s.mdct(st);
     pacx_launch_band_sanitize(h->T, frame_flags, s.n_ch, n_cf, bit_alloc_in, bit_alloc, status, PACX_PAYLOAD_STRIDE, st);
-    pacx_launch_vq(h->T, h->vq_view.data(), frame_flags, s.n_ch, n_cf, h->ws_lines, overall_scale, bit_alloc, nullptr,
-                   status, payload, PACX_PAYLOAD_STRIDE, n_bytes, h->ws_unit_words, h->ws_unit_bits, nullptr, nullptr, 0,
-                   0, nullptr, nullptr, h->force.vq_frame, h->force.vq_bfs, st);
+    s.vq({bit_alloc, status, payload, n_bytes, nullptr, nullptr, nullptr, 0}, 0, nullptr, nullptr, st);
     return post_launch(h, what);
 }
 
@@ -2200,8 +2170,8 @@ static int solve(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32
 {
     if (!h)
         return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (int rc = scalar_only(h, what))
+        return rc;
     if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
     if (!result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)) ||
@@ -2272,8 +2242,8 @@ extern "C" int pacx_band_pick(pacx_handle *h, int64_t n_cf, const double *nmr, c
     const char *what = "pacx_band_pick";
     if (!h)
         return PACX_E_ARG;
-    if (h->T.use_vq || h->T.use_sbr)
-        return fail(h, PACX_E_UNSUPPORTED, std::string(what) + ": scalar handles only (created without use_vq, use_sbr)");
+    if (int rc = scalar_only(h, what))
+        return rc;
     if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
         return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
     if (n_cf > 0 && (!nmr || !cap || !cap_alloc || !bit_alloc || !n_bytes || !capped))

@@ -256,33 +256,39 @@ class Encoder:
         return sf, mant
 
     # -------------------------------------------------------------- whole path
+    def _encode(self, pcm, flags, out, default, call):
+        """The frame the encode* methods and the curves share: the flags tensor, `out` or default(n_cf),
+        call(view, flags pointer, out), and the flags in the dict."""
+        fl = self.flags_tensor(flags, pcm.n_frames)
+        if out is None:
+            out = default(pcm.n_cf)
+        call(ctypes.byref(pcm.c), _ptr(fl), out)
+        out["flags"] = fl
+        return out
+
+    def _pack_outputs(self, n_cf):
+        return self.alloc_outputs(n_cf, with_payload=True)
+
+    @staticmethod
+    def _pack_ptrs(out, want_mantissa):
+        """the outputs of the packing scalar encodes, in the order their entry points take them"""
+        return [_ptr(out["overall"]), _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
+                _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]), _ptr(out["payload"]),
+                _ptr(out["n_bytes"])]
+
     def encode(self, pcm, flags=None, out=None):
         """codec.Encode for every channel of every frame of `pcm`.
         Returns dict of device tensors: overall [n_cf,8], scale_factor / bit_alloc
         [n_cf, band_stride], mantissa [n_cf,1024] (line-indexed), status [n_cf]."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = self.alloc_outputs(n_cf)
-        self._call("pacx_encode_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(out["overall"]),
-                   _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]), _ptr(out["mantissa"]),
-                   _ptr(out["status"]), self._stream())
-        out["flags"] = fl
-        return out
+        return self._encode(pcm, flags, out, self.alloc_outputs, lambda view, fl, o: self._call(
+            "pacx_encode_batch", view, fl, _ptr(o["overall"]), _ptr(o["scale_factor"]), _ptr(o["bit_alloc"]),
+            _ptr(o["mantissa"]), _ptr(o["status"]), self._stream()))
 
     def encode_pack(self, pcm, flags=None, out=None, want_mantissa=False):
         """encode() + pack() in one call (long frames: one fused kernel after the
         masking stage).  `out` as alloc_outputs(n_cf, with_payload=True)."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = self.alloc_outputs(n_cf, with_payload=True)
-        self._call("pacx_encode_pack_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(out["overall"]),
-                   _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
-                   _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]),
-                   _ptr(out["payload"]), _ptr(out["n_bytes"]), self._stream())
-        out["flags"] = fl
-        return out
+        return self._encode(pcm, flags, out, self._pack_outputs, lambda view, fl, o: self._call(
+            "pacx_encode_pack_batch", view, fl, *self._pack_ptrs(o, want_mantissa), self._stream()))
 
     def _call_rate(self, name, *args):
         """the constant-quality entry points: PACX_E_UNSUPPORTED (a gain-shape or SBR handle) is NotImplementedError"""
@@ -297,35 +303,30 @@ class Encoder:
         BitAlloc budget a bisection finds for it -- predicted noise at most target_nmr_db of the mask in every band,
         at most the budget of the cap rate max_bits_per_sample.  Returns encode_pack()'s dict plus budget
         [n_cf, 8] int32 (bits; long frames use [:, 0]); status carries ST_RATE_CAP where the cap was reached."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = self.alloc_outputs(n_cf, with_payload=True)
-        if "budget" not in out:
-            out["budget"] = torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
-        self._call_rate("pacx_encode_pack_nmr_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(target_nmr_db),
-                        ctypes.c_double(max_bits_per_sample), _ptr(out["overall"]), _ptr(out["scale_factor"]),
-                        _ptr(out["bit_alloc"]), _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]),
-                        _ptr(out["payload"]), _ptr(out["n_bytes"]), _ptr(out["budget"]), self._stream())
-        out["flags"] = fl
-        return out
+        def call(view, fl, o):
+            if "budget" not in o:
+                o["budget"] = torch.zeros((pcm.n_cf, _lib.SUB), dtype=torch.int32, device=self.device)
+            self._call_rate("pacx_encode_pack_nmr_batch", view, fl, ctypes.c_double(target_nmr_db),
+                            ctypes.c_double(max_bits_per_sample), *self._pack_ptrs(o, want_mantissa), _ptr(o["budget"]),
+                            self._stream())
+        return self._encode(pcm, flags, out, self._pack_outputs, call)
 
     def encode_pack_budget(self, pcm, flags, budget, out=None, want_mantissa=False):
         """encode_pack() with the BitAlloc budget of every long block / short sub-block given by the caller
         (pacx_encode_pack_budget_batch): budget int32 [n_cf, 8] in bits, long frames use [:, 0]."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        budget = torch.as_tensor(budget, device=self.device).to(torch.int32).contiguous()
-        if tuple(budget.shape) != (n_cf, _lib.SUB):
-            raise ValueError(f"budget: int32 [{n_cf}, {_lib.SUB}]")
-        if out is None:
-            out = self.alloc_outputs(n_cf, with_payload=True)
-        self._call_rate("pacx_encode_pack_budget_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(budget),
-                        _ptr(out["overall"]), _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
-                        _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]), _ptr(out["payload"]),
-                        _ptr(out["n_bytes"]), self._stream())
-        out["flags"], out["budget"] = fl, budget
-        return out
+        def call(view, fl, o):
+            given = self._given(budget, "budget", (pcm.n_cf, _lib.SUB))
+            self._call_rate("pacx_encode_pack_budget_batch", view, fl, _ptr(given), *self._pack_ptrs(o, want_mantissa),
+                            self._stream())
+            o["budget"] = given
+        return self._encode(pcm, flags, out, self._pack_outputs, call)
+
+    def _given(self, values, name, shape):
+        """the caller's budgets or allocation as an int32 device tensor of this shape"""
+        t = torch.as_tensor(values, device=self.device).to(torch.int32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: int32 [{shape[0]}, {shape[1]}]")
+        return t
 
     def rate_curve_layout(self, max_bits_per_sample):
         """(row, sub_stride) of a rate curve with this cap rate (pacx_rate_curve_layout)"""
@@ -459,21 +460,26 @@ class Encoder:
         slots as bit_alloc; cap [n_cf, 8] int32, the cap budget 32 J of every long block / short sub-block, -1 where
         there is none; cap_alloc [n_cf, band_stride] int32, BitAlloc's allocation at that budget.  Slots no band uses
         are not written (they keep what `out` held; NaN in a dict made here).  -> dict nmr, cap, cap_alloc."""
+        return self._band_curve("pacx_band_curve_batch", pcm, flags, max_bits_per_sample, out)
+
+    def _band_curve(self, name, pcm, flags, max_bits_per_sample, out):
+        """band_curve and vq_band_curve: the same dict from either entry point"""
         n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = {"nmr": torch.full((n_cf, self.band_stride, _lib.BAND_CAND), float("nan"), dtype=torch.float64,
-                                     device=self.device),
-                   "cap": torch.full((n_cf, _lib.SUB), -1, dtype=torch.int32, device=self.device),
-                   "cap_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device)}
-        if tuple(out["nmr"].shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or \
-                tuple(out["cap"].shape) != (n_cf, _lib.SUB) or tuple(out["cap_alloc"].shape) != (n_cf, self.band_stride):
-            raise ValueError(f"band curve: nmr [{n_cf}, {self.band_stride}, {_lib.BAND_CAND}], cap [{n_cf}, {_lib.SUB}], "
-                             f"cap_alloc [{n_cf}, {self.band_stride}]")
-        self._call_rate("pacx_band_curve_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(max_bits_per_sample),
-                        _ptr(out["nmr"]), _ptr(out["cap"]), _ptr(out["cap_alloc"]), self._stream())
-        out["flags"] = fl
-        return out
+        shapes = {"nmr": (n_cf, self.band_stride, _lib.BAND_CAND), "cap": (n_cf, _lib.SUB),
+                  "cap_alloc": (n_cf, self.band_stride)}
+
+        def default(n_cf):
+            return {"nmr": torch.full(shapes["nmr"], float("nan"), dtype=torch.float64, device=self.device),
+                    "cap": torch.full(shapes["cap"], -1, dtype=torch.int32, device=self.device),
+                    "cap_alloc": torch.zeros(shapes["cap_alloc"], dtype=torch.int32, device=self.device)}
+
+        def call(view, fl, o):
+            if any(tuple(o[k].shape) != shape for k, shape in shapes.items()):
+                raise ValueError(f"band curve: nmr [{n_cf}, {self.band_stride}, {_lib.BAND_CAND}], cap [{n_cf}, {_lib.SUB}], "
+                                 f"cap_alloc [{n_cf}, {self.band_stride}]")
+            self._call_rate(name, view, fl, ctypes.c_double(max_bits_per_sample), _ptr(o["nmr"]), _ptr(o["cap"]),
+                            _ptr(o["cap_alloc"]), self._stream())
+        return self._encode(pcm, flags, out, default, call)
 
     def _band_arrays(self, curve, what):
         nmr, cap, cap_alloc = (curve[k].contiguous() for k in ("nmr", "cap", "cap_alloc"))
@@ -519,19 +525,11 @@ class Encoder:
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):
         bit_alloc int32 [n_cf, band_stride]; values below 2 count as 0, values above maxMantBits as maxMantBits, and
         out["bit_alloc"] holds what was coded."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        bit_alloc = torch.as_tensor(bit_alloc, device=self.device).to(torch.int32).contiguous()
-        if tuple(bit_alloc.shape) != (n_cf, self.band_stride):
-            raise ValueError(f"bit_alloc: int32 [{n_cf}, {self.band_stride}]")
-        if out is None:
-            out = self.alloc_outputs(n_cf, with_payload=True)
-        self._call_rate("pacx_encode_pack_alloc_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(bit_alloc),
-                        _ptr(out["overall"]), _ptr(out["scale_factor"]), _ptr(out["bit_alloc"]),
-                        _ptr(out["mantissa"]) if want_mantissa else None, _ptr(out["status"]), _ptr(out["payload"]),
-                        _ptr(out["n_bytes"]), self._stream())
-        out["flags"] = fl
-        return out
+        def call(view, fl, o):
+            given = self._given(bit_alloc, "bit_alloc", (pcm.n_cf, self.band_stride))
+            self._call_rate("pacx_encode_pack_alloc_batch", view, fl, _ptr(given), *self._pack_ptrs(o, want_mantissa),
+                            self._stream())
+        return self._encode(pcm, flags, out, self._pack_outputs, call)
 
     def encode_vq(self, pcm, flags=None, out=None, want_entries=False, entries_per_band=160):
         """The shipped configuration (gain-shape PVQ, SBR if the handle has it) from
@@ -539,29 +537,17 @@ class Encoder:
         [n_cf, band_stride] (final), payload [n_cf, payload_stride], n_bytes, status;
         with want_entries also entries [n_cf,8,32,cap] (structured: value, width,
         band) and entry_count [n_cf,8,32]."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = {
-                "overall": self._empty((n_cf, _lib.SUB), torch.int32),
-                "bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
-                "status": self._empty((n_cf,), torch.int32),
-                "payload": self._empty((n_cf, self.payload_stride), torch.uint8),
-                "n_bytes": self._empty((n_cf,), torch.int32),
-            }
-        ent = cnt = None
-        if want_entries:
-            ent = torch.zeros((n_cf, _lib.SUB, _lib.MAX_BANDS, entries_per_band, 2), dtype=torch.int64,
-                              device=self.device)
-            cnt = torch.zeros((n_cf, _lib.SUB, _lib.MAX_BANDS), dtype=torch.int32, device=self.device)
-        self._call("pacx_encode_vq_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(out["overall"]),
-                   _ptr(out["bit_alloc"]), _ptr(out["payload"]), _ptr(out["n_bytes"]), _ptr(out["status"]),
-                   _ptr(ent), _ptr(cnt), ctypes.c_int32(entries_per_band if want_entries else 0),
-                   self._stream())
-        out["flags"] = fl
-        if want_entries:
-            out["entries"], out["entry_count"] = ent, cnt
-        return out
+        def call(view, fl, o):
+            ent = cnt = None
+            if want_entries:
+                ent = torch.zeros((pcm.n_cf, _lib.SUB, _lib.MAX_BANDS, entries_per_band, 2), dtype=torch.int64,
+                                  device=self.device)
+                cnt = torch.zeros((pcm.n_cf, _lib.SUB, _lib.MAX_BANDS), dtype=torch.int32, device=self.device)
+            self._call("pacx_encode_vq_batch", view, fl, *self._vq_ptrs(o), _ptr(ent), _ptr(cnt),
+                       ctypes.c_int32(entries_per_band if want_entries else 0), self._stream())
+            if want_entries:
+                o["entries"], o["entry_count"] = ent, cnt
+        return self._encode(pcm, flags, out, self.alloc_vq_outputs, call)
 
     def vq_band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """band_curve for a gain-shape handle without SBR (pacx_vq_band_curve_batch, include/pacx.h): the same dict in
@@ -569,44 +555,33 @@ class Encoder:
         band coded with (i + 1) x lines bits.  A band whose lines are all zero holds -inf (it codes nothing at any
         size).  The pick and the solves run on the scalar sibling of this handle (context.scalar_sibling), the second
         pass is encode_vq_alloc."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        if out is None:
-            out = {"nmr": torch.full((n_cf, self.band_stride, _lib.BAND_CAND), float("nan"), dtype=torch.float64,
-                                     device=self.device),
-                   "cap": torch.full((n_cf, _lib.SUB), -1, dtype=torch.int32, device=self.device),
-                   "cap_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device)}
-        if tuple(out["nmr"].shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or \
-                tuple(out["cap"].shape) != (n_cf, _lib.SUB) or tuple(out["cap_alloc"].shape) != (n_cf, self.band_stride):
-            raise ValueError(f"band curve: nmr [{n_cf}, {self.band_stride}, {_lib.BAND_CAND}], cap [{n_cf}, {_lib.SUB}], "
-                             f"cap_alloc [{n_cf}, {self.band_stride}]")
-        self._call_rate("pacx_vq_band_curve_batch", ctypes.byref(pcm.c), _ptr(fl), ctypes.c_double(max_bits_per_sample),
-                        _ptr(out["nmr"]), _ptr(out["cap"]), _ptr(out["cap_alloc"]), self._stream())
-        out["flags"] = fl
-        return out
+        return self._band_curve("pacx_vq_band_curve_batch", pcm, flags, max_bits_per_sample, out)
 
     def encode_vq_alloc(self, pcm, flags, bit_alloc, out=None):
         """encode_vq() with the allocation of every band given by the caller (pacx_encode_vq_alloc_batch): bit_alloc
         int32 [n_cf, band_stride]; values below 2 count as 0, values above maxMantBits as maxMantBits, and
         out["bit_alloc"] holds what was coded (a band whose lines are all zero drops to 0).  -> encode_vq's dict."""
-        n_cf = pcm.n_cf
-        fl = self.flags_tensor(flags, pcm.n_frames)
-        bit_alloc = torch.as_tensor(bit_alloc, device=self.device).to(torch.int32).contiguous()
-        if tuple(bit_alloc.shape) != (n_cf, self.band_stride):
-            raise ValueError(f"bit_alloc: int32 [{n_cf}, {self.band_stride}]")
-        if out is None:
-            out = {
-                "overall": self._empty((n_cf, _lib.SUB), torch.int32),
-                "bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
-                "status": self._empty((n_cf,), torch.int32),
-                "payload": self._empty((n_cf, self.payload_stride), torch.uint8),
-                "n_bytes": self._empty((n_cf,), torch.int32),
-            }
-        self._call_rate("pacx_encode_vq_alloc_batch", ctypes.byref(pcm.c), _ptr(fl), _ptr(bit_alloc),
-                        _ptr(out["overall"]), _ptr(out["bit_alloc"]), _ptr(out["payload"]), _ptr(out["n_bytes"]),
-                        _ptr(out["status"]), self._stream())
-        out["flags"] = fl
-        return out
+        def call(view, fl, o):
+            given = self._given(bit_alloc, "bit_alloc", (pcm.n_cf, self.band_stride))
+            self._call_rate("pacx_encode_vq_alloc_batch", view, fl, _ptr(given), *self._vq_ptrs(o), self._stream())
+        return self._encode(pcm, flags, out, self.alloc_vq_outputs, call)
+
+    @staticmethod
+    def _vq_ptrs(out):
+        """the outputs of the gain-shape encodes, in the order their entry points take them"""
+        return [_ptr(out["overall"]), _ptr(out["bit_alloc"]), _ptr(out["payload"]), _ptr(out["n_bytes"]), _ptr(out["status"])]
+
+    def alloc_vq_outputs(self, n_cf, with_payload=True):
+        """what the gain-shape coder writes per channel-frame (the decoder reads the first three back)"""
+        o = {
+            "overall": self._empty((n_cf, _lib.SUB), torch.int32),
+            "bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
+            "status": self._empty((n_cf,), torch.int32),
+        }
+        if with_payload:
+            o["payload"] = self._empty((n_cf, self.payload_stride), torch.uint8)
+            o["n_bytes"] = self._empty((n_cf,), torch.int32)
+        return o
 
     def alloc_outputs(self, n_cf, with_payload=False):
         o = {
@@ -704,9 +679,7 @@ class Encoder:
         n_blocks = n_cf // n_channels
         out = {
             "flags": self._empty((n_cf,), torch.uint8),
-            "overall": self._empty((n_cf, _lib.SUB), torch.int32),
-            "bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
-            "status": self._empty((n_cf,), torch.int32),
+            **self.alloc_vq_outputs(n_cf, with_payload=False),
             "lines": self._empty((n_cf, N_LONG), torch.float64) if want_lines else None,
             "blocks": self._empty((n_cf, 2 * N_LONG), torch.float64) if want_blocks else None,
             "pcm": self._empty(((n_blocks + 1) * N_LONG, n_channels), torch.int16) if want_pcm else None,
