@@ -2284,6 +2284,61 @@ extern "C" int pacx_band_solve_peak(pacx_handle *h, int64_t n_cf, const double *
                  peak_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream, &peak);
 }
 
+/* ---- the size at every target of the grid, and the solve on it ---- */
+static int profile_range(pacx_handle *h, const char *what, double nmr_lo_db, double nmr_hi_db, int *t_lo, int *t_hi)
+{
+    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, t_lo, t_hi))
+        return rc;
+    if ((long long)*t_hi - *t_lo + 1 > PACX_PROFILE_MAX)
+        return fail(h, PACX_E_ARG, std::string(what) + ": a profile holds at most " + std::to_string(PACX_PROFILE_MAX) +
+                                       " targets (a range of " +
+                                       std::to_string((PACX_PROFILE_MAX - 1) / PACX_RATE_TARGET_GRID) + " dB)");
+    return PACX_OK;
+}
+
+extern "C" int pacx_band_profile(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                 const int32_t *cap_alloc, double nmr_lo_db, double nmr_hi_db, int64_t *profile,
+                                 void *stream)
+{
+    const char *what = "pacx_band_profile";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (!profile || (n_cf > 0 && (!nmr || !cap || !cap_alloc)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    int t_lo, t_hi;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_profile(h->T, n_cf, t_lo, t_hi, nmr, cap, cap_alloc, profile, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_profile_solve(pacx_handle *h, const int64_t *profile, int64_t limit_bytes, double nmr_lo_db,
+                                  double nmr_hi_db, pacx_rate_result *result, void *stream)
+{
+    const char *what = "pacx_profile_solve";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (!profile || !result)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    int t_lo, t_hi;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_profile_solve(profile, limit_bytes, t_lo, t_hi, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                                 const double *nmr_db, uint64_t *summary, void *stream)
 {

@@ -231,6 +231,13 @@ void pacx_launch_band_solve_peak(const PacxTables &T, const PacxSolve &v, const 
 void pacx_launch_band_sanitize(const PacxTables &T, const uint8_t *flags, int n_ch, long long n_cf, const int32_t *in,
                                int32_t *out, uint32_t *status, int payload_stride, hipStream_t st);
 
+/* k_profile.hip: total(t / 64) of a band curve added into profile [t_hi - t_lo + 1] for every t of the range at once
+   (t_hi - t_lo + 1 <= PACX_PROFILE_MAX), and the solve's decision read from such a profile: one launch each */
+void pacx_launch_band_profile(const PacxTables &T, long long n_cf, int t_lo, int t_hi, const double *nmr,
+                              const int32_t *cap, const int32_t *cap_alloc, int64_t *profile, hipStream_t st);
+void pacx_launch_profile_solve(const int64_t *profile, long long limit, int t_lo, int t_hi, pacx_rate_result *result,
+                               hipStream_t st);
+
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
    row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr

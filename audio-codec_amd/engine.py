@@ -510,6 +510,54 @@ class Encoder:
         target_nmr_db, met, total_bytes and band_pick's bit_alloc, n_bytes, capped at that target."""
         return self._solve("band_solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
 
+    @staticmethod
+    def _profile_len(what, nmr_lo_db, nmr_hi_db):
+        """G of a profile over this range, checked as the C side checks it"""
+        grid = _lib.RATE_TARGET_GRID
+        lo, hi = float(nmr_lo_db) * grid, float(nmr_hi_db) * grid
+        if not (np.isfinite(lo) and np.isfinite(hi)) or max(abs(lo), abs(hi)) > 2.0 ** 20 * grid or \
+                lo != np.floor(lo) or hi != np.floor(hi) or lo > hi:
+            raise ValueError(f"{what}: nmr_lo_db <= nmr_hi_db, finite multiples of 1/{grid} dB")
+        if hi - lo + 1 > _lib.PROFILE_MAX:
+            raise ValueError(f"{what}: a profile holds at most {_lib.PROFILE_MAX} targets "
+                             f"(a range of {(_lib.PROFILE_MAX - 1) // grid} dB)")
+        return int(hi - lo) + 1
+
+    def _profile_tensor(self, what, profile, n):
+        if not isinstance(profile, torch.Tensor) or profile.dtype != torch.int64 or tuple(profile.shape) != (n,) or \
+                profile.device != torch.device(self.device) or not profile.is_contiguous():
+            raise ValueError(f"{what}: a profile is a contiguous int64 device tensor [{n}] for this range")
+        return profile
+
+    def band_profile(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """The body size of a band curve at every target of the grid in one pass (pacx_band_profile, include/pacx.h):
+        int64 device tensor [G], G = 64 (nmr_hi_db - nmr_lo_db) + 1, entry g = what band_pick at nmr_lo_db + g / 64 dB
+        gives as sum(n_bytes + 4 where n_bytes > 0).  With `out` (such a tensor) the sizes are ADDED to it: the profile
+        of a stream is the sum of its pieces' in any order, which is what lets a stream too long for one batch be
+        solved (profile_solve).  -> the tensor."""
+        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, "band_profile")
+        n = self._profile_len("band_profile", nmr_lo_db, nmr_hi_db)
+        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_tensor("band_profile", out, n)
+        self._call_rate("pacx_band_profile", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
+        return profile
+
+    def profile_solve(self, profile, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
+        """band_solve's decision read from a profile (pacx_profile_solve): the lowest target of the range whose size on
+        the profile stays within limit_bytes, by the same bisection.  On the profile of a whole curve:
+        band_solve(curve, ...)'s target_nmr_db, met, total_bytes.  -> dict of those three."""
+        n = self._profile_len("profile_solve", nmr_lo_db, nmr_hi_db)
+        profile = self._profile_tensor("profile_solve", profile, n)
+        if int(limit_bytes) != limit_bytes or limit_bytes < 0:
+            raise ValueError(f"profile_solve: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+        result = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
+        self._call_rate("pacx_profile_solve", _ptr(profile), ctypes.c_int64(int(limit_bytes)),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(result), self._stream())
+        res = result.cpu().numpy()
+        return {"target_nmr_db": float(res[0, 0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[0, 1]),
+                "total_bytes": int(res[:, 2:].copy().view(np.int64)[0, 0])}
+
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,

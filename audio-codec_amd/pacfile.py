@@ -413,11 +413,10 @@ def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False, hea
     return head + body[:n].cpu().numpy().tobytes()
 
 
-def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples, use_vq=False):
-    """(CodingParams, encoder, PCM view, flags) of the one-batch scalar path with the cap rate as the handle's; use_vq:
-    of the gain-shape path without SBR"""
+def _rate_coding_params(pcm, sample_rate, max_kbps_per_channel, header_samples, use_vq=False):
+    """the CodingParams of the rate-control streams, the cap rate as the handle's: checks the PCM's shape and type (pcm:
+    anything with ndim, dtype, shape and len) and the cap, touches no sample and no GPU"""
     from .audiofile import CodingParams
-    pcm = np.ascontiguousarray(pcm)
     hop = 1024
     if pcm.ndim != 2 or pcm.dtype != np.int16 or len(pcm) % hop:
         raise ValueError("pcm: int16 [n, nCh], n a multiple of 1024")
@@ -433,6 +432,15 @@ def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, 
                          f"{cp.targetBitsPerSample:.3g} bits per sample: the cap must lie in (0, 16] bits per sample "
                          f"(at most {16 * cp.sampleRate / 1000:g} kb/s here)")
     cp.useSBR, cp.useVQ = False, bool(use_vq)
+    return cp
+
+
+def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples, use_vq=False):
+    """(CodingParams, encoder, PCM view, flags) of the one-batch scalar path with the cap rate as the handle's; use_vq:
+    of the gain-shape path without SBR"""
+    pcm = np.ascontiguousarray(pcm)
+    hop = 1024
+    cp = _rate_coding_params(pcm, sample_rate, max_kbps_per_channel, header_samples, use_vq)
     enc = context.encoder_for_params(cp)
     planar = device_stream(enc, pcm, hop)
     view = PcmView.stream(planar, hop)
@@ -559,6 +567,13 @@ def _abr_range(nmr_range_db):
     return lo, hi
 
 
+def _unreachable(limit, total, hi, head):
+    """what an average-rate call says when even the highest target of its range does not fit"""
+    return (f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
+            f"{total} bytes ({len(head) + total} with the header), the "
+            f"smallest size this range of targets gives")
+
+
 def _check_peak(peak_kbps_per_channel, segment_hops):
     """the peak_kbps_per_channel keyword, before any GPU work"""
     if peak_kbps_per_channel is None:
@@ -603,9 +618,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
     n_ch = cp.nChannels
 
     def unreachable(limit, total):
-        return (f"a body of {limit} bytes cannot be reached: at the highest target, {hi:g} dB, it takes "
-                f"{total} bytes ({len(head) + total} with the header), the "
-                f"smallest size this range of targets gives")
+        return _unreachable(limit, total, hi, head)
 
     done = []
     for (kbps, _), limit in zip(sizes, limits):
@@ -695,6 +708,75 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
                                  block_switching, header_samples, nmr_range_db, allocation, segment_hops,
                                  peak_kbps_per_channel)
     return done[0][0]
+
+
+class _Blocks:
+    """what _abr_limit reads of a PCM view: the blocks the driver writes"""
+
+    def __init__(self, n_frames):
+        self.n_frames = n_frames
+
+
+def _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching, header_samples,
+                       nmr_range_db, use_vq):
+    """everything encode_stream_abr_chunked refuses, before any GPU work -> (CodingParams, header bytes, make), make()
+    -> the streaming.HostStreamRateEncoder of the call"""
+    from .engine import Encoder
+    try:
+        hops = int(chunk_hops)
+    except (TypeError, ValueError):
+        hops = 0
+    if isinstance(chunk_hops, bool) or hops != chunk_hops or hops < 1:
+        raise ValueError(f"chunk_hops = {chunk_hops!r}: a whole number of blocks, at least 1")
+    lo, hi = _abr_range(nmr_range_db)
+    Encoder._profile_len("nmr_range_db", lo, hi)
+    cp = _rate_coding_params(pcm, sample_rate, max_kbps_per_channel, header_samples, use_vq)
+    if len(pcm) == 0:
+        raise ValueError("pcm: at least one block of 1024 samples")
+
+    def make():
+        from .streaming import HostStreamRateEncoder
+        return HostStreamRateEncoder(context.encoder_for_params(cp), cp.nChannels, hops, cp.targetBitsPerSample,
+                                     block_switching=block_switching, nmr_lo_db=lo, nmr_hi_db=hi)
+    return cp, header_bytes(cp), make
+
+
+def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
+                            max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                            nmr_range_db=(-30, 30), use_vq=False):
+    """encode_stream_abr_chunked piece by piece: an iterator that gives the file's header, then the bodies of the
+    chunks in order (bytes; their concatenation is that call's result).  The arguments are checked, the stream is
+    analysed and the target solved when this is called; the second pass runs as the iterator is consumed."""
+    cp, head, make = _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching,
+                                        header_samples, nmr_range_db, use_vq)
+    limit = _abr_limit(cp, _Blocks(len(pcm) // 1024 + 2), head, kbps_per_channel, max_bytes)
+    hr = make()
+    hr.analyse(pcm)
+    sol = hr.solve(limit)
+    if not sol["met"]:
+        raise ValueError(_unreachable(limit, sol["total_bytes"], hr.hi, head))
+
+    def parts():
+        yield head
+        for body in hr.encode(pcm, sol["target_nmr_db"]):
+            yield body.tobytes()
+    return parts()
+
+
+def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
+                              max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                              nmr_range_db=(-30, 30), use_vq=False):
+    """encode_stream_abr(allocation="band") for a stream too long for one batch -> the same .pac bytes, from host
+    memory to host memory in chunks of chunk_hops blocks, with device memory bounded by the chunk.  pcm: anything that
+    slices to int16 [n, nCh] pieces (an np.memmap included), n a multiple of 1024 and at least 1024.  Two passes
+    (streaming.HostStreamRateEncoder): per chunk the band curve and its size at EVERY target of nmr_range_db, added
+    into one profile (Encoder.band_profile; at most 128 dB of range); the solve of encode_stream_abr read from that
+    profile (Encoder.profile_solve); then per chunk curve, pick at the target found and second pass.  The sizes
+    (kbps_per_channel or max_bytes), max_kbps_per_channel and the ValueError when even the highest target does not fit
+    are encode_stream_abr's.  use_vq: the gain-shape coder without SBR, the bytes of encode_stream_vq_abr.  No
+    segments, no peaks, no allocation="budget".  iter_encode_abr_chunked gives the same bytes piece by piece."""
+    return b"".join(iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
+                                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq))
 
 
 def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,

@@ -464,6 +464,22 @@ def band_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False
             "cap_alloc": c["cap_alloc"].cpu().numpy().reshape(-1, n_ch, enc.band_stride)}
 
 
+def stream_rate_profile(pcm, sample_rate, chunk_hops=4096, max_kbps_per_channel=320, block_switching=False,
+                        nmr_range_db=(-30, 30), use_vq=False):
+    """The body size of a stream at every target of a range, for plotting size against quality, from one analysis
+    pass in chunks of chunk_hops blocks (pacfile.encode_stream_abr_chunked's first pass; pcm as there): ->
+    (targets_db float64 [G], total_bytes int64 [G]), the grid of 1/64 dB over nmr_range_db and what
+    encode_stream_nmr(target, allocation="band") -- use_vq: encode_stream_vq_nmr -- takes for its body there."""
+    from . import pacfile
+    _, _, make = pacfile._abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching, None,
+                                            nmr_range_db, use_vq)
+    hr = make()
+    profile = hr.analyse(pcm)
+    hr.s_k.synchronize()                               # the pass runs on the encoder's kernel stream
+    total = profile.cpu().numpy()
+    return float(hr.lo) + np.arange(len(total)) / float(_lib.RATE_TARGET_GRID), total
+
+
 def nmr_of_file(pcm, pac_bytes, block_switching=None, chunk_hops=4096):
     """Report of a .pac made elsewhere (by the reference itself, say) against the PCM it was made from.  The
     hop-to-record map is re-derived the way the writer makes it: the transient detector gives the flags, a

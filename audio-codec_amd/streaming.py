@@ -17,6 +17,8 @@ body (round 2 measured this pipeline in tools/pcie_probe.py: 24.8 M cf/s at 131 
 or, for a stream already in memory, `for body in hs.encode(pcm): ...` / `pacfile.encode_stream(...,
 chunk_hops=N)`, whose bytes equal the one-batch path's (tests/test_gpu_round3.py).  HostStreamDecoder (below) is
 the same arrangement for the way back: .pac bytes in, PCM out, `pacfile.decode_stream(..., chunk_bytes=N)`.
+HostStreamRateEncoder is the average-bit-rate encode on the same chunk front end (_chunk_front), in two passes:
+`pacfile.encode_stream_abr_chunked(..., chunk_hops=N)`.
 
 Chunks are consecutive pieces of ONE stream: the one-hop halo (frame f spans hops f-1, f) and, with
 block switching, the transient decisions of the two hops before a chunk are carried from chunk to chunk
@@ -32,6 +34,33 @@ from . import _lib
 from .engine import PcmView, _ptr
 
 HOP = 1024
+
+
+def _chunk_front(enc, n_ch, dev_in, n_hops, halo, carry, tr, block_switching, tail):
+    """The front end of one chunk of a stream, queued on the current stream: dev_in [nCh, (F + 1) * 1024] holds the
+    chunk's n_hops hops from column 1024 on.  The hop before them comes from `halo` (frame f spans hops f - 1, f), which
+    then takes the chunk's last hop; with block switching the detector runs on the chunk's hops and `carry`, the
+    decisions of the two hops before the chunk, turns them into the packed flags (last, cur, next) of its frames and
+    takes the chunk's last two.  tail: the driver's last two blocks (the last hop again, Close): no detection, Close
+    writes (0, 0, 0).  -> (PcmView of the chunk's frames, flags or None)"""
+    dev_in[:, :HOP].copy_(halo)                                      # frame 0 of the chunk starts in the previous chunk
+    halo.copy_(dev_in[:, n_hops * HOP:(n_hops + 1) * HOP])
+    view = PcmView(dev_in, n_ch, n_hops, HOP, dev_in.shape[1], 1)
+    flags = None
+    if block_switching:
+        tr = tr[:n_hops]
+        if tail:
+            tr.zero_()                                               # the pass after EOF and Close: no detection
+        else:
+            hops = _lib.PacxPcm(dev_in.data_ptr() + 2 * HOP, _lib.PCM_I16, n_ch, n_hops, HOP, dev_in.shape[1], 1)
+            enc._call("pacx_transient_flags", ctypes.byref(hops), _ptr(tr), None, enc._stream())
+        ext = torch.cat((carry, tr))                                 # decisions of hops g-2, g-1, g, ...
+        flags = ext[:n_hops] | (ext[1:n_hops + 1] << 1) | (ext[2:n_hops + 2] << 2)
+        if tail:
+            flags[-1] = 0                                            # Close writes (0, 0, 0)
+        carry.copy_(ext[n_hops:n_hops + 2])
+        flags = flags.contiguous()
+    return view, flags
 
 
 class HostStreamEncoder:
@@ -103,24 +132,8 @@ class HostStreamEncoder:
         with torch.cuda.stream(self.s_k):
             self.s_k.wait_event(self.ev_in[k])
             self.s_k.wait_event(self.ev_out[k])                      # the body that last sat in bodies[k] has left
-            dev_in[:, :HOP].copy_(self.halo)                         # frame 0 of the chunk starts in the previous chunk
-            self.halo.copy_(dev_in[:, n_hops * HOP:(n_hops + 1) * HOP])
-            view = PcmView(dev_in, self.n_ch, n_hops, HOP, dev_in.shape[1], 1)
-            flags = None
-            if self.block_switching:
-                tr = self.tr[:n_hops]
-                if _tail:
-                    tr.zero_()                                       # the pass after EOF and Close: no detection
-                else:
-                    hops = _lib.PacxPcm(dev_in.data_ptr() + 2 * HOP, _lib.PCM_I16, self.n_ch, n_hops, HOP,
-                                        dev_in.shape[1], 1)
-                    enc._call("pacx_transient_flags", ctypes.byref(hops), _ptr(tr), None, enc._stream())
-                ext = torch.cat((self.carry, tr))                    # decisions of hops g-2, g-1, g, ...
-                flags = ext[:n_hops] | (ext[1:n_hops + 1] << 1) | (ext[2:n_hops + 2] << 2)
-                if _tail:
-                    flags[-1] = 0                                    # Close writes (0, 0, 0)
-                self.carry.copy_(ext[n_hops:n_hops + 2])
-                flags = flags.contiguous()
+            view, flags = _chunk_front(enc, self.n_ch, dev_in, n_hops, self.halo, self.carry, self.tr,
+                                       self.block_switching, _tail)
             sub = {name: (t[:n_cf] if t is not None else None) for name, t in out.items()}
             if enc.use_vq:
                 enc.encode_vq(view, flags, sub)
@@ -203,6 +216,151 @@ class HostStreamEncoder:
         self.carry.zero_()
         self.raises.zero_()
         self.pending = [False] * self.depth
+
+
+class HostStreamRateEncoder:
+    """The average-bit-rate encode with band-by-band allocation (pacfile.encode_stream_abr(allocation="band")) in
+    chunks of bounded size, host memory to host memory, in two passes over the PCM:
+
+        hr = HostStreamRateEncoder(enc, n_channels=2, hops_per_chunk=4096, max_bits_per_sample=cap, block_switching=True)
+        hr.analyse(pcm)                       # per chunk: band curve -> its size at every target, added to the profile
+        sol = hr.solve(limit_bytes)           # band_solve's decision on the profile: target_nmr_db, met, total_bytes
+        for body in hr.encode(pcm, sol["target_nmr_db"]): ...     # per chunk: curve -> pick -> second pass -> body
+
+    The profile (Encoder.band_profile: G int64 words) is all that the first pass keeps, so device memory is bounded by
+    the chunk and the bodies are those of the one-batch call: the curve of a frame, the pick at the target and the
+    second pass do not depend on how the stream is cut.  The curve is taken twice -- once per pass -- instead of kept.
+    Chunks run on HostStreamEncoder's front end (_chunk_front): the PCM of chunk i + 1 goes up while chunk i computes,
+    halo and transient carry stay on the device, the driver's last two blocks are a chunk of their own.  pcm is
+    anything that slices to int16 [n, nCh] pieces (an np.memmap included); only a chunk of it is touched at a time.
+    enc: a scalar encoder, or a gain-shape one without SBR (its curve and second pass, the pick and the solve on its
+    scalar sibling), with the cap rate as its rate."""
+
+    def __init__(self, enc, n_channels, hops_per_chunk, max_bits_per_sample, block_switching=False, nmr_lo_db=-30,
+                 nmr_hi_db=30, depth=2):
+        from .pacfile import _BandPath
+        self.enc, self.n_ch, self.F, self.depth = enc, int(n_channels), int(hops_per_chunk), int(depth)
+        if self.F < 1 or self.depth < 2:
+            raise ValueError("hops_per_chunk must be at least 1 and depth at least 2")
+        self.block_switching, self.max_bps = bool(block_switching), float(max_bits_per_sample)
+        self.lo, self.hi = nmr_lo_db, nmr_hi_db
+        self.path = _BandPath(enc)
+        dev, F, n_ch = enc.device, self.F, self.n_ch
+        self.n_cf = max(F, 2) * n_ch                                   # the tail chunk holds two blocks
+        enc.reserve(self.n_cf)
+        self.cap = self.n_cf * (enc.payload_stride + 4)
+        rng = range(self.depth)
+        self.s_in, self.s_k, self.s_out = (torch.cuda.Stream(device=dev) for _ in range(3))
+        self.host_in = [torch.zeros((n_ch, max(F, 2) * HOP), dtype=torch.int16).pin_memory() for _ in rng]
+        self.dev_in = [torch.zeros((n_ch, (max(F, 2) + 1) * HOP), dtype=torch.int16, device=dev) for _ in rng]
+        self.bodies = [torch.empty(self.cap, dtype=torch.uint8, device=dev) for _ in rng]
+        self.totals = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in rng]
+        self.host_body = [torch.empty(self.cap, dtype=torch.uint8).pin_memory() for _ in rng]
+        self.host_total = [torch.zeros(1, dtype=torch.int64).pin_memory() for _ in rng]
+        self.ev_in = [torch.cuda.Event() for _ in rng]
+        self.ev_k = [torch.cuda.Event() for _ in rng]
+        self.ev_out = [torch.cuda.Event() for _ in rng]
+        self.halo = torch.zeros((n_ch, HOP), dtype=torch.int16, device=dev)
+        self.carry = torch.zeros(2, dtype=torch.uint8, device=dev)
+        self.tr = torch.zeros(max(F, 2), dtype=torch.uint8, device=dev)
+        self.profile = self.path.solver.band_profile(self._no_frames(), self.lo, self.hi)      # zeros [G]; checks the range
+        self.n_frames = 0                                              # blocks the last analyse() saw
+
+    def _no_frames(self):
+        e = self.path.solver
+        return {"nmr": torch.zeros((0, e.band_stride, _lib.BAND_CAND), dtype=torch.float64, device=e.device),
+                "cap": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device),
+                "cap_alloc": torch.zeros((0, e.band_stride), dtype=torch.int32, device=e.device)}
+
+    def _chunks(self, pcm):
+        """the chunks of a stream and the driver's last two blocks, one after the other: fills the pinned buffer of
+        the next slot, queues its way up and yields (slot, hops, tail).  The caller then queues the chunk's work on
+        the kernel stream, _front() first and ev_k[slot] last."""
+        if len(pcm) % HOP or len(pcm) == 0:
+            raise ValueError("pcm: int16 [n, nCh], n a multiple of 1024 and at least 1024")
+        torch.cuda.synchronize(self.enc.device)                        # a new pass over the stream
+        with torch.cuda.stream(self.s_k):
+            self.halo.zero_()
+            self.carry.zero_()
+        n_hops = len(pcm) // HOP
+        pieces = [(h0, min(self.F, n_hops - h0), False) for h0 in range(0, n_hops, self.F)] + [(n_hops - 1, 2, True)]
+        for i, (h0, n, tail) in enumerate(pieces):
+            k = i % self.depth
+            self.ev_in[k].synchronize()                                # the copy that last read host_in[k] is done
+            buf = self.host_in[k].numpy()
+            piece = np.asarray(pcm[h0 * HOP:(h0 + (1 if tail else n)) * HOP])
+            if piece.dtype != np.int16 or piece.ndim != 2 or piece.shape[1] != self.n_ch:
+                raise ValueError(f"pcm: int16 [n, {self.n_ch}]")
+            buf[:, :len(piece)] = piece.T
+            if tail:
+                buf[:, HOP:2 * HOP] = 0                                # Close
+            with torch.cuda.stream(self.s_in):
+                self.s_in.wait_event(self.ev_k[k])                     # the kernels that last read dev_in[k] are done
+                self.dev_in[k][:, HOP:(n + 1) * HOP].copy_(self.host_in[k][:, :n * HOP], non_blocking=True)
+                self.ev_in[k].record(self.s_in)
+            yield k, n, tail
+
+    def _front(self, k, n, tail):
+        """on the kernel stream: wait for the chunk's PCM, then the front end -> (view, flags)"""
+        self.s_k.wait_event(self.ev_in[k])
+        return _chunk_front(self.enc, self.n_ch, self.dev_in[k], n, self.halo, self.carry, self.tr,
+                            self.block_switching, tail)
+
+    def analyse(self, pcm):
+        """the first pass: the stream's size at every target of the range, into self.profile (zeroed first).
+        -> the profile, int64 device tensor [G]; the host does not wait for it"""
+        with torch.cuda.stream(self.s_k):
+            self.profile.zero_()
+        frames = 0
+        for k, n, tail in self._chunks(pcm):
+            with torch.cuda.stream(self.s_k):
+                view, flags = self._front(k, n, tail)
+                self.path.solver.band_profile(self.path.curve(view, flags, self.max_bps), self.lo, self.hi,
+                                              out=self.profile)
+                self.ev_k[k].record(self.s_k)
+            frames += n
+        self.n_frames = frames
+        return self.profile
+
+    def solve(self, limit_bytes):
+        """Encoder.profile_solve on the profile of the last analyse(): dict target_nmr_db, met, total_bytes"""
+        with torch.cuda.stream(self.s_k):
+            return self.path.solver.profile_solve(self.profile, limit_bytes, self.lo, self.hi)
+
+    def _result(self, k):
+        """the body of the chunk in slot k: a uint8 NumPy view of pinned memory, valid until the slot is used again"""
+        self.ev_out[k].synchronize()
+        n = int(self.host_total[k].item())
+        if n > self.cap:
+            raise RuntimeError(f"body of {n} bytes does not fit its {self.cap}-byte buffer")
+        with torch.cuda.stream(self.s_out):
+            self.host_body[k][:n].copy_(self.bodies[k][:n], non_blocking=True)
+        self.s_out.synchronize()
+        return self.host_body[k][:n].numpy()
+
+    def encode(self, pcm, target_nmr_db):
+        """the second pass: yields the chunks' bodies in order ('<L nBytes' + payload per channel-block), every band at
+        the smallest size that keeps it at or below target_nmr_db (Encoder.band_pick), the driver's last two blocks
+        last.  A body is a view of pinned memory, valid until the next one is taken."""
+        enc, order = self.enc, []
+        for k, n, tail in self._chunks(pcm):
+            if len(order) == self.depth:                               # slot k still holds a body nobody took
+                yield self._result(order.pop(0))
+            with torch.cuda.stream(self.s_k):
+                view, flags = self._front(k, n, tail)
+                pick = self.path.solver.band_pick(self.path.curve(view, flags, self.max_bps), float(target_nmr_db))
+                out = self.path.encode(view, flags, pick["bit_alloc"])
+                self.s_k.wait_event(self.ev_out[k])                    # the total that last sat in totals[k] has left
+                enc._call("pacx_gather_body", ctypes.c_int64(n * self.n_ch), _ptr(out["payload"]), _ptr(out["n_bytes"]),
+                          _ptr(self.bodies[k]), ctypes.c_int64(self.cap), _ptr(self.totals[k]), enc._stream())
+                self.ev_k[k].record(self.s_k)
+            with torch.cuda.stream(self.s_out):
+                self.s_out.wait_event(self.ev_k[k])
+                self.host_total[k].copy_(self.totals[k], non_blocking=True)
+                self.ev_out[k].record(self.s_out)
+            order.append(k)
+        for k in order:
+            yield self._result(k)
 
 
 class HostStreamDecoder:

@@ -886,6 +886,52 @@ int pacx_band_solve(pacx_handle *h, int64_t n_cf, const double *nmr, const int32
                     int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc, int32_t *n_bytes,
                     uint8_t *capped, pacx_rate_result *result, void *stream);
 
+/* ---- the size at every target of the grid: a stream solved piece by piece ---- */
+
+#define PACX_PROFILE_MAX 8193     /* grid targets of one profile: a range of 128 dB */
+
+/*
+ * pacx_band_solve needs the whole stream's curve resident: it bisects with one pick per target tried.  total(T) is a
+ * sum over channel-frames of integers, so the size at EVERY target of the grid can be taken in one pass instead, piece
+ * by piece in any order, and the solve read from that.  With [t_lo, t_hi] = 64 [nmr_lo_db, nmr_hi_db] and
+ * G = t_hi - t_lo + 1:
+ *
+ *   for g = 0 ... G - 1:  profile[g] += total(T_g) over the n_cf channel-frames given,  T_g = (t_lo + g) / 64
+ *
+ * total, bytes, pick, the miss rule and the cap rule are exactly pacx_band_pick's: a NaN entry never passes, -inf
+ * passes everywhere and +inf nowhere, a dropped hop (cap all -1) adds nothing, a unit whose sum exceeds its cap takes
+ * cap_alloc.  The call ADDS to what profile holds -- the caller zeroes it before the first piece -- and integer sums
+ * make the result independent of how the stream is cut and of the order of execution.
+ *
+ * It is not G picks.  Per (unit, band) the size picked is a step function of the target with at most PACX_BAND_CAND
+ * steps: nmr[b][i] <= t / 64 is 64 nmr[b][i] <= t (both scalings are exact), so size i passes from the grid index
+ * e_i = ceil(64 nmr[b][i]) - t_lo on -- 0 where that is negative, never where the entry is NaN or above nmr_hi_db,
+ * decided by comparisons in double before any conversion to an integer -- and the pick at g is the smallest i with
+ * e_i <= g, bits(n_cand - 1) below all of them.  A workgroup puts a unit's steps as deltas into a difference array
+ * over the grid in LDS, scans it, applies the cap rule to the unit's sum at every g and keeps the bytes of its
+ * frames per g; it adds them to profile with one 64-bit atomicAdd per entry at its end.  One launch, no host wait.
+ *
+ *   nmr, cap, cap_alloc: a band curve as pacx_band_curve_batch or pacx_vq_band_curve_batch writes it
+ *   nmr_lo_db <= nmr_hi_db: pacx_band_solve's rules, and G <= PACX_PROFILE_MAX
+ *   profile (in/out):    int64 [G] in device memory
+ * n_cf = 0 is a valid call that adds nothing.  Any scalar handle with the curve's band layout serves, as for the
+ * pick.  PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr; PACX_E_ARG for a null pointer, a bad count,
+ * bounds that are not finite, inverted, off the grid or more than PACX_PROFILE_MAX targets apart.
+ */
+int pacx_band_profile(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                      double nmr_lo_db, double nmr_hi_db, int64_t *profile, void *stream);
+
+/*
+ * The decision of pacx_rate_solve (above), word for word, with total(t) := profile[t - t_lo]: met = 0 and t = t_hi
+ * if profile[G - 1] > limit_bytes, else the bisection from lo = t_lo - 1, hi = t_hi; result->total = profile[t - t_lo].
+ * On a profile of a whole curve the result is pacx_band_solve's on that curve.  One single-thread kernel with a trip
+ * count fixed by G; nothing waits for the device.
+ *   profile: int64 [G] in device memory, the range it was taken with;  limit_bytes >= 0;  result (out): device memory
+ * Errors as pacx_band_profile, and PACX_E_ARG for a negative limit.
+ */
+int pacx_profile_solve(pacx_handle *h, const int64_t *profile, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                       pacx_rate_result *result, void *stream);
+
 /* ---- one target per stretch of a stream: the two solves, segment by segment ---- */
 
 /*
