@@ -16,6 +16,7 @@ RATE_STEP = 32             # PACX_RATE_STEP: budgets of the constant-quality mod
 RATE_TARGET_GRID = 64      # PACX_RATE_TARGET_GRID: targets of pacx_rate_solve are multiples of 1 / 64 dB
 BAND_CAND = 16             # PACX_BAND_CAND: mantissa sizes on a band curve, candidate i = 0 bits for i = 0, else i + 1
 PROFILE_MAX = 8193         # PACX_PROFILE_MAX: grid targets of one pacx_band_profile
+SEG_CF_MAX = 1 << 40       # PACX_SEG_CF_MAX: channel-frames of one segment given by value
 E_ARG, E_UNSUPPORTED = -1, -2
 # what the reference raises where PACX_ST_REF_RAISES is set (coder/quantize.py:74, see include/pacx.h)
 REF_SCALAR_SBR_ERROR = "'numpy.int64' object does not support item assignment"
@@ -162,6 +163,14 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P]),
     "pacx_band_profile": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
     "pacx_profile_solve": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
+    # seg_cf, first_off by value; limit_bytes, target_t, result, worst_above: device memory
+    "pacx_band_profile_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64,
+                                                  ctypes.c_double, ctypes.c_double, _P, _P]),
+    "pacx_profile_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P,
+                                                   _P]),
+    "pacx_profile_clamp_add": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
+    "pacx_band_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P,
+                                               _P, _P]),
     "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                     _P]),
     "pacx_vq_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),

@@ -14,6 +14,8 @@
  *   k_band_pick       works on the arrays alone: one wave per channel-frame, a lane per (unit, band) pair scans the
  *                     band's sizes in ascending order for the first at or below the target; the unit sums go through
  *                     LDS, the frame's bits through the wave (band_frame).
+ *   k_band_pick_useg  pacx_band_pick_segments: k_band_pick with the target of the frame's segment, the segments uniform
+ *                     stretches given by value ((first_off + cf) / seg_cf) and one grid target each in an array.
  *   k_band_pick_seg   pacx_band_solve / pacx_band_solve_segments: the same frame work with one SolveState per stretch of
  *                     consecutive channel-frames (the whole stream is one stretch); the wave finds its frame's segment
  *                     in the boundaries (segment_of, rate_dev.h) and adds the frame's bytes to that segment's total:
@@ -258,6 +260,26 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, long l
         band_frame(T, cf, target, nmr, cap, cap_alloc, true, bit_alloc, n_bytes, capped, unit_sum[w], unit_miss[w]);
 }
 
+/* k_band_pick with one target per uniform segment (pacx_band_pick_segments): the wave's frame lies in segment
+   (first_off + cf) / seg_cf and takes target_t[segment] / 64, read through the scalar cache */
+__global__ __launch_bounds__(PICK_THREADS) void k_band_pick_useg(PacxTables T, long long n_cf, long long seg_cf,
+                                                                long long first_off,
+                                                                const int32_t *__restrict__ target_t,
+                                                                const double *__restrict__ nmr,
+                                                                const int32_t *__restrict__ cap,
+                                                                const int32_t *__restrict__ cap_alloc,
+                                                                int32_t *__restrict__ bit_alloc,
+                                                                int32_t *__restrict__ n_bytes,
+                                                                uint8_t *__restrict__ capped)
+{
+    __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
+    if (cf < n_cf)                                 /* wave-uniform */
+        band_frame(T, cf, (double)target_t[(first_off + cf) / seg_cf] / 64.0, nmr, cap, cap_alloc, true, bit_alloc,
+                   n_bytes, capped, unit_sum[w], unit_miss[w]);
+}
+
 /* k_band_pick as a pick of the solve, with a state per segment: the wave takes the target its frame's segment has in
    flight and adds to that segment's total; a frame whose segment is done is not scanned before the last launch.
    final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose four frames lie in
@@ -391,6 +413,18 @@ void pacx_k::pacx_launch_band_pick(const PacxTables &T, long long n_cf, double t
     const unsigned grid = (unsigned)((n_cf + PICK_WAVES - 1) / PICK_WAVES);
     hipLaunchKernelGGL(k_band_pick, dim3(grid), dim3(PICK_THREADS), 0, st, T, n_cf, target, nmr, cap, cap_alloc, bit_alloc,
                        n_bytes, capped);
+}
+
+void pacx_k::pacx_launch_band_pick_segments(const PacxTables &T, long long n_cf, long long seg_cf, long long first_off,
+                                            const int32_t *target_t, const double *nmr, const int32_t *cap,
+                                            const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes,
+                                            uint8_t *capped, hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    const unsigned grid = (unsigned)((n_cf + PICK_WAVES - 1) / PICK_WAVES);
+    hipLaunchKernelGGL(k_band_pick_useg, dim3(grid), dim3(PICK_THREADS), 0, st, T, n_cf, seg_cf, first_off, target_t, nmr,
+                       cap, cap_alloc, bit_alloc, n_bytes, capped);
 }
 
 void pacx_k::pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolve &v, const double *nmr,

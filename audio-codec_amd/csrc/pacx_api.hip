@@ -2339,6 +2339,105 @@ extern "C" int pacx_profile_solve(pacx_handle *h, const int64_t *profile, int64_
     return post_launch(h, what);
 }
 
+/* ---- the same per uniform segment of a piece ---- */
+/* what the two calls on a curve share: the handle's kind, the count, the segments given by value.  seg_cf is bounded
+   so that first_off + cf stays far from the end of 64 bits in the kernels */
+static int segments_by_value(pacx_handle *h, const char *what, int64_t n_cf, int64_t seg_cf, int64_t first_off)
+{
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (seg_cf < 1 || seg_cf > PACX_SEG_CF_MAX)
+        return fail(h, PACX_E_ARG, std::string(what) + ": seg_cf must lie in [1, 2^40]");
+    if (first_off < 0 || first_off >= seg_cf)
+        return fail(h, PACX_E_ARG, std::string(what) + ": first_off must lie in [0, seg_cf)");
+    return PACX_OK;
+}
+
+extern "C" int pacx_band_profile_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                          const int32_t *cap_alloc, int64_t seg_cf, int64_t first_off, double nmr_lo_db,
+                                          double nmr_hi_db, int64_t *profile, void *stream)
+{
+    const char *what = "pacx_band_profile_segments";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = segments_by_value(h, what, n_cf, seg_cf, first_off))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (!profile || (n_cf > 0 && (!nmr || !cap || !cap_alloc)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_profile_segments(h->T, n_cf, seg_cf, first_off, t_lo, t_hi, nmr, cap, cap_alloc, profile,
+                                      (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+/* the two calls on rows alone */
+static int rows_only(pacx_handle *h, const char *what, int64_t n_seg, const void *a, const void *b, const void *c,
+                     double nmr_lo_db, double nmr_hi_db, int *t_lo, int *t_hi)
+{
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (n_seg < 1 || n_seg > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad segment count");
+    if (!a || !b || !c)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    return profile_range(h, what, nmr_lo_db, nmr_hi_db, t_lo, t_hi);
+}
+
+extern "C" int pacx_profile_solve_segments(pacx_handle *h, int64_t n_seg, const int64_t *profile,
+                                           const int64_t *limit_bytes, double nmr_lo_db, double nmr_hi_db,
+                                           pacx_rate_result *result, int64_t *worst_above, void *stream)
+{
+    const char *what = "pacx_profile_solve_segments";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = rows_only(h, what, n_seg, profile, limit_bytes, result, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_profile_solve_segments(n_seg, profile, limit_bytes, t_lo, t_hi, result, worst_above, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_profile_clamp_add(pacx_handle *h, int64_t n_seg, const int64_t *profile,
+                                      const pacx_rate_result *result, double nmr_lo_db, double nmr_hi_db,
+                                      int64_t *stream_profile, void *stream)
+{
+    const char *what = "pacx_profile_clamp_add";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = rows_only(h, what, n_seg, profile, result, stream_profile, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_profile_clamp_add(n_seg, profile, result, t_lo, t_hi, stream_profile, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_pick_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                       const int32_t *cap_alloc, int64_t seg_cf, int64_t first_off,
+                                       const int32_t *target_t, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                                       void *stream)
+{
+    const char *what = "pacx_band_pick_segments";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = segments_by_value(h, what, n_cf, seg_cf, first_off))
+        return rc;
+    if (n_cf > 0 && (!nmr || !cap || !cap_alloc || !target_t || !bit_alloc || !n_bytes || !capped))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_pick_segments(h->T, n_cf, seg_cf, first_off, target_t, nmr, cap, cap_alloc, bit_alloc, n_bytes, capped,
+                                   (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                                 const double *nmr_db, uint64_t *summary, void *stream)
 {

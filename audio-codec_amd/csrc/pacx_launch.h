@@ -222,6 +222,11 @@ void pacx_launch_band_curve(const PacxTables &T, const uint8_t *flags, int n_ch,
 void pacx_launch_band_pick(const PacxTables &T, long long n_cf, double target, const double *nmr, const int32_t *cap,
                            const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
                            hipStream_t st);
+/* the pick with one grid target per uniform segment: frame cf takes target_t[(first_off + cf) / seg_cf] / 64 */
+void pacx_launch_band_pick_segments(const PacxTables &T, long long n_cf, long long seg_cf, long long first_off,
+                                    const int32_t *target_t, const double *nmr, const int32_t *cap,
+                                    const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                                    hipStream_t st);
 void pacx_launch_band_solve_segments(const PacxTables &T, const PacxSolve &v, const double *nmr, const int32_t *cap,
                                      const int32_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
                                      hipStream_t st);
@@ -237,6 +242,18 @@ void pacx_launch_band_profile(const PacxTables &T, long long n_cf, int t_lo, int
                               const int32_t *cap, const int32_t *cap_alloc, int64_t *profile, hipStream_t st);
 void pacx_launch_profile_solve(const int64_t *profile, long long limit, int t_lo, int t_hi, pacx_rate_result *result,
                                hipStream_t st);
+
+/* k_seg_profile.hip: the profile per uniform segment of a piece (profile [n_seg][G], row (first_off + cf) / seg_cf of
+   frame cf, added to), the solve's decision per row against limit_bytes [n_seg] on the device with the row's maximum
+   from the target found on (worst_above, may be null), and the rows clamped below their targets summed into one
+   stream profile [G]: one launch each */
+void pacx_launch_band_profile_segments(const PacxTables &T, long long n_cf, long long seg_cf, long long first_off,
+                                       int t_lo, int t_hi, const double *nmr, const int32_t *cap,
+                                       const int32_t *cap_alloc, int64_t *profile, hipStream_t st);
+void pacx_launch_profile_solve_segments(long long n_seg, const int64_t *profile, const int64_t *limit_bytes, int t_lo,
+                                        int t_hi, pacx_rate_result *result, int64_t *worst_above, hipStream_t st);
+void pacx_launch_profile_clamp_add(long long n_seg, const int64_t *profile, const pacx_rate_result *result, int t_lo,
+                                   int t_hi, int64_t *stream_profile, hipStream_t st);
 
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];

@@ -558,6 +558,136 @@ class Encoder:
         return {"target_nmr_db": float(res[0, 0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[0, 1]),
                 "total_bytes": int(res[:, 2:].copy().view(np.int64)[0, 0])}
 
+    # ---- a profile per uniform segment of a piece (pacx_band_profile_segments and its three companions, include/pacx.h):
+    # frame cf of the piece lies in local segment (first_off + cf) // seg_cf
+    @staticmethod
+    def _uniform_segments(what, n_cf, seg_cf, first_off):
+        """n_seg of a piece, the two numbers checked as the C side checks them"""
+        if isinstance(seg_cf, bool) or int(seg_cf) != seg_cf or not 1 <= seg_cf <= _lib.SEG_CF_MAX:
+            raise ValueError(f"{what}: seg_cf = {seg_cf!r}: a whole number of channel-frames in [1, 2^40]")
+        if isinstance(first_off, bool) or int(first_off) != first_off or not 0 <= first_off < seg_cf:
+            raise ValueError(f"{what}: first_off = {first_off!r}: a whole number in [0, seg_cf)")
+        return -(-(int(first_off) + n_cf) // int(seg_cf))
+
+    def _profile_rows(self, what, rows, n, at_least=1):
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.ndim != 2 or rows.shape[1] != n or \
+                rows.shape[0] < at_least or rows.device != torch.device(self.device) or not rows.is_contiguous():
+            raise ValueError(f"{what}: profile rows are a contiguous int64 device tensor [n_seg >= {at_least}, {n}] for "
+                             f"this range")
+        return rows
+
+    def _seg_results(self, what, result, n_seg):
+        if not isinstance(result, torch.Tensor) or result.dtype != torch.int32 or tuple(result.shape) != (n_seg, 4) or \
+                result.device != torch.device(self.device) or not result.is_contiguous():
+            raise ValueError(f"{what}: results are a contiguous int32 device tensor [{n_seg}, 4] (pacx_rate_result)")
+        return result
+
+    def band_profile_segments(self, curve, seg_cf, first_off=0, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """band_profile with a row per segment (pacx_band_profile_segments): int64 device tensor [n_seg, G], row s what
+        band_profile gives for the frames of local segment s, n_seg = ceil((first_off + n_cf) / seg_cf).  With `out`
+        (such a tensor of at least n_seg rows) the sizes are ADDED to its first n_seg rows and the others are left
+        alone: a segment cut by the piece gets the rest of its row from the next piece's call.  -> the tensor."""
+        what = "band_profile_segments"
+        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, what)
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
+        rows = torch.zeros((n_seg, n), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_rows(what, out, n, n_seg)
+        if n_seg == 0:                                                  # no frame and no segment begun: nothing to add to
+            return rows
+        self._call_rate("pacx_band_profile_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), ctypes.c_double(nmr_lo_db),
+                        ctypes.c_double(nmr_hi_db), _ptr(rows), self._stream())
+        return rows
+
+    def profile_solve_segments(self, rows, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """profile_solve on every row against its own limit (pacx_profile_solve_segments), and per row the largest
+        size from the target found on.  limit_bytes: a sequence of whole numbers, one per row, checked here (none
+        negative) and sent up; or an int64 device tensor [n_seg] the caller has checked.  -> dict of NumPy arrays
+        target_nmr_db, met, total_bytes, worst_above [n_seg] and "result", the pacx_rate_result words as an int32
+        device tensor [n_seg, 4] (profile_clamp_add takes it).  out = (result, worst_above), device tensors int32
+        [n_seg, 4] and int64 [n_seg]: written instead, nothing is read back and the host does not wait -> out."""
+        what = "profile_solve_segments"
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        rows = self._profile_rows(what, rows, n)
+        n_seg = rows.shape[0]
+        if isinstance(limit_bytes, torch.Tensor):
+            limit = limit_bytes
+            if limit.dtype != torch.int64 or tuple(limit.shape) != (n_seg,) or limit.device != rows.device or \
+                    not limit.is_contiguous():
+                raise ValueError(f"{what}: limits on the device are a contiguous int64 tensor [{n_seg}]")
+        else:
+            try:
+                host = np.ascontiguousarray(np.asarray(limit_bytes).astype(np.int64, casting="same_kind"))
+            except TypeError:
+                raise ValueError(f"{what}: limit_bytes is a sequence of integers") from None
+            if host.shape != (n_seg,):
+                raise ValueError(f"{what}: one limit per row, limit_bytes [{n_seg}]")
+            if (host < 0).any():
+                raise ValueError(f"{what}: negative limit for segment {int(np.argmax(host < 0))}")
+            limit = torch.as_tensor(host).to(self.device)
+        if out is None:
+            result = torch.zeros((n_seg, 4), dtype=torch.int32, device=self.device)
+            worst = torch.zeros((n_seg,), dtype=torch.int64, device=self.device)
+        else:
+            result, worst = out
+            self._seg_results(what, result, n_seg)
+            if not isinstance(worst, torch.Tensor) or worst.dtype != torch.int64 or tuple(worst.shape) != (n_seg,) or \
+                    worst.device != rows.device or not worst.is_contiguous():
+                raise ValueError(f"{what}: worst_above is a contiguous int64 device tensor [{n_seg}]")
+        self._call_rate("pacx_profile_solve_segments", ctypes.c_int64(n_seg), _ptr(rows), _ptr(limit),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(result), _ptr(worst), self._stream())
+        if out is not None:
+            return out
+        res = self.decode_results(result)
+        res.update(worst_above=worst.cpu().numpy(), result=result)
+        return res
+
+    @staticmethod
+    def decode_results(result):
+        """pacx_rate_result words (int32 device tensor [n, 4]) -> dict of NumPy arrays target_nmr_db, met, total_bytes"""
+        res = result.cpu().numpy()
+        return {"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID), "met": res[:, 1] != 0,
+                "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]}
+
+    def profile_clamp_add(self, rows, result, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """Every row held at its own target's size below that target, summed into one profile (pacx_profile_clamp_add):
+        out[g] += sum over s of rows[s][max(g, t_s - t_lo)], t_s from `result` (profile_solve_segments' "result").  With
+        the targets the floors of a peak solve, the sum over a stream's segments is the size of the stream at every
+        stream target, and profile_solve on it is the peak solve's decision.  out: a profile [G], added to (zeros when
+        not given).  -> the tensor."""
+        what = "profile_clamp_add"
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        rows = self._profile_rows(what, rows, n)
+        result = self._seg_results(what, result, rows.shape[0])
+        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_tensor(what, out, n)
+        self._call_rate("pacx_profile_clamp_add", ctypes.c_int64(rows.shape[0]), _ptr(rows), _ptr(result),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
+        return profile
+
+    def band_pick_segments(self, curve, seg_cf, first_off, target_t):
+        """band_pick with one target per segment (pacx_band_pick_segments): target_t, whole grid units (64 per dB), one
+        per local segment -- a sequence, or an int32 device tensor [n_seg].  -> band_pick's dict."""
+        what = "band_pick_segments"
+        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, what)
+        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
+        if isinstance(target_t, torch.Tensor):
+            t = target_t
+            if t.dtype != torch.int32 or tuple(t.shape) != (n_seg,) or t.device != torch.device(self.device) or \
+                    not t.is_contiguous():
+                raise ValueError(f"{what}: targets on the device are a contiguous int32 tensor [{n_seg}]")
+        else:
+            host = np.asarray(target_t)
+            if host.shape != (n_seg,) or not np.array_equal(host, np.round(host)) or (np.abs(host) > 2 ** 26).any():
+                raise ValueError(f"{what}: target_t [{n_seg}], whole grid units")
+            t = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
+        self._call_rate("pacx_band_pick_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), _ptr(t), _ptr(out["bit_alloc"]),
+                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,

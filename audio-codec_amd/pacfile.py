@@ -574,6 +574,38 @@ def _unreachable(limit, total, hi, head):
             f"smallest size this range of targets gives")
 
 
+def _segment_unreachable(s, first, count, seg_limit, total, hi):
+    """what a segmented average-rate call says of the first segment that even the highest target does not fit"""
+    return (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) cannot be reached: "
+            f"its limit is {int(seg_limit[s])} bytes and at the highest target, {hi:g} dB, it "
+            f"takes {int(total)} bytes, the smallest size this range of targets "
+            f"gives")
+
+
+def _segment_over_peak(s, first, count, seg_limit, total, floor, hi, stream_target):
+    """what a peak call says of the first segment beyond its peak at its final target"""
+    unmet = (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) exceeds its peak of "
+             f"{int(seg_limit[s])} bytes: it takes {int(total)} bytes; ")
+    unmet += (f"it cannot be reached at all: its floor is the highest target, {hi:g} dB, the smallest size "
+              f"this range of targets gives") if floor == hi else \
+        (f"it fits at its own floor, {floor:g} dB, but not at the stream's target, "
+         f"{stream_target:g} dB (its bytes rise with the target there)")
+    return unmet
+
+
+def _check_segment_keywords(segment_hops, peak_kbps_per_channel, sizes):
+    """segment_hops and peak_kbps_per_channel against the sizes [(kbps_per_channel, max_bytes)], before any GPU work"""
+    peak = peak_kbps_per_channel is not None
+    _check_peak(peak_kbps_per_channel, segment_hops)
+    if segment_hops is not None:
+        if not peak and any(b is not None for _, b in sizes):
+            raise ValueError("segment_hops goes with kbps_per_channel: max_bytes is the size of a file, not of a segment")
+        if not peak and any(k is None for k, _ in sizes):
+            raise ValueError("give exactly one of kbps_per_channel and max_bytes")
+        segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
+    return peak
+
+
 def _check_peak(peak_kbps_per_channel, segment_hops):
     """the peak_kbps_per_channel keyword, before any GPU work"""
     if peak_kbps_per_channel is None:
@@ -598,14 +630,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
     if use_vq and not band:
         raise NotImplementedError("gain-shape streams: allocation 'band' only")
     lo, hi = _abr_range(nmr_range_db)
-    peak = peak_kbps_per_channel is not None
-    _check_peak(peak_kbps_per_channel, segment_hops)
-    if segment_hops is not None:
-        if not peak and any(b is not None for _, b in sizes):
-            raise ValueError("segment_hops goes with kbps_per_channel: max_bytes is the size of a file, not of a segment")
-        if not peak and any(k is None for k, _ in sizes):
-            raise ValueError("give exactly one of kbps_per_channel and max_bytes")
-        segment_limits(1.0, 1, 1, 1, segment_hops)              # a bad segment_hops before any GPU work
+    peak = _check_segment_keywords(segment_hops, peak_kbps_per_channel, sizes)
     cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples,
                                               use_vq)
     head = header_bytes(cp)
@@ -637,12 +662,8 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
             elif sol["met"].all():
                 unmet = None
             else:
-                unmet = (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) exceeds its peak of "
-                         f"{int(seg_limit[s])} bytes: it takes {int(sol['total_bytes'][s])} bytes; ")
-                unmet += (f"it cannot be reached at all: its floor is the highest target, {hi:g} dB, the smallest size "
-                          f"this range of targets gives") if sol["floor_nmr_db"][s] == hi else \
-                    (f"it fits at its own floor, {sol['floor_nmr_db'][s]:g} dB, but not at the stream's target, "
-                     f"{sol['stream_target_nmr_db']:g} dB (its bytes rise with the target there)")
+                unmet = _segment_over_peak(s, first, count, seg_limit, sol["total_bytes"][s], sol["floor_nmr_db"][s], hi,
+                                           sol["stream_target_nmr_db"])
             sol["segments"] = {"first_block": first, "blocks": count, "limit_bytes": seg_limit}
         else:
             first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
@@ -651,10 +672,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
                 enc.rate_solve_segments(curve, seg_first, seg_limit, lo, hi)
             s = int(np.argmin(sol["met"]))
             unmet = None if sol["met"].all() else \
-                (f"segment {s} (from block {int(first[s])}, {int(count[s])} blocks) cannot be reached: "
-                 f"its limit is {int(seg_limit[s])} bytes and at the highest target, {hi:g} dB, it "
-                 f"takes {int(sol['total_bytes'][s])} bytes, the smallest size this range of targets "
-                 f"gives")
+                _segment_unreachable(s, first, count, seg_limit, sol["total_bytes"][s], hi)
             sol["segments"] = {"first_block": first, "blocks": count, "limit_bytes": seg_limit}
             limit = int(seg_limit.sum())
         if unmet:
@@ -743,29 +761,76 @@ def _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block
 
 def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
                             max_kbps_per_channel=320, block_switching=False, header_samples=None,
-                            nmr_range_db=(-30, 30), use_vq=False):
+                            nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None):
     """encode_stream_abr_chunked piece by piece: an iterator that gives the file's header, then the bodies of the
     chunks in order (bytes; their concatenation is that call's result).  The arguments are checked, the stream is
-    analysed and the target solved when this is called; the second pass runs as the iterator is consumed."""
+    analysed and the target solved when this is called; the second pass runs as the iterator is consumed.
+    With peak_kbps_per_channel one error can come from the ITERATOR instead: a segment that fits its peak at its own
+    floor but whose bytes rise with the target (encode_stream_abr_chunked explains); the pieces before the chunk in
+    which that segment ends have been handed out by then."""
+    peak = _check_segment_keywords(segment_hops, peak_kbps_per_channel, [(kbps_per_channel, max_bytes)])
     cp, head, make = _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching,
                                         header_samples, nmr_range_db, use_vq)
-    limit = _abr_limit(cp, _Blocks(len(pcm) // 1024 + 2), head, kbps_per_channel, max_bytes)
+    blocks = len(pcm) // 1024 + 2
+    if segment_hops is None or peak:
+        limit = _abr_limit(cp, _Blocks(blocks), head, kbps_per_channel, max_bytes)
+    if segment_hops is not None:
+        first, count, seg_limit = segment_limits(peak_kbps_per_channel if peak else kbps_per_channel, cp.nChannels,
+                                                 cp.sampleRate, blocks, segment_hops)
     hr = make()
-    hr.analyse(pcm)
-    sol = hr.solve(limit)
-    if not sol["met"]:
-        raise ValueError(_unreachable(limit, sol["total_bytes"], hr.hi, head))
+    check = None
+    if segment_hops is None:
+        hr.analyse(pcm)
+        sol = hr.solve(limit)
+        if not sol["met"]:
+            raise ValueError(_unreachable(limit, sol["total_bytes"], hr.hi, head))
+        targets = sol["target_nmr_db"]
+    elif not peak:
+        hr.analyse(pcm, segment_hops=segment_hops, segment_limits=seg_limit)
+        sol = hr.solve_segments()
+        if not sol["met"].all():
+            s = int(np.argmin(sol["met"]))
+            raise ValueError(_segment_unreachable(s, first, count, seg_limit, sol["total_bytes"][s], hr.hi))
+        targets = sol["target_nmr_db"]
+    else:
+        hr.analyse(pcm, segment_hops=segment_hops, segment_limits=seg_limit, peak=True)
+        sol = hr.solve_peak(limit)
+        if not sol["stream_met"]:
+            raise ValueError(_unreachable(limit, sol["stream_total_bytes"], hr.hi, head))
+        targets = sol["target_nmr_db"]
+
+        def over_peak(s, total):
+            return _segment_over_peak(s, first, count, seg_limit, total, sol["floor_nmr_db"][s], hr.hi,
+                                      sol["stream_target_nmr_db"])
+        # a segment that cannot be reached is beyond its peak for certain; a reachable one whose size somewhere above
+        # its floor exceeds the peak may be (its row is gone): the first of those, if it comes earlier, decides in
+        # the second pass which segment is named
+        doubtful = sol["floor_met"] & (sol["worst_above"] > seg_limit)
+        if not sol["floor_met"].all():
+            s = int(np.argmin(sol["floor_met"]))
+            if not doubtful[:s].any():
+                raise ValueError(over_peak(s, sol["floor_total_bytes"][s]))
+        check = over_peak if doubtful.any() else None
 
     def parts():
+        from .streaming import SegmentOverLimit
         yield head
-        for body in hr.encode(pcm, sol["target_nmr_db"]):
-            yield body.tobytes()
+        try:
+            if segment_hops is None:
+                bodies = hr.encode(pcm, targets)
+            else:
+                bodies = hr.encode(pcm, targets, segment_hops=segment_hops,
+                                   segment_limits=seg_limit if check else None)
+            for body in bodies:
+                yield body.tobytes()
+        except SegmentOverLimit as e:
+            raise ValueError(check(e.segment, e.total_bytes)) from None
     return parts()
 
 
 def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
                               max_kbps_per_channel=320, block_switching=False, header_samples=None,
-                              nmr_range_db=(-30, 30), use_vq=False):
+                              nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None):
     """encode_stream_abr(allocation="band") for a stream too long for one batch -> the same .pac bytes, from host
     memory to host memory in chunks of chunk_hops blocks, with device memory bounded by the chunk.  pcm: anything that
     slices to int16 [n, nCh] pieces (an np.memmap included), n a multiple of 1024 and at least 1024.  Two passes
@@ -774,9 +839,21 @@ def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes
     profile (Encoder.profile_solve); then per chunk curve, pick at the target found and second pass.  The sizes
     (kbps_per_channel or max_bytes), max_kbps_per_channel and the ValueError when even the highest target does not fit
     are encode_stream_abr's.  use_vq: the gain-shape coder without SBR, the bytes of encode_stream_vq_abr.  No
-    segments, no peaks, no allocation="budget".  iter_encode_abr_chunked gives the same bytes piece by piece."""
+    allocation="budget".  iter_encode_abr_chunked gives the same bytes piece by piece.
+    segment_hops=S and peak_kbps_per_channel=P mean what they mean for encode_stream_abr, under its rules, with its
+    bytes and its error messages: the first pass keeps a profile row per segment the chunk touches
+    (Encoder.band_profile_segments), solves and drops the rows of the segments that end in it
+    (profile_solve_segments) and, with a peak, adds them clamped at their floors into the stream's profile
+    (profile_clamp_add), on which the stream's solve is the peak solve's; the second pass picks per segment
+    (band_pick_segments).  A segment that cannot be reached and a stream size that cannot be reached are refused
+    before any byte is produced.  One case is found only in the second pass: a segment that fits its peak at its floor
+    but not at the stream's target, because its bytes rise with the target there -- its row is gone by the time the
+    stream's target is known.  The second pass then sums the records of every segment and raises encode_stream_abr's
+    message when the first offending segment ends; this call returns nothing in that case, the iterator form has
+    handed out the pieces before."""
     return b"".join(iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
-                                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq))
+                                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq,
+                                            segment_hops, peak_kbps_per_channel))
 
 
 def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,

@@ -218,6 +218,15 @@ class HostStreamEncoder:
         self.pending = [False] * self.depth
 
 
+class SegmentOverLimit(ValueError):
+    """HostStreamRateEncoder.encode(..., segment_limits=...): a segment's records took more than its limit.  Raised when
+    the chunk in which the first such segment ends is taken; .segment, .total_bytes, .limit_bytes"""
+
+    def __init__(self, segment, total_bytes, limit_bytes):
+        super().__init__(f"segment {segment} takes {total_bytes} bytes, its limit is {limit_bytes}")
+        self.segment, self.total_bytes, self.limit_bytes = int(segment), int(total_bytes), int(limit_bytes)
+
+
 class HostStreamRateEncoder:
     """The average-bit-rate encode with band-by-band allocation (pacfile.encode_stream_abr(allocation="band")) in
     chunks of bounded size, host memory to host memory, in two passes over the PCM:
@@ -234,7 +243,25 @@ class HostStreamRateEncoder:
     halo and transient carry stay on the device, the driver's last two blocks are a chunk of their own.  pcm is
     anything that slices to int16 [n, nCh] pieces (an np.memmap included); only a chunk of it is touched at a time.
     enc: a scalar encoder, or a gain-shape one without SBR (its curve and second pass, the pick and the solve on its
-    scalar sibling), with the cap rate as its rate."""
+    scalar sibling), with the cap rate as its rate.
+
+    With segments (pacfile.segment_limits: the n + 2 blocks the driver writes, cut every S blocks, the tail chunk
+    included) the first pass keeps a profile ROW per segment the current chunk touches instead
+    (Encoder.band_profile_segments), solves the rows of the segments that end in the chunk
+    (Encoder.profile_solve_segments) and forgets them:
+
+        hr.analyse(pcm, segment_hops=S, segment_limits=limits)             # one limit per segment
+        seg = hr.solve_segments()                                          # target_nmr_db, met, total_bytes, worst_above [n_seg]
+        for body in hr.encode(pcm, seg["target_nmr_db"], segment_hops=S): ...
+
+        hr.analyse(pcm, segment_hops=S, segment_limits=peaks, peak=True)   # the limits are peaks: the solved rows are also
+        sol = hr.solve_peak(limit_bytes)                                   # clamp-added into the stream's profile
+        for body in hr.encode(pcm, sol["target_nmr_db"], segment_hops=S, segment_limits=peaks): ...
+
+    The row buffer holds ceil(max(hops_per_chunk, 2) * nCh / (S * nCh)) + 1 rows of G int64 words -- bounded by the
+    chunk; the row of a segment still open at a chunk's end is carried to the next chunk.  Per segment the object
+    keeps the solve's result and worst_above on the device, 24 bytes: the only thing that grows with the stream, read
+    back once.  The limits and targets of the segments a chunk touches go up with the chunk's PCM."""
 
     def __init__(self, enc, n_channels, hops_per_chunk, max_bits_per_sample, block_switching=False, nmr_lo_db=-30,
                  nmr_hi_db=30, depth=2):
@@ -265,6 +292,10 @@ class HostStreamRateEncoder:
         self.tr = torch.zeros(max(F, 2), dtype=torch.uint8, device=dev)
         self.profile = self.path.solver.band_profile(self._no_frames(), self.lo, self.hi)      # zeros [G]; checks the range
         self.n_frames = 0                                              # blocks the last analyse() saw
+        self.seg = None                                                # the segments of the last analyse(), if any
+        self.rows = None
+        self.stage = {}                                                # per-segment words that go up with a chunk
+        self.seg_check = [None] * self.depth                           # encode(): (first segment, count) of a slot's sums
 
     def _no_frames(self):
         e = self.path.solver
@@ -306,17 +337,109 @@ class HostStreamRateEncoder:
         return _chunk_front(self.enc, self.n_ch, self.dev_in[k], n, self.halo, self.carry, self.tr,
                             self.block_switching, tail)
 
-    def analyse(self, pcm):
+    # ------------------------------------------------------------------ segments: uniform stretches of S blocks
+    def _segments(self, pcm, segment_hops, per_segment, what):
+        """(S * nCh, number of segments, per_segment as an array of that length) for the n + 2 blocks of pcm"""
+        hops = int(segment_hops)
+        if isinstance(segment_hops, bool) or hops != segment_hops or hops < 1:
+            raise ValueError(f"segment_hops = {segment_hops!r}: a whole number of blocks, at least 1")
+        n_seg = -(-(len(pcm) // HOP + 2) // hops)
+        per_segment = np.asarray(per_segment)
+        if per_segment.shape != (n_seg,):
+            raise ValueError(f"{what}: one per segment, [{n_seg}] for this stream")
+        return hops * self.n_ch, n_seg, per_segment
+
+    def _piece(self, blocks_before, n, tail, seg_cf):
+        """where a chunk of n blocks lies among the segments -> (first_off, index of its first segment, segments it
+        touches, how many of them end in it: the stream's last segment ends with the tail chunk)"""
+        cf0, n_cf = blocks_before * self.n_ch, n * self.n_ch
+        first_off, s0 = cf0 % seg_cf, cf0 // seg_cf
+        touched, closed = -(-(first_off + n_cf) // seg_cf), (first_off + n_cf) // seg_cf
+        return first_off, s0, touched, touched if tail else closed
+
+    def _stage_up(self, name, k, values, dtype):
+        """per-segment words of a chunk on their way up behind the chunk's PCM (copy-in stream, the slot's pinned
+        buffer; ev_in[k] then stands for both) -> the device tensor, valid for the kernels of this chunk"""
+        R = self.rows_max
+        if (name, R) not in self.stage:                                # kept for good: see _rows_max
+            self.stage[name, R] = ([torch.zeros(R, dtype=dtype).pin_memory() for _ in range(self.depth)],
+                                   [torch.zeros(R, dtype=dtype, device=self.enc.device) for _ in range(self.depth)])
+        host, dev = self.stage[name, R]
+        m = len(values)
+        host[k].numpy()[:m] = values
+        with torch.cuda.stream(self.s_in):
+            dev[k][:m].copy_(host[k][:m], non_blocking=True)
+            self.ev_in[k].record(self.s_in)
+        return dev[k][:m]
+
+    def _rows_max(self, seg_cf):
+        """the segments a chunk can touch.  What is staged per segment (self.stage) is keyed by this number and never
+        dropped: work queued on it may outlive an encode() that is given up half-way"""
+        self.rows_max = -(-max(self.F, 2) * self.n_ch // seg_cf) + 1
+
+    def _row_buffer(self, seg_cf):
+        """the first pass's rows"""
+        self._rows_max(seg_cf)
+        G = self.profile.numel()
+        if self.rows is None or tuple(self.rows.shape) != (self.rows_max, G):
+            torch.cuda.synchronize(self.enc.device)                    # nothing queued still works on the old rows
+            self.rows = torch.zeros((self.rows_max, G), dtype=torch.int64, device=self.enc.device)
+
+    def analyse(self, pcm, segment_hops=None, segment_limits=None, peak=False):
         """the first pass: the stream's size at every target of the range, into self.profile (zeroed first).
-        -> the profile, int64 device tensor [G]; the host does not wait for it"""
+        -> the profile, int64 device tensor [G]; the host does not wait for it.
+        segment_hops=S, segment_limits=[n_seg]: a profile row per segment instead; per chunk the rows of the segments
+        the chunk touches are added to, those of the segments that end in it are solved against their limits (result and
+        worst_above stay on the device, for solve_segments()) and cleared, the row of a segment still open is carried.
+        peak: the limits are peaks, and the solved rows are clamp-added into self.profile, which is then the stream's
+        size at every stream target with every segment held at its floor (solve_peak()).  The row buffer has
+        ceil(max(hops_per_chunk, 2) nCh / (S nCh)) + 1 rows.  No host wait per chunk either way."""
+        solver = self.path.solver
+        segmented = segment_hops is not None
+        if segmented:
+            seg_cf, n_seg, limits = self._segments(pcm, segment_hops, segment_limits, "segment_limits")
+            try:
+                limits = limits.astype(np.int64, casting="same_kind")
+            except TypeError:
+                raise ValueError("segment_limits: whole numbers of bytes") from None
+            if (limits < 0).any():
+                raise ValueError(f"segment_limits: negative limit for segment {int(np.argmax(limits < 0))}")
+            self._row_buffer(seg_cf)
+            dev = self.enc.device
+            self.seg = {"seg_cf": seg_cf, "n_seg": n_seg, "peak": bool(peak), "limits": limits,
+                        "result": torch.zeros((n_seg, 4), dtype=torch.int32, device=dev),
+                        "worst": torch.zeros((n_seg,), dtype=torch.int64, device=dev)}
+        elif segment_limits is not None or peak:
+            raise ValueError("segment_limits and peak go with segment_hops")
+        else:
+            self.seg = None
         with torch.cuda.stream(self.s_k):
             self.profile.zero_()
+            if segmented:
+                self.rows.zero_()
         frames = 0
         for k, n, tail in self._chunks(pcm):
+            if segmented:
+                first_off, s0, touched, closed = self._piece(frames, n, tail, seg_cf)
+                limit_dev = self._stage_up("limit", k, limits[s0:s0 + closed], torch.int64)
             with torch.cuda.stream(self.s_k):
                 view, flags = self._front(k, n, tail)
-                self.path.solver.band_profile(self.path.curve(view, flags, self.max_bps), self.lo, self.hi,
-                                              out=self.profile)
+                curve = self.path.curve(view, flags, self.max_bps)
+                if not segmented:
+                    solver.band_profile(curve, self.lo, self.hi, out=self.profile)
+                else:
+                    solver.band_profile_segments(curve, seg_cf, first_off, self.lo, self.hi, out=self.rows)
+                    if closed:
+                        done, res = self.rows[:closed], self.seg["result"][s0:s0 + closed]
+                        solver.profile_solve_segments(done, limit_dev, self.lo, self.hi,
+                                                      out=(res, self.seg["worst"][s0:s0 + closed]))
+                        if peak:
+                            solver.profile_clamp_add(done, res, self.lo, self.hi, out=self.profile)
+                        if touched > closed:                           # the open segment's row moves to the front
+                            self.rows[0].copy_(self.rows[closed])
+                            self.rows[1:touched].zero_()
+                        else:
+                            self.rows[:touched].zero_()
                 self.ev_k[k].record(self.s_k)
             frames += n
         self.n_frames = frames
@@ -327,38 +450,122 @@ class HostStreamRateEncoder:
         with torch.cuda.stream(self.s_k):
             return self.path.solver.profile_solve(self.profile, limit_bytes, self.lo, self.hi)
 
+    def solve_segments(self):
+        """what the last analyse(segment_hops=...) found per segment, read back once: dict of NumPy arrays
+        target_nmr_db (the lowest target of the range at which the segment fits its limit; the highest where it cannot),
+        met, total_bytes at that target, worst_above (the most it takes at that target or any higher one)"""
+        if self.seg is None:
+            raise RuntimeError("solve_segments: the last analyse() had no segments")
+        with torch.cuda.stream(self.s_k):
+            out = self.path.solver.decode_results(self.seg["result"])
+            out["worst_above"] = self.seg["worst"].cpu().numpy()
+        return out
+
+    def solve_peak(self, limit_bytes):
+        """the two-level solve after analyse(..., peak=True): Encoder.profile_solve on the clamped stream profile is
+        the stream's result, and every segment takes T_s = max(stream target, its floor).  -> dict
+        stream_target_nmr_db, stream_met, stream_total_bytes; NumPy arrays per segment target_nmr_db (T_s),
+        floor_nmr_db, pinned, floor_met (False: the segment cannot be reached), floor_total_bytes, worst_above (a
+        segment whose worst_above is within its peak is within it at T_s, whatever T_s)"""
+        if self.seg is None or not self.seg["peak"]:
+            raise RuntimeError("solve_peak: the last analyse() was not one with peak=True")
+        stream, seg = self.solve(limit_bytes), self.solve_segments()
+        floor = seg["target_nmr_db"]
+        return {"stream_target_nmr_db": stream["target_nmr_db"], "stream_met": stream["met"],
+                "stream_total_bytes": stream["total_bytes"], "floor_nmr_db": floor,
+                "target_nmr_db": np.maximum(floor, stream["target_nmr_db"]), "pinned": floor > stream["target_nmr_db"],
+                "floor_met": seg["met"], "floor_total_bytes": seg["total_bytes"], "worst_above": seg["worst_above"]}
+
     def _result(self, k):
         """the body of the chunk in slot k: a uint8 NumPy view of pinned memory, valid until the slot is used again"""
         self.ev_out[k].synchronize()
         n = int(self.host_total[k].item())
         if n > self.cap:
             raise RuntimeError(f"body of {n} bytes does not fit its {self.cap}-byte buffer")
+        if self.seg_check[k] is not None:                              # the segments that ended in this chunk
+            (s0, m, limits), self.seg_check[k] = self.seg_check[k], None
+            took = self.host_sum[k][:m].numpy()
+            over = took > limits[s0:s0 + m]
+            if over.any():
+                i = int(np.argmax(over))
+                raise SegmentOverLimit(s0 + i, took[i], limits[s0 + i])
         with torch.cuda.stream(self.s_out):
             self.host_body[k][:n].copy_(self.bodies[k][:n], non_blocking=True)
         self.s_out.synchronize()
         return self.host_body[k][:n].numpy()
 
-    def encode(self, pcm, target_nmr_db):
+    def encode(self, pcm, target_nmr_db, segment_hops=None, segment_limits=None):
         """the second pass: yields the chunks' bodies in order ('<L nBytes' + payload per channel-block), every band at
         the smallest size that keeps it at or below target_nmr_db (Encoder.band_pick), the driver's last two blocks
-        last.  A body is a view of pinned memory, valid until the next one is taken."""
+        last.  A body is a view of pinned memory, valid until the next one is taken.
+        segment_hops=S with target_nmr_db [n_seg] (multiples of 1/64 dB): one target per segment
+        (Encoder.band_pick_segments).  segment_limits=[n_seg] besides: every segment's records are summed as they are
+        picked (n_bytes + 4 each), and SegmentOverLimit is raised in place of the body of the chunk in which the first
+        segment beyond its limit ends -- the bodies before it have been handed out by then."""
         enc, order = self.enc, []
+        segmented = segment_hops is not None
+        if segmented:
+            seg_cf, n_seg, targets = self._segments(pcm, segment_hops, target_nmr_db, "target_nmr_db")
+            grid = targets.astype(np.float64) * _lib.RATE_TARGET_GRID
+            if not np.isfinite(grid).all() or (grid != np.round(grid)).any() or (np.abs(grid) > 2 ** 26).any():
+                raise ValueError(f"target_nmr_db: finite multiples of 1/{_lib.RATE_TARGET_GRID} dB")
+            grid = grid.astype(np.int32)
+            self._rows_max(seg_cf)
+            limits = None
+            if segment_limits is not None:
+                limits = self._segments(pcm, segment_hops, segment_limits, "segment_limits")[2].astype(np.int64)
+                R = self.rows_max
+                if ("sums", R) not in self.stage:
+                    self.stage["sums", R] = (
+                        [torch.zeros(R, dtype=torch.int64).pin_memory() for _ in range(self.depth)],
+                        [torch.zeros(R, dtype=torch.int64, device=enc.device) for _ in range(self.depth)],
+                        torch.zeros(R, dtype=torch.int64, device=enc.device))
+                # sums: per local segment, [0] starts with the carry; sums_done[k]: the chunk's, on their way down
+                self.host_sum, sums_done, sums = self.stage["sums", R]
+        elif segment_limits is not None:
+            raise ValueError("segment_limits goes with segment_hops")
+        self.seg_check = [None] * self.depth
+        frames = 0
         for k, n, tail in self._chunks(pcm):
             if len(order) == self.depth:                               # slot k still holds a body nobody took
                 yield self._result(order.pop(0))
+            if segmented:
+                first_off, s0, touched, closed = self._piece(frames, n, tail, seg_cf)
+                target_dev = self._stage_up("target", k, grid[s0:s0 + touched], torch.int32)
             with torch.cuda.stream(self.s_k):
                 view, flags = self._front(k, n, tail)
-                pick = self.path.solver.band_pick(self.path.curve(view, flags, self.max_bps), float(target_nmr_db))
+                curve = self.path.curve(view, flags, self.max_bps)
+                if segmented:
+                    pick = self.path.solver.band_pick_segments(curve, seg_cf, first_off, target_dev)
+                    if limits is not None:
+                        if frames == 0:                                # cleared on this stream, behind whatever an encode()
+                            sums.zero_()                               # given up half-way still had queued on it
+                        # what the segments take; the open one's bytes so far sit in sums[0], from the chunk before
+                        nb = pick["n_bytes"].to(torch.int64)
+                        ids = (torch.arange(n * self.n_ch, device=enc.device) + first_off) // seg_cf
+                        sums.index_add_(0, ids, torch.where(nb > 0, nb + 4, torch.zeros_like(nb)))
+                else:
+                    pick = self.path.solver.band_pick(curve, float(target_nmr_db))
                 out = self.path.encode(view, flags, pick["bit_alloc"])
                 self.s_k.wait_event(self.ev_out[k])                    # the total that last sat in totals[k] has left
                 enc._call("pacx_gather_body", ctypes.c_int64(n * self.n_ch), _ptr(out["payload"]), _ptr(out["n_bytes"]),
                           _ptr(self.bodies[k]), ctypes.c_int64(self.cap), _ptr(self.totals[k]), enc._stream())
+                if segmented and limits is not None:                   # after the wait above: sums_done[k] has left too
+                    sums_done[k].copy_(sums)
+                    carry = sums[closed].clone() if touched > closed else None
+                    sums.zero_()
+                    if carry is not None:
+                        sums[0] = carry
                 self.ev_k[k].record(self.s_k)
             with torch.cuda.stream(self.s_out):
                 self.s_out.wait_event(self.ev_k[k])
                 self.host_total[k].copy_(self.totals[k], non_blocking=True)
+                if segmented and limits is not None and closed:
+                    self.host_sum[k][:closed].copy_(sums_done[k][:closed], non_blocking=True)
+                    self.seg_check[k] = (s0, closed, limits)
                 self.ev_out[k].record(self.s_out)
             order.append(k)
+            frames += n
         for k in order:
             yield self._result(k)
 

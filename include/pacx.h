@@ -932,6 +932,61 @@ int pacx_band_profile(pacx_handle *h, int64_t n_cf, const double *nmr, const int
 int pacx_profile_solve(pacx_handle *h, const int64_t *profile, int64_t limit_bytes, double nmr_lo_db, double nmr_hi_db,
                        pacx_rate_result *result, void *stream);
 
+/* ---- a profile per segment: segmented and peak solves piece by piece ---- */
+
+#define PACX_SEG_CF_MAX (1LL << 40)   /* channel-frames of one segment given by value, at most */
+
+/*
+ * A profile per segment is additive over pieces of a stream exactly as the stream's profile is, and that carries the
+ * segmented solve and the two-level peak solve (below) to streams of any length.  Segments here are uniform
+ * stretches of the stream given by value -- no table, no upload, nothing the host waits for:
+ *
+ *   seg_cf    in [1, PACX_SEG_CF_MAX]: channel-frames per segment
+ *   first_off in [0, seg_cf): channel-frames of the piece's first segment that lie before the piece
+ *   frame cf of the piece lies in local segment (first_off + cf) / seg_cf;  n_seg = ceil((first_off + n_cf) / seg_cf)
+ *
+ * pacx_band_profile_segments: for every local segment s, row s of profile += what pacx_band_profile adds for that
+ * segment's frames of the piece, under every rule of pacx_band_profile (the steps decided in double before any cast,
+ * NaN and the infinities, dropped hops, the cap rule, integer sums; n_cf = 0 adds nothing).  A segment cut by the
+ * piece's start or end gets the rest of its row from the neighbouring piece's call.  The kernel is pacx_band_profile's
+ * per frame; a workgroup walks a contiguous run of frames and adds the bytes it holds in registers to the row of the
+ * segment it is in whenever that changes (one 64-bit atomicAdd per entry), so a flush happens once per workgroup and
+ * segment touched, not once per frame.  One launch, no host wait.
+ *   profile (in/out): int64 [n_seg][G] in device memory; rows beyond n_seg are not touched
+ *
+ * pacx_profile_solve_segments: result[s] = pacx_profile_solve's decision on row s against limit_bytes[s], and
+ * worst_above[s] = max over g >= result[s].t - t_lo of row_s[g]: the most the segment takes at its target or any higher
+ * one.  A negative limit is never met (met = 0, t = t_hi).  An all-zero row gives t = t_lo, met = 1, total = 0.  One
+ * launch, a wave per row, trip counts fixed by G.
+ *   n_seg >= 1;  profile: int64 [n_seg][G];  limit_bytes: int64 [n_seg] in DEVICE memory
+ *   result (out): pacx_rate_result [n_seg];  worst_above (out): int64 [n_seg], may be NULL -- device memory
+ *
+ * pacx_profile_clamp_add: stream_profile[g] += sum over s of row_s[max(g, result[s].t - t_lo)].  With result[s].t the
+ * floor u_s of pacx_band_solve_peak's stage A (the solve above against the peaks), the sum over all segments of a
+ * stream is total*(t) of stage B at every t of the grid, and pacx_profile_solve on it against the stream's limit is
+ * stage B's decision word for word; T_s = max(t*, u_s).  One launch.
+ *   result: pacx_rate_result [n_seg] with t in [t_lo, t_hi];  stream_profile (in/out): int64 [G] -- device memory
+ *
+ * pacx_band_pick_segments: pacx_band_pick with the target target_t[s] / 64 for the frames of local segment s.  With
+ * all targets equal it gives pacx_band_pick's outputs bit for bit.
+ *   target_t: int32 [n_seg] in device memory, targets in grid units (64 per dB)
+ *
+ * PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr.  PACX_E_ARG for a null pointer, a bad count, seg_cf
+ * outside [1, PACX_SEG_CF_MAX], first_off outside [0, seg_cf), bounds that are not finite, inverted, off the grid or more than
+ * PACX_PROFILE_MAX targets apart.
+ */
+int pacx_band_profile_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                               const int32_t *cap_alloc, int64_t seg_cf, int64_t first_off, double nmr_lo_db,
+                               double nmr_hi_db, int64_t *profile, void *stream);
+int pacx_profile_solve_segments(pacx_handle *h, int64_t n_seg, const int64_t *profile, const int64_t *limit_bytes,
+                                double nmr_lo_db, double nmr_hi_db, pacx_rate_result *result, int64_t *worst_above,
+                                void *stream);
+int pacx_profile_clamp_add(pacx_handle *h, int64_t n_seg, const int64_t *profile, const pacx_rate_result *result,
+                           double nmr_lo_db, double nmr_hi_db, int64_t *stream_profile, void *stream);
+int pacx_band_pick_segments(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                            int64_t seg_cf, int64_t first_off, const int32_t *target_t, int32_t *bit_alloc,
+                            int32_t *n_bytes, uint8_t *capped, void *stream);
+
 /* ---- one target per stretch of a stream: the two solves, segment by segment ---- */
 
 /*
