@@ -787,7 +787,8 @@ def wav_effective_stream(raw, hop=1024):
 
 
 def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False,
-                  max_hops=None, collect=None, header_samples=None, use_sbr=False, n_lines=1024):
+                  max_hops=None, collect=None, header_samples=None, use_sbr=False, n_lines=1024,
+                  n_scale_bits=4, n_mant_size_bits=12):
     """Whole-file scalar-path encode: the driver loop of
     coder/pacfile.py:716-757 plus Close (:612-625) on int16 PCM [nSamples, nCh].
     Returns the .pac bytes.  The last hop is written twice (the loop body runs
@@ -796,7 +797,7 @@ def encode_stream(pcm, sample_rate, kbps_per_channel, block_switching=False,
     (flags, per-channel parts or None) per written hop."""
     pcm = np.asarray(pcm)
     n_samples, n_ch = pcm.shape
-    p = make_params(sample_rate, n_ch, kbps_per_channel, n_lines)
+    p = make_params(sample_rate, n_ch, kbps_per_channel, n_lines, n_scale_bits, n_mant_size_bits)
     if use_sbr:                                   # scalar mantissas + SBR: see encode_channel_sbr
         p.useSBR = True
         p.omittedBands = list(omitted_bands(p.sfBands))

@@ -213,9 +213,9 @@ def quantize_gain_shape(x, bit_alloc, trace=None):
 
 
 # ------------------------------------------------------------ channel-frame encode
-def make_params_vq(sample_rate, n_channels, kbps_per_channel):
+def make_params_vq(sample_rate, n_channels, kbps_per_channel, n_scale_bits=4, n_mant_size_bits=12):
     """The shipped driver's settings, coder/pacfile.py:699-707."""
-    p = po.make_params(sample_rate, n_channels, kbps_per_channel)
+    p = po.make_params(sample_rate, n_channels, kbps_per_channel, 1024, n_scale_bits, n_mant_size_bits)
     p.useVQ = True
     p.useSBR = kbps_per_channel < 128
     p.omittedBands = (list(po.omitted_bands(p.sfBands)) if p.useSBR else [])
@@ -390,14 +390,14 @@ def encode_hop_vq(p, prior, hop, flags, trace=None, carries=None):
 
 def encode_stream_vq(pcm, sample_rate, kbps_per_channel, block_switching=True,
                      max_hops=None, collect=None, header_samples=None,
-                     trace=None, carries=None):
+                     trace=None, carries=None, n_scale_bits=4, n_mant_size_bits=12):
     """Whole-file encode with the shipped driver's settings
     (coder/pacfile.py:699-757 + Close :612-625): useVQ on, useSBR below
     128 kb/s, transient detector on.  Same loop quirks as
     pac_oracle.encode_stream."""
     pcm = np.asarray(pcm)
     n_samples, n_ch = pcm.shape
-    p = make_params_vq(sample_rate, n_ch, kbps_per_channel)
+    p = make_params_vq(sample_rate, n_ch, kbps_per_channel, n_scale_bits, n_mant_size_bits)
     hop_n = p.nMDCTLines
     out = [po.pac_header(p, n_samples if header_samples is None else header_samples)]
     n_hops = -(-n_samples // hop_n)

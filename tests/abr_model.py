@@ -26,7 +26,7 @@ SUB, STEP, GRID = rm.SUB, rm.STEP, 64
 
 def steps_of(a, max_kbps, short, last_or_next):
     """J of a long block / short sub-block with these flags: the budget rule with the cap rate, in steps of 32 bits"""
-    pc = po.make_params(a["sample_rate"], a["n_ch"], max_kbps)
+    pc = po.make_params(a["sample_rate"], a["n_ch"], max_kbps, rm.HOP, *rm.widths(a))
     if short:
         pc.nMDCTLines = pc.nSamplesPerBlock = rm.SHORT
     return max(int(np.floor(po.bit_budget(pc, last_or_next, short, False) / STEP)), 0)

@@ -81,10 +81,17 @@ def record_map(pcm, block_switching):
     return flags, rec, at
 
 
+def header_fields(data):
+    """the '<LHLLHHHH' fields of a .pac header: sample rate, channels, samples, lines, nScaleBits, nMantSizeBits,
+    useSBR, useVQ"""
+    fmt = '<LHLLHHHH'
+    return struct.unpack(fmt, data[4:4 + struct.calcsize(fmt)])
+
+
 def records(data):
     """payload (offset, size) of every record of a .pac, and the header's (sample rate, channels, useSBR, useVQ)"""
     fmt = '<LHLLHHHH'
-    (sr, n_ch, _, n_lines, _, _, use_sbr, use_vq) = struct.unpack(fmt, data[4:4 + struct.calcsize(fmt)])
+    (sr, n_ch, _, n_lines, _, _, use_sbr, use_vq) = header_fields(data)
     assert n_lines == HOP
     pos = 4 + struct.calcsize(fmt)
     pos += 4 + 2 * struct.unpack('<L', data[pos:pos + 4])[0]
@@ -132,7 +139,7 @@ def model(pcm, data, block_switching):
     (sub-)block: what the tests' line bars are relative to), flags, record."""
     data = bytes(data)
     recs, (sr, n_ch, use_sbr, use_vq) = records(data)
-    p = po.make_params(sr, n_ch, 128)
+    p = po.make_params(sr, n_ch, 128, HOP, *header_fields(data)[4:6])      # the widths the stream itself declares
     p.useVQ, p.useSBR = use_vq, use_sbr
     p.omittedBands = list(po.omitted_bands(p.sfBands)) if use_sbr else []
     buf = fractions(pcm)

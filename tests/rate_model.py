@@ -33,12 +33,12 @@ class Unit:
                               for b in range(bands.nBands)])
 
 
-def analysis(pcm, sample_rate, block_switching):
+def analysis(pcm, sample_rate, block_switching, n_scale_bits=4, n_mant_size_bits=12):
     """-> dict: p (oracle params), flags per block, dropped per block, units [block][ch] = list of 1 or 8 Unit (None
-    for a dropped hop)"""
+    for a dropped hop), and the two field widths the stream is coded with"""
     pcm = np.asarray(pcm)
     n_ch = pcm.shape[1]
-    p = po.make_params(sample_rate, n_ch, 128)
+    p = po.make_params(sample_rate, n_ch, 128, HOP, n_scale_bits, n_mant_size_bits)
     buf = nm.fractions(pcm)
     flags = nm.block_flags(buf, block_switching)
     drop = nm.dropped(buf, flags)
@@ -68,7 +68,13 @@ def analysis(pcm, sample_rate, block_switching):
                 p.nMDCTLines = p.nSamplesPerBlock = HOP
             row.append(subs)
         units.append(row)
-    return {"p": p, "flags": flags, "dropped": drop, "units": units, "n_ch": n_ch, "sample_rate": sample_rate}
+    return {"p": p, "flags": flags, "dropped": drop, "units": units, "n_ch": n_ch, "sample_rate": sample_rate,
+            "n_scale_bits": n_scale_bits, "n_mant_size_bits": n_mant_size_bits}
+
+
+def widths(a):
+    """(nScaleBits, nMantSizeBits) of an analysis"""
+    return a.get("n_scale_bits", 4), a.get("n_mant_size_bits", 12)
 
 
 def code_unit(p, u, budget):
@@ -94,7 +100,7 @@ def worst_nmr(p, u, budget):
 
 def cap_steps(a, u, max_kbps):
     """J of a unit: the budget rule with the cap rate, in steps of 32 bits"""
-    pc = po.make_params(a["sample_rate"], a["n_ch"], max_kbps)
+    pc = po.make_params(a["sample_rate"], a["n_ch"], max_kbps, HOP, *widths(a))
     if u.short:
         pc.nMDCTLines = pc.nSamplesPerBlock = SHORT
     return max(int(np.floor(po.bit_budget(pc, *u.flags) / STEP)), 0)

@@ -152,7 +152,7 @@ def code_unit(p, u, alloc):
 
 
 def params_vq(a):
-    p = po.make_params(a["sample_rate"], a["n_ch"], 128)
+    p = po.make_params(a["sample_rate"], a["n_ch"], 128, rm.HOP, *rm.widths(a))
     p.useVQ = True
     return p
 
