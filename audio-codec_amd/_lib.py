@@ -171,6 +171,16 @@ SIGNATURES = {
     "pacx_profile_clamp_add": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
     "pacx_band_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P,
                                                _P, _P]),
+    # the same on a rate curve (row, sub_stride by value behind n_cf)
+    "pacx_rate_profile": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
+                                         ctypes.c_double, _P, _P]),
+    "pacx_rate_profile_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P,
+                                                  _P]),
+    "pacx_rate_pick": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
+                                      _P, _P, _P, _P]),
+    "pacx_rate_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                               ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P]),
     "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                     _P]),
     "pacx_vq_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),

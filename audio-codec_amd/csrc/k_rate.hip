@@ -20,6 +20,8 @@
  *                      the boundaries (segment_of, rate_dev.h), picks the budget of each of its units from the curve
  *                      at the target its segment has in flight and sums the frame's bytes; one 64-bit atomicAdd per
  *                      workgroup and segment present.
+ *   k_rate_pick        pacx_rate_pick / pacx_rate_pick_segments: the same pick of every frame (solve_frame, the only one)
+ *                      at a target given with the call, one per uniform segment; writes the outputs, sums nothing.
  *   k_solve_init, k_solve_step
  *                      one thread per segment: a SolveState each, and the bisection's decision on the segment's total.
  *                      The host enqueues a fixed number of pick / step pairs and waits for none; pairs after a
@@ -456,6 +458,24 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__rest
         atomicAdd(&s[seg].total, mine);
 }
 
+/* solve_frame at a known target, outputs written (pacx_rate_pick / pacx_rate_pick_segments): one channel-frame per
+   thread, no reduction, no state.  The frame lies in uniform segment (first_off + cf) / seg_cf and takes
+   target_t[segment] / 64; target_t == nullptr: every frame takes t_all / 64 */
+__global__ __launch_bounds__(SOLVE_THREADS) void k_rate_pick(long long n_cf, long long seg_cf, long long first_off,
+                                                            const int32_t *__restrict__ target_t, int t_all, int row,
+                                                            int sub_stride, const double *__restrict__ worst,
+                                                            const int32_t *__restrict__ bits,
+                                                            const int32_t *__restrict__ steps,
+                                                            int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
+                                                            uint8_t *__restrict__ capped)
+{
+    const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
+    if (cf >= n_cf)
+        return;
+    const int t = target_t ? target_t[(first_off + cf) / seg_cf] : t_all;
+    solve_frame(cf, (double)t / 64.0, row, sub_stride, worst, bits, steps, 1, budget, n_bytes, capped);
+}
+
 /* one thread per segment: solve_step with the segment's limit; final: result[seg] */
 __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_step(SolveState *s, int n_seg,
                                                              const long long *__restrict__ limit, int final,
@@ -569,6 +589,18 @@ void pacx_k::pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int su
         hipLaunchKernelGGL(k_solve_pick<false>, dim3(grid), dim3(SOLVE_THREADS), 0, st, (SolveState *)v.ws, v.seg,
                            v.n_seg, search, v.n_cf, row, sub_stride, worst, bits, steps, final, budget, n_bytes, capped);
     });
+}
+
+void pacx_k::pacx_launch_rate_pick_segments(long long n_cf, int row, int sub_stride, const double *worst,
+                                            const int32_t *bits, const int32_t *steps, long long seg_cf,
+                                            long long first_off, const int32_t *target_t, int t_all, int32_t *budget,
+                                            int32_t *n_bytes, uint8_t *capped, hipStream_t st)
+{
+    if (n_cf <= 0)
+        return;
+    const unsigned grid = (unsigned)((n_cf + SOLVE_THREADS - 1) / SOLVE_THREADS);
+    hipLaunchKernelGGL(k_rate_pick, dim3(grid), dim3(SOLVE_THREADS), 0, st, n_cf, seg_cf, first_off, target_t, t_all, row,
+                       sub_stride, worst, bits, steps, budget, n_bytes, capped);
 }
 
 /* the second level's init, step and finish for pacx_peak_drive (pacx_launch.h) */

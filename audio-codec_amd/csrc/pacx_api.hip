@@ -2438,6 +2438,99 @@ extern "C" int pacx_band_pick_segments(pacx_handle *h, int64_t n_cf, const doubl
     return post_launch(h, what);
 }
 
+/* ---- the same on a rate curve: the profile, per stream and per uniform segment, and the pick at known targets ---- */
+/* what the four calls share beyond segments_by_value: the row's layout (pacx_rate_solve's rule) */
+static int rate_rows(pacx_handle *h, const char *what, int64_t n_cf, int64_t seg_cf, int64_t first_off, int32_t row,
+                     int32_t sub_stride)
+{
+    if (int rc = segments_by_value(h, what, n_cf, seg_cf, first_off))
+        return rc;
+    if (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1)
+        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
+    return PACX_OK;
+}
+
+static int rate_profile(pacx_handle *h, const char *what, int64_t n_cf, int32_t row, int32_t sub_stride,
+                        const double *worst, const int32_t *bits, const int32_t *steps, int64_t seg_cf,
+                        int64_t first_off, double nmr_lo_db, double nmr_hi_db, int64_t *profile, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = rate_rows(h, what, n_cf, seg_cf, first_off, row, sub_stride))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (!profile || (n_cf > 0 && (!worst || !bits || !steps)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_rate_profile_segments(n_cf, row, sub_stride, worst, bits, steps, seg_cf, first_off, t_lo, t_hi, profile,
+                                      (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_profile(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                                 const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db,
+                                 int64_t *profile, void *stream)
+{
+    /* the whole stream is the one-segment case */
+    return rate_profile(h, "pacx_rate_profile", n_cf, row, sub_stride, worst, bits, steps, PACX_SEG_CF_MAX, 0, nmr_lo_db,
+                        nmr_hi_db, profile, stream);
+}
+
+extern "C" int pacx_rate_profile_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride,
+                                          const double *worst, const int32_t *bits, const int32_t *steps, int64_t seg_cf,
+                                          int64_t first_off, double nmr_lo_db, double nmr_hi_db, int64_t *profile,
+                                          void *stream)
+{
+    return rate_profile(h, "pacx_rate_profile_segments", n_cf, row, sub_stride, worst, bits, steps, seg_cf, first_off,
+                        nmr_lo_db, nmr_hi_db, profile, stream);
+}
+
+static int rate_pick(pacx_handle *h, const char *what, int64_t n_cf, int32_t row, int32_t sub_stride,
+                     const double *worst, const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
+                     const int32_t *target_t, bool by_segment, int t_all, int32_t *budget, int32_t *n_bytes,
+                     uint8_t *capped, void *stream)
+{
+    if (int rc = rate_rows(h, what, n_cf, seg_cf, first_off, row, sub_stride))
+        return rc;
+    if (n_cf > 0 && (!worst || !bits || !steps || (by_segment && !target_t) || !budget || !n_bytes || !capped))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_rate_pick_segments(n_cf, row, sub_stride, worst, bits, steps, seg_cf, first_off,
+                                   by_segment ? target_t : nullptr, t_all, budget, n_bytes, capped, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_pick(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                              const int32_t *bits, const int32_t *steps, double target_nmr_db, int32_t *budget,
+                              int32_t *n_bytes, uint8_t *capped, void *stream)
+{
+    const char *what = "pacx_rate_pick";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = scalar_only(h, what))
+        return rc;
+    int t, t_same;                                 /* the target on the grid: solve_range's rules for one bound */
+    if (int rc = solve_range(h, what, target_nmr_db, target_nmr_db, &t, &t_same))
+        return rc;
+    return rate_pick(h, what, n_cf, row, sub_stride, worst, bits, steps, PACX_SEG_CF_MAX, 0, nullptr, false, t, budget,
+                     n_bytes, capped, stream);
+}
+
+extern "C" int pacx_rate_pick_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride,
+                                       const double *worst, const int32_t *bits, const int32_t *steps, int64_t seg_cf,
+                                       int64_t first_off, const int32_t *target_t, int32_t *budget, int32_t *n_bytes,
+                                       uint8_t *capped, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    return rate_pick(h, "pacx_rate_pick_segments", n_cf, row, sub_stride, worst, bits, steps, seg_cf, first_off, target_t,
+                     true, 0, budget, n_bytes, capped, stream);
+}
+
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                                 const double *nmr_db, uint64_t *summary, void *stream)
 {

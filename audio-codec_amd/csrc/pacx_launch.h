@@ -173,6 +173,19 @@ void pacx_launch_rate_solve_segments(const PacxSolve &v, int row, int sub_stride
                                      const int32_t *bits, const int32_t *steps, int32_t *budget, int32_t *n_bytes,
                                      uint8_t *capped, hipStream_t st);
 
+/* the pick on a rate curve at targets given with the call (k_rate.hip, k_rate_pick): frame cf takes
+   target_t[(first_off + cf) / seg_cf] / 64; target_t == nullptr: every frame takes t_all / 64 */
+void pacx_launch_rate_pick_segments(long long n_cf, int row, int sub_stride, const double *worst, const int32_t *bits,
+                                    const int32_t *steps, long long seg_cf, long long first_off, const int32_t *target_t,
+                                    int t_all, int32_t *budget, int32_t *n_bytes, uint8_t *capped, hipStream_t st);
+
+/* k_rate_profile.hip: total(t / 64) of a rate curve added into profile [n_seg][G], row (first_off + cf) / seg_cf of
+   frame cf, for every t of the range at once (G = t_hi - t_lo + 1 <= PACX_PROFILE_MAX); the whole stream is the
+   one-segment case (seg_cf = PACX_SEG_CF_MAX, first_off = 0).  One launch */
+void pacx_launch_rate_profile_segments(long long n_cf, int row, int sub_stride, const double *worst, const int32_t *bits,
+                                       const int32_t *steps, long long seg_cf, long long first_off, int t_lo, int t_hi,
+                                       int64_t *profile, hipStream_t st);
+
 /* The second level (pacx_rate_solve_peak / pacx_band_solve_peak): a limit for the whole batch above the segments'
    peaks.  v is a segmented solve with the peaks as its limits and ws holding n_seg + 1 states: the last one is the
    stream's. */

@@ -368,15 +368,8 @@ class Encoder:
             *arrays, n_cf, out = self._band_arrays(curve, what)
             head, per_cf = [], "bit_alloc"
         else:
-            arrays = worst, bits, steps = tuple(curve[k].contiguous() for k in ("worst", "bits", "steps"))
-            n_cf, row = worst.shape
-            if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
-                    tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
-                raise ValueError(f"{what}: a curve as rate_curve returns it")
-            head, per_cf = [int(row), int(curve["sub_stride"])], "budget"
-            out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
-                   "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
-                   "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+            *arrays, n_cf, head, out = self._rate_arrays(curve, what)
+            per_cf = "budget"
         if segmented:
             first, limit = self._segments(what, seg_first, limit_bytes, n_cf)
             limits = [ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data]
@@ -453,6 +446,75 @@ class Encoder:
         that target against the peak), total_bytes, floor_nmr_db, pinned (target above the stream's); and
         stream_target_nmr_db, stream_met, stream_total_bytes for the whole."""
         return self._solve("rate_solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
+
+    def _rate_arrays(self, curve, what):
+        """a rate curve's three arrays, checked -> (worst, bits, steps, n_cf, [row, sub_stride], the per-frame outputs)"""
+        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
+        n_cf, row = worst.shape
+        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
+                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
+            raise ValueError(f"{what}: a curve as rate_curve returns it")
+        out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
+               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+        return worst, bits, steps, n_cf, [int(row), int(curve["sub_stride"])], out
+
+    # ---- the whole-grid profile of a rate curve and the pick at known targets (pacx_rate_profile and its three
+    # companions, include/pacx.h): the band siblings below on the other curve, with their checks
+    def rate_profile(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """band_profile on a rate curve (pacx_rate_profile): int64 device tensor [G], entry g = what rate_pick at
+        nmr_lo_db + g / 64 dB gives as sum(n_bytes + 4 where n_bytes > 0) -- rate_solve's total at that target.  With
+        `out` the sizes are ADDED to it.  profile_solve on the profile of a whole curve is rate_solve's decision.
+        -> the tensor."""
+        what = "rate_profile"
+        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_tensor(what, out, n)
+        self._call_rate("pacx_rate_profile", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
+        return profile
+
+    def rate_profile_segments(self, curve, seg_cf, first_off=0, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """band_profile_segments on a rate curve (pacx_rate_profile_segments): int64 device tensor [n_seg, G], row s
+        what rate_profile gives for the frames of local segment s; with `out` ADDED to its first n_seg rows, the others
+        left alone.  profile_solve_segments and profile_clamp_add take the rows as they take a band curve's.
+        -> the tensor."""
+        what = "rate_profile_segments"
+        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
+        rows = torch.zeros((n_seg, n), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_rows(what, out, n, n_seg)
+        if n_seg == 0:                                                  # no frame and no segment begun: nothing to add to
+            return rows
+        self._call_rate("pacx_rate_profile_segments", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
+                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), ctypes.c_double(nmr_lo_db),
+                        ctypes.c_double(nmr_hi_db), _ptr(rows), self._stream())
+        return rows
+
+    def rate_pick(self, curve, target_nmr_db):
+        """Every unit at the budget the curve gives at target_nmr_db, a multiple of 1/64 dB (pacx_rate_pick): what
+        rate_solve returns at the target it finds.  -> dict budget [n_cf, 8] int32 for encode_pack_budget, n_bytes
+        [n_cf] int32 (predicted), capped [n_cf] bool."""
+        worst, bits, steps, n_cf, head, out = self._rate_arrays(curve, "rate_pick")
+        self._call_rate("pacx_rate_pick", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
+                        ctypes.c_double(target_nmr_db), _ptr(out["budget"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
+                        self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def rate_pick_segments(self, curve, seg_cf, first_off, target_t):
+        """rate_pick with one target per segment (pacx_rate_pick_segments); target_t as band_pick_segments takes it.
+        -> rate_pick's dict."""
+        what = "rate_pick_segments"
+        worst, bits, steps, n_cf, head, out = self._rate_arrays(curve, what)
+        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
+        self._call_rate("pacx_rate_pick_segments", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
+                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), _ptr(t), _ptr(out["budget"]),
+                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
 
     def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
@@ -666,22 +728,25 @@ class Encoder:
                         ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
         return profile
 
-    def band_pick_segments(self, curve, seg_cf, first_off, target_t):
-        """band_pick with one target per segment (pacx_band_pick_segments): target_t, whole grid units (64 per dB), one
-        per local segment -- a sequence, or an int32 device tensor [n_seg].  -> band_pick's dict."""
-        what = "band_pick_segments"
-        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, what)
-        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
+    def _segment_targets(self, what, target_t, n_seg):
+        """one target per local segment in whole grid units -> a contiguous int32 device tensor [n_seg]"""
         if isinstance(target_t, torch.Tensor):
             t = target_t
             if t.dtype != torch.int32 or tuple(t.shape) != (n_seg,) or t.device != torch.device(self.device) or \
                     not t.is_contiguous():
                 raise ValueError(f"{what}: targets on the device are a contiguous int32 tensor [{n_seg}]")
-        else:
-            host = np.asarray(target_t)
-            if host.shape != (n_seg,) or not np.array_equal(host, np.round(host)) or (np.abs(host) > 2 ** 26).any():
-                raise ValueError(f"{what}: target_t [{n_seg}], whole grid units")
-            t = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
+            return t
+        host = np.asarray(target_t)
+        if host.shape != (n_seg,) or not np.array_equal(host, np.round(host)) or (np.abs(host) > 2 ** 26).any():
+            raise ValueError(f"{what}: target_t [{n_seg}], whole grid units")
+        return torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
+
+    def band_pick_segments(self, curve, seg_cf, first_off, target_t):
+        """band_pick with one target per segment (pacx_band_pick_segments): target_t, whole grid units (64 per dB), one
+        per local segment -- a sequence, or an int32 device tensor [n_seg].  -> band_pick's dict."""
+        what = "band_pick_segments"
+        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, what)
+        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
         self._call_rate("pacx_band_pick_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
                         ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), _ptr(t), _ptr(out["bit_alloc"]),
                         _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())

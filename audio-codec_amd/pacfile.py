@@ -467,6 +467,65 @@ class _BandPath:
             return self.enc.encode_vq_alloc(view, flags, bit_alloc)
         return self.enc.encode_pack_alloc(view, flags, bit_alloc)
 
+    # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve above, its profile, the pick
+    # at known targets and the second pass on that pick -- _BudgetPath answers the same five on the other curve
+    def no_frames(self, max_bits_per_sample):
+        """the curve of no frame at all"""
+        import torch
+        e = self.solver
+        return {"nmr": torch.zeros((0, e.band_stride, _lib.BAND_CAND), dtype=torch.float64, device=e.device),
+                "cap": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device),
+                "cap_alloc": torch.zeros((0, e.band_stride), dtype=torch.int32, device=e.device)}
+
+    def profile(self, curve, lo, hi, out=None):
+        return self.solver.band_profile(curve, lo, hi, out=out)
+
+    def profile_segments(self, curve, seg_cf, first_off, lo, hi, out=None):
+        return self.solver.band_profile_segments(curve, seg_cf, first_off, lo, hi, out=out)
+
+    def pick(self, curve, target_nmr_db):
+        return self.solver.band_pick(curve, target_nmr_db)
+
+    def pick_segments(self, curve, seg_cf, first_off, target_t):
+        return self.solver.band_pick_segments(curve, seg_cf, first_off, target_t)
+
+    def second_pass(self, view, flags, pick):
+        return self.encode(view, flags, pick["bit_alloc"])
+
+
+class _BudgetPath:
+    """_BandPath's chunked quintet for allocation="budget": BitAlloc with one budget per block, read from the rate
+    curve (Encoder.rate_curve, rate_profile[_segments], rate_pick[_segments], encode_pack_budget).  Scalar coder only."""
+
+    def __init__(self, enc):
+        self.enc = self.solver = enc
+
+    def curve(self, view, flags, max_bits_per_sample):
+        return self.enc.rate_curve(view, flags, max_bits_per_sample)
+
+    def no_frames(self, max_bits_per_sample):
+        import torch
+        e = self.enc
+        row, sub = e.rate_curve_layout(max_bits_per_sample)
+        return {"worst": torch.zeros((0, row), dtype=torch.float64, device=e.device),
+                "bits": torch.zeros((0, row), dtype=torch.int32, device=e.device),
+                "steps": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device), "row": row, "sub_stride": sub}
+
+    def profile(self, curve, lo, hi, out=None):
+        return self.enc.rate_profile(curve, lo, hi, out=out)
+
+    def profile_segments(self, curve, seg_cf, first_off, lo, hi, out=None):
+        return self.enc.rate_profile_segments(curve, seg_cf, first_off, lo, hi, out=out)
+
+    def pick(self, curve, target_nmr_db):
+        return self.enc.rate_pick(curve, target_nmr_db)
+
+    def pick_segments(self, curve, seg_cf, first_off, target_t):
+        return self.enc.rate_pick_segments(curve, seg_cf, first_off, target_t)
+
+    def second_pass(self, view, flags, pick):
+        return self.enc.encode_pack_budget(view, flags, pick["budget"])
+
 
 def _check_allocation(allocation):
     if allocation not in ("budget", "band"):
@@ -736,10 +795,12 @@ class _Blocks:
 
 
 def _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching, header_samples,
-                       nmr_range_db, use_vq):
+                       nmr_range_db, use_vq, allocation="band"):
     """everything encode_stream_abr_chunked refuses, before any GPU work -> (CodingParams, header bytes, make), make()
     -> the streaming.HostStreamRateEncoder of the call"""
     from .engine import Encoder
+    if use_vq and not _check_allocation(allocation):
+        raise NotImplementedError("gain-shape streams: allocation 'band' only")
     try:
         hops = int(chunk_hops)
     except (TypeError, ValueError):
@@ -755,22 +816,24 @@ def _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block
     def make():
         from .streaming import HostStreamRateEncoder
         return HostStreamRateEncoder(context.encoder_for_params(cp), cp.nChannels, hops, cp.targetBitsPerSample,
-                                     block_switching=block_switching, nmr_lo_db=lo, nmr_hi_db=hi)
+                                     block_switching=block_switching, nmr_lo_db=lo, nmr_hi_db=hi, allocation=allocation)
     return cp, header_bytes(cp), make
 
 
 def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
                             max_kbps_per_channel=320, block_switching=False, header_samples=None,
-                            nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None):
+                            nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None,
+                            allocation="band"):
     """encode_stream_abr_chunked piece by piece: an iterator that gives the file's header, then the bodies of the
     chunks in order (bytes; their concatenation is that call's result).  The arguments are checked, the stream is
     analysed and the target solved when this is called; the second pass runs as the iterator is consumed.
     With peak_kbps_per_channel one error can come from the ITERATOR instead: a segment that fits its peak at its own
     floor but whose bytes rise with the target (encode_stream_abr_chunked explains); the pieces before the chunk in
     which that segment ends have been handed out by then."""
+    _check_allocation(allocation)
     peak = _check_segment_keywords(segment_hops, peak_kbps_per_channel, [(kbps_per_channel, max_bytes)])
     cp, head, make = _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching,
-                                        header_samples, nmr_range_db, use_vq)
+                                        header_samples, nmr_range_db, use_vq, allocation)
     blocks = len(pcm) // 1024 + 2
     if segment_hops is None or peak:
         limit = _abr_limit(cp, _Blocks(blocks), head, kbps_per_channel, max_bytes)
@@ -830,7 +893,8 @@ def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=N
 
 def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
                               max_kbps_per_channel=320, block_switching=False, header_samples=None,
-                              nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None):
+                              nmr_range_db=(-30, 30), use_vq=False, segment_hops=None, peak_kbps_per_channel=None,
+                              allocation="band"):
     """encode_stream_abr(allocation="band") for a stream too long for one batch -> the same .pac bytes, from host
     memory to host memory in chunks of chunk_hops blocks, with device memory bounded by the chunk.  pcm: anything that
     slices to int16 [n, nCh] pieces (an np.memmap included), n a multiple of 1024 and at least 1024.  Two passes
@@ -838,8 +902,11 @@ def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes
     into one profile (Encoder.band_profile; at most 128 dB of range); the solve of encode_stream_abr read from that
     profile (Encoder.profile_solve); then per chunk curve, pick at the target found and second pass.  The sizes
     (kbps_per_channel or max_bytes), max_kbps_per_channel and the ValueError when even the highest target does not fit
-    are encode_stream_abr's.  use_vq: the gain-shape coder without SBR, the bytes of encode_stream_vq_abr.  No
-    allocation="budget".  iter_encode_abr_chunked gives the same bytes piece by piece.
+    are encode_stream_abr's.  use_vq: the gain-shape coder without SBR, the bytes of encode_stream_vq_abr.
+    iter_encode_abr_chunked gives the same bytes piece by piece.
+    allocation="budget": the bytes of encode_stream_abr(allocation="budget") -- that call's default -- instead, by the
+    same two passes on the rate curve (Encoder.rate_curve, rate_profile[_segments], rate_pick[_segments],
+    encode_pack_budget), with segment_hops and peak_kbps_per_channel as below; not with use_vq (NotImplementedError).
     segment_hops=S and peak_kbps_per_channel=P mean what they mean for encode_stream_abr, under its rules, with its
     bytes and its error messages: the first pass keeps a profile row per segment the chunk touches
     (Encoder.band_profile_segments), solves and drops the rows of the segments that end in it
@@ -853,7 +920,7 @@ def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes
     handed out the pieces before."""
     return b"".join(iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
                                             max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq,
-                                            segment_hops, peak_kbps_per_channel))
+                                            segment_hops, peak_kbps_per_channel, allocation))
 
 
 def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,

@@ -465,14 +465,16 @@ def band_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False
 
 
 def stream_rate_profile(pcm, sample_rate, chunk_hops=4096, max_kbps_per_channel=320, block_switching=False,
-                        nmr_range_db=(-30, 30), use_vq=False):
+                        nmr_range_db=(-30, 30), use_vq=False, allocation="band"):
     """The body size of a stream at every target of a range, for plotting size against quality, from one analysis
     pass in chunks of chunk_hops blocks (pacfile.encode_stream_abr_chunked's first pass; pcm as there): ->
     (targets_db float64 [G], total_bytes int64 [G]), the grid of 1/64 dB over nmr_range_db and what
-    encode_stream_nmr(target, allocation="band") -- use_vq: encode_stream_vq_nmr -- takes for its body there."""
+    encode_stream_nmr(target, allocation="band") -- use_vq: encode_stream_vq_nmr -- takes for its body there.
+    allocation="budget" (not with use_vq): what encode_stream_nmr(target, allocation="budget") takes instead."""
     from . import pacfile
+    pacfile._check_allocation(allocation)
     _, _, make = pacfile._abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching, None,
-                                            nmr_range_db, use_vq)
+                                            nmr_range_db, use_vq, allocation)
     hr = make()
     profile = hr.analyse(pcm)
     hr.s_k.synchronize()                               # the pass runs on the encoder's kernel stream

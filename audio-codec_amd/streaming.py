@@ -261,17 +261,26 @@ class HostStreamRateEncoder:
     The row buffer holds ceil(max(hops_per_chunk, 2) * nCh / (S * nCh)) + 1 rows of G int64 words -- bounded by the
     chunk; the row of a segment still open at a chunk's end is carried to the next chunk.  Per segment the object
     keeps the solve's result and worst_above on the device, 24 bytes: the only thing that grows with the stream, read
-    back once.  The limits and targets of the segments a chunk touches go up with the chunk's PCM."""
+    back once.  The limits and targets of the segments a chunk touches go up with the chunk's PCM.
+
+    allocation="budget" (scalar encoders): pacfile.encode_stream_abr(allocation="budget") instead -- BitAlloc with one
+    budget per block.  The same two passes on the other curve (pacfile._BudgetPath): Encoder.rate_curve,
+    rate_profile[_segments], rate_pick[_segments] and encode_pack_budget in place of band_curve, band_profile[_segments],
+    band_pick[_segments] and encode_pack_alloc; the rows, their solves, the clamped sum, the staging and the check of the
+    segments' sums are shared."""
 
     def __init__(self, enc, n_channels, hops_per_chunk, max_bits_per_sample, block_switching=False, nmr_lo_db=-30,
-                 nmr_hi_db=30, depth=2):
-        from .pacfile import _BandPath
+                 nmr_hi_db=30, depth=2, allocation="band"):
+        from .pacfile import _BandPath, _BudgetPath, _check_allocation
         self.enc, self.n_ch, self.F, self.depth = enc, int(n_channels), int(hops_per_chunk), int(depth)
         if self.F < 1 or self.depth < 2:
             raise ValueError("hops_per_chunk must be at least 1 and depth at least 2")
         self.block_switching, self.max_bps = bool(block_switching), float(max_bits_per_sample)
         self.lo, self.hi = nmr_lo_db, nmr_hi_db
-        self.path = _BandPath(enc)
+        band = _check_allocation(allocation)
+        if enc.use_vq and not band:
+            raise NotImplementedError("gain-shape streams: allocation 'band' only")
+        self.path = _BandPath(enc) if band else _BudgetPath(enc)
         dev, F, n_ch = enc.device, self.F, self.n_ch
         self.n_cf = max(F, 2) * n_ch                                   # the tail chunk holds two blocks
         enc.reserve(self.n_cf)
@@ -290,18 +299,12 @@ class HostStreamRateEncoder:
         self.halo = torch.zeros((n_ch, HOP), dtype=torch.int16, device=dev)
         self.carry = torch.zeros(2, dtype=torch.uint8, device=dev)
         self.tr = torch.zeros(max(F, 2), dtype=torch.uint8, device=dev)
-        self.profile = self.path.solver.band_profile(self._no_frames(), self.lo, self.hi)      # zeros [G]; checks the range
+        self.profile = self.path.profile(self.path.no_frames(self.max_bps), self.lo, self.hi)  # zeros [G]; checks the range
         self.n_frames = 0                                              # blocks the last analyse() saw
         self.seg = None                                                # the segments of the last analyse(), if any
         self.rows = None
         self.stage = {}                                                # per-segment words that go up with a chunk
         self.seg_check = [None] * self.depth                           # encode(): (first segment, count) of a slot's sums
-
-    def _no_frames(self):
-        e = self.path.solver
-        return {"nmr": torch.zeros((0, e.band_stride, _lib.BAND_CAND), dtype=torch.float64, device=e.device),
-                "cap": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device),
-                "cap_alloc": torch.zeros((0, e.band_stride), dtype=torch.int32, device=e.device)}
 
     def _chunks(self, pcm):
         """the chunks of a stream and the driver's last two blocks, one after the other: fills the pinned buffer of
@@ -426,9 +429,9 @@ class HostStreamRateEncoder:
                 view, flags = self._front(k, n, tail)
                 curve = self.path.curve(view, flags, self.max_bps)
                 if not segmented:
-                    solver.band_profile(curve, self.lo, self.hi, out=self.profile)
+                    self.path.profile(curve, self.lo, self.hi, out=self.profile)
                 else:
-                    solver.band_profile_segments(curve, seg_cf, first_off, self.lo, self.hi, out=self.rows)
+                    self.path.profile_segments(curve, seg_cf, first_off, self.lo, self.hi, out=self.rows)
                     if closed:
                         done, res = self.rows[:closed], self.seg["result"][s0:s0 + closed]
                         solver.profile_solve_segments(done, limit_dev, self.lo, self.hi,
@@ -536,7 +539,7 @@ class HostStreamRateEncoder:
                 view, flags = self._front(k, n, tail)
                 curve = self.path.curve(view, flags, self.max_bps)
                 if segmented:
-                    pick = self.path.solver.band_pick_segments(curve, seg_cf, first_off, target_dev)
+                    pick = self.path.pick_segments(curve, seg_cf, first_off, target_dev)
                     if limits is not None:
                         if frames == 0:                                # cleared on this stream, behind whatever an encode()
                             sums.zero_()                               # given up half-way still had queued on it
@@ -545,8 +548,8 @@ class HostStreamRateEncoder:
                         ids = (torch.arange(n * self.n_ch, device=enc.device) + first_off) // seg_cf
                         sums.index_add_(0, ids, torch.where(nb > 0, nb + 4, torch.zeros_like(nb)))
                 else:
-                    pick = self.path.solver.band_pick(curve, float(target_nmr_db))
-                out = self.path.encode(view, flags, pick["bit_alloc"])
+                    pick = self.path.pick(curve, float(target_nmr_db))
+                out = self.path.second_pass(view, flags, pick)
                 self.s_k.wait_event(self.ev_out[k])                    # the total that last sat in totals[k] has left
                 enc._call("pacx_gather_body", ctypes.c_int64(n * self.n_ch), _ptr(out["payload"]), _ptr(out["n_bytes"]),
                           _ptr(self.bodies[k]), ctypes.c_int64(self.cap), _ptr(self.totals[k]), enc._stream())

@@ -987,6 +987,64 @@ int pacx_band_pick_segments(pacx_handle *h, int64_t n_cf, const double *nmr, con
                             int64_t seg_cf, int64_t first_off, const int32_t *target_t, int32_t *bit_alloc,
                             int32_t *n_bytes, uint8_t *capped, void *stream);
 
+/* ---- the same on a rate curve: BitAlloc budgets solved piece by piece ---- */
+
+/*
+ * pacx_rate_solve needs the whole stream's rate curve resident for the same reason pacx_band_solve does.  With pick,
+ * bytes and total of pacx_rate_solve (above), word for word, [t_lo, t_hi] = 64 [nmr_lo_db, nmr_hi_db] and
+ * G = t_hi - t_lo + 1 <= PACX_PROFILE_MAX:
+ *
+ *   pacx_rate_profile:           profile[g] += total((t_lo + g) / 64) over the n_cf channel-frames given
+ *   pacx_rate_profile_segments:  row_s[g] += sum over the piece's channel-frames cf in local segment
+ *                                s = (first_off + cf) / seg_cf of (bytes(cf, (t_lo + g) / 64) + 4 where bytes > 0)
+ *
+ * The whole stream is the one-segment case: one kernel serves both.  The calls ADD to what profile holds -- the caller
+ * zeroes it before the first piece -- and integer sums make the result independent of how the stream is cut and of the
+ * order of execution; n_cf = 0 is a valid call that adds nothing.  On such profiles pacx_profile_solve is
+ * pacx_rate_solve's decision, pacx_profile_solve_segments per row is pacx_rate_solve_segments', and with
+ * pacx_profile_clamp_add pacx_rate_solve_peak's: those three work on rows alone.
+ *
+ * It is not G picks.  worst[j] <= t / 64 is 64 worst[j] <= t (both scalings are exact), so entry j of a unit passes from
+ * the grid index e_j = ceil(64 worst[j]) - t_lo on -- 0 where that is at or below t_lo, never where the entry is NaN,
+ * +inf or above nmr_hi_db, decided by comparisons in double before any conversion to an integer -- and the pick at g
+ * is pacx_rate_solve's bisection with ok(j) := e_j <= g: the cap test on entry J first (a capped unit takes J), the
+ * same halvings, a J that would leave its row cut to the row, a unit with steps < 0 does not exist, a frame without
+ * units adds nothing, a short-coded frame's eight units are summed before the bytes are taken.  A workgroup of 1024
+ * threads walks a contiguous run of frames; per frame it turns the row of worst into 16-bit e_j in LDS with the row of
+ * bits beside them, every thread runs the bisection for the grid entries it owns, and the bytes it holds in registers
+ * go to the row of the segment it is in whenever that changes and at its end, one 64-bit atomicAdd per entry.  A row
+ * of more than 8 x 513 entries (no pacx_rate_curve_layout gives one) is read in place instead, with the comparison
+ * 64 worst[j] <= t_lo + g itself.  One launch, no host wait.
+ *
+ *   worst, bits, steps, row, sub_stride: a curve as pacx_rate_curve_batch writes it (row >= 7 sub_stride + 1)
+ *   seg_cf, first_off:  as pacx_band_profile_segments;  n_seg = ceil((first_off + n_cf) / seg_cf)
+ *   profile (in/out):   int64 [G], of the segmented call [n_seg][G], in device memory; rows beyond n_seg are not touched
+ *
+ * pacx_rate_pick: pick(unit, T) for every unit at T = target_nmr_db, on the arrays alone, one channel-frame per thread:
+ * what pacx_rate_solve's last launch writes at the t it returns.  The call is defined on the grid: target_nmr_db is a
+ * finite multiple of 1 / 64 dB, at most 2^20 dB in magnitude.  pacx_rate_pick_segments: the same with the target
+ * target_t[s] / 64 for the frames of local segment s; with all targets equal it gives pacx_rate_pick's outputs bit for
+ * bit, with the targets of pacx_rate_solve_segments its outputs.  Neither keeps state in the handle.
+ *   target_t: int32 [n_seg] in device memory, targets in grid units (64 per dB)
+ *   budget (out): int32 [n_cf][8];  n_bytes (out): int32 [n_cf];  capped (out): uint8 [n_cf] -- pacx_rate_solve's layout
+ *
+ * PACX_E_UNSUPPORTED on a handle created with use_vq or use_sbr.  PACX_E_ARG for a null pointer, a bad count, a bad
+ * row, seg_cf outside [1, PACX_SEG_CF_MAX], first_off outside [0, seg_cf), a target off the grid, bounds that are not
+ * finite, inverted, off the grid or more than PACX_PROFILE_MAX targets apart.
+ */
+int pacx_rate_profile(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                      const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db, int64_t *profile,
+                      void *stream);
+int pacx_rate_profile_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                               const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
+                               double nmr_lo_db, double nmr_hi_db, int64_t *profile, void *stream);
+int pacx_rate_pick(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                   const int32_t *bits, const int32_t *steps, double target_nmr_db, int32_t *budget, int32_t *n_bytes,
+                   uint8_t *capped, void *stream);
+int pacx_rate_pick_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                            const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
+                            const int32_t *target_t, int32_t *budget, int32_t *n_bytes, uint8_t *capped, void *stream);
+
 /* ---- one target per stretch of a stream: the two solves, segment by segment ---- */
 
 /*
