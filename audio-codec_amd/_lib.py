@@ -181,6 +181,20 @@ SIGNATURES = {
                                       _P, _P, _P, _P]),
     "pacx_rate_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
                                                ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    # a curve kept as 16-bit thresholds and the picks on it (range by value; a single target by value, target_t on the device)
+    "pacx_band_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P,
+                                            _P]),
+    "pacx_band_pick_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_band_pick_thresholds_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64,
+                                                          ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
+    "pacx_rate_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                            ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_rate_pick_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
+    "pacx_rate_pick_thresholds_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
+                                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                                          ctypes.c_double, _P, _P, _P, _P, _P]),
     "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                     _P]),
     "pacx_vq_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),

@@ -2531,6 +2531,159 @@ extern "C" int pacx_rate_pick_segments(pacx_handle *h, int64_t n_cf, int32_t row
                      true, 0, budget, n_bytes, capped, stream);
 }
 
+/* ---- a curve kept as grid indices, and the picks on it (k_kept.hip) ---- */
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+/* a target given by value: on the grid (solve_range's rules for one bound) and inside the range */
+static int kept_target(pacx_handle *h, const char *what, double target_nmr_db, int t_lo, int t_hi, int *t)
+{
+    int t_same;
+    if (int rc = solve_range(h, what, target_nmr_db, target_nmr_db, t, &t_same))
+        return rc;
+    if (*t < t_lo || *t > t_hi)
+        return fail(h, PACX_E_ARG, std::string(what) + ": target_nmr_db lies outside [nmr_lo_db, nmr_hi_db]");
+    return PACX_OK;
+}
+
+extern "C" int pacx_band_thresholds(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap,
+                                    const int32_t *cap_alloc, double nmr_lo_db, double nmr_hi_db, uint16_t *e,
+                                    int32_t *kept_cap, uint8_t *kept_cap_alloc, void *stream)
+{
+    const char *what = "pacx_band_thresholds";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = segments_by_value(h, what, n_cf, PACX_SEG_CF_MAX, 0))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (n_cf > 0 && (!nmr || !cap || !cap_alloc || !e || !kept_cap || !kept_cap_alloc))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (!aligned16(nmr) || !aligned16(e))
+        return fail(h, PACX_E_ARG, std::string(what) + ": nmr and e must be 16-byte aligned");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_thresholds(h->T, n_cf, t_lo, t_hi, nmr, cap, cap_alloc, e, kept_cap, kept_cap_alloc,
+                                (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+static int band_pick_kept(pacx_handle *h, const char *what, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                          const uint8_t *cap_alloc, int64_t seg_cf, int64_t first_off, double nmr_lo_db, double nmr_hi_db,
+                          const int32_t *target_t, const double *target_nmr_db, int32_t *bit_alloc, int32_t *n_bytes,
+                          uint8_t *capped, void *stream)
+{
+    int t_lo, t_hi, t_all = 0;
+    if (int rc = segments_by_value(h, what, n_cf, seg_cf, first_off))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (target_nmr_db)
+        if (int rc = kept_target(h, what, *target_nmr_db, t_lo, t_hi, &t_all))
+            return rc;
+    if (n_cf > 0 && (!e || !cap || !cap_alloc || (!target_nmr_db && !target_t) || !bit_alloc || !n_bytes || !capped))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (!aligned16(e))
+        return fail(h, PACX_E_ARG, std::string(what) + ": e must be 16-byte aligned");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_pick_thresholds(h->T, n_cf, seg_cf, first_off, target_nmr_db ? nullptr : target_t, t_all, t_lo, t_hi,
+                                     e, cap, cap_alloc, bit_alloc, n_bytes, capped, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_pick_thresholds(pacx_handle *h, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                                         const uint8_t *cap_alloc, double nmr_lo_db, double nmr_hi_db,
+                                         double target_nmr_db, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                                         void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    return band_pick_kept(h, "pacx_band_pick_thresholds", n_cf, e, cap, cap_alloc, PACX_SEG_CF_MAX, 0, nmr_lo_db,
+                          nmr_hi_db, nullptr, &target_nmr_db, bit_alloc, n_bytes, capped, stream);
+}
+
+extern "C" int pacx_band_pick_thresholds_segments(pacx_handle *h, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                                                  const uint8_t *cap_alloc, int64_t seg_cf, int64_t first_off,
+                                                  double nmr_lo_db, double nmr_hi_db, const int32_t *target_t,
+                                                  int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    return band_pick_kept(h, "pacx_band_pick_thresholds_segments", n_cf, e, cap, cap_alloc, seg_cf, first_off, nmr_lo_db,
+                          nmr_hi_db, target_t, nullptr, bit_alloc, n_bytes, capped, stream);
+}
+
+extern "C" int pacx_rate_thresholds(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                                    const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db,
+                                    uint16_t *e, int32_t *kept_bits, int32_t *kept_steps, void *stream)
+{
+    const char *what = "pacx_rate_thresholds";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = rate_rows(h, what, n_cf, PACX_SEG_CF_MAX, 0, row, sub_stride))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (n_cf > 0 && (!worst || !bits || !steps || !e || !kept_bits || !kept_steps))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_rate_thresholds(n_cf, row, sub_stride, t_lo, t_hi, worst, bits, steps, e, kept_bits, kept_steps,
+                                (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+static int rate_pick_kept(pacx_handle *h, const char *what, int64_t n_cf, int32_t row, int32_t sub_stride,
+                          const uint16_t *e, const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
+                          double nmr_lo_db, double nmr_hi_db, const int32_t *target_t, const double *target_nmr_db,
+                          int32_t *budget, int32_t *n_bytes, uint8_t *capped, void *stream)
+{
+    int t_lo, t_hi, t_all = 0;
+    if (int rc = rate_rows(h, what, n_cf, seg_cf, first_off, row, sub_stride))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (target_nmr_db)
+        if (int rc = kept_target(h, what, *target_nmr_db, t_lo, t_hi, &t_all))
+            return rc;
+    if (n_cf > 0 && (!e || !bits || !steps || (!target_nmr_db && !target_t) || !budget || !n_bytes || !capped))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_rate_pick_thresholds(n_cf, row, sub_stride, seg_cf, first_off, target_nmr_db ? nullptr : target_t, t_all,
+                                     t_lo, t_hi, e, bits, steps, budget, n_bytes, capped, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_pick_thresholds(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const uint16_t *e,
+                                         const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db,
+                                         double target_nmr_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped,
+                                         void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    return rate_pick_kept(h, "pacx_rate_pick_thresholds", n_cf, row, sub_stride, e, bits, steps, PACX_SEG_CF_MAX, 0,
+                          nmr_lo_db, nmr_hi_db, nullptr, &target_nmr_db, budget, n_bytes, capped, stream);
+}
+
+extern "C" int pacx_rate_pick_thresholds_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride,
+                                                  const uint16_t *e, const int32_t *bits, const int32_t *steps,
+                                                  int64_t seg_cf, int64_t first_off, double nmr_lo_db, double nmr_hi_db,
+                                                  const int32_t *target_t, int32_t *budget, int32_t *n_bytes,
+                                                  uint8_t *capped, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    return rate_pick_kept(h, "pacx_rate_pick_thresholds_segments", n_cf, row, sub_stride, e, bits, steps, seg_cf,
+                          first_off, nmr_lo_db, nmr_hi_db, target_t, nullptr, budget, n_bytes, capped, stream);
+}
+
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                                 const double *nmr_db, uint64_t *summary, void *stream)
 {

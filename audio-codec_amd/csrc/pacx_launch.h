@@ -268,6 +268,26 @@ void pacx_launch_profile_solve_segments(long long n_seg, const int64_t *profile,
 void pacx_launch_profile_clamp_add(long long n_seg, const int64_t *profile, const pacx_rate_result *result, int t_lo,
                                    int t_hi, int64_t *stream_profile, hipStream_t st);
 
+/* k_kept.hip: a curve as the 16-bit grid indices from which its entries pass (G = t_hi - t_lo + 1: never), and the
+   picks on them.  Band: e uint16 [n_cf][band_stride][PACX_BAND_CAND] (16-byte aligned, as nmr), cap copied, cap_alloc
+   as bytes.  Rate: e uint16 [n_cf][row], bits copied (0 where no unit uses the entry), steps cut to the row.  The
+   picks: frame cf takes target_t[(first_off + cf) / seg_cf], target_t == nullptr: every frame takes t_all; grid units,
+   clamped into [t_lo, t_hi].  One launch each */
+void pacx_launch_band_thresholds(const PacxTables &T, long long n_cf, int t_lo, int t_hi, const double *nmr,
+                                 const int32_t *cap, const int32_t *cap_alloc, uint16_t *e, int32_t *kept_cap,
+                                 uint8_t *kept_cap_alloc, hipStream_t st);
+void pacx_launch_band_pick_thresholds(const PacxTables &T, long long n_cf, long long seg_cf, long long first_off,
+                                      const int32_t *target_t, int t_all, int t_lo, int t_hi, const uint16_t *e,
+                                      const int32_t *cap, const uint8_t *cap_alloc, int32_t *bit_alloc, int32_t *n_bytes,
+                                      uint8_t *capped, hipStream_t st);
+void pacx_launch_rate_thresholds(long long n_cf, int row, int sub_stride, int t_lo, int t_hi, const double *worst,
+                                 const int32_t *bits, const int32_t *steps, uint16_t *e, int32_t *kept_bits,
+                                 int32_t *kept_steps, hipStream_t st);
+void pacx_launch_rate_pick_thresholds(long long n_cf, int row, int sub_stride, long long seg_cf, long long first_off,
+                                      const int32_t *target_t, int t_all, int t_lo, int t_hi, const uint16_t *e,
+                                      const int32_t *bits, const int32_t *steps, int32_t *budget, int32_t *n_bytes,
+                                      uint8_t *capped, hipStream_t st);
+
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
    row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr

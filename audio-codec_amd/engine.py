@@ -753,6 +753,127 @@ class Encoder:
         out["capped"] = out["capped"].bool()
         return out
 
+    # ---- a curve kept as 16-bit thresholds and the picks on it (pacx_band_thresholds and its five companions,
+    # include/pacx.h): what a chunked encode keeps between its passes instead of taking every curve twice
+    def _kept_out(self, what, out, shapes):
+        """the arrays of a kept curve: made here, or the caller's (contiguous device tensors of these shapes and types)"""
+        if out is None:
+            return {k: torch.empty(shape, dtype=dtype, device=self.device) for k, (shape, dtype) in shapes.items()}
+        for k, (shape, dtype) in shapes.items():
+            t = out.get(k)
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or \
+                    t.device != torch.device(self.device) or not t.is_contiguous():
+                raise ValueError(f"{what}: out[{k!r}] is a contiguous {dtype} device tensor {list(shape)}")
+        return {k: out[k] for k in shapes}
+
+    def _kept_range(self, what, kept):
+        lo, hi = kept["nmr_lo_db"], kept["nmr_hi_db"]
+        self._profile_len(what, lo, hi)
+        return ctypes.c_double(lo), ctypes.c_double(hi)
+
+    def band_thresholds(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """A band curve in the form that decides a pick on the grid of 1/64 dB in [nmr_lo_db, nmr_hi_db]
+        (pacx_band_thresholds, include/pacx.h): e [n_cf, band_stride, 16] uint16, the grid index from which each size
+        passes (G = the number of grid targets where it never does, and in every entry no band uses), cap copied,
+        cap_alloc as uint8: a quarter of the curve's bytes.  band_pick_thresholds[_segments] on it give band_pick's
+        outputs at every grid target of the range.  out: a dict with e, cap, cap_alloc to write into.  -> dict e, cap,
+        cap_alloc, nmr_lo_db, nmr_hi_db."""
+        what = "band_thresholds"
+        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, what)
+        self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        kept = self._kept_out(what, out, {"e": ((n_cf, self.band_stride, _lib.BAND_CAND), torch.uint16),
+                                          "cap": ((n_cf, _lib.SUB), torch.int32),
+                                          "cap_alloc": ((n_cf, self.band_stride), torch.uint8)})
+        self._call_rate("pacx_band_thresholds", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(kept["e"]), _ptr(kept["cap"]),
+                        _ptr(kept["cap_alloc"]), self._stream())
+        kept.update(nmr_lo_db=nmr_lo_db, nmr_hi_db=nmr_hi_db)
+        return kept
+
+    def _kept_band_arrays(self, kept, what):
+        e, cap, cap_alloc = (kept[k].contiguous() for k in ("e", "cap", "cap_alloc"))
+        n_cf = e.shape[0]
+        if e.dtype != torch.uint16 or cap.dtype != torch.int32 or cap_alloc.dtype != torch.uint8 or \
+                tuple(e.shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or tuple(cap.shape) != (n_cf, _lib.SUB) or \
+                tuple(cap_alloc.shape) != (n_cf, self.band_stride):
+            raise ValueError(f"{what}: a kept curve as band_thresholds returns it")
+        out = {"bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
+               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+        return e, cap, cap_alloc, n_cf, out
+
+    def band_pick_thresholds(self, kept, target_nmr_db):
+        """band_pick on a kept curve (pacx_band_pick_thresholds): target_nmr_db a multiple of 1/64 dB inside the range
+        the thresholds were made for.  -> band_pick's dict, equal to band_pick's on the curve itself."""
+        what = "band_pick_thresholds"
+        e, cap, cap_alloc, n_cf, out = self._kept_band_arrays(kept, what)
+        self._call_rate("pacx_band_pick_thresholds", ctypes.c_int64(n_cf), _ptr(e), _ptr(cap), _ptr(cap_alloc),
+                        *self._kept_range(what, kept), ctypes.c_double(target_nmr_db), _ptr(out["bit_alloc"]),
+                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def band_pick_thresholds_segments(self, kept, seg_cf, first_off, target_t):
+        """band_pick_segments on a kept curve (pacx_band_pick_thresholds_segments); target_t as band_pick_segments takes
+        it, every target inside the range.  -> band_pick's dict."""
+        what = "band_pick_thresholds_segments"
+        e, cap, cap_alloc, n_cf, out = self._kept_band_arrays(kept, what)
+        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
+        self._call_rate("pacx_band_pick_thresholds_segments", ctypes.c_int64(n_cf), _ptr(e), _ptr(cap), _ptr(cap_alloc),
+                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), *self._kept_range(what, kept),
+                        _ptr(t), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def rate_thresholds(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
+        """band_thresholds for a rate curve (pacx_rate_thresholds): e [n_cf, row] uint16, bits copied (0 where no unit
+        uses the entry), steps with a J that would leave its row cut to the row: half of the curve's bytes.  out: a dict
+        with e, bits, steps to write into.  -> dict e, bits, steps, row, sub_stride, nmr_lo_db, nmr_hi_db."""
+        what = "rate_thresholds"
+        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
+        self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        kept = self._kept_out(what, out, {"e": ((n_cf, head[0]), torch.uint16), "bits": ((n_cf, head[0]), torch.int32),
+                                          "steps": ((n_cf, _lib.SUB), torch.int32)})
+        self._call_rate("pacx_rate_thresholds", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
+                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(kept["e"]), _ptr(kept["bits"]),
+                        _ptr(kept["steps"]), self._stream())
+        kept.update(row=head[0], sub_stride=head[1], nmr_lo_db=nmr_lo_db, nmr_hi_db=nmr_hi_db)
+        return kept
+
+    def _kept_rate_arrays(self, kept, what):
+        e, bits, steps = (kept[k].contiguous() for k in ("e", "bits", "steps"))
+        n_cf, row = e.shape
+        if e.dtype != torch.uint16 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
+                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
+            raise ValueError(f"{what}: a kept curve as rate_thresholds returns it")
+        out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
+               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+        return e, bits, steps, n_cf, [int(row), int(kept["sub_stride"])], out
+
+    def rate_pick_thresholds(self, kept, target_nmr_db):
+        """rate_pick on a kept curve (pacx_rate_pick_thresholds): target_nmr_db a multiple of 1/64 dB inside the range
+        the thresholds were made for.  -> rate_pick's dict, equal to rate_pick's on the curve itself."""
+        what = "rate_pick_thresholds"
+        e, bits, steps, n_cf, head, out = self._kept_rate_arrays(kept, what)
+        self._call_rate("pacx_rate_pick_thresholds", ctypes.c_int64(n_cf), *head, _ptr(e), _ptr(bits), _ptr(steps),
+                        *self._kept_range(what, kept), ctypes.c_double(target_nmr_db), _ptr(out["budget"]),
+                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def rate_pick_thresholds_segments(self, kept, seg_cf, first_off, target_t):
+        """rate_pick_segments on a kept curve (pacx_rate_pick_thresholds_segments).  -> rate_pick's dict."""
+        what = "rate_pick_thresholds_segments"
+        e, bits, steps, n_cf, head, out = self._kept_rate_arrays(kept, what)
+        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
+        self._call_rate("pacx_rate_pick_thresholds_segments", ctypes.c_int64(n_cf), *head, _ptr(e), _ptr(bits),
+                        _ptr(steps), ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)),
+                        *self._kept_range(what, kept), _ptr(t), _ptr(out["budget"]), _ptr(out["n_bytes"]),
+                        _ptr(out["capped"]), self._stream())
+        out["capped"] = out["capped"].bool()
+        return out
+
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,

@@ -492,6 +492,29 @@ class _BandPath:
     def second_pass(self, view, flags, pick):
         return self.encode(view, flags, pick["bit_alloc"])
 
+    # the curve kept between the passes (HostStreamRateEncoder.keep_curves): its thresholds, the picks on them, and
+    # the layout of a chunk's kept arrays in one run of bytes
+    def kept_bytes_per_cf(self, max_bits_per_sample):
+        return 33 * self.solver.band_stride + 32
+
+    def kept_views(self, buf, n_cf, max_bits_per_sample):
+        """the arrays of n_cf kept channel-frames as views of the first n_cf * kept_bytes_per_cf bytes of buf (uint8,
+        256-byte aligned): e, then cap, then cap_alloc, each contiguous"""
+        import torch
+        bs = self.solver.band_stride
+        a, b = 32 * bs * n_cf, (32 * bs + 32) * n_cf
+        return {"e": buf[:a].view(torch.uint16).view(n_cf, bs, _lib.BAND_CAND),
+                "cap": buf[a:b].view(torch.int32).view(n_cf, _lib.SUB), "cap_alloc": buf[b:b + bs * n_cf].view(n_cf, bs)}
+
+    def thresholds(self, curve, lo, hi, out=None):
+        return self.solver.band_thresholds(curve, lo, hi, out=out)
+
+    def pick_kept(self, kept, target_nmr_db):
+        return self.solver.band_pick_thresholds(kept, target_nmr_db)
+
+    def pick_kept_segments(self, kept, seg_cf, first_off, target_t):
+        return self.solver.band_pick_thresholds_segments(kept, seg_cf, first_off, target_t)
+
 
 class _BudgetPath:
     """_BandPath's chunked quintet for allocation="budget": BitAlloc with one budget per block, read from the rate
@@ -525,6 +548,26 @@ class _BudgetPath:
 
     def second_pass(self, view, flags, pick):
         return self.enc.encode_pack_budget(view, flags, pick["budget"])
+
+    def kept_bytes_per_cf(self, max_bits_per_sample):
+        return 6 * self.enc.rate_curve_layout(max_bits_per_sample)[0] + 32
+
+    def kept_views(self, buf, n_cf, max_bits_per_sample):
+        """_BandPath.kept_views for the rate curve: bits, then steps, then e (the widest first: every array aligned)"""
+        import torch
+        row, sub = self.enc.rate_curve_layout(max_bits_per_sample)
+        a, b = 4 * row * n_cf, (4 * row + 32) * n_cf
+        return {"bits": buf[:a].view(torch.int32).view(n_cf, row), "steps": buf[a:b].view(torch.int32).view(n_cf, _lib.SUB),
+                "e": buf[b:b + 2 * row * n_cf].view(torch.uint16).view(n_cf, row), "row": row, "sub_stride": sub}
+
+    def thresholds(self, curve, lo, hi, out=None):
+        return self.enc.rate_thresholds(curve, lo, hi, out=out)
+
+    def pick_kept(self, kept, target_nmr_db):
+        return self.enc.rate_pick_thresholds(kept, target_nmr_db)
+
+    def pick_kept_segments(self, kept, seg_cf, first_off, target_t):
+        return self.enc.rate_pick_thresholds_segments(kept, seg_cf, first_off, target_t)
 
 
 def _check_allocation(allocation):
@@ -830,6 +873,33 @@ def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=N
     With peak_kbps_per_channel one error can come from the ITERATOR instead: a segment that fits its peak at its own
     floor but whose bytes rise with the target (encode_stream_abr_chunked explains); the pieces before the chunk in
     which that segment ends have been handed out by then."""
+    return _iter_encode_abr(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops, max_kbps_per_channel,
+                            block_switching, header_samples, nmr_range_db, use_vq, segment_hops, peak_kbps_per_channel,
+                            allocation, None)
+
+
+def _kept_bytes_per_cf(cp, allocation):
+    """_BandPath / _BudgetPath.kept_bytes_per_cf from the CodingParams alone (header_bytes has set the band tables), so
+    that a caller's store is refused before an encoder exists: 33 band_stride + 32, or 6 row + 32 with the row of
+    pacx_rate_curve_layout (the budget rule of coder/codec.py:288-299 at the cap rate, in steps of 32 bits)"""
+    nb_long, nb_short = cp.sfBands.nBands, cp.sfBandsShort.nBands
+    if allocation == "band":
+        return 33 * max(nb_long, _lib.SUB * nb_short) + 32
+
+    def steps(half_n, short, last_or_next, nb):
+        n_eff = int(1.45 * half_n) if short else half_n
+        if last_or_next:
+            n_eff = int(0.85 * n_eff)
+        cap = cp.targetBitsPerSample * float(n_eff) - float(cp.nScaleBits * (nb + 1)) - float(cp.nMantSizeBits * nb)
+        return min(max(int(np.floor(cap / 32.0)), 0), 2047)
+    j_long = max(steps(1024, False, lon, nb_long) for lon in (False, True))
+    j_short = max(steps(128, True, lon, nb_short) for lon in (False, True))
+    return 6 * max(j_long + 1, _lib.SUB * (j_short + 1)) + 32
+
+
+def _iter_encode_abr(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops, max_kbps_per_channel, block_switching,
+                     header_samples, nmr_range_db, use_vq, segment_hops, peak_kbps_per_channel, allocation, keep):
+    """iter_encode_abr_chunked (keep None) and iter_encode_abr_kept (keep = (curve_store,)): one implementation"""
     _check_allocation(allocation)
     peak = _check_segment_keywords(segment_hops, peak_kbps_per_channel, [(kbps_per_channel, max_bytes)])
     cp, head, make = _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching,
@@ -840,7 +910,13 @@ def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=N
     if segment_hops is not None:
         first, count, seg_limit = segment_limits(peak_kbps_per_channel if peak else kbps_per_channel, cp.nChannels,
                                                  cp.sampleRate, blocks, segment_hops)
+    if keep is not None and keep[0] is not None:                       # refused here: no encoder yet
+        from .streaming import HostStreamRateEncoder
+        HostStreamRateEncoder.check_store(keep[0], blocks * cp.nChannels * _kept_bytes_per_cf(cp, allocation),
+                                          "curve_store")
     hr = make()
+    if keep is not None:
+        hr.keep_curves(keep[0])
     check = None
     if segment_hops is None:
         hr.analyse(pcm)
@@ -921,6 +997,37 @@ def encode_stream_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes
     return b"".join(iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
                                             max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq,
                                             segment_hops, peak_kbps_per_channel, allocation))
+
+
+def iter_encode_abr_kept(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
+                         max_kbps_per_channel=320, block_switching=False, header_samples=None, nmr_range_db=(-30, 30),
+                         use_vq=False, segment_hops=None, peak_kbps_per_channel=None, allocation="band",
+                         curve_store=None):
+    """encode_stream_abr_kept piece by piece, as iter_encode_abr_chunked gives encode_stream_abr_chunked's."""
+    return _iter_encode_abr(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops, max_kbps_per_channel,
+                            block_switching, header_samples, nmr_range_db, use_vq, segment_hops, peak_kbps_per_channel,
+                            allocation, (curve_store,))
+
+
+def encode_stream_abr_kept(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, chunk_hops=4096,
+                           max_kbps_per_channel=320, block_switching=False, header_samples=None, nmr_range_db=(-30, 30),
+                           use_vq=False, segment_hops=None, peak_kbps_per_channel=None, allocation="band",
+                           curve_store=None):
+    """encode_stream_abr_chunked with every chunk's curve taken ONCE -> the same .pac bytes, the same refusals and
+    error messages.  The first pass writes each chunk's curve out as 16-bit thresholds (Encoder.band_thresholds /
+    rate_thresholds, include/pacx.h: what a pick at a grid target of nmr_range_db reads of the curve -- a quarter of a
+    band curve's bytes, half of a rate curve's, about as many per channel-frame as the PCM itself) and copies them down
+    behind the kernels; the second pass sends them up behind the PCM and picks from them
+    (Encoder.band_pick_thresholds[_segments] / rate_pick_thresholds[_segments]) instead of taking the curve again
+    (streaming.HostStreamRateEncoder.keep_curves).  Device memory stays bounded by the chunk; host memory holds
+    HostStreamRateEncoder.kept_bytes(len(pcm) // 1024) bytes between the passes.
+    curve_store=None: that memory is made by the call; else a writable C-contiguous uint8 buffer of at least that many
+    bytes, for instance an np.memmap over a scratch file (ValueError before any GPU work otherwise).  The other
+    parameters are encode_stream_abr_chunked's, in its order.  The curve is the expensive part of a chunk for
+    gain-shape streams and for allocation="budget" (README has the figures)."""
+    return b"".join(iter_encode_abr_kept(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
+                                         max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq,
+                                         segment_hops, peak_kbps_per_channel, allocation, curve_store))
 
 
 def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,

@@ -238,7 +238,10 @@ class HostStreamRateEncoder:
 
     The profile (Encoder.band_profile: G int64 words) is all that the first pass keeps, so device memory is bounded by
     the chunk and the bodies are those of the one-batch call: the curve of a frame, the pick at the target and the
-    second pass do not depend on how the stream is cut.  The curve is taken twice -- once per pass -- instead of kept.
+    second pass do not depend on how the stream is cut.  The curve is taken twice -- once per pass -- unless keep_curves()
+    was called: then analyse() also writes every chunk's curve out as 16-bit thresholds (Encoder.band_thresholds /
+    rate_thresholds), copies them down behind the kernels into host memory or the caller's buffer, and encode() sends them
+    up behind the PCM and picks from them without taking the curve again (pacfile.encode_stream_abr_kept).
     Chunks run on HostStreamEncoder's front end (_chunk_front): the PCM of chunk i + 1 goes up while chunk i computes,
     halo and transient carry stay on the device, the driver's last two blocks are a chunk of their own.  pcm is
     anything that slices to int16 [n, nCh] pieces (an np.memmap included); only a chunk of it is touched at a time.
@@ -305,6 +308,53 @@ class HostStreamRateEncoder:
         self.rows = None
         self.stage = {}                                                # per-segment words that go up with a chunk
         self.seg_check = [None] * self.depth                           # encode(): (first segment, count) of a slot's sums
+        self.keep = None                                               # keep_curves(): (the caller's store or None,)
+        self.kept = None                                               # the last analyse()'s kept curves, if it kept them
+
+    # ------------------------------------------------------------------ the curves kept between the passes
+    def keep_curves(self, store=None):
+        """From the next analyse() on, keep every chunk's curve as 16-bit thresholds (Encoder.band_thresholds /
+        rate_thresholds: what a pick at a grid target of the object's range reads of it) in host memory, so that
+        encode() picks from them and takes no curve a second time.  store=None: host memory the object allocates when
+        the stream is analysed; else a writable C-contiguous uint8 buffer (an np.memmap included) of at least
+        kept_bytes(n_hops) bytes, checked by analyse() -- ValueError before any GPU work.  -> self."""
+        self.keep, self.kept = (store,), None
+        return self
+
+    def kept_bytes(self, n_hops):
+        """bytes of the store for a stream of n_hops hops: the n_hops + 2 blocks the driver writes, every channel"""
+        return (int(n_hops) + 2) * self.n_ch * self.path.kept_bytes_per_cf(self.max_bps)
+
+    @staticmethod
+    def check_store(store, need, what="store"):
+        """a caller's store as a flat uint8 NumPy view of it, or ValueError"""
+        msg = f"{what}: a writable C-contiguous uint8 buffer of at least {need} bytes"
+        try:
+            mv = memoryview(store)
+        except TypeError:
+            raise ValueError(msg) from None
+        if mv.format != "B" or mv.itemsize != 1:
+            raise ValueError(f"{msg} (its items are not uint8)")
+        if mv.readonly:
+            raise ValueError(f"{msg} (it is read-only)")
+        if not mv.c_contiguous:
+            raise ValueError(f"{msg} (it is not C-contiguous)")
+        if mv.nbytes < need:
+            raise ValueError(f"{msg} (it holds {mv.nbytes})")
+        return np.frombuffer(mv, dtype=np.uint8)
+
+    def _kept_buffers(self):
+        """per slot: the chunk's kept bytes on the device and their pinned staging buffer, for both ways"""
+        if not hasattr(self, "dev_kept"):
+            n = self.n_cf * self.path.kept_bytes_per_cf(self.max_bps)
+            self.dev_kept = [torch.zeros(n, dtype=torch.uint8, device=self.enc.device) for _ in range(self.depth)]
+            self.host_kept = [torch.zeros(n, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+            self.ev_keep = [torch.cuda.Event() for _ in range(self.depth)]
+
+    def _kept_views(self, k, n):
+        kept = self.path.kept_views(self.dev_kept[k], n * self.n_ch, self.max_bps)
+        kept.update(nmr_lo_db=self.lo, nmr_hi_db=self.hi)
+        return kept
 
     def _chunks(self, pcm):
         """the chunks of a stream and the driver's last two blocks, one after the other: fills the pinned buffer of
@@ -396,9 +446,17 @@ class HostStreamRateEncoder:
         worst_above stay on the device, for solve_segments()) and cleared, the row of a segment still open is carried.
         peak: the limits are peaks, and the solved rows are clamp-added into self.profile, which is then the stream's
         size at every stream target with every segment held at its floor (solve_peak()).  The row buffer has
-        ceil(max(hops_per_chunk, 2) nCh / (S nCh)) + 1 rows.  No host wait per chunk either way."""
+        ceil(max(hops_per_chunk, 2) nCh / (S nCh)) + 1 rows.  No host wait per chunk either way.
+        After keep_curves(): one more step per chunk behind the profile step, the chunk's thresholds on the kernel
+        stream and their copy down on the copy-out stream into the slot's pinned staging buffer; the host moves a
+        slot's buffer into the store when the slot comes round again and after the last chunk, its only new wait."""
         solver = self.path.solver
         segmented = segment_hops is not None
+        self.kept = None
+        keep, store = self.keep is not None, None
+        if keep:                                                       # refused before any GPU work
+            need = self.kept_bytes(len(pcm) // HOP)
+            store = np.empty(need, np.uint8) if self.keep[0] is None else self.check_store(self.keep[0], need)
         if segmented:
             seg_cf, n_seg, limits = self._segments(pcm, segment_hops, segment_limits, "segment_limits")
             try:
@@ -420,8 +478,21 @@ class HostStreamRateEncoder:
             self.profile.zero_()
             if segmented:
                 self.rows.zero_()
+        if keep:
+            self._kept_buffers()
+            per_block = self.n_ch * self.path.kept_bytes_per_cf(self.max_bps)
+            waiting = [None] * self.depth                              # (offset in the store, bytes) of a slot's staging buffer
+
+            def land(k):
+                """a slot's kept bytes from its staging buffer into the store: the one host wait keeping adds"""
+                if waiting[k] is not None:
+                    (at, nb), waiting[k] = waiting[k], None
+                    self.ev_keep[k].synchronize()
+                    store[at:at + nb] = self.host_kept[k].numpy()[:nb]
         frames = 0
         for k, n, tail in self._chunks(pcm):
+            if keep:
+                land(k)                                                # the slot comes round again
             if segmented:
                 first_off, s0, touched, closed = self._piece(frames, n, tail, seg_cf)
                 limit_dev = self._stage_up("limit", k, limits[s0:s0 + closed], torch.int64)
@@ -443,9 +514,24 @@ class HostStreamRateEncoder:
                             self.rows[1:touched].zero_()
                         else:
                             self.rows[:touched].zero_()
+                if keep:                                               # after the profile step: the curve as thresholds
+                    self.s_k.wait_event(self.ev_keep[k])               # the bytes that last sat in dev_kept[k] have left
+                    self.path.thresholds(curve, self.lo, self.hi,
+                                         out=self.path.kept_views(self.dev_kept[k], n * self.n_ch, self.max_bps))
                 self.ev_k[k].record(self.s_k)
+            if keep:
+                nb = n * per_block
+                with torch.cuda.stream(self.s_out):
+                    self.s_out.wait_event(self.ev_k[k])
+                    self.host_kept[k][:nb].copy_(self.dev_kept[k][:nb], non_blocking=True)
+                    self.ev_keep[k].record(self.s_out)
+                waiting[k] = (frames * per_block, nb)
             frames += n
         self.n_frames = frames
+        if keep:
+            for k in range(self.depth):
+                land(k)                                                # after the last chunk
+            self.kept = {"store": store, "hops": len(pcm) // HOP, "per_block": per_block}
         return self.profile
 
     def solve(self, limit_bytes):
@@ -497,16 +583,28 @@ class HostStreamRateEncoder:
         self.s_out.synchronize()
         return self.host_body[k][:n].numpy()
 
-    def encode(self, pcm, target_nmr_db, segment_hops=None, segment_limits=None):
+    def encode(self, pcm, target_nmr_db, segment_hops=None, segment_limits=None, use_kept=True):
         """the second pass: yields the chunks' bodies in order ('<L nBytes' + payload per channel-block), every band at
         the smallest size that keeps it at or below target_nmr_db (Encoder.band_pick), the driver's last two blocks
         last.  A body is a view of pinned memory, valid until the next one is taken.
         segment_hops=S with target_nmr_db [n_seg] (multiples of 1/64 dB): one target per segment
         (Encoder.band_pick_segments).  segment_limits=[n_seg] besides: every segment's records are summed as they are
         picked (n_bytes + 4 each), and SegmentOverLimit is raised in place of the body of the chunk in which the first
-        segment beyond its limit ends -- the bodies before it have been handed out by then."""
+        segment beyond its limit ends -- the bodies before it have been handed out by then.
+        After keep_curves() and an analyse() of a stream of this length the curves are not taken again: every chunk's
+        kept bytes go up behind its PCM and the pick runs on them (Encoder.band_pick_thresholds[_segments]); the front
+        end still runs, the second pass needs its flags.  The targets must then be multiples of 1/64 dB inside the
+        object's range (ValueError).  The store belongs to the last analyse(): the length of pcm is checked, that it
+        is the same stream cannot be.  use_kept=False: the curves are taken again whatever is kept."""
         enc, order = self.enc, []
         segmented = segment_hops is not None
+        kept = self.kept if use_kept and self.kept is not None and self.kept["hops"] == len(pcm) // HOP else None
+        if kept is not None:
+            g = np.atleast_1d(np.asarray(target_nmr_db, np.float64)) * _lib.RATE_TARGET_GRID
+            if not np.isfinite(g).all() or (g != np.round(g)).any() or (g < self.lo * _lib.RATE_TARGET_GRID).any() or \
+                    (g > self.hi * _lib.RATE_TARGET_GRID).any():
+                raise ValueError(f"target_nmr_db: with kept curves, multiples of 1/{_lib.RATE_TARGET_GRID} dB in "
+                                 f"[{self.lo}, {self.hi}]")
         if segmented:
             seg_cf, n_seg, targets = self._segments(pcm, segment_hops, target_nmr_db, "target_nmr_db")
             grid = targets.astype(np.float64) * _lib.RATE_TARGET_GRID
@@ -535,11 +633,18 @@ class HostStreamRateEncoder:
             if segmented:
                 first_off, s0, touched, closed = self._piece(frames, n, tail, seg_cf)
                 target_dev = self._stage_up("target", k, grid[s0:s0 + touched], torch.int32)
+            if kept is not None:                                       # the chunk's kept bytes go up behind its PCM
+                at, kb = frames * kept["per_block"], n * kept["per_block"]
+                self.host_kept[k].numpy()[:kb] = kept["store"][at:at + kb]
+                with torch.cuda.stream(self.s_in):
+                    self.dev_kept[k][:kb].copy_(self.host_kept[k][:kb], non_blocking=True)
+                    self.ev_in[k].record(self.s_in)
             with torch.cuda.stream(self.s_k):
                 view, flags = self._front(k, n, tail)
-                curve = self.path.curve(view, flags, self.max_bps)
+                curve = self.path.curve(view, flags, self.max_bps) if kept is None else self._kept_views(k, n)
                 if segmented:
-                    pick = self.path.pick_segments(curve, seg_cf, first_off, target_dev)
+                    pick = self.path.pick_segments(curve, seg_cf, first_off, target_dev) if kept is None else \
+                        self.path.pick_kept_segments(curve, seg_cf, first_off, target_dev)
                     if limits is not None:
                         if frames == 0:                                # cleared on this stream, behind whatever an encode()
                             sums.zero_()                               # given up half-way still had queued on it
@@ -547,8 +652,10 @@ class HostStreamRateEncoder:
                         nb = pick["n_bytes"].to(torch.int64)
                         ids = (torch.arange(n * self.n_ch, device=enc.device) + first_off) // seg_cf
                         sums.index_add_(0, ids, torch.where(nb > 0, nb + 4, torch.zeros_like(nb)))
-                else:
+                elif kept is None:
                     pick = self.path.pick(curve, float(target_nmr_db))
+                else:
+                    pick = self.path.pick_kept(curve, float(target_nmr_db))
                 out = self.path.second_pass(view, flags, pick)
                 self.s_k.wait_event(self.ev_out[k])                    # the total that last sat in totals[k] has left
                 enc._call("pacx_gather_body", ctypes.c_int64(n * self.n_ch), _ptr(out["payload"]), _ptr(out["n_bytes"]),

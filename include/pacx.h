@@ -1045,6 +1045,84 @@ int pacx_rate_pick_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t s
                             const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
                             const int32_t *target_t, int32_t *budget, int32_t *n_bytes, uint8_t *capped, void *stream);
 
+/* ---- a curve kept as thresholds: what a pick on the grid reads of it, in 16 bits an entry ---- */
+
+/*
+ * A chunked encode takes every chunk's curve twice, once for the profile and once for the pick, because a curve in
+ * doubles is too large to keep.  The pick does not need the doubles.  Every target it is asked for is a point of the
+ * 1/64 dB grid inside a known range, and there the decision on an entry x is the threshold the profiles above already
+ * use.  With [t_lo, t_hi] = 64 [nmr_lo_db, nmr_hi_db] and G = t_hi - t_lo + 1 <= PACX_PROFILE_MAX:
+ *
+ *   threshold(x) = 0                     where 64 x <= t_lo
+ *                  ceil(64 x) - t_lo     where t_lo < 64 x <= t_hi
+ *                  G ("never")           where x is NaN, +inf or above nmr_hi_db
+ *
+ * decided by comparisons in double before anything is converted to an integer (e_i of pacx_band_profile, e_j of
+ * pacx_rate_profile).  x <= t / 64 holds iff threshold(x) <= t - t_lo for every grid target t of the range.  G <= 8193
+ * fits 16 bits.
+ *
+ * The kept band curve, made by pacx_band_thresholds from a curve as pacx_band_curve_batch or pacx_vq_band_curve_batch
+ * writes it:
+ *   e              uint16 [n_cf][band_stride][PACX_BAND_CAND]
+ *   kept_cap       int32 [n_cf][8], cap copied
+ *   kept_cap_alloc uint8 [n_cf][band_stride]: cap_alloc (0 ... 16; a value outside 0 ... 255 saturates, no curve call
+ *                  writes one)
+ * EVERY entry is written: e = G for candidates i >= n_cand, for slots no band of the frame uses and for every slot of a
+ * dropped hop, kept_cap_alloc = 0 in those slots.  Whether a unit exists is read from cap as pacx_band_pick reads it,
+ * the band layout from the handle's tables.  The kept arrays are therefore a function of the curve's defined entries
+ * alone, 33 band_stride + 32 bytes per channel-frame where the curve has 132 band_stride + 32.
+ *
+ * The kept rate curve, made by pacx_rate_thresholds from a curve as pacx_rate_curve_batch writes it:
+ *   e              uint16 [n_cf][row]
+ *   kept_bits      int32 [n_cf][row], not narrowed: the solves accept any int32
+ *   kept_steps     int32 [n_cf][8], steps with a J that would leave its row cut to the row, as the pick cuts it
+ * Entries no unit uses (outside [sb sub_stride, sb sub_stride + J] of every unit of the frame) hold e = G and
+ * kept_bits = 0.  6 row + 32 bytes per channel-frame where the curve has 12 row + 32.
+ *
+ * The picks, for a grid target t of the range, g = t - t_lo:
+ *   pacx_band_pick_thresholds  per band the smallest i, in ascending order, with e_i <= g; the miss rule, the cap rule
+ *                              with cap_alloc, bits(unit), bytes(cf) and capped are pacx_band_pick's, word for word
+ *   pacx_rate_pick_thresholds  pacx_rate_pick's bisection with ok(j) := e_j <= g: the cap test on entry J first, the
+ *                              same halvings, a short-coded frame's eight units summed before the bytes are taken
+ *   ..._segments               the same with the target target_t[s] for the frames of local segment
+ *                              s = (first_off + cf) / seg_cf, as pacx_band_pick_segments / pacx_rate_pick_segments
+ *                              take their segments; target_t: int32 [n_seg] in device memory, grid units (64 per dB)
+ * One kernel serves a pair: the target by value is the one-segment case.  Outputs have the layouts of the picks on the
+ * curve: bit_alloc int32 [n_cf][band_stride] or budget int32 [n_cf][8], then n_bytes int32 [n_cf], capped uint8 [n_cf].
+ *
+ * The contract: for every grid target of the range, every output equals that of pacx_band_pick / pacx_rate_pick (and
+ * their _segments forms) on the curve the thresholds were made from, with the same range given to both calls here.
+ * A target in target_t that lies outside the range is clamped into it; that is outside the contract.
+ *
+ * Handle and argument rules are those of pacx_band_profile / pacx_rate_profile and of the picks: a scalar handle with
+ * the curve's band layout (a gain-shape stream uses its scalar sibling, as for pacx_band_pick); n_cf = 0 is a valid
+ * call that does nothing; no state is kept in the handle and nothing waits for the device.  nmr and the band form's e
+ * are 16-byte aligned (any slice of whole channel-frames of an aligned array is).  PACX_E_UNSUPPORTED on a handle
+ * created with use_vq or use_sbr.  PACX_E_ARG for a null pointer, a bad count, a bad row, seg_cf or first_off, a
+ * misaligned nmr or e, bounds that are not finite, inverted, off the grid or more than PACX_PROFILE_MAX targets apart,
+ * and a target given by value that is off the grid or outside the range.
+ */
+int pacx_band_thresholds(pacx_handle *h, int64_t n_cf, const double *nmr, const int32_t *cap, const int32_t *cap_alloc,
+                         double nmr_lo_db, double nmr_hi_db, uint16_t *e, int32_t *kept_cap, uint8_t *kept_cap_alloc,
+                         void *stream);
+int pacx_band_pick_thresholds(pacx_handle *h, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                              const uint8_t *cap_alloc, double nmr_lo_db, double nmr_hi_db, double target_nmr_db,
+                              int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped, void *stream);
+int pacx_band_pick_thresholds_segments(pacx_handle *h, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                                       const uint8_t *cap_alloc, int64_t seg_cf, int64_t first_off, double nmr_lo_db,
+                                       double nmr_hi_db, const int32_t *target_t, int32_t *bit_alloc, int32_t *n_bytes,
+                                       uint8_t *capped, void *stream);
+int pacx_rate_thresholds(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const double *worst,
+                         const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db, uint16_t *e,
+                         int32_t *kept_bits, int32_t *kept_steps, void *stream);
+int pacx_rate_pick_thresholds(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const uint16_t *e,
+                              const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db,
+                              double target_nmr_db, int32_t *budget, int32_t *n_bytes, uint8_t *capped, void *stream);
+int pacx_rate_pick_thresholds_segments(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const uint16_t *e,
+                                       const int32_t *bits, const int32_t *steps, int64_t seg_cf, int64_t first_off,
+                                       double nmr_lo_db, double nmr_hi_db, const int32_t *target_t, int32_t *budget,
+                                       int32_t *n_bytes, uint8_t *capped, void *stream);
+
 /* ---- one target per stretch of a stream: the two solves, segment by segment ---- */
 
 /*
