@@ -13,7 +13,8 @@
  *                     what its bands ask for.
  *   k_band_pick       works on the arrays alone: one wave per channel-frame, a lane per (unit, band) pair scans the
  *                     band's sizes in ascending order for the first at or below the target; the unit sums go through
- *                     LDS, the frame's bits through the wave (band_frame).
+ *                     LDS, the frame's bits through the wave: band_frame (pick_dev.h) on the stored doubles
+ *                     (BandCurveNmr), the frame work k_kept.hip runs on kept grid indices.
  *   k_band_pick_useg  pacx_band_pick_segments: k_band_pick with the target of the frame's segment, the segments uniform
  *                     stretches given by value ((first_off + cf) / seg_cf) and one grid target each in an array.
  *   k_band_pick_seg   pacx_band_solve / pacx_band_solve_segments: the same frame work with one SolveState per stretch of
@@ -35,6 +36,7 @@
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "quant_dev.h"
 #include "rate_dev.h"
+#include "pick_dev.h"   /* band_frame, BandCurveNmr; frame_target (grid_dev.h) */
 
 using namespace pacx_k;
 
@@ -42,8 +44,6 @@ namespace {
 
 constexpr int BAND_CAND = PACX_BAND_CAND;
 constexpr int PICK_THREADS = 256;                  /* four channel-frames per workgroup, one per wave */
-
-__device__ __forceinline__ int cand_bits(int i) { return i ? i + 1 : 0; }
 
 /* NMR_b of every band from the n[k] in S.v: lane b keeps band b's value (k_nmr's order of additions) */
 template <int M>
@@ -165,86 +165,6 @@ __global__ __launch_bounds__(64) void k_band_curve(PacxTables T, const uint8_t *
 
 constexpr int PICK_WAVES = PICK_THREADS / 64;
 
-/* pick(unit, T) of include/pacx.h for every unit of one channel-frame, by one wave, the only one: a lane per (unit,
-   band) pair scans the band's sizes in ascending order, the unit sums go through the wave's LDS row (unit_sum,
-   unit_miss: zeroed here), the cap rule, the frame's bits through the wave.  write: the outputs are written.
-   -> what the frame adds to the body: its bytes and their length prefix (every lane holds it) */
-__device__ __forceinline__ unsigned long long band_frame(const PacxTables &T, long long cf, double target,
-                                                         const double *__restrict__ nmr,
-                                                         const int32_t *__restrict__ cap,
-                                                         const int32_t *__restrict__ cap_alloc, bool write,
-                                                         int32_t *__restrict__ bit_alloc, int32_t *__restrict__ n_bytes,
-                                                         uint8_t *__restrict__ capped, int *unit_sum, int *unit_miss)
-{
-    constexpr int SLOTS = PACX_SUB * PACX_MAX_BANDS / 64;          /* band slots of a row per lane, at most */
-    const int lane = threadIdx.x & 63;
-    if (lane < PACX_SUB) {
-        unit_sum[lane] = 0;
-        unit_miss[lane] = 0;
-    }
-    wave_lds_fence();
-    const int32_t *__restrict__ cp = cap + cf * PACX_SUB;
-    const bool is_short = cp[1] >= 0;              /* a long frame's slots 1-7 and a dropped hop's eight hold -1 */
-    const int nb = is_short ? T.nb_short : T.nb_long;
-    const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
-    int n_cand = 1 << T.n_mant_size_bits;
-    if (n_cand > BAND_CAND)
-        n_cand = BAND_CAND;
-    const long long row = cf * T.band_stride;
-    int a[SLOTS], nl[SLOTS], sbs[SLOTS];
-#pragma unroll
-    for (int q = 0; q < SLOTS; ++q) {
-        const int slot = lane + 64 * q;
-        const int sb = is_short ? slot / nb : (slot < nb ? 0 : PACX_SUB);
-        const int b = is_short ? slot - sb * nb : slot;
-        a[q] = 0;
-        nl[q] = 0;
-        sbs[q] = -1;
-        if (slot < T.band_stride && sb < PACX_SUB && cp[sb] >= 0) {
-            const double *__restrict__ r = nmr + (row + slot) * BAND_CAND;
-            int pick = -1;
-            for (int i = n_cand - 1; i >= 0; --i)              /* the ascending scan's first pass = the lowest passing i */
-                if (r[i] <= target)
-                    pick = i;
-            sbs[q] = sb;
-            nl[q] = count[b];
-            a[q] = cand_bits(pick < 0 ? n_cand - 1 : pick);
-            atomicAdd(&unit_sum[sb], a[q] * nl[q]);
-            if (pick < 0)
-                atomicOr(&unit_miss[sb], 1);
-        }
-    }
-    wave_lds_fence();
-    int sum = 0;
-    bool any_cap = false;
-#pragma unroll
-    for (int q = 0; q < SLOTS; ++q) {
-        const int slot = lane + 64 * q;
-        if (sbs[q] >= 0) {
-            const bool over = unit_sum[sbs[q]] > cp[sbs[q]];
-            if (over)
-                a[q] = cap_alloc[row + slot];
-            any_cap = any_cap || over || unit_miss[sbs[q]] != 0;
-            sum += T.n_mant_size_bits + T.n_scale_bits + a[q] * nl[q];
-        }
-        if (write && slot < T.band_stride)
-            bit_alloc[row + slot] = a[q];
-    }
-    int units = 0;
-    for (int sb = 0; sb < PACX_SUB; ++sb)
-        units += cp[sb] >= 0 ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        sum += __shfl_xor(sum, off, 64);
-    const bool cap_cf = __builtin_amdgcn_ballot_w64(any_cap) != 0ull;
-    const int nby = units ? (sum + units * T.n_scale_bits + 4 + 7) >> 3 : 0;
-    if (write && lane == 0) {
-        n_bytes[cf] = nby;
-        capped[cf] = cap_cf ? 1 : 0;
-    }
-    return nby > 0 ? (unsigned long long)nby + 4ull : 0ull;
-}
-
 /* band_frame for one channel-frame per wave at `target` (pacx_band_pick): the outputs are written */
 __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, long long n_cf, double target,
                                                            const double *__restrict__ nmr,
@@ -257,7 +177,8 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick(PacxTables T, long l
     const int w = threadIdx.x >> 6;
     const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
     if (cf < n_cf)                                 /* wave-uniform */
-        band_frame(T, cf, target, nmr, cap, cap_alloc, true, bit_alloc, n_bytes, capped, unit_sum[w], unit_miss[w]);
+        band_frame(T, cf, BandCurveNmr{nmr, cap_alloc, target}, cap, true, bit_alloc, n_bytes, capped, unit_sum[w],
+                   unit_miss[w]);
 }
 
 /* k_band_pick with one target per uniform segment (pacx_band_pick_segments): the wave's frame lies in segment
@@ -275,9 +196,11 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_useg(PacxTables T, l
     __shared__ int unit_sum[PICK_WAVES][PACX_SUB], unit_miss[PICK_WAVES][PACX_SUB];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long cf = (long long)blockIdx.x * PICK_WAVES + w;
-    if (cf < n_cf)                                 /* wave-uniform */
-        band_frame(T, cf, (double)target_t[(first_off + cf) / seg_cf] / 64.0, nmr, cap, cap_alloc, true, bit_alloc,
-                   n_bytes, capped, unit_sum[w], unit_miss[w]);
+    if (cf < n_cf) {                               /* wave-uniform */
+        const double target = (double)frame_target(target_t, 0, cf, seg_cf, first_off) / 64.0;
+        band_frame(T, cf, BandCurveNmr{nmr, cap_alloc, target}, cap, true, bit_alloc, n_bytes, capped, unit_sum[w],
+                   unit_miss[w]);
+    }
 }
 
 /* k_band_pick as a pick of the solve, with a state per segment: the wave takes the target its frame's segment has in
@@ -315,8 +238,8 @@ __global__ __launch_bounds__(PICK_THREADS) void k_band_pick_seg(PacxTables T, So
             int mid = flying->mid;
             if (PEAK && mystate->mid > mid)
                 mid = mystate->mid;                /* the segment's floor */
-            mine = band_frame(T, cf, (double)mid / 64.0, nmr, cap, cap_alloc, final != 0, bit_alloc, n_bytes, capped,
-                              unit_sum[w], unit_miss[w]);
+            mine = band_frame(T, cf, BandCurveNmr{nmr, cap_alloc, (double)mid / 64.0}, cap, final != 0, bit_alloc,
+                              n_bytes, capped, unit_sum[w], unit_miss[w]);
         }
     }
     if (lane == 0) {

@@ -20,8 +20,9 @@
  *                      the boundaries (segment_of, rate_dev.h), picks the budget of each of its units from the curve
  *                      at the target its segment has in flight and sums the frame's bytes; one 64-bit atomicAdd per
  *                      workgroup and segment present.
- *   k_rate_pick        pacx_rate_pick / pacx_rate_pick_segments: the same pick of every frame (solve_frame, the only one)
- *                      at a target given with the call, one per uniform segment; writes the outputs, sums nothing.
+ *   k_rate_pick        pacx_rate_pick / pacx_rate_pick_segments: the same pick of every frame at a target given with
+ *                      the call, one per uniform segment; writes the outputs, sums nothing.  Both run solve_frame
+ *                      (pick_dev.h) with ok := the stored double <= the target; k_kept.hip runs it on kept grid indices.
  *   k_solve_init, k_solve_step
  *                      one thread per segment: a SolveState each, and the bisection's decision on the segment's total.
  *                      The host enqueues a fixed number of pick / step pairs and waits for none; pairs after a
@@ -44,6 +45,7 @@
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "quant_dev.h"
 #include "rate_dev.h"   /* RateLds, RateUnit, rate_unit, wave_sum, SolveState */
+#include "pick_dev.h"   /* solve_frame; frame_target, floor_half (grid_dev.h) */
 
 using namespace pacx_k;
 
@@ -270,12 +272,6 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
 /* ---- the solve of pacx_rate_solve_segments (include/pacx.h): one target per stretch of consecutive channel-frames,
    on the stored curves, a SolveState each; pacx_rate_solve's whole stream is one such stretch ---- */
 constexpr int SOLVE_THREADS = 256;
-constexpr int SOLVE_MAX_LOOKUP = 12;               /* 1 + ceil(log2(J + 1)) for J < 2048, as RATE_MAX_EVAL */
-
-__device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either sign */
-{
-    return (a - (a < 0 ? 1 : 0)) / 2;
-}
 
 /* the decision of include/pacx.h on the total the pick before it left, the only one: k_solve_step takes it for every
    segment.  final: write the result */
@@ -327,55 +323,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_init(SolveState *s, int
     }
 }
 
-/* pick(unit, T) of every unit of one channel-frame, the only one: the look-ups in the curve, the frame's bytes and,
-   in the launch that writes, its outputs.  -> what the frame adds to the body: its bytes and their length prefix */
-__device__ __forceinline__ unsigned long long solve_frame(long long cf, double target, int row, int sub_stride,
-                                                          const double *__restrict__ worst,
-                                                          const int32_t *__restrict__ bits,
-                                                          const int32_t *__restrict__ steps, int final,
-                                                          int32_t *__restrict__ budget, int32_t *__restrict__ n_bytes,
-                                                          uint8_t *__restrict__ capped)
-{
-    int sum = 0, units = 0;
-    bool cap = false;
-    for (int sb = 0; sb < PACX_SUB; ++sb) {
-        int J = steps[cf * PACX_SUB + sb];
-        int b = 0;
-        if (J >= 0) {
-            const int base = sb * sub_stride;
-            if (base + J >= row)                   /* never read past the row */
-                J = row - 1 - base;
-        }
-        if (J >= 0) {
-            const long long at = cf * (long long)row + sb * sub_stride;
-            int hi = J;
-            if (!(worst[at + J] <= target)) {
-                cap = true;
-            } else {
-                int lo = -1;
-                for (int it = 0; it < SOLVE_MAX_LOOKUP && hi - lo > 1; ++it) {
-                    const int mid = (lo + hi) / 2;
-                    if (worst[at + mid] <= target)
-                        hi = mid;
-                    else
-                        lo = mid;
-                }
-            }
-            sum += bits[at + hi];
-            b = 32 * hi;
-            ++units;
-        }
-        if (final)
-            budget[cf * PACX_SUB + sb] = b;
-    }
-    const int nby = units ? (sum + 4 + 7) >> 3 : 0;
-    if (final) {
-        n_bytes[cf] = nby;
-        capped[cf] = cap ? 1 : 0;
-    }
-    return nby > 0 ? (unsigned long long)nby + 4ull : 0ull;
-}
-
 /* the sum of a workgroup's frames: through the waves, then LDS; thread 0 holds it */
 __device__ __forceinline__ unsigned long long solve_block_sum(unsigned long long mine, unsigned long long *part)
 {
@@ -392,8 +339,9 @@ __device__ __forceinline__ unsigned long long solve_block_sum(unsigned long long
     return all;
 }
 
-/* one channel-frame per thread (solve_frame) with a state per segment: every frame takes the target of its segment's
-   state and adds to that segment's total.  A frame whose segment is done does no look-ups before the last launch.
+/* one channel-frame per thread (solve_frame, pick_dev.h) with a state per segment: every frame takes the target of
+   its segment's state and adds to that segment's total.  A frame whose segment is done does no look-ups before the
+   last launch.
    final: the last launch, at the targets found, which also writes the outputs.  A workgroup whose frames lie in one
    segment (every workgroup of a whole-stream solve) sums them through the waves and adds once; one that straddles
    boundaries sums the runs of equal segments in LDS (the frames of a segment are consecutive) and adds once per
@@ -426,8 +374,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_pick(SolveState *__rest
             int mid = flying->mid;
             if (PEAK && mystate->mid > mid)
                 mid = mystate->mid;                /* the segment's floor */
-            mine = solve_frame(cf, (double)mid / 64.0, row, sub_stride, worst, bits, steps, final, budget, n_bytes,
-                               capped);
+            const double target = (double)mid / 64.0;
+            mine = solve_frame(cf, row, sub_stride, [&](long long i) { return worst[i] <= target; }, bits, steps, final,
+                               budget, n_bytes, capped);
         }
     }
     seg_of[t] = seg;
@@ -472,8 +421,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_rate_pick(long long n_cf, lon
     const long long cf = (long long)blockIdx.x * SOLVE_THREADS + threadIdx.x;
     if (cf >= n_cf)
         return;
-    const int t = target_t ? target_t[(first_off + cf) / seg_cf] : t_all;
-    solve_frame(cf, (double)t / 64.0, row, sub_stride, worst, bits, steps, 1, budget, n_bytes, capped);
+    const double target = (double)frame_target(target_t, t_all, cf, seg_cf, first_off) / 64.0;
+    solve_frame(cf, row, sub_stride, [&](long long i) { return worst[i] <= target; }, bits, steps, 1, budget, n_bytes,
+                capped);
 }
 
 /* one thread per segment: solve_step with the segment's limit; final: result[seg] */

@@ -6,16 +6,10 @@
  * stream profile of G words.  Segments are uniform stretches given by value: frame cf of the piece lies in local
  * segment (first_off + cf) / seg_cf.
  *
- *   k_band_profile_seg   k_band_profile's work per frame under the same rules (its body is repeated here,
- *                        k_profile.hip is left as it is): a workgroup of 16 waves keeps the frame's bits
- *                        and its running bytes at the entries a thread owns in registers.  It walks a CONTIGUOUS run of
- *                        frames -- workgroup b takes [b run, (b + 1) run) -- and adds its bytes to the row of the
- *                        segment it is in whenever that segment changes and at its end, one 64-bit atomicAdd per
- *                        entry.  With every 512th frame per workgroup, as k_band_profile strides, a segment shorter
- *                        than 512 frames would change at every frame and every frame would cost G atomics; with runs
- *                        a workgroup flushes once per segment its run touches.  Integer sums; trip counts are
- *                        arguments' and tables'.
- *   k_profile_solve_seg  one wave per row: k_profile_solve's decision against the row's limit (every lane takes the
+ *   k_band_profile_seg   band_profile_frame (grid_dev.h), k_band_profile's work per frame, on a CONTIGUOUS run of
+ *                        frames (RunWalk, grid_dev.h): the workgroup adds its bytes to the row of the segment it is in
+ *                        whenever that segment changes and at its end (flush_row), one 64-bit atomicAdd per entry.
+ *   k_profile_solve_seg  one wave per row: profile_decide (grid_dev.h) against the row's limit (every lane takes the
  *                        same wave-uniform path), then worst_above = max of the row from the target found on, the
  *                        lanes striding over it.  A negative limit is never met.
  *   k_profile_clamp_add  stream_profile[g] += sum over s of row_s[max(g, result[s].t - t_lo)]: a thread per entry and
@@ -23,56 +17,15 @@
  */
 #include <hip/hip_runtime.h>
 
-#include <math.h>
-
-#include "pacx_launch.h"
+#include "grid_dev.h"
 
 using namespace pacx_k;
 
 namespace {
 
-constexpr int BAND_CAND = PACX_BAND_CAND;
-constexpr int PROF_THREADS = 1024, PROF_WAVES = PROF_THREADS / 64;
-constexpr int PROF_TILES = (PACX_PROFILE_MAX + PROF_THREADS - 1) / PROF_THREADS;      /* entries a thread owns, at most */
-constexpr int PROF_GROUPS = 512;                   /* workgroups at most: two per CU */
 constexpr int CLAMP_THREADS = 256, CLAMP_SEGS = 32, CLAMP_GRID_Y = 4096;
 
-static_assert(PACX_SUB * PACX_MAX_BANDS <= PROF_THREADS, "a thread per band slot");
-static_assert(PACX_PROFILE_MAX < 65536, "grid indices are kept in 16 bits");
-
-__device__ __forceinline__ int cand_bits(int i) { return i ? i + 1 : 0; }
-
-/* inclusive sum over the wave's lanes 0 ... lane */
-__device__ __forceinline__ int wave_scan(int v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(v, off, 64);
-        if (lane >= off)
-            v += o;
-    }
-    return v;
-}
-
-/* the workgroup's bytes into one row, and cleared: entry g of thread (w, lane) is base + 64 t.  The flush sits in the
-   loop over the run's segments; `base` goes through an empty asm so that the entries' addresses and bounds are worked
-   out here and not hoisted out of the loops, where they would stay in 18 vector registers across every frame and
-   spill */
-__device__ __forceinline__ void flush_row(long long (&bytes)[PROF_TILES], int base, int n_tiles, int G,
-                                          unsigned long long *__restrict__ row)
-{
-    asm volatile("" : "+v"(base));
-#pragma unroll
-    for (int t = 0; t < PROF_TILES; ++t) {
-        const int g = base + 64 * t;
-        if (t < n_tiles && g < G && bytes[t])
-            atomicAdd(&row[g], (unsigned long long)bytes[t]);
-        bytes[t] = 0;
-    }
-}
-
-/* diff: n_tiles * PROF_THREADS int32 (dynamic LDS), as k_band_profile's.  Workgroup b walks the frames
-   [b run, min((b + 1) run, n_cf)); profile: [n_seg][G], row (first_off + cf) / seg_cf for frame cf */
+/* diff: n_tiles * PROF_THREADS int32 (dynamic LDS), see band_profile_frame; profile: [n_seg][G] */
 __global__ __launch_bounds__(PROF_THREADS) void k_band_profile_seg(PacxTables T, long long n_cf, int run,
                                                                   long long seg_cf, long long first_off, int t_lo,
                                                                   int t_hi, int n_tiles, const double *__restrict__ nmr,
@@ -82,30 +35,9 @@ __global__ __launch_bounds__(PROF_THREADS) void k_band_profile_seg(PacxTables T,
 {
     extern __shared__ int diff[];
     __shared__ int wave_tot[PROF_WAVES];
-    __shared__ int unit_ca[PACX_SUB];              /* sum_b cap_alloc_b lines_b of the frame's units */
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int G = t_hi - t_lo + 1;
-    const int base = w * (n_tiles * 64) + lane;
-    int n_cand = 1 << T.n_mant_size_bits;
-    if (n_cand > BAND_CAND)
-        n_cand = BAND_CAND;
-    const int miss = cand_bits(n_cand - 1);
-    /* what a unit takes below every step: every band missed */
-    int miss_long = 0, miss_short = 0;
-    for (int b = 0; b < T.nb_long; ++b)
-        miss_long += miss * T.band_lines_long[b];
-    for (int b = 0; b < T.nb_short; ++b)
-        miss_short += miss * T.band_lines_short[b];
-
-    /* the run, and the segment its first frame lies in: the one division, before anything is held in registers.  What
-       the loop carries is 32 bits wide (n_cf < 2^28): the frame, the run's end, the frames left in the segment */
-    const int cf0 = blockIdx.x * run;
-    const int cf1 = cf0 + run < (int)n_cf ? cf0 + run : (int)n_cf;
-    const long long seg0 = (first_off + cf0) / seg_cf;
-    const long long left0 = (seg0 + 1) * seg_cf - first_off - cf0;     /* >= 1: frames of segment seg0 from cf0 on */
-    const int seg_len = seg_cf < run ? (int)seg_cf : run;              /* beyond the run's length no boundary matters */
-    int left = left0 < run ? (int)left0 : run;
-    unsigned long long *__restrict__ out = profile + seg0 * G;         /* the row the bytes in registers belong to */
+    __shared__ int unit_ca[PACX_SUB];
+    const BandProfileWg P = band_profile_wg(T, t_lo, t_hi, n_tiles);
+    RunWalk W = run_walk(n_cf, run, seg_cf, first_off, P.G, profile);
 
     long long bytes[PROF_TILES];
     int fbits[PROF_TILES];
@@ -114,130 +46,21 @@ __global__ __launch_bounds__(PROF_THREADS) void k_band_profile_seg(PacxTables T,
         bytes[t] = 0;
         fbits[t] = 0;
         if (t < n_tiles)
-            diff[base + 64 * t] = 0;
+            diff[P.base + 64 * t] = 0;
     }
 
-    /* segment by segment of the run: the frames of one, then its bytes into its row */
 #pragma unroll 1
-    for (int cf = cf0; cf < cf1; left = seg_len, out += G) {
-        const int end = cf + left < cf1 ? cf + left : cf1;
+    for (int cf = W.cf0; cf < W.cf1; W.left = W.seg_len, W.out += P.G) {
+        const int end = cf + W.left < W.cf1 ? cf + W.left : W.cf1;
 #pragma unroll 1
-        for (; cf < end; ++cf) {
-            const int32_t *__restrict__ cp = cap + (long long)cf * PACX_SUB;
-            int units = 0;
-            for (int sb = 0; sb < PACX_SUB; ++sb)
-                units += cp[sb] >= 0 ? 1 : 0;
-            if (!units)                            /* a dropped hop: no bytes.  Workgroup-uniform, as all of cp is */
-                continue;
-            const bool is_short = cp[1] >= 0;          /* a long frame's slots 1-7 hold -1 */
-            const int nb = is_short ? T.nb_short : T.nb_long;
-            const int32_t *__restrict__ count = is_short ? T.band_lines_short : T.band_lines_long;
-            const long long row = (long long)cf * T.band_stride;
-            if (tid < PACX_SUB)
-                unit_ca[tid] = 0;
-            __syncthreads();                           /* also: the frame before is through with diff and wave_tot */
-
-            /* ---- a thread per band slot: the grid index from which each size passes */
-            int my_unit = -1, nl = 0;
-            unsigned e2[BAND_CAND / 2];                /* e_i of sizes 2 j, 2 j + 1 in the halves of a word: G < 2^16 */
-#pragma unroll
-            for (int j = 0; j < BAND_CAND / 2; ++j)
-                e2[j] = (unsigned)G * 0x10001u;        /* never */
-            if (tid < T.band_stride) {
-                const int sb = is_short ? tid / nb : (tid < nb ? 0 : PACX_SUB);
-                if (sb < PACX_SUB && cp[sb] >= 0) {
-                    my_unit = sb;
-                    nl = count[is_short ? tid - sb * nb : tid];
-                    atomicAdd(&unit_ca[sb], cap_alloc[row + tid] * nl);
-                    const double *__restrict__ r = nmr + (row + tid) * BAND_CAND;
-#pragma unroll
-                    for (int i = 0; i < BAND_CAND; ++i) {
-                        /* r <= t / 64 is 64 r <= t, both scalings exact; decided in double: NaN and +inf fail the first
-                           comparison, -inf and anything below the range pass the second, and only what lies in
-                           (t_lo, t_hi] reaches the cast */
-                        const double x = r[i] * (double)PACX_RATE_TARGET_GRID;
-                        if (i < n_cand && x <= (double)t_hi) {
-                            const unsigned e = x <= (double)t_lo ? 0u : (unsigned)((int)ceil(x) - t_lo);
-                            e2[i / 2] = i & 1 ? (e2[i / 2] & 0xffffu) | (e << 16) : (e2[i / 2] & 0xffff0000u) | e;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-
-            int live = 0;
-#pragma unroll 1
-            for (int u = 0; u < PACX_SUB; ++u) {
-                const int cap_u = cp[u];
-                if (cap_u < 0)                         /* workgroup-uniform */
-                    continue;
-                ++live;
-                /* ---- the unit's steps: size i holds on [e_i, the lowest e before it), relative to every band
-                   missed */
-                if (my_unit == u) {
-                    int hi = G;
-#pragma unroll
-                    for (int i = 0; i < BAND_CAND; ++i) {
-                        const int e = (int)(i & 1 ? e2[i / 2] >> 16 : e2[i / 2] & 0xffffu);
-                        if (e < hi) {
-                            const int d = (cand_bits(i) - miss) * nl;
-                            if (d) {
-                                atomicAdd(&diff[e], d);
-                                if (hi < G)
-                                    atomicAdd(&diff[hi], -d);
-                            }
-                            hi = e;
-                        }
-                    }
-                }
-                __syncthreads();
-                const int ca_u = unit_ca[u];
-                /* ---- scan, in place: the wave's own entries, 64 at a time, the running sum carried */
-                int run_sum = 0;
-#pragma unroll 1
-                for (int t = 0; t < n_tiles; ++t) {
-                    const int v = wave_scan(diff[base + 64 * t], lane);
-                    diff[base + 64 * t] = run_sum + v;
-                    run_sum += __shfl(v, 63, 64);
-                }
-                if (lane == 0)
-                    wave_tot[w] = run_sum;
-                __syncthreads();
-                int carry = is_short ? miss_short : miss_long;
-#pragma unroll
-                for (int i = 0; i < PROF_WAVES; ++i)
-                    carry += i < w ? wave_tot[i] : 0;
-                /* ---- the cap rule at every g: a unit whose sum exceeds its cap takes cap_alloc; diff is left zeroed
-                   for the next unit, whose deltas any wave may write: they wait for the barrier */
-#pragma unroll
-                for (int t = 0; t < PROF_TILES; ++t) {
-                    if (t < n_tiles) {
-                        const int sum = diff[base + 64 * t] + carry;
-                        diff[base + 64 * t] = 0;
-                        fbits[t] += sum > cap_u ? ca_u : sum;
-                    }
-                }
-                __syncthreads();
-            }
-            /* ---- the frame's bytes and their length prefix (k_band_pick's size rule) */
-            const int head = live * (T.n_scale_bits + nb * (T.n_mant_size_bits + T.n_scale_bits)) + 4 + 7;
-#pragma unroll
-            for (int t = 0; t < PROF_TILES; ++t) {
-                bytes[t] += (long long)(((fbits[t] + head) >> 3) + 4);
-                fbits[t] = 0;
-            }
-        }
-        flush_row(bytes, base, n_tiles, G, out);
+        for (; cf < end; ++cf)
+            band_profile_frame(T, P, cf, t_lo, t_hi, n_tiles, nmr, cap, cap_alloc, diff, wave_tot, unit_ca, bytes, fbits);
+        flush_row(bytes, P.base, n_tiles, P.G, W.out);
     }
 }
 
-__device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either sign */
-{
-    return (a - (a < 0 ? 1 : 0)) / 2;
-}
-
-/* one wave per row.  The decision of k_profile_solve with total(t) = row[t - t_lo] against limit[s], taken by every
-   lane alike (the loads are wave-uniform); `halvings` bounds the bisection whatever the data.  Then the largest entry
+/* one wave per row.  profile_decide on the row against limit[s], taken by every lane alike (the loads are
+   wave-uniform).  Then the largest entry
    of the row from the target found on: `strides` = ceil(G / 64) trips, the lanes 64 apart. */
 __global__ __launch_bounds__(64) void k_profile_solve_seg(const unsigned long long *__restrict__ profile,
                                                          const long long *__restrict__ limits, int t_lo, int t_hi,
@@ -249,20 +72,8 @@ __global__ __launch_bounds__(64) void k_profile_solve_seg(const unsigned long lo
     const unsigned long long *__restrict__ row = profile + s * G;
     const long long limit = limits[s];
     int t = t_hi, met = 0;
-    if (limit >= 0 && row[t_hi - t_lo] <= (unsigned long long)limit) {
-        int lo = t_lo - 1, hi = t_hi;
-        met = 1;
-        for (int it = 0; it < halvings; ++it) {
-            if (hi - lo > 1) {
-                const int mid = floor_half(lo + hi);
-                if (row[mid - t_lo] <= (unsigned long long)limit)
-                    hi = mid;
-                else
-                    lo = mid;
-            }
-        }
-        t = hi;
-    }
+    if (limit >= 0)                                /* a negative limit is never met */
+        t = profile_decide(row, limit, t_lo, t_hi, halvings, met);
     if (lane == 0) {
         result[s].t = t;
         result[s].met = met;

@@ -47,6 +47,9 @@ HOT = [
     (r"^k_imdct_long\(", None, None),
     (r"^k_imdct_short\(", None, None),
     (r"^k_transient\(", None, None),
+    (r"::k_band_profile\(", 128, 4),                     # 1024 threads: 128 registers are all a workgroup may have
+    (r"::k_band_profile_seg\(", 128, 4),
+    (r"::k_rate_profile<true>\(", None, 8),
 ]
 
 
