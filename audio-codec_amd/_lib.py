@@ -155,63 +155,39 @@ SIGNATURES = {
     "pacx_rate_curve_layout": (ctypes.c_int, [_P, ctypes.c_double, c_int32_p, c_int32_p]),
     "pacx_rate_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, ctypes.c_int32, _P, _P, _P,
                                              _P]),
-    "pacx_rate_solve": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64,
-                                       ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
     "pacx_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),
-    "pacx_band_pick": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, _P, _P, _P, _P]),
-    "pacx_band_solve": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                                       _P, _P, _P, _P, _P]),
-    "pacx_band_profile": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
     "pacx_profile_solve": (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P, _P]),
-    # seg_cf, first_off by value; limit_bytes, target_t, result, worst_above: device memory
-    "pacx_band_profile_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64,
-                                                  ctypes.c_double, ctypes.c_double, _P, _P]),
+    # limit_bytes, result, worst_above: device memory
     "pacx_profile_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P,
                                                    _P]),
     "pacx_profile_clamp_add": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P]),
-    "pacx_band_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P,
-                                               _P, _P]),
-    # the same on a rate curve (row, sub_stride by value behind n_cf)
-    "pacx_rate_profile": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
-                                         ctypes.c_double, _P, _P]),
-    "pacx_rate_profile_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _P,
-                                                  _P]),
-    "pacx_rate_pick": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
-                                      _P, _P, _P, _P]),
-    "pacx_rate_pick_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                               ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P]),
-    # a curve kept as 16-bit thresholds and the picks on it (range by value; a single target by value, target_t on the device)
-    "pacx_band_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P,
-                                            _P]),
-    "pacx_band_pick_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_double, ctypes.c_double,
-                                                 ctypes.c_double, _P, _P, _P, _P]),
-    "pacx_band_pick_thresholds_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, ctypes.c_int64,
-                                                          ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
-    "pacx_rate_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                            ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
-    "pacx_rate_pick_thresholds": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
-    "pacx_rate_pick_thresholds_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
-                                                          ctypes.c_double, _P, _P, _P, _P, _P]),
     "pacx_encode_pack_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                     _P]),
     "pacx_vq_band_curve_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, ctypes.c_double, _P, _P, _P, _P]),
     "pacx_encode_vq_alloc_batch": (ctypes.c_int, [_P, ctypes.POINTER(PacxPcm), _P, _P, _P, _P, _P, _P, _P, _P]),
-    # seg_first, limit_bytes: int64 arrays in host memory
-    "pacx_rate_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                                ctypes.c_int64, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P,
-                                                _P]),
-    "pacx_band_solve_segments": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_double,
-                                                ctypes.c_double, _P, _P, _P, _P, _P]),
-    # seg_first, peak_bytes: int64 arrays in host memory; limit_bytes by value; floor, result [n_seg], result_stream
-    "pacx_rate_solve_peak": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P,
-                                            ctypes.c_int64, _P, _P, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                                            _P, _P, _P, _P, _P, _P, _P]),
-    "pacx_band_solve_peak": (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64,
-                                            ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P, _P, _P]),
 }
+# The operations on a curve, pacx_<kind>_<operation>(handle, n_cf, the kind's head, the curve's three arrays, the
+# operation's tail): a rate curve's row and sub_stride go by value behind n_cf, a band curve has no head.  The tails end
+# with the three per-channel-frame outputs of a pick (or a profile, or the three kept arrays) and the stream.
+_I64, _D = ctypes.c_int64, ctypes.c_double
+CURVE_HEADS = {"rate": [ctypes.c_int32, ctypes.c_int32], "band": []}
+CURVE_TAILS = {
+    "solve": [_I64, _D, _D, _P, _P, _P, _P, _P],                               # limit_bytes, the range; result
+    # n_seg, then seg_first and limit_bytes, int64 arrays in host memory
+    "solve_segments": [_I64, _P, _P, _D, _D, _P, _P, _P, _P, _P],
+    # the limits are the peaks; limit_bytes by value; floor, result [n_seg], result_stream
+    "solve_peak": [_I64, _P, _P, _I64, _D, _D, _P, _P, _P, _P, _P, _P, _P],
+    "profile": [_D, _D, _P, _P],
+    "profile_segments": [_I64, _I64, _D, _D, _P, _P],                          # seg_cf, first_off by value
+    "pick": [_D, _P, _P, _P, _P],
+    "pick_segments": [_I64, _I64, _P, _P, _P, _P, _P],                         # target_t on the device
+    # a curve kept as 16-bit thresholds and the picks on it: the range by value before the target(s)
+    "thresholds": [_D, _D, _P, _P, _P, _P],
+    "pick_thresholds": [_D, _D, _D, _P, _P, _P, _P],
+    "pick_thresholds_segments": [_I64, _I64, _D, _D, _P, _P, _P, _P, _P],
+}
+SIGNATURES.update({f"pacx_{kind}_{op}": (ctypes.c_int, [_P, _I64, *head, _P, _P, _P, *tail])
+                   for kind, head in CURVE_HEADS.items() for op, tail in CURVE_TAILS.items()})
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320
 NMR_HIST_LO, NMR_HIST_STEP = -120.0, 0.5

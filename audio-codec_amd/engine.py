@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
+from .curves import BAND, RATE
 from .psychoac import ScaleFactorBands, AssignMDCTLinesFromFreqLimits
 
 N_LONG, N_SHORT = 1024, 128          # MDCT lines of long / short blocks
@@ -356,20 +357,50 @@ class Encoder:
         out["row"], out["sub_stride"], out["flags"] = row, sub, fl
         return out
 
-    def _solve(self, what, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None):
-        """The six solves: `what` names the method, band_* on a band curve and rate_* on a rate curve, *_segments with
-        seg_first and one limit per segment, *_peak with those (the limits are then the peaks) and stream_limit for the
-        whole batch, else the whole stream with its one limit (the plain C entry point).  Checks the curve, makes the
-        outputs, calls pacx_<what> and decodes the pacx_rate_result of every segment: t, met, total (int64) in four
-        int32."""
-        band, peak = what.startswith("band"), what.endswith("_peak")
-        segmented = peak or what.endswith("_segments")
-        if band:
-            *arrays, n_cf, out = self._band_arrays(curve, what)
-            head, per_cf = [], "bit_alloc"
+    # ---- the operations on a curve, each written once for both kinds (curves.RATE, curves.BAND): the public methods
+    # below are their names, signatures and documentation
+    def _checked(self, kind, curve, what, kept=False):
+        """The one checker of a curve's arrays, or of a kept curve's: -> (the arrays, n_cf, width, the head arguments
+        behind n_cf).  A rate curve's width is its own row, a band curve's the handle's band_stride."""
+        arrays = [curve[a.key].contiguous() for a in (kind.kept if kept else kind.curve)]
+        if kind.head:
+            n_cf, width = arrays[0].shape
         else:
-            *arrays, n_cf, head, out = self._rate_arrays(curve, what)
-            per_cf = "budget"
+            n_cf, width = arrays[0].shape[0], self.band_stride
+        if any(t.dtype != a.dtype or tuple(t.shape) != a.shape(n_cf, width)
+               for t, a in zip(arrays, kind.kept if kept else kind.curve)):
+            raise ValueError(f"{what}: {kind.as_kept if kept else kind.as_curve}")
+        head = [int(width)] + [int(curve[k]) for k in kind.head[1:]] if kind.head else []
+        return arrays, n_cf, width, head
+
+    def _curve_call(self, what, checked, *tail):
+        """pacx_<what>(handle, n_cf, head, the three arrays, tail, stream)"""
+        arrays, n_cf, _, head = checked
+        self._call_rate("pacx_" + what, ctypes.c_int64(n_cf), *head, *(_ptr(t) for t in arrays), *tail, self._stream())
+
+    def _picked(self, kind, checked):
+        """what a pick or a solve writes per channel-frame"""
+        _, n_cf, width, _ = checked
+        return {kind.per_cf.key: torch.zeros(kind.per_cf.shape(n_cf, width), dtype=torch.int32, device=self.device),
+                "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
+                "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
+
+    def _pick_call(self, kind, what, checked, *middle):
+        """the frame of every pick: middle, then the three outputs -> dict budget / bit_alloc, n_bytes, capped (bool)"""
+        out = self._picked(kind, checked)
+        self._curve_call(what, checked, *middle, _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]), _ptr(out["capped"]))
+        out["capped"] = out["capped"].bool()
+        return out
+
+    def _solve(self, kind, op, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None):
+        """The six solves: op "solve_segments" with seg_first and one limit per segment, "solve_peak" with those (the
+        limits are then the peaks) and stream_limit for the whole batch, else "solve", the whole stream with its one
+        limit (the plain C entry point).  Checks the curve, makes the outputs, calls pacx_<kind>_<op> and decodes the
+        pacx_rate_result of every segment: t, met, total (int64) in four int32."""
+        what, peak = f"{kind.prefix}_{op}", op == "solve_peak"
+        segmented = peak or op == "solve_segments"
+        checked = self._checked(kind, curve, what)
+        n_cf, out = checked[1], self._picked(kind, checked)
         if segmented:
             first, limit = self._segments(what, seg_first, limit_bytes, n_cf)
             limits = [ctypes.c_int64(len(limit)), first.ctypes.data, limit.ctypes.data]
@@ -386,9 +417,8 @@ class Encoder:
             more = [_ptr(result[n_seg + 1:]), _ptr(result), _ptr(result[n_seg:])]       # floor, result, result_stream
         else:
             more = [_ptr(result)]
-        self._call_rate("pacx_" + what, ctypes.c_int64(n_cf), *head, *(_ptr(t) for t in arrays), *limits,
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(out[per_cf]), _ptr(out["n_bytes"]),
-                        _ptr(out["capped"]), *more, self._stream())
+        self._curve_call(what, checked, *limits, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
+                         _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]), _ptr(out["capped"]), *more)
         grid = float(_lib.RATE_TARGET_GRID)
         res = result.cpu().numpy()
         out["capped"] = out["capped"].bool()
@@ -411,7 +441,55 @@ class Encoder:
         given to rate_curve (the curve's steps already carry what the solve needs of them).  -> dict
         target_nmr_db, met (False: not even nmr_hi_db fits; the outputs are then that target's), total_bytes,
         budget [n_cf, 8] int32 for encode_pack_budget, n_bytes [n_cf] int32 (predicted), capped [n_cf] bool."""
-        return self._solve("rate_solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
+        return self._solve(RATE, "solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
+
+    def _profile(self, kind, curve, nmr_lo_db, nmr_hi_db, out):
+        what = kind.prefix + "_profile"
+        checked = self._checked(kind, curve, what)
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_tensor(what, out, n)
+        self._curve_call(what, checked, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile))
+        return profile
+
+    def _profile_segments(self, kind, curve, seg_cf, first_off, nmr_lo_db, nmr_hi_db, out):
+        what = kind.prefix + "_profile_segments"
+        checked = self._checked(kind, curve, what)
+        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        n_seg = self._uniform_segments(what, checked[1], seg_cf, first_off)
+        rows = torch.zeros((n_seg, n), dtype=torch.int64, device=self.device) if out is None else \
+            self._profile_rows(what, out, n, n_seg)
+        if n_seg == 0:                                                  # no frame and no segment begun: nothing to add to
+            return rows
+        self._curve_call(what, checked, ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)),
+                         ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(rows))
+        return rows
+
+    def _pick(self, kind, curve, target_nmr_db, kept=False):
+        """the pick at one target, on a curve or (kept) on its thresholds, whose range then goes before the target"""
+        what = kind.prefix + ("_pick_thresholds" if kept else "_pick")
+        checked = self._checked(kind, curve, what, kept)
+        return self._pick_call(kind, what, checked, *(self._kept_range(what, curve) if kept else ()),
+                               ctypes.c_double(target_nmr_db))
+
+    def _pick_segments(self, kind, curve, seg_cf, first_off, target_t, kept=False):
+        """the pick at one target per uniform segment, on a curve or (kept) on its thresholds"""
+        what = kind.prefix + ("_pick_thresholds_segments" if kept else "_pick_segments")
+        checked = self._checked(kind, curve, what, kept)
+        t = self._segment_targets(what, target_t, self._uniform_segments(what, checked[1], seg_cf, first_off))
+        return self._pick_call(kind, what, checked, ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)),
+                               *(self._kept_range(what, curve) if kept else ()), _ptr(t))
+
+    def _thresholds(self, kind, curve, nmr_lo_db, nmr_hi_db, out):
+        what = kind.prefix + "_thresholds"
+        checked = self._checked(kind, curve, what)
+        _, n_cf, width, head = checked
+        self._profile_len(what, nmr_lo_db, nmr_hi_db)
+        kept = self._kept_out(what, out, {a.key: (a.shape(n_cf, width), a.dtype) for a in kind.kept})
+        self._curve_call(what, checked, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
+                         *(_ptr(kept[a.key]) for a in kind.kept))
+        kept.update(zip(kind.head, head), nmr_lo_db=nmr_lo_db, nmr_hi_db=nmr_hi_db)
+        return kept
 
     @staticmethod
     def _segments(what, seg_first, limit_bytes, n_cf):
@@ -436,7 +514,7 @@ class Encoder:
         is the same solve with the one segment [0, n_cf].  seg_first [n_seg + 1] and limit_bytes [n_seg]: any integer
         sequences.  -> dict budget, n_bytes, capped as rate_solve, and NumPy arrays target_nmr_db [n_seg] float64, met
         [n_seg] bool, total_bytes [n_seg] int64."""
-        return self._solve("rate_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
+        return self._solve(RATE, "solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     def rate_solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """An average for the stream and a peak for every segment (pacx_rate_solve_peak, include/pacx.h): one target for
@@ -445,19 +523,7 @@ class Encoder:
         rate_solve; NumPy arrays per segment target_nmr_db (max of the stream's target and the floor), met (the bytes at
         that target against the peak), total_bytes, floor_nmr_db, pinned (target above the stream's); and
         stream_target_nmr_db, stream_met, stream_total_bytes for the whole."""
-        return self._solve("rate_solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
-
-    def _rate_arrays(self, curve, what):
-        """a rate curve's three arrays, checked -> (worst, bits, steps, n_cf, [row, sub_stride], the per-frame outputs)"""
-        worst, bits, steps = (curve[k].contiguous() for k in ("worst", "bits", "steps"))
-        n_cf, row = worst.shape
-        if worst.dtype != torch.float64 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
-                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
-            raise ValueError(f"{what}: a curve as rate_curve returns it")
-        out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
-               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
-               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
-        return worst, bits, steps, n_cf, [int(row), int(curve["sub_stride"])], out
+        return self._solve(RATE, "solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
 
     # ---- the whole-grid profile of a rate curve and the pick at known targets (pacx_rate_profile and its three
     # companions, include/pacx.h): the band siblings below on the other curve, with their checks
@@ -466,55 +532,25 @@ class Encoder:
         nmr_lo_db + g / 64 dB gives as sum(n_bytes + 4 where n_bytes > 0) -- rate_solve's total at that target.  With
         `out` the sizes are ADDED to it.  profile_solve on the profile of a whole curve is rate_solve's decision.
         -> the tensor."""
-        what = "rate_profile"
-        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
-        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
-        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
-            self._profile_tensor(what, out, n)
-        self._call_rate("pacx_rate_profile", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
-        return profile
+        return self._profile(RATE, curve, nmr_lo_db, nmr_hi_db, out)
 
     def rate_profile_segments(self, curve, seg_cf, first_off=0, nmr_lo_db=-30, nmr_hi_db=30, out=None):
         """band_profile_segments on a rate curve (pacx_rate_profile_segments): int64 device tensor [n_seg, G], row s
         what rate_profile gives for the frames of local segment s; with `out` ADDED to its first n_seg rows, the others
         left alone.  profile_solve_segments and profile_clamp_add take the rows as they take a band curve's.
         -> the tensor."""
-        what = "rate_profile_segments"
-        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
-        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
-        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
-        rows = torch.zeros((n_seg, n), dtype=torch.int64, device=self.device) if out is None else \
-            self._profile_rows(what, out, n, n_seg)
-        if n_seg == 0:                                                  # no frame and no segment begun: nothing to add to
-            return rows
-        self._call_rate("pacx_rate_profile_segments", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
-                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), ctypes.c_double(nmr_lo_db),
-                        ctypes.c_double(nmr_hi_db), _ptr(rows), self._stream())
-        return rows
+        return self._profile_segments(RATE, curve, seg_cf, first_off, nmr_lo_db, nmr_hi_db, out)
 
     def rate_pick(self, curve, target_nmr_db):
         """Every unit at the budget the curve gives at target_nmr_db, a multiple of 1/64 dB (pacx_rate_pick): what
         rate_solve returns at the target it finds.  -> dict budget [n_cf, 8] int32 for encode_pack_budget, n_bytes
         [n_cf] int32 (predicted), capped [n_cf] bool."""
-        worst, bits, steps, n_cf, head, out = self._rate_arrays(curve, "rate_pick")
-        self._call_rate("pacx_rate_pick", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
-                        ctypes.c_double(target_nmr_db), _ptr(out["budget"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
-                        self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick(RATE, curve, target_nmr_db)
 
     def rate_pick_segments(self, curve, seg_cf, first_off, target_t):
         """rate_pick with one target per segment (pacx_rate_pick_segments); target_t as band_pick_segments takes it.
         -> rate_pick's dict."""
-        what = "rate_pick_segments"
-        worst, bits, steps, n_cf, head, out = self._rate_arrays(curve, what)
-        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
-        self._call_rate("pacx_rate_pick_segments", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
-                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), _ptr(t), _ptr(out["budget"]),
-                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick_segments(RATE, curve, seg_cf, first_off, target_t)
 
     def band_curve(self, pcm, flags, max_bits_per_sample, out=None):
         """The noise-to-mask ratio of every band at every mantissa size (pacx_band_curve_batch, include/pacx.h): nmr
@@ -527,8 +563,7 @@ class Encoder:
     def _band_curve(self, name, pcm, flags, max_bits_per_sample, out):
         """band_curve and vq_band_curve: the same dict from either entry point"""
         n_cf = pcm.n_cf
-        shapes = {"nmr": (n_cf, self.band_stride, _lib.BAND_CAND), "cap": (n_cf, _lib.SUB),
-                  "cap_alloc": (n_cf, self.band_stride)}
+        shapes = {a.key: a.shape(n_cf, self.band_stride) for a in BAND.curve}
 
         def default(n_cf):
             return {"nmr": torch.full(shapes["nmr"], float("nan"), dtype=torch.float64, device=self.device),
@@ -543,34 +578,17 @@ class Encoder:
                             _ptr(o["cap_alloc"]), self._stream())
         return self._encode(pcm, flags, out, default, call)
 
-    def _band_arrays(self, curve, what):
-        nmr, cap, cap_alloc = (curve[k].contiguous() for k in ("nmr", "cap", "cap_alloc"))
-        n_cf = nmr.shape[0]
-        if nmr.dtype != torch.float64 or cap.dtype != torch.int32 or cap_alloc.dtype != torch.int32 or \
-                tuple(nmr.shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or tuple(cap.shape) != (n_cf, _lib.SUB) or \
-                tuple(cap_alloc.shape) != (n_cf, self.band_stride):
-            raise ValueError(f"{what}: a curve as band_curve returns it")
-        out = {"bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
-               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
-               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
-        return nmr, cap, cap_alloc, n_cf, out
-
     def band_pick(self, curve, target_nmr_db):
         """Per band the smallest mantissa size whose NMR on the curve is at or below target_nmr_db (pacx_band_pick,
         include/pacx.h); a unit whose bands ask for more than its cap gets cap_alloc.  -> dict bit_alloc
         [n_cf, band_stride] int32 for encode_pack_alloc, n_bytes [n_cf] int32 (predicted), capped [n_cf] bool."""
-        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, "band_pick")
-        self._call_rate("pacx_band_pick", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_double(target_nmr_db), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]),
-                        self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick(BAND, curve, target_nmr_db)
 
     def band_solve(self, curve, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """rate_solve on a band curve (pacx_band_solve, include/pacx.h): the lowest target on the grid of 1/64 dB in
         [nmr_lo_db, nmr_hi_db] whose body, every band at band_pick's size, stays within limit_bytes.  -> dict
         target_nmr_db, met, total_bytes and band_pick's bit_alloc, n_bytes, capped at that target."""
-        return self._solve("band_solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
+        return self._solve(BAND, "solve", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     @staticmethod
     def _profile_len(what, nmr_lo_db, nmr_hi_db):
@@ -597,13 +615,7 @@ class Encoder:
         gives as sum(n_bytes + 4 where n_bytes > 0).  With `out` (such a tensor) the sizes are ADDED to it: the profile
         of a stream is the sum of its pieces' in any order, which is what lets a stream too long for one batch be
         solved (profile_solve).  -> the tensor."""
-        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, "band_profile")
-        n = self._profile_len("band_profile", nmr_lo_db, nmr_hi_db)
-        profile = torch.zeros((n,), dtype=torch.int64, device=self.device) if out is None else \
-            self._profile_tensor("band_profile", out, n)
-        self._call_rate("pacx_band_profile", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(profile), self._stream())
-        return profile
+        return self._profile(BAND, curve, nmr_lo_db, nmr_hi_db, out)
 
     def profile_solve(self, profile, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve's decision read from a profile (pacx_profile_solve): the lowest target of the range whose size on
@@ -649,18 +661,7 @@ class Encoder:
         band_profile gives for the frames of local segment s, n_seg = ceil((first_off + n_cf) / seg_cf).  With `out`
         (such a tensor of at least n_seg rows) the sizes are ADDED to its first n_seg rows and the others are left
         alone: a segment cut by the piece gets the rest of its row from the next piece's call.  -> the tensor."""
-        what = "band_profile_segments"
-        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, what)
-        n = self._profile_len(what, nmr_lo_db, nmr_hi_db)
-        n_seg = self._uniform_segments(what, n_cf, seg_cf, first_off)
-        rows = torch.zeros((n_seg, n), dtype=torch.int64, device=self.device) if out is None else \
-            self._profile_rows(what, out, n, n_seg)
-        if n_seg == 0:                                                  # no frame and no segment begun: nothing to add to
-            return rows
-        self._call_rate("pacx_band_profile_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), ctypes.c_double(nmr_lo_db),
-                        ctypes.c_double(nmr_hi_db), _ptr(rows), self._stream())
-        return rows
+        return self._profile_segments(BAND, curve, seg_cf, first_off, nmr_lo_db, nmr_hi_db, out)
 
     def profile_solve_segments(self, rows, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30, out=None):
         """profile_solve on every row against its own limit (pacx_profile_solve_segments), and per row the largest
@@ -744,14 +745,7 @@ class Encoder:
     def band_pick_segments(self, curve, seg_cf, first_off, target_t):
         """band_pick with one target per segment (pacx_band_pick_segments): target_t, whole grid units (64 per dB), one
         per local segment -- a sequence, or an int32 device tensor [n_seg].  -> band_pick's dict."""
-        what = "band_pick_segments"
-        nmr, cap, cap_alloc, n_cf, out = self._band_arrays(curve, what)
-        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
-        self._call_rate("pacx_band_pick_segments", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), _ptr(t), _ptr(out["bit_alloc"]),
-                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick_segments(BAND, curve, seg_cf, first_off, target_t)
 
     # ---- a curve kept as 16-bit thresholds and the picks on it (pacx_band_thresholds and its five companions,
     # include/pacx.h): what a chunked encode keeps between its passes instead of taking every curve twice
@@ -778,112 +772,43 @@ class Encoder:
         cap_alloc as uint8: a quarter of the curve's bytes.  band_pick_thresholds[_segments] on it give band_pick's
         outputs at every grid target of the range.  out: a dict with e, cap, cap_alloc to write into.  -> dict e, cap,
         cap_alloc, nmr_lo_db, nmr_hi_db."""
-        what = "band_thresholds"
-        nmr, cap, cap_alloc, n_cf, _ = self._band_arrays(curve, what)
-        self._profile_len(what, nmr_lo_db, nmr_hi_db)
-        kept = self._kept_out(what, out, {"e": ((n_cf, self.band_stride, _lib.BAND_CAND), torch.uint16),
-                                          "cap": ((n_cf, _lib.SUB), torch.int32),
-                                          "cap_alloc": ((n_cf, self.band_stride), torch.uint8)})
-        self._call_rate("pacx_band_thresholds", ctypes.c_int64(n_cf), _ptr(nmr), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(kept["e"]), _ptr(kept["cap"]),
-                        _ptr(kept["cap_alloc"]), self._stream())
-        kept.update(nmr_lo_db=nmr_lo_db, nmr_hi_db=nmr_hi_db)
-        return kept
-
-    def _kept_band_arrays(self, kept, what):
-        e, cap, cap_alloc = (kept[k].contiguous() for k in ("e", "cap", "cap_alloc"))
-        n_cf = e.shape[0]
-        if e.dtype != torch.uint16 or cap.dtype != torch.int32 or cap_alloc.dtype != torch.uint8 or \
-                tuple(e.shape) != (n_cf, self.band_stride, _lib.BAND_CAND) or tuple(cap.shape) != (n_cf, _lib.SUB) or \
-                tuple(cap_alloc.shape) != (n_cf, self.band_stride):
-            raise ValueError(f"{what}: a kept curve as band_thresholds returns it")
-        out = {"bit_alloc": torch.zeros((n_cf, self.band_stride), dtype=torch.int32, device=self.device),
-               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
-               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
-        return e, cap, cap_alloc, n_cf, out
+        return self._thresholds(BAND, curve, nmr_lo_db, nmr_hi_db, out)
 
     def band_pick_thresholds(self, kept, target_nmr_db):
         """band_pick on a kept curve (pacx_band_pick_thresholds): target_nmr_db a multiple of 1/64 dB inside the range
         the thresholds were made for.  -> band_pick's dict, equal to band_pick's on the curve itself."""
-        what = "band_pick_thresholds"
-        e, cap, cap_alloc, n_cf, out = self._kept_band_arrays(kept, what)
-        self._call_rate("pacx_band_pick_thresholds", ctypes.c_int64(n_cf), _ptr(e), _ptr(cap), _ptr(cap_alloc),
-                        *self._kept_range(what, kept), ctypes.c_double(target_nmr_db), _ptr(out["bit_alloc"]),
-                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick(BAND, kept, target_nmr_db, kept=True)
 
     def band_pick_thresholds_segments(self, kept, seg_cf, first_off, target_t):
         """band_pick_segments on a kept curve (pacx_band_pick_thresholds_segments); target_t as band_pick_segments takes
         it, every target inside the range.  -> band_pick's dict."""
-        what = "band_pick_thresholds_segments"
-        e, cap, cap_alloc, n_cf, out = self._kept_band_arrays(kept, what)
-        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
-        self._call_rate("pacx_band_pick_thresholds_segments", ctypes.c_int64(n_cf), _ptr(e), _ptr(cap), _ptr(cap_alloc),
-                        ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)), *self._kept_range(what, kept),
-                        _ptr(t), _ptr(out["bit_alloc"]), _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick_segments(BAND, kept, seg_cf, first_off, target_t, kept=True)
 
     def rate_thresholds(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
         """band_thresholds for a rate curve (pacx_rate_thresholds): e [n_cf, row] uint16, bits copied (0 where no unit
         uses the entry), steps with a J that would leave its row cut to the row: half of the curve's bytes.  out: a dict
         with e, bits, steps to write into.  -> dict e, bits, steps, row, sub_stride, nmr_lo_db, nmr_hi_db."""
-        what = "rate_thresholds"
-        worst, bits, steps, n_cf, head, _ = self._rate_arrays(curve, what)
-        self._profile_len(what, nmr_lo_db, nmr_hi_db)
-        kept = self._kept_out(what, out, {"e": ((n_cf, head[0]), torch.uint16), "bits": ((n_cf, head[0]), torch.int32),
-                                          "steps": ((n_cf, _lib.SUB), torch.int32)})
-        self._call_rate("pacx_rate_thresholds", ctypes.c_int64(n_cf), *head, _ptr(worst), _ptr(bits), _ptr(steps),
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(kept["e"]), _ptr(kept["bits"]),
-                        _ptr(kept["steps"]), self._stream())
-        kept.update(row=head[0], sub_stride=head[1], nmr_lo_db=nmr_lo_db, nmr_hi_db=nmr_hi_db)
-        return kept
-
-    def _kept_rate_arrays(self, kept, what):
-        e, bits, steps = (kept[k].contiguous() for k in ("e", "bits", "steps"))
-        n_cf, row = e.shape
-        if e.dtype != torch.uint16 or bits.dtype != torch.int32 or steps.dtype != torch.int32 or \
-                tuple(bits.shape) != (n_cf, row) or tuple(steps.shape) != (n_cf, _lib.SUB):
-            raise ValueError(f"{what}: a kept curve as rate_thresholds returns it")
-        out = {"budget": torch.zeros((n_cf, _lib.SUB), dtype=torch.int32, device=self.device),
-               "n_bytes": torch.zeros((n_cf,), dtype=torch.int32, device=self.device),
-               "capped": torch.zeros((n_cf,), dtype=torch.uint8, device=self.device)}
-        return e, bits, steps, n_cf, [int(row), int(kept["sub_stride"])], out
+        return self._thresholds(RATE, curve, nmr_lo_db, nmr_hi_db, out)
 
     def rate_pick_thresholds(self, kept, target_nmr_db):
         """rate_pick on a kept curve (pacx_rate_pick_thresholds): target_nmr_db a multiple of 1/64 dB inside the range
         the thresholds were made for.  -> rate_pick's dict, equal to rate_pick's on the curve itself."""
-        what = "rate_pick_thresholds"
-        e, bits, steps, n_cf, head, out = self._kept_rate_arrays(kept, what)
-        self._call_rate("pacx_rate_pick_thresholds", ctypes.c_int64(n_cf), *head, _ptr(e), _ptr(bits), _ptr(steps),
-                        *self._kept_range(what, kept), ctypes.c_double(target_nmr_db), _ptr(out["budget"]),
-                        _ptr(out["n_bytes"]), _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick(RATE, kept, target_nmr_db, kept=True)
 
     def rate_pick_thresholds_segments(self, kept, seg_cf, first_off, target_t):
         """rate_pick_segments on a kept curve (pacx_rate_pick_thresholds_segments).  -> rate_pick's dict."""
-        what = "rate_pick_thresholds_segments"
-        e, bits, steps, n_cf, head, out = self._kept_rate_arrays(kept, what)
-        t = self._segment_targets(what, target_t, self._uniform_segments(what, n_cf, seg_cf, first_off))
-        self._call_rate("pacx_rate_pick_thresholds_segments", ctypes.c_int64(n_cf), *head, _ptr(e), _ptr(bits),
-                        _ptr(steps), ctypes.c_int64(int(seg_cf)), ctypes.c_int64(int(first_off)),
-                        *self._kept_range(what, kept), _ptr(t), _ptr(out["budget"]), _ptr(out["n_bytes"]),
-                        _ptr(out["capped"]), self._stream())
-        out["capped"] = out["capped"].bool()
-        return out
+        return self._pick_segments(RATE, kept, seg_cf, first_off, target_t, kept=True)
 
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,
         n_bytes, capped as band_solve, and NumPy arrays target_nmr_db, met, total_bytes [n_seg]."""
-        return self._solve("band_solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
+        return self._solve(BAND, "solve_segments", curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db)
 
     def band_solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """rate_solve_peak on a band curve (pacx_band_solve_peak, include/pacx.h).  -> dict bit_alloc, n_bytes, capped as
         band_solve and rate_solve_peak's results per segment and for the stream."""
-        return self._solve("band_solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
+        return self._solve(BAND, "solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

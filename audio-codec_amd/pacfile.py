@@ -12,7 +12,7 @@ from struct import pack
 
 import numpy as np
 
-from . import _lib, codec, context
+from . import _lib, codec, context, curves
 from .audiofile import AudioFile
 from .engine import PcmView
 from .pcmfile import codes_to_fraction
@@ -448,14 +448,81 @@ def _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, 
     return cp, enc, view, flags
 
 
-class _BandPath:
-    """What the band-by-band streams call, for the scalar coder and for the gain-shape one: the curve and the second
-    pass are the coder's own, the pick and the solves work on the arrays alone and run on a scalar handle -- for a
-    gain-shape encoder its scalar sibling (context.scalar_sibling)."""
+class _CurvePath:
+    """What the rate-control streams call on a curve, for both kinds (curves.RATE, curves.BAND): an operation is the
+    solver's method of that name behind the kind's prefix, the layout of the kept bytes the kind's.  A subclass says
+    which encoder solves, how the curve is taken (curve, layout) and what the second pass is (encode)."""
+    kind = None
+
+    def __init__(self, enc):
+        self.enc = self.solver = enc
+
+    def _op(self, name, *args, **kw):
+        return getattr(self.solver, f"{self.kind.prefix}_{name}")(*args, **kw)
+
+    def solve(self, curve, flags, limit_bytes, lo, hi):
+        """flags: as given to curve(); only rate_solve takes them"""
+        return self._op("solve", curve, limit_bytes, lo, hi)
+
+    def solve_segments(self, curve, seg_first, limit_bytes, lo, hi):
+        return self._op("solve_segments", curve, seg_first, limit_bytes, lo, hi)
+
+    def solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, lo, hi):
+        return self._op("solve_peak", curve, seg_first, peak_bytes, limit_bytes, lo, hi)
+
+    # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve, its profile, the pick at
+    # known targets and the second pass on that pick
+    def no_frames(self, max_bits_per_sample):
+        """the curve of no frame at all"""
+        width, head = self.layout(max_bits_per_sample)
+        return self.kind.no_frames(width, self.solver.device, **head)
+
+    def profile(self, curve, lo, hi, out=None):
+        return self._op("profile", curve, lo, hi, out=out)
+
+    def profile_segments(self, curve, seg_cf, first_off, lo, hi, out=None):
+        return self._op("profile_segments", curve, seg_cf, first_off, lo, hi, out=out)
+
+    def pick(self, curve, target_nmr_db):
+        """on a curve, or on a curve kept as thresholds (kept_views, thresholds)"""
+        return self._op("pick_thresholds" if self.kind.is_kept(curve) else "pick", curve, target_nmr_db)
+
+    def pick_segments(self, curve, seg_cf, first_off, target_t):
+        return self._op("pick_thresholds_segments" if self.kind.is_kept(curve) else "pick_segments", curve, seg_cf,
+                        first_off, target_t)
+
+    pick_kept, pick_kept_segments = pick, pick_segments
+
+    def second_pass(self, view, flags, pick):
+        """pick: what a pick or a solve returned"""
+        return self.encode(view, flags, pick[self.kind.per_cf.key])
+
+    # the curve kept between the passes (HostStreamRateEncoder.keep_curves): its thresholds and the layout of a chunk's
+    # kept arrays in one run of bytes
+    def kept_bytes_per_cf(self, max_bits_per_sample):
+        return self.kind.kept_bytes_per_cf(self.layout(max_bits_per_sample)[0])
+
+    def kept_views(self, buf, n_cf, max_bits_per_sample):
+        width, head = self.layout(max_bits_per_sample)
+        return self.kind.kept_views(buf, n_cf, width, **head)
+
+    def thresholds(self, curve, lo, hi, out=None):
+        return self._op("thresholds", curve, lo, hi, out=out)
+
+
+class _BandPath(_CurvePath):
+    """allocation="band", for the scalar coder and for the gain-shape one: the curve and the second pass are the
+    coder's own, the pick and the solves work on the arrays alone and run on a scalar handle -- for a gain-shape
+    encoder its scalar sibling (context.scalar_sibling)."""
+    kind = curves.BAND
 
     def __init__(self, enc):
         self.enc = enc
         self.solver = context.scalar_sibling(enc) if enc.use_vq else enc
+
+    def layout(self, max_bits_per_sample):
+        """(width, the extra keys of a dict of the kind) at this cap rate"""
+        return self.solver.band_stride, {}
 
     def curve(self, view, flags, max_bits_per_sample):
         if self.enc.use_vq:
@@ -467,107 +534,26 @@ class _BandPath:
             return self.enc.encode_vq_alloc(view, flags, bit_alloc)
         return self.enc.encode_pack_alloc(view, flags, bit_alloc)
 
-    # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve above, its profile, the pick
-    # at known targets and the second pass on that pick -- _BudgetPath answers the same five on the other curve
-    def no_frames(self, max_bits_per_sample):
-        """the curve of no frame at all"""
-        import torch
-        e = self.solver
-        return {"nmr": torch.zeros((0, e.band_stride, _lib.BAND_CAND), dtype=torch.float64, device=e.device),
-                "cap": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device),
-                "cap_alloc": torch.zeros((0, e.band_stride), dtype=torch.int32, device=e.device)}
 
-    def profile(self, curve, lo, hi, out=None):
-        return self.solver.band_profile(curve, lo, hi, out=out)
+class _BudgetPath(_CurvePath):
+    """allocation="budget": BitAlloc with one budget per block, read from the rate curve.  Scalar coder only."""
+    kind = curves.RATE
 
-    def profile_segments(self, curve, seg_cf, first_off, lo, hi, out=None):
-        return self.solver.band_profile_segments(curve, seg_cf, first_off, lo, hi, out=out)
-
-    def pick(self, curve, target_nmr_db):
-        return self.solver.band_pick(curve, target_nmr_db)
-
-    def pick_segments(self, curve, seg_cf, first_off, target_t):
-        return self.solver.band_pick_segments(curve, seg_cf, first_off, target_t)
-
-    def second_pass(self, view, flags, pick):
-        return self.encode(view, flags, pick["bit_alloc"])
-
-    # the curve kept between the passes (HostStreamRateEncoder.keep_curves): its thresholds, the picks on them, and
-    # the layout of a chunk's kept arrays in one run of bytes
-    def kept_bytes_per_cf(self, max_bits_per_sample):
-        return 33 * self.solver.band_stride + 32
-
-    def kept_views(self, buf, n_cf, max_bits_per_sample):
-        """the arrays of n_cf kept channel-frames as views of the first n_cf * kept_bytes_per_cf bytes of buf (uint8,
-        256-byte aligned): e, then cap, then cap_alloc, each contiguous"""
-        import torch
-        bs = self.solver.band_stride
-        a, b = 32 * bs * n_cf, (32 * bs + 32) * n_cf
-        return {"e": buf[:a].view(torch.uint16).view(n_cf, bs, _lib.BAND_CAND),
-                "cap": buf[a:b].view(torch.int32).view(n_cf, _lib.SUB), "cap_alloc": buf[b:b + bs * n_cf].view(n_cf, bs)}
-
-    def thresholds(self, curve, lo, hi, out=None):
-        return self.solver.band_thresholds(curve, lo, hi, out=out)
-
-    def pick_kept(self, kept, target_nmr_db):
-        return self.solver.band_pick_thresholds(kept, target_nmr_db)
-
-    def pick_kept_segments(self, kept, seg_cf, first_off, target_t):
-        return self.solver.band_pick_thresholds_segments(kept, seg_cf, first_off, target_t)
-
-
-class _BudgetPath:
-    """_BandPath's chunked quintet for allocation="budget": BitAlloc with one budget per block, read from the rate
-    curve (Encoder.rate_curve, rate_profile[_segments], rate_pick[_segments], encode_pack_budget).  Scalar coder only."""
-
-    def __init__(self, enc):
-        self.enc = self.solver = enc
+    def layout(self, max_bits_per_sample):
+        row, sub = self.enc.rate_curve_layout(max_bits_per_sample)
+        return row, {"row": row, "sub_stride": sub}
 
     def curve(self, view, flags, max_bits_per_sample):
         return self.enc.rate_curve(view, flags, max_bits_per_sample)
 
-    def no_frames(self, max_bits_per_sample):
-        import torch
-        e = self.enc
-        row, sub = e.rate_curve_layout(max_bits_per_sample)
-        return {"worst": torch.zeros((0, row), dtype=torch.float64, device=e.device),
-                "bits": torch.zeros((0, row), dtype=torch.int32, device=e.device),
-                "steps": torch.zeros((0, _lib.SUB), dtype=torch.int32, device=e.device), "row": row, "sub_stride": sub}
+    def solve(self, curve, flags, limit_bytes, lo, hi):
+        return self.enc.rate_solve(curve, flags, limit_bytes, lo, hi)
 
-    def profile(self, curve, lo, hi, out=None):
-        return self.enc.rate_profile(curve, lo, hi, out=out)
+    def encode(self, view, flags, budget):
+        return self.enc.encode_pack_budget(view, flags, budget)
 
-    def profile_segments(self, curve, seg_cf, first_off, lo, hi, out=None):
-        return self.enc.rate_profile_segments(curve, seg_cf, first_off, lo, hi, out=out)
 
-    def pick(self, curve, target_nmr_db):
-        return self.enc.rate_pick(curve, target_nmr_db)
-
-    def pick_segments(self, curve, seg_cf, first_off, target_t):
-        return self.enc.rate_pick_segments(curve, seg_cf, first_off, target_t)
-
-    def second_pass(self, view, flags, pick):
-        return self.enc.encode_pack_budget(view, flags, pick["budget"])
-
-    def kept_bytes_per_cf(self, max_bits_per_sample):
-        return 6 * self.enc.rate_curve_layout(max_bits_per_sample)[0] + 32
-
-    def kept_views(self, buf, n_cf, max_bits_per_sample):
-        """_BandPath.kept_views for the rate curve: bits, then steps, then e (the widest first: every array aligned)"""
-        import torch
-        row, sub = self.enc.rate_curve_layout(max_bits_per_sample)
-        a, b = 4 * row * n_cf, (4 * row + 32) * n_cf
-        return {"bits": buf[:a].view(torch.int32).view(n_cf, row), "steps": buf[a:b].view(torch.int32).view(n_cf, _lib.SUB),
-                "e": buf[b:b + 2 * row * n_cf].view(torch.uint16).view(n_cf, row), "row": row, "sub_stride": sub}
-
-    def thresholds(self, curve, lo, hi, out=None):
-        return self.enc.rate_thresholds(curve, lo, hi, out=out)
-
-    def pick_kept(self, kept, target_nmr_db):
-        return self.enc.rate_pick_thresholds(kept, target_nmr_db)
-
-    def pick_kept_segments(self, kept, seg_cf, first_off, target_t):
-        return self.enc.rate_pick_thresholds_segments(kept, seg_cf, first_off, target_t)
+_PATHS = {"band": _BandPath, "budget": _BudgetPath}
 
 
 def _check_allocation(allocation):
@@ -591,8 +577,8 @@ def _encode_stream_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel, bl
         if not np.isfinite(float(target_nmr_db)):
             raise ValueError("target_nmr_db must be finite")
         path = _BandPath(enc)
-        pick = path.solver.band_pick(path.curve(view, flags, cp.targetBitsPerSample), float(target_nmr_db))
-        out = path.encode(view, flags, pick["bit_alloc"])
+        pick = path.pick(path.curve(view, flags, cp.targetBitsPerSample), float(target_nmr_db))
+        out = path.second_pass(view, flags, pick)
         out["capped"] = pick["capped"]
     else:
         out = enc.encode_pack_nmr(view, flags, float(target_nmr_db), cp.targetBitsPerSample)
@@ -738,10 +724,8 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
     head = header_bytes(cp)
     limits = [None] * len(sizes) if segment_hops is not None and not peak else \
         [_abr_limit(cp, view, head, k, b) for k, b in sizes]
-    path = _BandPath(enc) if band else None
-    solver = path.solver if band else enc
-    curve = path.curve(view, flags, cp.targetBitsPerSample) if band else \
-        enc.rate_curve(view, flags, cp.targetBitsPerSample)
+    path = _PATHS[allocation](enc)
+    curve = path.curve(view, flags, cp.targetBitsPerSample)
     n_ch = cp.nChannels
 
     def unreachable(limit, total):
@@ -750,14 +734,13 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
     done = []
     for (kbps, _), limit in zip(sizes, limits):
         if segment_hops is None:        # the whole stream: the partition [0, n_cf] with its one limit, the plain method
-            sol = solver.band_solve(curve, limit, lo, hi) if band else enc.rate_solve(curve, flags, limit, lo, hi)
+            sol = path.solve(curve, flags, limit, lo, hi)
             unmet = None if sol["met"] else unreachable(limit, sol["total_bytes"])
         elif peak:                      # the stream's limit above the segments' peaks
             first, count, seg_limit = segment_limits(peak_kbps_per_channel, n_ch, cp.sampleRate, view.n_frames,
                                                      segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
-            sol = solver.band_solve_peak(curve, seg_first, seg_limit, limit, lo, hi) if band else \
-                enc.rate_solve_peak(curve, seg_first, seg_limit, limit, lo, hi)
+            sol = path.solve_peak(curve, seg_first, seg_limit, limit, lo, hi)
             s = int(np.argmin(sol["met"]))
             if not sol["stream_met"]:
                 unmet = unreachable(limit, sol["stream_total_bytes"])
@@ -770,8 +753,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
         else:
             first, count, seg_limit = segment_limits(kbps, n_ch, cp.sampleRate, view.n_frames, segment_hops)
             seg_first = np.append(first, view.n_frames) * n_ch
-            sol = solver.band_solve_segments(curve, seg_first, seg_limit, lo, hi) if band else \
-                enc.rate_solve_segments(curve, seg_first, seg_limit, lo, hi)
+            sol = path.solve_segments(curve, seg_first, seg_limit, lo, hi)
             s = int(np.argmin(sol["met"]))
             unmet = None if sol["met"].all() else \
                 _segment_unreachable(s, first, count, seg_limit, sol["total_bytes"][s], hi)
@@ -779,8 +761,7 @@ def _encode_stream_abr(pcm, sample_rate, sizes, max_kbps_per_channel, block_swit
             limit = int(seg_limit.sum())
         if unmet:
             raise ValueError(unmet)
-        out = path.encode(view, flags, sol["bit_alloc"]) if band else \
-            enc.encode_pack_budget(view, flags, sol["budget"])
+        out = path.second_pass(view, flags, sol)
         body, total = enc.gather_body(out["payload"], out["n_bytes"])
         done.append((head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, limit))
     return done, enc
@@ -880,11 +861,11 @@ def iter_encode_abr_chunked(pcm, sample_rate, kbps_per_channel=None, max_bytes=N
 
 def _kept_bytes_per_cf(cp, allocation):
     """_BandPath / _BudgetPath.kept_bytes_per_cf from the CodingParams alone (header_bytes has set the band tables), so
-    that a caller's store is refused before an encoder exists: 33 band_stride + 32, or 6 row + 32 with the row of
-    pacx_rate_curve_layout (the budget rule of coder/codec.py:288-299 at the cap rate, in steps of 32 bits)"""
+    that a caller's store is refused before an encoder exists: the kind's bytes at the handle's band_stride, or at the
+    row of pacx_rate_curve_layout (the budget rule of coder/codec.py:288-299 at the cap rate, in steps of 32 bits)"""
     nb_long, nb_short = cp.sfBands.nBands, cp.sfBandsShort.nBands
     if allocation == "band":
-        return 33 * max(nb_long, _lib.SUB * nb_short) + 32
+        return curves.BAND.kept_bytes_per_cf(max(nb_long, _lib.SUB * nb_short))
 
     def steps(half_n, short, last_or_next, nb):
         n_eff = int(1.45 * half_n) if short else half_n
@@ -894,7 +875,7 @@ def _kept_bytes_per_cf(cp, allocation):
         return min(max(int(np.floor(cap / 32.0)), 0), 2047)
     j_long = max(steps(1024, False, lon, nb_long) for lon in (False, True))
     j_short = max(steps(128, True, lon, nb_short) for lon in (False, True))
-    return 6 * max(j_long + 1, _lib.SUB * (j_short + 1)) + 32
+    return curves.RATE.kept_bytes_per_cf(max(j_long + 1, _lib.SUB * (j_short + 1)))
 
 
 def _iter_encode_abr(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops, max_kbps_per_channel, block_switching,

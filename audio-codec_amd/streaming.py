@@ -274,16 +274,15 @@ class HostStreamRateEncoder:
 
     def __init__(self, enc, n_channels, hops_per_chunk, max_bits_per_sample, block_switching=False, nmr_lo_db=-30,
                  nmr_hi_db=30, depth=2, allocation="band"):
-        from .pacfile import _BandPath, _BudgetPath, _check_allocation
+        from .pacfile import _PATHS, _check_allocation
         self.enc, self.n_ch, self.F, self.depth = enc, int(n_channels), int(hops_per_chunk), int(depth)
         if self.F < 1 or self.depth < 2:
             raise ValueError("hops_per_chunk must be at least 1 and depth at least 2")
         self.block_switching, self.max_bps = bool(block_switching), float(max_bits_per_sample)
         self.lo, self.hi = nmr_lo_db, nmr_hi_db
-        band = _check_allocation(allocation)
-        if enc.use_vq and not band:
+        if not _check_allocation(allocation) and enc.use_vq:
             raise NotImplementedError("gain-shape streams: allocation 'band' only")
-        self.path = _BandPath(enc) if band else _BudgetPath(enc)
+        self.path = _PATHS[allocation](enc)
         dev, F, n_ch = enc.device, self.F, self.n_ch
         self.n_cf = max(F, 2) * n_ch                                   # the tail chunk holds two blocks
         enc.reserve(self.n_cf)
@@ -643,8 +642,7 @@ class HostStreamRateEncoder:
                 view, flags = self._front(k, n, tail)
                 curve = self.path.curve(view, flags, self.max_bps) if kept is None else self._kept_views(k, n)
                 if segmented:
-                    pick = self.path.pick_segments(curve, seg_cf, first_off, target_dev) if kept is None else \
-                        self.path.pick_kept_segments(curve, seg_cf, first_off, target_dev)
+                    pick = self.path.pick_segments(curve, seg_cf, first_off, target_dev)
                     if limits is not None:
                         if frames == 0:                                # cleared on this stream, behind whatever an encode()
                             sums.zero_()                               # given up half-way still had queued on it
@@ -652,10 +650,8 @@ class HostStreamRateEncoder:
                         nb = pick["n_bytes"].to(torch.int64)
                         ids = (torch.arange(n * self.n_ch, device=enc.device) + first_off) // seg_cf
                         sums.index_add_(0, ids, torch.where(nb > 0, nb + 4, torch.zeros_like(nb)))
-                elif kept is None:
-                    pick = self.path.pick(curve, float(target_nmr_db))
                 else:
-                    pick = self.path.pick_kept(curve, float(target_nmr_db))
+                    pick = self.path.pick(curve, float(target_nmr_db))
                 out = self.path.second_pass(view, flags, pick)
                 self.s_k.wait_event(self.ev_out[k])                    # the total that last sat in totals[k] has left
                 enc._call("pacx_gather_body", ctypes.c_int64(n * self.n_ch), _ptr(out["payload"]), _ptr(out["n_bytes"]),
