@@ -97,6 +97,39 @@ __global__ __launch_bounds__(64) void k_mdct_long(PacxTables T, PacxPcmView in,
 /* ----------------------------------------------------------------- short */
 /* 8 sub-blocks of 256 samples at n = 448 + 128 g (coder/pacfile.py:526-527),
  * sine window, 128 lines each: lane = 8 g + r works on sub-block g. */
+/* coder/pacfile.py:530-533 drops a hop for EVERY channel when any channel holds an all-zero sub-block, so each
+ * channel-frame looks at its siblings too: bit g of the result says that sub-block g of channel `ch` of frame `f`
+ * is all zeros (the code -32768 reads as 0).  Straight from memory, in the round trip that stages the own samples. */
+template <int DT, bool FAST>
+__device__ __forceinline__ unsigned zero_subblocks_of(const PacxPcmView &in, long long f, int ch, int lane)
+{
+    typedef typename PcmStage<DT>::elem E;
+    const int SPAN = PACX_N_SHORT + (PACX_SUB - 1) * PACX_M_SHORT;
+    const E *src = (const E *)in.base + f * in.frame_stride + (long long)ch * in.ch_stride;
+    unsigned seg = 0;                                  /* bit s: a non-zero sample among 128 s ... 128 s + 127 of the span */
+    if constexpr (FAST) {
+        const int4 *s4 = (const int4 *)(src + PACX_SHORT_FIRST);
+        for (int i = lane; i < SPAN / 8; i += 64) {
+            const int4 q = s4[i];
+            if ((q.x | q.y | q.z | q.w) & 0x7fff7fff)
+                seg |= 1u << (i >> 4);
+        }
+    } else {
+        for (int i = lane; i < SPAN; i += 64)
+            if (PcmStage<DT>::get(src + (long long)(PACX_SHORT_FIRST + i) * in.samp_stride, 0) != 0.0)
+                seg |= 1u << (i >> 7);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        seg |= (unsigned)__shfl_xor((int)seg, off, 64);
+    unsigned zero = 0;
+#pragma unroll
+    for (int g = 0; g < PACX_SUB; ++g)
+        if (!((seg >> g) & 3u))                        /* sub-block g: samples 128 g ... 128 g + 255 */
+            zero |= 1u << g;
+    return zero;
+}
+
 template <int DT, bool FAST>
 __global__ __launch_bounds__(64) void k_mdct_short(PacxTables T, PacxPcmView in,
                                                   const uint8_t *__restrict__ flags, long long n_cf,
@@ -129,11 +162,19 @@ __global__ __launch_bounds__(64) void k_mdct_short(PacxTables T, PacxPcmView in,
     __shared__ __attribute__((aligned(16))) double w[PACX_N_SHORT];
     __shared__ __attribute__((aligned(16))) cplx tws[PACX_N_SHORT / 4];
     __shared__ __attribute__((aligned(16))) cplx w64s[8][8];          /* W64^(r k2) at [k2][r] */
+    unsigned sibling_zero = 0;                     /* all-zero sub-blocks in the other channels of this frame */
     {
         const double2 wa = *(const double2 *)(wg + 4 * lane), wb = *(const double2 *)(wg + 4 * lane + 2);
         const cplx tv = T.tw_short[lane];
         const cplx wv = T.w512[(8 * (lane & 7) * (lane >> 3)) & 511];
         stage_samples<DT, FAST>(raw, in, cf, PACX_SHORT_FIRST, SPAN, lane);
+        if (status && in.n_ch > 1) {
+            const long long f = cf / in.n_ch;
+            const int own = (int)(cf - f * in.n_ch);
+            for (int c = 0; c < in.n_ch; ++c)
+                if (c != own)
+                    sibling_zero |= zero_subblocks_of<DT, FAST>(in, f, c, lane);
+        }
         *(double2 *)(w + 4 * lane) = wa;
         *(double2 *)(w + 4 * lane + 2) = wb;
         tws[lane] = tv;
@@ -144,13 +185,14 @@ __global__ __launch_bounds__(64) void k_mdct_short(PacxTables T, PacxPcmView in,
     const int g = lane >> 3, r = lane & 7;
     const E *sub = raw + g * PACX_M_SHORT;
 
-    /* coder/pacfile.py:530-533: an all-zero sub-block makes the writer drop the hop */
+    /* coder/pacfile.py:530-533: an all-zero sub-block in any channel makes the writer drop the hop, and every
+       channel-frame of the hop says so */
     if (status) {
         bool nz = false;
         for (int i = r; i < PACX_N_SHORT; i += 8)
             nz = nz || (PcmStage<DT>::get(sub, i) != 0.0);
         const unsigned long long any = __ballot(nz);
-        bool dropped = false;
+        bool dropped = sibling_zero != 0;
         for (int q = 0; q < PACX_SUB; ++q)
             dropped = dropped || (((any >> (8 * q)) & 0xFFull) == 0);
         if (lane == 0)

@@ -76,9 +76,10 @@ extern "C" {
 
 /* per-cf status word bits written by pacx_encode_batch */
 #define PACX_ST_SHORT        1u   /* coded as 8 short sub-blocks               */
-#define PACX_ST_ZERO_SUBBLOCK 2u  /* a short sub-block was all zeros: the
-                                     reference drops the whole hop
-                                     (coder/pacfile.py:530-533)                */
+#define PACX_ST_ZERO_SUBBLOCK 2u  /* a short sub-block of some channel of the
+                                     hop was all zeros: the reference drops the
+                                     whole hop (coder/pacfile.py:530-533); set
+                                     in every channel-frame of that hop        */
 #define PACX_ST_ALLOC_CAP    4u   /* BitAlloc left through its 200-pass guard
                                      (coder/bitalloc.py:116-119)               */
 
