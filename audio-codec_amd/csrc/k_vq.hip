@@ -33,6 +33,7 @@
 #include "../../include/pacx.h"
 #include "pacx_launch.h"
 #include "pvq_dev.h"
+#include "vq_exact.h" /* the split rule: angle bits, angle code and value, mid/side bits, the gain's quantiser */
 #include "quant_dev.h"  /* put_bits: the MSB-first bit writer into LDS words shared by the block's waves */
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "wave_np_sum.h"
@@ -133,10 +134,14 @@ struct VqOut {
 #endif
 };
 
+/* the time stamp of the measuring aids below (PACX_VQ_DEBUG, PACX_VQ_WAITDBG): the LDS and scalar-memory queues
+   drained (VQ_NOW_VM: vector memory too), the clock read, and waited for */
+#define VQ_NOW(v) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
+#define VQ_NOW_VM(v) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
 #ifdef PACX_VQ_DEBUG
 __device__ long long g_vq_dbg[32];
-/* inside the band walk: slots 8.. = split arithmetic, quad attempt, leaf pair, single leaf, climb, band set-up, gain */
-#define VQ_S(o, k) do { long long t_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
+/* inside the band walk: slots 8.. = split arithmetic, choice of the pair path (slot 9), leaf pair, single leaf, climb, band set-up, gain */
+#define VQ_S(o, k) do { long long t_; VQ_NOW(t_); \
                         if ((threadIdx.x & 63) == 0) atomicAdd((unsigned long long *)&g_vq_dbg[k], (unsigned long long)(t_ - (o).t_last)); \
                         (o).t_last = t_; } while (0)
 #else
@@ -179,9 +184,7 @@ __device__ __forceinline__ void vq_emit(VqOut &o, unsigned long long hi, unsigne
     o.pos += width;
 }
 
-/* QuantizeUniform(x, n_bits) for x >= 0 (coder/quantize.py:14-36) evaluated the
- * way Python does: the factor 2^n - 1 becomes a float64 (exact up to 53 bits,
- * 2^n beyond), one multiply, +1, floor-divide by 2. */
+/* QuantizeUniform(x, n_bits) for x >= 0 (coder/quantize.py:14-36, vq_quantize_wide) into the stream */
 __device__ __forceinline__ void vq_quantize_emit(VqOut &o, double x, int n_bits, int lane)
 {
     if (n_bits <= 0) {
@@ -193,26 +196,8 @@ __device__ __forceinline__ void vq_quantize_emit(VqOut &o, double x, int n_bits,
         vq_emit(o, 0, 0, 0, lane);
         return;
     }
-    unsigned long long hi = 0, lo = 0;
-    if (x >= 1.0) {                           /* code = 2^(n-1) - 1 */
-        const int ones = n_bits - 1;
-        if (ones >= 64) {
-            lo = ~0ull;
-            hi = (ones - 64 >= 64) ? ~0ull : ((1ull << (ones - 64)) - 1ull);
-        } else {
-            lo = (ones == 0) ? 0ull : ((~0ull) >> (64 - ones));
-        }
-    } else {
-        const double factor = (n_bits <= 53) ? (double)((1ull << n_bits) - 1ull) : ldexp(1.0, n_bits);
-        const double code = floor((factor * x + 1.0) * 0.5);
-        if (n_bits <= 64) {
-            lo = (unsigned long long)code;
-        } else {
-            const double top = floor(ldexp(code, -64));
-            hi = (unsigned long long)top;
-            lo = (unsigned long long)(code - ldexp(top, 64));
-        }
-    }
+    unsigned long long hi, lo;
+    vq_quantize_wide(x, n_bits, hi, lo);
     vq_emit(o, hi, lo, n_bits, lane);
 }
 
@@ -449,101 +434,6 @@ __device__ __forceinline__ void vq_leaf_pair(const VqView &V, VqOut &o, const do
     vq_emit(o, 0, ((okm >> 32) & 1ull) ? idx_side : 0ull, w_side, lane);
 }
 
-/* Two sibling bottom splits at once.  xa / xb: the two unit vectors (n <= 32
- * components each, bits_a / bits_b > 32 bits).  Split a runs on lanes 0-31, split
- * b on lanes 32-63 (fold, norms, angle, bit split: the arithmetic of vq_shape's
- * split step); if all four grandchildren turn out to be leaves, they are coded
- * on the four 16-lane quarters and the six fields go out in the reference's
- * order (theta a, a.mid, a.side, theta b, b.mid, b.side).  Otherwise nothing is
- * emitted and the caller walks the two subtrees the ordinary way. */
-__device__ __forceinline__ bool vq_quad_try(const VqView &V, VqOut &o, const double *xa, const double *xb,
-                                            int n, int bits_a, int bits_b, int lane)
-{
-    const double half_pi = 1.5707963267948966;
-    const int h = lane >> 5, l = lane & 31;
-    const double *xs = h ? xb : xa;
-    const int bits = h ? bits_b : bits_a;
-    const int cut = n / 2, hh = n - cut;                    /* hh <= 16 */
-    const double left = (l < cut) ? xs[l] : 0.0;
-    const double right = (l < hh) ? xs[cut + l] : 0.0;
-    double m = (l < hh) ? (left + right) / 2.0 : 0.0;
-    double sd = (l < hh) ? (left - right) / 2.0 : 0.0;
-    double mm = fma(m, m, 0.0), ss = fma(sd, sd, 0.0);
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) {
-        mm = mm + __shfl_xor(mm, off, 32);
-        ss = ss + __shfl_xor(ss, off, 32);
-    }
-    const double m_l2 = sqrt(mm), s_l2 = sqrt(ss);
-    if (m_l2 != 0.0)
-        m = m / m_l2;
-    if (s_l2 != 0.0)
-        sd = sd / s_l2;
-    const double theta = (m_l2 == 0.0) ? 0.0 : vq_atan(s_l2 / m_l2);
-    const int a_theta = (int)floor((double)bits / (double)hh + ldc(&V.tab.half_log2[hh]));
-    int a_rest = bits - a_theta;
-    if (a_rest < 0)
-        a_rest = 0;
-    bool fine = a_theta > 0 && a_theta <= 62 && hh >= 2;
-    unsigned long long code = 0;
-    double theta_q = 0.0;
-    if (fine) {
-        const double tn = theta / half_pi;
-        if (tn >= 1.0) {
-            code = (1ull << (a_theta - 1)) - 1ull;
-        } else {
-            const double factor = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-            code = (unsigned long long)floor((factor * tn + 1.0) * 0.5);
-        }
-        const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-        const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-        double dq = (double)(2ull * mag) / den;
-        if (code >> (a_theta - 1))
-            dq = -dq;
-        theta_q = dq * half_pi;
-    }
-    int a_mid = 0;
-    if (fine && theta_q != 0.0) {
-        double lt;
-        if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta_q > 0.0)
-            lt = V.log2_tan[((1 << (a_theta - 1)) - 1) + (int)code];
-        else
-            lt = vq_log2_tan(theta_q);
-        const double v = ((double)a_rest - (double)(hh - 1) * lt) / 2.0;
-        const double f = floor(v);
-        a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
-    }
-    const int a_side = a_rest - a_mid;
-    fine = fine && a_mid > 0 && a_mid <= PACX_VQ_SPLIT_BITS && a_side > 0 && a_side <= PACX_VQ_SPLIT_BITS;
-    if (__builtin_amdgcn_ballot_w64(!fine))
-        return false;                                       /* not two bottom splits: ordinary walk */
-    /* the four leaves, one per 16-lane quarter: (a.mid, a.side, b.mid, b.side) */
-    const int q = lane >> 4, ll = lane & 15;
-    const double from_side = __shfl(sd, 32 * h + ll, 64);
-    const double from_mid = __shfl(m, 32 * h + ll, 64);
-    const double x = (ll < hh) ? ((q & 1) ? from_side : from_mid) : 0.0;
-    const int lbits = (q & 1) ? a_side : a_mid;
-    const int K = ldc(&V.tab.k_of[hh * 33 + lbits]);
-    const int width = ldc(&V.tab.w_of[hh * 33 + lbits]);
-    bool ok;
-    const unsigned long long term = vq_leaf_group<16>(V, x, hh, K, ll, ok);
-    const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-    if ((okm & 0x0001000100010001ull) != 0x0001000100010001ull)
-        o.flags |= PACX_ST_VQ_UNDEFINED;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const unsigned long long th = (unsigned long long)__shfl((long long)code, 32 * g, 64);
-        vq_emit(o, 0, th, __shfl(a_theta, 32 * g, 64), lane);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int src = 32 * g + 16 * c;
-            const unsigned long long idx = (unsigned long long)__shfl((long long)term, src, 64);
-            vq_emit(o, 0, ((okm >> src) & 1ull) ? idx : 0ull, __shfl(width, src, 64), lane);
-        }
-    }
-    return true;
-}
-
 /* ---- the split tree of one band ------------------------------------------- */
 /* region: LDS doubles for the mid/side vectors of every depth (2 n0 + 4 VQ_DEPTH:
  * depth d takes 2*ceil(n_d/2)); a leaf borrows the still unused tail of it for
@@ -552,7 +442,6 @@ __device__ __forceinline__ bool vq_quad_try(const VqView &V, VqOut &o, const dou
 __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double *x0, int n0, int bits0,
                                          double *region, int *stack, int lane)
 {
-    const double half_pi = 1.5707963267948966;           /* np.pi / 2 */
     const double *cur = x0;
     int n = n0, bits = bits0, depth = 0;
     double *reg = region;                                  /* region of the current depth */
@@ -582,13 +471,12 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
             }
             wave_lds_fence();
             const double theta = (m_l2 == 0.0) ? 0.0 : vq_atan(s_l2 / m_l2);
-            /* gain_shape_alloc(bits, half): floor(bits/half + 0.5 log2(half)) for the angle */
-            int a_theta = (int)floor((double)bits / (double)half + ldc(&V.tab.half_log2[half]));
+            /* the split rule (vq_exact.h): the angle's bits, its code and value, the mid half's bits */
+            int a_theta = vq_first_bits(bits, half, ldc(&V.tab.half_log2[half]));
             int a_rest = bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
-            /* QuantizeUniform / DequantizeUniform of theta/(pi/2) */
-            const double tn = theta / half_pi;
+            const double tn = theta / vq_half_pi;
             double theta_q = 0.0;
             unsigned long long theta_code = 0;
             if (a_theta <= 0) {
@@ -597,36 +485,17 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
                 o.flags |= PACX_ST_VQ_UNDEFINED;
                 vq_emit(o, 0, 0, 0, lane);
             } else {
-                unsigned long long code;
-                if (tn >= 1.0) {
-                    code = (1ull << (a_theta - 1)) - 1ull;
-                } else {
-                    const double factor = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull)
-                                                          : ldexp(1.0, a_theta);
-                    code = (unsigned long long)floor((factor * tn + 1.0) * 0.5);
-                }
-                vq_emit(o, 0, code, a_theta, lane);
-                theta_code = code;
-                const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-                const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                double dq = (double)(2ull * mag) / den;
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta_q = dq * half_pi;
+                theta_code = vq_angle_code(tn, a_theta);
+                vq_emit(o, 0, theta_code, a_theta, lane);
+                theta_q = vq_angle_value(theta_code, a_theta);
             }
-            /* bit_allocation_ms */
             int a_mid = 0;
             if (theta_q != 0.0) {
                 /* log2(tan(theta_q) + eps): quantised angles of up to 12 bits come from the
                    table the caller evaluated (one scalar load instead of tan + log2) */
-                double lt;
-                if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta_q > 0.0)
-                    lt = V.log2_tan[((1 << (a_theta - 1)) - 1) + (int)theta_code];
-                else
-                    lt = vq_log2_tan(theta_q);
-                const double v = ((double)a_rest - (double)(half - 1) * lt) / 2.0;
-                const double f = floor(v);
-                a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
+                const double lt = vq_log2_tan_tabled(a_theta, theta_q) ? V.log2_tan[vq_log2_tan_slot(a_theta, theta_code)]
+                                                                       : vq_log2_tan(theta_q);
+                a_mid = vq_mid_bits(a_rest, half, lt);
             }
             const int a_side = a_rest - a_mid;
             stack[2 * depth] = half;
@@ -635,17 +504,9 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
             reg = reg + 2 * half;
             depth += 1;
             VQ_S(o, 8);
-#ifdef VQ_WITH_QUAD      /* depth-first walk only: the level-by-level walk takes the trees with sibling bottom splits */
-            if (a_mid > PACX_VQ_SPLIT_BITS && a_side > PACX_VQ_SPLIT_BITS && half >= 4 && half <= 32 &&
-                depth < VQ_DEPTH && vq_quad_try(V, o, mv, sv, half, a_mid, a_side, lane)) {
-                /* both children were bottom splits: their six fields are out */
-                stack[2 * (depth - 1) + 1] = -1;            /* side done */
-                VQ_S(o, 9);
-            } else
-#endif
             if (a_mid > 0 && a_mid <= PACX_VQ_SPLIT_BITS && a_side > 0 && a_side <= PACX_VQ_SPLIT_BITS &&
-                       half >= 2 && half <= 32) {
-                VQ_S(o, 9);                                 /* a quad attempt that fell through counts as one */
+                half >= 2 && half <= 32) {
+                VQ_S(o, 9);                                 /* (keeps the leaf pair's own time in slot 10) */
                 /* both children are small leaves: code them side by side */
                 vq_leaf_pair(V, o, mv, sv, half, a_mid, a_side, lane);
                 stack[2 * (depth - 1) + 1] = -1;            /* side done */
@@ -703,8 +564,8 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
  *   - nothing is written while walking: every node keeps its field (value, width); at the end
  *     the subtree widths go bottom-up, the stream positions top-down (the reference writes depth
  *     first: angle, mid subtree, side subtree) and all fields are ORed in at once, one per lane.
- * Same arithmetic per node as vq_shape; returns false without having written anything when the
- * tree does not fit the node store (then vq_shape codes the band). */
+ * The split rule of a node is vq_exact.h's, as in vq_shape; returns false without having written
+ * anything when the tree does not fit the node store (then vq_shape codes the band). */
 #define VQ_NC 96                       /* nodes per band tree */
 #define VQ_NODE_BYTES (VQ_NC * 8 + 5 * VQ_NC * 2 + 4 * VQ_NC + 128 + 32)
 struct VqNodes {
@@ -773,7 +634,6 @@ __device__ __forceinline__ int wave_excl_scan_i32(int v, int lane, int &total)
 __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const double *x0, int n0, int bits0,
                                              double *region, int region_len, const VqNodes &N, int lane)
 {
-    const double half_pi = 1.5707963267948966;
     const unsigned long long below = (1ull << lane) - 1ull;
     const int buf_cap = region_len / 2;
     double *bufs[2] = {region, region + buf_cap};
@@ -988,11 +848,11 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const int half = has ? shalf : 1;
             const double q = has ? __longlong_as_double((long long)N.val[snode]) : -1.0;
             const double theta = (q < 0.0) ? 0.0 : vq_atan(q);
-            const int a_theta = (int)floor((double)bits / (double)half + V.tab.half_log2[half]);
+            const int a_theta = vq_first_bits(bits, half, V.tab.half_log2[half]);
             int a_rest = bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
-            const double tn = theta / half_pi;
+            const double tn = theta / vq_half_pi;
             double theta_q = 0.0;
             unsigned long long code = 0ull;
             int w_theta = 0;
@@ -1000,30 +860,15 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                 if (has)
                     undefined = true;
             } else if (a_theta > 0) {
-                if (tn >= 1.0) {
-                    code = (1ull << (a_theta - 1)) - 1ull;
-                } else {
-                    const double factor = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                    code = (unsigned long long)floor((factor * tn + 1.0) * 0.5);
-                }
+                code = vq_angle_code(tn, a_theta);
                 w_theta = a_theta;
-                const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-                const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                double dq = (double)(2ull * mag) / den;
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta_q = dq * half_pi;
+                theta_q = vq_angle_value(code, a_theta);
             }
             int a_mid = 0;
             if (theta_q != 0.0) {
-                double lt;
-                if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta_q > 0.0)
-                    lt = V.log2_tan[((1 << (a_theta - 1)) - 1) + (int)code];
-                else
-                    lt = vq_log2_tan(theta_q);
-                const double v = ((double)a_rest - (double)(half - 1) * lt) / 2.0;
-                const double f = floor(v);
-                a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
+                const double lt = vq_log2_tan_tabled(a_theta, theta_q) ? V.log2_tan[vq_log2_tan_slot(a_theta, code)]
+                                                                       : vq_log2_tan(theta_q);
+                a_mid = vq_mid_bits(a_rest, half, lt);
             }
             const int a_side = a_rest - a_mid;
             const int c_mid = (has && a_mid > 0) ? 1 : 0, c_side = (has && a_side > 0) ? 1 : 0;
@@ -1155,7 +1000,7 @@ struct VqArgs {
 
 #ifdef PACX_VQ_DEBUG
 /* phase stamps (s_memtime) summed over all waves: a measuring aid (build.py --phase-debug) */
-#define VQ_T(k) do { long long t_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
+#define VQ_T(k) do { long long t_; VQ_NOW(t_); \
                      if ((threadIdx.x & 63) == 0 && vq_last) atomicAdd((unsigned long long *)&g_vq_dbg[k], (unsigned long long)(t_ - vq_last)); \
                      vq_last = t_; } while (0)
 extern "C" int pacx_debug_read_vq(long long *out, int n)
@@ -1319,7 +1164,7 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
         o.band = b;
         o.flags = 0;
 #ifdef PACX_VQ_DEBUG
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(o.t_last) :: "memory");
+        VQ_NOW(o.t_last);
 #endif
         const double gain = gain_s[b];
         if (b >= first_omit) {
@@ -1329,7 +1174,7 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
         } else {
             const int lo = ldc(&lower[b]), cnt = ldc(&count[b]);
             const int r_bits = ba * cnt;
-            int bits_gain = (int)floor((double)r_bits / (double)cnt + ldc(&V.tab.half_log2[cnt]));
+            int bits_gain = vq_first_bits(r_bits, cnt, ldc(&V.tab.half_log2[cnt]));
             int bits_shape = r_bits - bits_gain;
             if (bits_shape < 0)
                 bits_shape = 0;
@@ -1429,7 +1274,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQ_OCC) void k_vq_redo(PacxTables T,
  *   nothing is written while walking; at the end subtree widths go bottom-up and stream positions
  *   top-down (depth-first order inside a band, bands at their static positions), every field is
  *   ORed in by its own lane, and the gains of all bands are quantised side by side.
- * Arithmetic per node is that of vq_shape / vq_leaf / vq_leaf_group.  A unit whose trees do not fit
+ * A split's rule is vq_exact.h's, the leaves are vq_leaf_idx / vq_leaf_group.  A unit whose trees do not fit
  * the store (bit rates far above the shipped ones) is left to k_vq (and k_vq_join): n_bytes = -1.
  * A short-coded frame is ONE unit too: its 8 x nb_short bands are the unit's bands, its eight strings are
  * written back to back by the same workgroup (no per-sub-block launch geometry, no join pass). */
@@ -1473,34 +1318,8 @@ struct VqfStore {
     }
 };
 
-/* QuantizeUniform(x, n_bits) for x >= 0 as vq_quantize_emit evaluates it: the code's two words */
-__device__ __forceinline__ void vq_quantize_code(double x, int n_bits, unsigned long long &hi, unsigned long long &lo)
-{
-    hi = 0;
-    lo = 0;
-    if (x >= 1.0) {
-        const int ones = n_bits - 1;
-        if (ones >= 64) {
-            lo = ~0ull;
-            hi = (ones - 64 >= 64) ? ~0ull : ((1ull << (ones - 64)) - 1ull);
-        } else {
-            lo = (ones == 0) ? 0ull : ((~0ull) >> (64 - ones));
-        }
-    } else {
-        const double factor = (n_bits <= 53) ? (double)((1ull << n_bits) - 1ull) : ldexp(1.0, n_bits);
-        const double code = floor((factor * x + 1.0) * 0.5);
-        if (n_bits <= 64) {
-            lo = (unsigned long long)code;
-        } else {
-            const double top = floor(ldexp(code, -64));
-            hi = (unsigned long long)top;
-            lo = (unsigned long long)(code - ldexp(top, 64));
-        }
-    }
-}
-
 #ifdef PACX_VQ_DEBUG
-#define VQF_SUB(k) do { long long t3_; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t3_) :: "memory"); \
+#define VQF_SUB(k) do { long long t3_; VQ_NOW_VM(t3_); \
                         if (lane == 0) atomicAdd((unsigned long long *)&g_vq_dbg[k], (unsigned long long)(t3_ - t_sub)); t_sub = t3_; } while (0)
 #else
 #define VQF_SUB(k) do { } while (0)
@@ -1520,8 +1339,7 @@ extern "C" int pacx_debug_read_vqw(long long *out, int n, int clear)
     }
     return rc;
 }
-#define VQW_NOW(v) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
-#define VQW_BARRIER(busy, wait) do { long long a_, b_; VQW_NOW(a_); __syncthreads(); VQW_NOW(b_); \
+#define VQW_BARRIER(busy, wait) do { long long a_, b_; VQ_NOW(a_); __syncthreads(); VQ_NOW(b_); \
                                      busy += a_ - vqw_t; wait += b_ - a_; vqw_t = b_; } while (0)
 #else
 #define VQW_BARRIER(busy, wait) __syncthreads()
@@ -1541,7 +1359,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 {
 #ifdef PACX_VQ_DEBUG
     long long vqf_last = 0;
-#define VQF_T(k) do { long long t_; asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
+#define VQF_T(k) do { long long t_; VQ_NOW(t_); \
                       if (threadIdx.x == 0 && vqf_last) atomicAdd((unsigned long long *)&g_vq_dbg[k], (unsigned long long)(t_ - vqf_last)); \
                       vqf_last = t_; } while (0)
 #else
@@ -1568,9 +1386,9 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef PACX_VQ_WAITDBG
     long long vqw_start, vqw_p;
-    VQW_NOW(vqw_start);
+    VQ_NOW(vqw_start);
     vqw_p = vqw_start;
-#define VQW_P(k) do { long long n_; VQW_NOW(n_); if (tid == 0) atomicAdd((unsigned long long *)&g_vqw_dbg[21 + (k)], (unsigned long long)(n_ - vqw_p)); vqw_p = n_; } while (0)
+#define VQW_P(k) do { long long n_; VQ_NOW(n_); if (tid == 0) atomicAdd((unsigned long long *)&g_vqw_dbg[21 + (k)], (unsigned long long)(n_ - vqw_p)); vqw_p = n_; } while (0)
 #else
 #define VQW_P(k) do { } while (0)
 #endif
@@ -1607,7 +1425,6 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     const int first_omit = (!is_short && T.use_sbr) ? T.first_omitted : nb;
     const long long boff = cf * T.band_stride;
     const double *__restrict__ lin = A.lines + cf * PACX_M_LONG;
-    const double half_pi = 1.5707963267948966;
     /* band vb = j nb + b */
     auto sub_of = [&](int vb) { return is_short ? vb / nb : 0; };
 
@@ -1711,7 +1528,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
         /* gain_shape_alloc of the band; an omitted band is one number: every bit to its gain */
         int bits_gain = ba, bits_shape = 0;
         if (vb < n_vb && b < first_omit && ba) {
-            bits_gain = (int)floor((double)r_bits / (double)cnt + V.tab.half_log2[cnt]);
+            bits_gain = vq_first_bits(r_bits, cnt, V.tab.half_log2[cnt]);
             bits_shape = r_bits - bits_gain;
             if (bits_shape < 0)
                 bits_shape = 0;
@@ -1817,7 +1634,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     VQF_T(0);
 #ifdef PACX_VQ_WAITDBG
     long long vqw_busy1 = 0, vqw_wait1 = 0, vqw_busy2 = 0, vqw_wait2 = 0, vqw_t, vqw_t0, vqw_levels = 0;
-    VQW_NOW(vqw_t);
+    VQ_NOW(vqw_t);
     vqw_t0 = vqw_t;
 #endif
     bool undefined = false;
@@ -1837,7 +1654,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
         auto do_item = [&](int c, int p0, int p_n) {
 #ifdef PACX_VQ_DEBUG
             long long t_in;
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_in) :: "memory");
+            VQ_NOW(t_in);
 #endif
             if (c <= 1) {
                 /* leaves, four or two per pass */
@@ -1968,7 +1785,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #ifdef PACX_VQ_DEBUG
             {
                 long long t_out;
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_out) :: "memory");
+                VQ_NOW_VM(t_out);
                 if (lane == 0) {
                     atomicAdd((unsigned long long *)&g_vq_dbg[8 + c], (unsigned long long)(t_out - t_in));
                     atomicAdd((unsigned long long *)&g_vq_dbg[16 + c], 1ull);
@@ -2007,9 +1824,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
         for (int k0 = 64 * wave; k0 < s_n; k0 += 64 * VQ_WAVES) {
 #ifdef PACX_VQ_DEBUG
             long long t_sc;
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_sc) :: "memory");
-#endif
-#ifdef PACX_VQ_DEBUG
+            VQ_NOW(t_sc);
             long long t_sub = t_sc;
 #endif
             const bool has = k0 + lane < s_n;
@@ -2025,49 +1840,29 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #endif
             VQF_SUB(26);
             const double hl = (half < VQF_HL) ? vqf_half_log2[half] : V.tab.half_log2[half];
-            const int a_theta = (int)floor((double)bits / (double)half + hl);
+            const int a_theta = vq_first_bits(bits, half, hl);
             int a_rest = bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
-            const double tn = theta / half_pi;
+            const double tn = theta / vq_half_pi;
             double theta_q = 0.0;
             unsigned long long code = 0ull;
             int w_theta = 0;
             if (!__builtin_amdgcn_ballot_w64(a_theta > 31)) {
-                /* every angle of this chunk has at most 31 bits (all but freak allocations): the same values
-                   in 32-bit integers -- one conversion instruction where the 64-bit ones take a dozen */
+                /* every angle of this chunk has at most 31 bits (all but freak allocations): the 32-bit form */
                 if (a_theta > 0) {
-                    const double factor = (double)((1u << a_theta) - 1u);
-                    unsigned c32;
-                    if (tn >= 1.0)
-                        c32 = (1u << (a_theta - 1)) - 1u;
-                    else
-                        c32 = (unsigned)floor((factor * tn + 1.0) * 0.5);
+                    const unsigned c32 = vq_angle_code32(tn, a_theta);
                     code = c32;
                     w_theta = a_theta;
-                    const unsigned mag = c32 & ((1u << (a_theta - 1)) - 1u);
-                    double dq = (double)(2u * mag) / factor;
-                    if (c32 >> (a_theta - 1))
-                        dq = -dq;
-                    theta_q = dq * half_pi;
+                    theta_q = vq_angle_value32(c32, a_theta);
                 }
             } else if (a_theta > 62) {
                 if (has)
                     undefined = true;
             } else if (a_theta > 0) {
-                if (tn >= 1.0) {
-                    code = (1ull << (a_theta - 1)) - 1ull;
-                } else {
-                    const double factor = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                    code = (unsigned long long)floor((factor * tn + 1.0) * 0.5);
-                }
+                code = vq_angle_code(tn, a_theta);
                 w_theta = a_theta;
-                const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-                const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                double dq = (double)(2ull * mag) / den;
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta_q = dq * half_pi;
+                theta_q = vq_angle_value(code, a_theta);
             }
             if (GUARD && has && a_theta > 0 && a_theta <= 53 && pacx_quant_guard(tn, a_theta, 1e-13))
                 guarded = true;                              /* the split angle sits at a boundary of its quantiser */
@@ -2075,15 +1870,13 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
             int a_mid = 0;
             if (theta_q != 0.0) {
                 double lt;
-                if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta_q > 0.0) {
-                    const int at_lt = ((1 << (a_theta - 1)) - 1) + (int)code;
+                if (vq_log2_tan_tabled(a_theta, theta_q)) {
+                    const int at_lt = vq_log2_tan_slot(a_theta, code);
                     lt = (at_lt < VQF_LT) ? vqf_log2_tan[at_lt] : V.log2_tan[at_lt];
-                }
-                else
+                } else {
                     lt = vq_log2_tan(theta_q);
-                const double v = ((double)a_rest - (double)(half - 1) * lt) / 2.0;
-                const double f = floor(v);
-                a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
+                }
+                a_mid = vq_mid_bits(a_rest, half, lt);
             }
             VQF_SUB(28);
             const int a_side = a_rest - a_mid;
@@ -2131,7 +1924,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #ifdef PACX_VQ_DEBUG
             {
                 long long t2_;
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t2_) :: "memory");
+                VQ_NOW_VM(t2_);
                 if (lane == 0) {
                     atomicAdd((unsigned long long *)&g_vq_dbg[24], (unsigned long long)(t2_ - t_sc));
                     atomicAdd((unsigned long long *)&g_vq_dbg[25], 1ull);
@@ -2196,7 +1989,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #ifdef PACX_VQ_WAITDBG
     {
         long long t_end;
-        VQW_NOW(t_end);
+        VQ_NOW(t_end);
         if (lane == 0) {
             atomicAdd((unsigned long long *)&g_vqw_dbg[wave * 4 + 0], (unsigned long long)vqw_busy1);
             atomicAdd((unsigned long long *)&g_vqw_dbg[wave * 4 + 1], (unsigned long long)vqw_wait1);
@@ -2251,7 +2044,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     }
     VQF_T(4);
 #ifdef PACX_VQ_WAITDBG
-    VQW_NOW(vqw_p);
+    VQ_NOW(vqw_p);
 #endif
     /* ---- every field by its own lane */
     for (int j = tid; j < n_nodes; j += 64 * VQ_WAVES) {
@@ -2295,7 +2088,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
                 undefined = true;
                 width = 0;
             } else if (bits_gain > 0) {
-                vq_quantize_code(g, bits_gain, hi, lo);
+                vq_quantize_wide(g, bits_gain, hi, lo);
                 if (GUARD && bits_gain <= 53 && pacx_quant_guard(g, bits_gain, 1e-13))
                     guarded = true;                          /* the band's mu-law gain sits at a boundary of its index */
             }
@@ -2343,7 +2136,7 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
 #ifdef PACX_VQ_WAITDBG
     {
         long long t_fin;
-        VQW_NOW(t_fin);
+        VQ_NOW(t_fin);
         if (tid == 0)
             atomicAdd((unsigned long long *)&g_vqw_dbg[20], (unsigned long long)(t_fin - vqw_start));         /* whole unit */
     }

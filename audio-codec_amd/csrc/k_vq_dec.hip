@@ -28,6 +28,7 @@
 #include "../../include/pacx.h"
 #include "pacx_launch.h"
 #include "pvq_dev.h"
+#include "vq_exact.h" /* the split rule, as the coder evaluates it */
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "wave_np_sum.h"
 
@@ -242,7 +243,6 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
                                           int out0, int n0, int bits0, int reg0, VqdFrame *fr, int lane,
                                           unsigned &flags)
 {
-    const double half_pi = 1.5707963267948966;
     if (bits0 <= PACX_VQ_SPLIT_BITS) {
         /* the non-split branch normalises a second time (:468-472) */
         vqd_leaf(V, words, pos, scr + out0, n0, bits0, lane, flags);
@@ -259,35 +259,25 @@ __device__ __forceinline__ void vqd_shape(const VqDecView &V, const unsigned *wo
                 return;
             }
             const int half = cur_n - cur_n / 2;
-            int a_theta = (int)floor((double)cur_bits / (double)half + V.tab.half_log2[half]);
+            /* the split rule (vq_exact.h), as the coder evaluated it */
+            int a_theta = vq_first_bits(cur_bits, half, V.tab.half_log2[half]);
             int a_rest = cur_bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
             double theta = 0.0;
             unsigned long long theta_code = 0;
             if (a_theta > 0 && a_theta <= 62) {
-                const unsigned long long code = vqd_get(words, pos, a_theta);
-                theta_code = code;
-                const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-                const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                double dq = (double)(2ull * mag) / den;
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta = dq * half_pi;
+                theta_code = vqd_get(words, pos, a_theta);
+                theta = vq_angle_value(theta_code, a_theta);
             } else if (a_theta > 62) {
                 flags |= PACX_ST_VQ_UNDEFINED;
             }
             pos += a_theta > 0 ? a_theta : 0;
             int a_mid = 0;
             if (theta != 0.0) {
-                double lt;
-                if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta > 0.0)
-                    lt = V.log2_tan[((1 << (a_theta - 1)) - 1) + (int)theta_code];
-                else
-                    lt = log2(tan(fabs(theta)) + PACX_EPS);
-                const double v = ((double)a_rest - (double)(half - 1) * lt) / 2.0;
-                const double f = floor(v);
-                a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
+                const double lt = vq_log2_tan_tabled(a_theta, theta) ? V.log2_tan[vq_log2_tan_slot(a_theta, theta_code)]
+                                                                     : log2(tan(fabs(theta)) + PACX_EPS);
+                a_mid = vq_mid_bits(a_rest, half, lt);
             }
             VqdFrame &F = fr[depth];
             if (lane == 0) {
@@ -524,7 +514,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES) void k_vq_dec(PacxTables T, VqDecVi
             at = lower[T.first_omitted] + (b - T.first_omitted);
         }
         const int r_bits = ba * n;
-        int bits_gain = (int)floor((double)r_bits / (double)n + V.tab.half_log2[n]);
+        int bits_gain = vq_first_bits(r_bits, n, V.tab.half_log2[n]);
         int bits_shape = r_bits - bits_gain;
         if (bits_shape < 0)
             bits_shape = 0;
@@ -789,7 +779,6 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
     const int nb = shrt ? T.nb_short : T.nb_long;
     const int32_t *__restrict__ lower = shrt ? T.band_lower_short : T.band_lower_long;
     const int32_t *__restrict__ count = shrt ? T.band_lines_short : T.band_lines_long;
-    const double half_pi = 1.5707963267948966;
     bool undefined = false;
 
     /* ---- 1. parse: one band per lane */
@@ -801,7 +790,7 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
         if (live && sbr && b >= T.first_omitted)
             n = 1;
         const int r_bits = live ? item_ba[vb] * n : 0;
-        int bits_gain = live ? (int)floor((double)r_bits / (double)n + V.tab.half_log2[n]) : 0;
+        int bits_gain = live ? vq_first_bits(r_bits, n, V.tab.half_log2[n]) : 0;
         int bits_shape = r_bits - bits_gain;
         if (bits_shape < 0)
             bits_shape = 0;
@@ -893,44 +882,28 @@ __global__ __launch_bounds__(64 * VQD_WAVES, 5) void k_vq_dec_frame(PacxTables T
             }
             /* split: the angle, the bit split */
             const int half = c_n - c_n / 2;
-            const int a_theta = (int)floor((double)c_bits / (double)half + V.tab.half_log2[half]);
+            const int a_theta = vq_first_bits(c_bits, half, V.tab.half_log2[half]);
             int a_rest = c_bits - a_theta;
             if (a_rest < 0)
                 a_rest = 0;
             double theta = 0.0;
             unsigned long long theta_code = 0;
-            if (a_theta > 0 && a_theta <= 31) {
-                /* (the same values in 32-bit integers: one conversion instruction where the 64-bit ones take a dozen) */
+            if (a_theta > 0 && a_theta <= 31) {          /* the 32-bit form */
                 const unsigned code = (unsigned)vqd_get(words, pos, a_theta);
                 theta_code = code;
-                const unsigned mag = code & ((1u << (a_theta - 1)) - 1u);
-                double dq = (double)(2u * mag) / (double)((1u << a_theta) - 1u);
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta = dq * half_pi;
+                theta = vq_angle_value32(code, a_theta);
             } else if (a_theta > 0 && a_theta <= 62) {
-                const unsigned long long code = vqd_get(words, pos, a_theta);
-                theta_code = code;
-                const unsigned long long mag = code & ((1ull << (a_theta - 1)) - 1ull);
-                const double den = (a_theta <= 53) ? (double)((1ull << a_theta) - 1ull) : ldexp(1.0, a_theta);
-                double dq = (double)(2ull * mag) / den;
-                if (code >> (a_theta - 1))
-                    dq = -dq;
-                theta = dq * half_pi;
+                theta_code = vqd_get(words, pos, a_theta);
+                theta = vq_angle_value(theta_code, a_theta);
             } else if (a_theta > 62) {
                 undefined = true;
             }
             pos += a_theta > 0 ? a_theta : 0;
             int a_mid = 0;
             if (theta != 0.0) {
-                double lt;
-                if (a_theta <= PACX_VQ_THETA_TABLE_BITS && theta > 0.0)
-                    lt = V.log2_tan[((1 << (a_theta - 1)) - 1) + (int)theta_code];
-                else
-                    lt = log2(tan(fabs(theta)) + PACX_EPS);
-                const double v = ((double)a_rest - (double)(half - 1) * lt) / 2.0;
-                const double f = floor(v);
-                a_mid = (f < 0.0) ? 0 : ((f > (double)a_rest) ? a_rest : (int)f);
+                const double lt = vq_log2_tan_tabled(a_theta, theta) ? V.log2_tan[vq_log2_tan_slot(a_theta, theta_code)]
+                                                                     : log2(tan(fabs(theta)) + PACX_EPS);
+                a_mid = vq_mid_bits(a_rest, half, lt);
             }
             N.kind[id] = 0;
             N.theta[id] = theta;

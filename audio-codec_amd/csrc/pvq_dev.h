@@ -3,6 +3,8 @@
  * (k_vq_dec.hip) share: the resident tables, the codebook sizes N(l,k) / P(l,k) with their closed
  * forms for l <= 2, and the wave helpers both walks use.  No kernels and no LDS here: the LDS
  * copies of the row offsets and the per-kernel sizing stay with the kernels they are tuned for.
+ * The other thing the two files share, the scalar rule of a split (angle bits, angle code and
+ * value, mid/side bits) and the gain's quantiser, is vq_exact.h: it also builds for the host.
  */
 #ifndef PACX_PVQ_DEV_H
 #define PACX_PVQ_DEV_H

@@ -1,7 +1,8 @@
-// Host build of audio-codec_amd/csrc/pacx_exact.h for the CPU test suite:
+// Host build of audio-codec_amd/csrc/pacx_exact.h and vq_exact.h for the CPU test suite:
 // the same source the HIP kernels compile, exported for ctypes.
 #include "pacx_exact.h"
 #include "pacx_vq_tables.h"
+#include "vq_exact.h"
 
 extern "C" {
 double hc_pcm16_to_f64(int c) { return pacx_pcm16_to_f64(c); }
@@ -47,4 +48,18 @@ int hc_vq_w(int l, int bits) { return g_vq.w_of[(size_t)l * 33 + bits]; }
 int hc_vq_row_len(int l) { return g_vq.row_len[l]; }
 unsigned long long hc_vq_n(int l, int k) { return g_vq.n_tab[g_vq.row_off[l] + k]; }
 unsigned long long hc_vq_p(int l, int k) { return g_vq.p_tab[g_vq.row_off[l] + k]; }
+
+/* the split rule of the gain-shape coder and decoder (vq_exact.h) */
+double hc_vq_half_pi(void) { return vq_half_pi; }
+int hc_vq_first_bits(int bits, int l, double half_log2_l) { return vq_first_bits(bits, l, half_log2_l); }
+unsigned long long hc_vq_angle_code(double tn, int a) { return vq_angle_code(tn, a); }
+unsigned hc_vq_angle_code32(double tn, int a) { return vq_angle_code32(tn, a); }
+double hc_vq_angle_value(unsigned long long code, int a) { return vq_angle_value(code, a); }
+double hc_vq_angle_value32(unsigned code, int a) { return vq_angle_value32(code, a); }
+int hc_vq_log2_tan_tabled(int a, double theta_q) { return vq_log2_tan_tabled(a, theta_q); }
+int hc_vq_log2_tan_slot(int a, unsigned long long code) { return vq_log2_tan_slot(a, code); }
+int hc_vq_theta_table_bits(void) { return PACX_VQ_THETA_TABLE_BITS; }
+int hc_vq_mid_bits(int a_rest, int half, double lt) { return vq_mid_bits(a_rest, half, lt); }
+void hc_vq_quantize_wide(double x, int n_bits, unsigned long long *hi, unsigned long long *lo)
+{ vq_quantize_wide(x, n_bits, *hi, *lo); }
 }

@@ -1,6 +1,7 @@
 """CPU checks of audio-codec_amd/csrc/pacx_exact.h (the order-sensitive scalar
-arithmetic shared by the HIP kernels) against the oracle: the header is built
-for the host with g++ and driven through ctypes.  No GPU needed."""
+arithmetic shared by the HIP kernels) and vq_exact.h (the split rule of the
+gain-shape coder and decoder) against the oracle: the headers are built for
+the host with g++ and driven through ctypes.  No GPU needed."""
 import ctypes
 import os
 import subprocess
@@ -391,3 +392,126 @@ def test_guard_band_of_the_quantiser(hc):
         assert hc.hc_scale_factor(edge * (1 - 1e-12), 4, 5) != hc.hc_scale_factor(edge * (1 + 1e-12), 4, 5)
         assert hc.hc_scale_guard(edge, 4, 5, err)
         assert not hc.hc_scale_guard(edge * 1.37, 4, 5, err)
+
+
+# ------------------------------------------------- the split rule of the gain-shape coder (vq_exact.h)
+@pytest.fixture(scope="module")
+def vq(hc):
+    hc.hc_vq_first_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    hc.hc_vq_angle_code.restype = ctypes.c_ulonglong
+    hc.hc_vq_angle_code.argtypes = [ctypes.c_double, ctypes.c_int]
+    hc.hc_vq_angle_code32.restype = ctypes.c_uint
+    hc.hc_vq_angle_code32.argtypes = [ctypes.c_double, ctypes.c_int]
+    hc.hc_vq_angle_value.restype = ctypes.c_double
+    hc.hc_vq_angle_value.argtypes = [ctypes.c_ulonglong, ctypes.c_int]
+    hc.hc_vq_angle_value32.restype = ctypes.c_double
+    hc.hc_vq_angle_value32.argtypes = [ctypes.c_uint, ctypes.c_int]
+    hc.hc_vq_log2_tan_tabled.argtypes = [ctypes.c_int, ctypes.c_double]
+    hc.hc_vq_log2_tan_slot.argtypes = [ctypes.c_int, ctypes.c_ulonglong]
+    hc.hc_vq_mid_bits.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    hc.hc_vq_half_pi.restype = ctypes.c_double
+    hc.hc_vq_quantize_wide.restype = None
+    hc.hc_vq_quantize_wide.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return hc
+
+
+def _boundary_codes(a):
+    """the first 16 and the last 16 magnitude codes c >= 1 of an a-bit angle"""
+    top = 2 ** (a - 1) - 1
+    return sorted(c for c in set(range(1, 17)) | set(range(top - 15, top + 1)) if 1 <= c <= top)
+
+
+def _angle_inputs(a):
+    """tn = theta / (pi/2): the ends, 200 seeded values, every decision boundary (2c - 1) / (2^a - 1) of the
+    boundary codes with its two neighbouring doubles"""
+    tn = [0.0, 1.0, float(np.nextafter(1.0, 0.0))]
+    tn += np.random.default_rng(1000 + a).uniform(0.0, 1.0, 200).tolist()
+    for c in _boundary_codes(a):
+        edge = (2 * c - 1) / (2 ** a - 1)
+        tn += [float(np.nextafter(edge, 0.0)), edge, float(np.nextafter(edge, 2.0))]
+    return [t for t in tn if t <= 1.0]
+
+
+def test_vq_first_bits_equal_gain_shape_alloc(vq):
+    """(a) the bits of a split's angle and of a band's gain: gain_shape_alloc(r, l)[0]"""
+    from oracle import pac_oracle_vq as pv
+    assert vq.hc_vq_half_pi() == np.pi / 2
+    for l in list(range(1, 183)) + [256, 304, 363]:
+        for r in (1, 2, 31, 32, 33, 34, 64, 100, 500, 2000, 12 * l):
+            assert vq.hc_vq_first_bits(r, l, float(0.5 * np.log2(l))) == pv.gain_shape_alloc(r, l)[0], (r, l)
+
+
+def test_vq_angle_code_and_value_equal_the_oracle(vq):
+    """(b) the 64-bit form against quantize_uniform / dequantize_uniform, every width the walkers accept"""
+    for a in range(1, 63):
+        for tn in _angle_inputs(a):
+            code = vq.hc_vq_angle_code(tn, a)
+            assert code == po.quantize_uniform(tn, a), (tn, a)
+            assert vq.hc_vq_angle_value(code, a) == po.dequantize_uniform(code, a) * (np.pi / 2), (tn, a, code)
+
+
+def test_vq_angle_32_bit_form_equals_the_64_bit_form(vq):
+    """(c) what k_vq_frame and k_vq_dec_frame evaluate in 32-bit integers for angles of up to 31 bits"""
+    for a in range(1, 32):
+        codes = set()
+        for tn in _angle_inputs(a):
+            code = vq.hc_vq_angle_code(tn, a)
+            assert vq.hc_vq_angle_code32(tn, a) == code, (tn, a)
+            codes.add(code)
+        if a <= 12:
+            codes |= set(range(2 ** a))                       # every code, the negative ones included
+        for code in sorted(codes):
+            want = vq.hc_vq_angle_value(code, a)
+            got = vq.hc_vq_angle_value32(code, a)
+            assert got == want and np.signbit(got) == np.signbit(want), (code, a)
+            if a <= 12:
+                assert want == po.dequantize_uniform(code, a) * (np.pi / 2), (code, a)
+
+
+def test_vq_mid_bits_equal_mid_side_alloc(vq):
+    """(d) the mid half's bits for the quantised angles, log2(tan) taken from numpy as the table's entries are"""
+    from oracle import pac_oracle_vq as pv
+    for a in range(1, 15):
+        codes = {vq.hc_vq_angle_code(tn, a) for tn in _angle_inputs(a)}
+        if a <= 8:
+            codes |= set(range(2 ** a))
+        for code in sorted(codes):
+            theta_q = vq.hc_vq_angle_value(code, a)
+            if theta_q == 0.0:
+                continue                                      # the caller's case: no bits for the mid half
+            assert theta_q == po.dequantize_uniform(code, a) * (np.pi / 2)
+            lt = float(np.log2(np.tan(abs(theta_q)) + pv.EPS))
+            for half in (1, 2, 3, 8, 16, 33, 91, 182):
+                for a_rest in (0, 1, 33, 64, 500, 4000):
+                    assert vq.hc_vq_mid_bits(a_rest, half, lt) == pv.mid_side_alloc(a_rest, theta_q, half)[0], \
+                        (a, code, half, a_rest)
+
+
+def test_vq_log2_tan_slots_cover_the_table(vq):
+    """the positive angle codes of 1..12 bits enumerate the 2^12 - 1 table slots in order, without gaps"""
+    bits = vq.hc_vq_theta_table_bits()
+    assert bits == 12
+    slots = [vq.hc_vq_log2_tan_slot(a, code) for a in range(1, bits + 1) for code in range(2 ** (a - 1))]
+    assert slots == list(range(2 ** bits - 1))
+    assert vq.hc_vq_log2_tan_tabled(bits, 0.1) and not vq.hc_vq_log2_tan_tabled(bits + 1, 0.1)
+    assert not vq.hc_vq_log2_tan_tabled(3, -0.1) and not vq.hc_vq_log2_tan_tabled(3, 0.0)
+
+
+def test_vq_quantize_wide_equals_the_reference_rule(vq):
+    """(e) the mu-law gain's index of up to 128 bits: coder/quantize.py:29-32 in Python's arithmetic -- an exact
+    integer factor up to 53 bits; beyond, the reference's own float64 steps (factor 2.0**n, one multiply, + 1,
+    floor-divide by 2)"""
+    xs = [0.0, 0.5, float(np.nextafter(1.0, 0.0)), 1.0, 1.5] + np.random.default_rng(77).uniform(0.0, 1.0, 50).tolist()
+    for n in (1, 2, 31, 32, 33, 53, 54, 63, 64, 65, 100, 128):
+        for x in xs:
+            if x >= 1.0:
+                want = 2 ** (n - 1) - 1
+            elif n <= 53:
+                want = int(((2 ** n - 1) * x + 1) // 2)
+                assert want == po.quantize_uniform(x, n)
+            else:
+                assert float(2 ** n - 1) == 2.0 ** n
+                want = int(np.floor_divide(np.float64(2.0 ** n) * np.float64(x) + np.float64(1.0), np.float64(2.0)))
+            hi, lo = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+            vq.hc_vq_quantize_wide(x, n, ctypes.byref(hi), ctypes.byref(lo))
+            assert (hi.value << 64) | lo.value == want, (x, n)
