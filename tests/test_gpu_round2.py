@@ -458,58 +458,115 @@ def test_scalar_sbr_block_mirrors(A, torch):
 
 
 # ------------------------------------------- transient detector: exact ties of peak / avg against 4.5
-def _tie_hop(rng, n_ch):
+TIE_BUFSIZE = 8192                     # NumPy's buffer: np.add.reduce starts a second pairwise run there (PACX_NP_BUFSIZE)
+TIE_A_MIN = {6: 866, 8: 525}           # peak columns from which n_ch * (a + 500) > 8192 (8 * (524 + 500) is 8192 itself)
+
+
+def _tie_hop(rng, n_ch, a_min=0):
     """one hop [1024, n_ch] of int16 whose peak-to-average ratio is EXACTLY 4.5 in rational arithmetic:
-    peak code P = 9 q in channel 0 at column a, upto = a + 500 columns counted (zeros past 1024), the codes
-    of all channels over those columns summing to 2 P n / 9 with n = n_ch * upto"""
+    peak code P = 9 q in channel 0 at column a >= a_min, upto = a + 500 columns counted (zeros past 1024), the codes
+    of all channels over those columns summing to 2 P n / 9 with n = n_ch * upto.  The detector's upto is the LARGEST
+    first-maximum column of any channel plus 500, so the first maximum of every channel but 0 is moved to a column
+    not after a (two codes of that channel change places; the sum stays), and its codes past the counted columns
+    stay at or below that maximum: a tie whatever the number of channels."""
     while True:
         q = int(rng.integers(1, 40))
         P = 9 * q
-        a = int(rng.integers(0, 1024))
+        a = int(rng.integers(a_min, 1024))
         upto = min(a + 500, 2048)
         cols = min(upto, 1024)
-        S = 2 * q * n_ch * upto                       # sum over the counted columns of every channel
-        m = np.zeros((n_ch, 1024), dtype=np.int64)
-        free = [(ch, i) for ch in range(n_ch) for i in range(cols) if (ch, i) != (0, a)]
-        rest = S - P
-        # codes before the peak stay below P (the first maximum is at a); the others at most P - 1 as well
-        if rest < 0 or rest > (P - 1) * len(free):
+        n_free = n_ch * cols - 1
+        rest = 2 * q * n_ch * upto - P
+        if rest < 0 or rest > (P - 1) * n_free:
             continue
-        base, extra = divmod(rest, len(free))
-        vals = np.full(len(free), base, dtype=np.int64)
-        vals[rng.permutation(len(free))[:extra]] += 1
-        for _ in range(4 * len(free)):                # shuffle mass around, the sum stays
-            i, j = rng.integers(0, len(free), 2)
-            d = int(rng.integers(0, P))
-            if vals[i] + d <= P - 1 and vals[j] - d >= 0:
-                vals[i] += d
-                vals[j] -= d
-        for (ch, i), v in zip(free, vals):
-            m[ch, i] = v
+        base, extra = divmod(rest, n_free)
+        vals = np.full(n_free, base, dtype=np.int64)
+        vals[rng.permutation(n_free)[:extra]] += 1
+        for _ in range(8):                            # shuffle mass around between drawn pairs, the sum stays
+            order = rng.permutation(n_free)
+            i, j = order[:n_free // 2], order[n_free // 2:2 * (n_free // 2)]
+            d = rng.integers(0, P, len(i))
+            ok = (vals[i] + d <= P - 1) & (vals[j] - d >= 0)
+            vals[i] += np.where(ok, d, 0)
+            vals[j] -= np.where(ok, d, 0)
+        m = np.zeros((n_ch, 1024), dtype=np.int64)
+        flat = np.delete(np.arange(n_ch * cols), a)   # (channel, column) of the free codes, channel-major; (0, a) left out
+        m[flat // cols, flat % cols] = vals
         m[0, a] = P
-        for ch in range(n_ch):                        # columns past upto do not count: anything below the peak
-            m[ch, cols:] = rng.integers(0, P, 1024 - cols)
-        assert m[:, :cols].sum() == S and m.max() == P and int(np.argmax(m[0])) == a
+        m[0, cols:] = rng.integers(0, P, 1024 - cols)
+        for ch in range(1, n_ch):
+            first, to = int(np.argmax(m[ch, :cols])), int(rng.integers(0, a + 1))
+            if first > a:
+                m[ch, first], m[ch, to] = m[ch, to], m[ch, first]
+            m[ch, cols:] = rng.integers(0, m[ch, :cols].max() + 1, 1024 - cols)
+        assert m[:, :cols].sum() == 2 * q * n_ch * upto and m.max() == P and int(np.argmax(m[0])) == a
+        assert np.argmax(m, axis=1).max() == a
         sign = rng.choice([-1, 1], size=m.shape)
         return (m * sign).T.astype(np.int16)
 
 
-@pytest.mark.parametrize("n_ch", [1, 2])
+def _tie_reference(A, pcm, n_ch):
+    """detect_transients.hop_transients (the reference expression on float64) of every hop of int16 [n * 1024, n_ch]"""
+    n_hops = len(pcm) // 1024
+    return A.detect_transients.hop_transients(
+        np.stack([A.pcmfile.codes_to_fraction(pcm[:, ch]) for ch in range(n_ch)]).reshape(n_ch, n_hops, 1024).transpose(1, 0, 2))
+
+
+def _tie_counts(pcm, n_ch):
+    """(upto, exact tie) of every hop, as the detector counts: upto = the largest first-maximum column of any channel
+    plus 500; a tie where 2 P n = 9 S for the peak code P, n = n_ch * upto and S the sum of the codes counted"""
+    mag = np.abs(pcm.astype(np.int64)).reshape(-1, 1024, n_ch)
+    upto = np.minimum(mag.argmax(axis=1).max(axis=1) + 500, 2048)
+    counted = np.arange(1024)[None, :, None] < upto[:, None, None]
+    return upto, 2 * mag.max(axis=(1, 2)) * n_ch * upto == 9 * (mag * counted).sum(axis=(1, 2))
+
+
+def _tie_decisions(A, enc, planar, n_hops):
+    tr, _ = enc.transient_flags(planar, n_hops)
+    return tr.cpu().numpy().astype(bool)
+
+
+@pytest.mark.parametrize("n_ch", [1, 2, 3, 5, 6, 8])
 def test_transient_detector_exact_ties(A, torch, n_ch):
     """Quiet passages of small codes put peak / avg exactly on the detector's threshold now and then (a parity
     soak found one stream in two thousand): coder/detect_transients.py:20-21 then goes by the rounding of its
     pairwise float mean.  k_transient decides by integers and redoes that mean in NumPy's order at a tie:
-    600 constructed ties per channel count, decisions equal to the reference expression's."""
+    600 constructed ties per channel count, decisions equal to the reference expression's.  One and two channels take
+    the kernel's register body, three and more its strided one.  With six and eight channels 200 further ties have
+    their peak so late that n_ch * upto passes 8192 elements, where NumPy's sum is made of more than one pairwise run;
+    and the two-channel ties are given once more as a view one sample off its alignment, which the strided body
+    serves.  That every hop is a tie in integers is asserted.  (Until the strided body was tested, _tie_hop let the
+    other channels have their maximum after channel 0's, which moves upto -- 267 of the 600 two-channel hops were
+    ties -- and shuffled codes in a Python loop, 15 s for that case.)"""
     rng = np.random.default_rng(2024 + n_ch)
     hops = [_tie_hop(rng, n_ch) for _ in range(600)]
     pcm = np.concatenate(hops)
-    want = A.detect_transients.hop_transients(
-        np.stack([A.pcmfile.codes_to_fraction(pcm[:, ch]) for ch in range(n_ch)]).reshape(n_ch, len(hops), 1024).transpose(1, 0, 2))
+    want = _tie_reference(A, pcm, n_ch)
     enc = A.context.encoder(48000, 128 / 48.0)
     tr, _ = enc.transient_flags(A.pacfile.device_stream(enc, pcm), len(hops))
     got = tr.cpu().numpy().astype(bool)
     assert got.tolist() == want.tolist(), f"{int((got != want).sum())} of {len(hops)} tie hops decided differently"
     print(f"exact ties, {n_ch} channel(s): {int(want.sum())} of {len(hops)} are transients to the reference")
+    assert _tie_counts(pcm, n_ch)[1].all()
+    if n_ch == 2:                          # the strided body at the channel count the register body normally serves
+        aligned = A.pacfile.device_stream(enc, pcm)
+        flat = torch.zeros(aligned.numel() + 8, dtype=torch.int16, device=enc.device)
+        off = flat[1:1 + aligned.numel()].view(aligned.shape)
+        off.copy_(aligned)
+        assert aligned.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 2 and off.is_contiguous()
+        got = _tie_decisions(A, enc, off, len(hops))
+        assert got.tolist() == want.tolist(), \
+            f"{int((got != want).sum())} of {len(hops)} tie hops decided differently through the view off its alignment"
+    if n_ch in TIE_A_MIN:
+        hops = [_tie_hop(rng, n_ch, TIE_A_MIN[n_ch]) for _ in range(200)]
+        pcm = np.concatenate(hops)
+        upto, ties = _tie_counts(pcm, n_ch)
+        assert ties.all() and (n_ch * upto > TIE_BUFSIZE).all() and n_ch * (TIE_A_MIN[n_ch] - 1 + 500) <= TIE_BUFSIZE
+        want = _tie_reference(A, pcm, n_ch)
+        got = _tie_decisions(A, enc, A.pacfile.device_stream(enc, pcm), len(hops))
+        assert got.tolist() == want.tolist(), \
+            f"{int((got != want).sum())} of {len(hops)} tie hops past NumPy's buffer border decided differently"
+        print(f"exact ties past {TIE_BUFSIZE} elements, {n_ch} channels: {int(want.sum())} of {len(hops)} are transients")
 
 
 # ------------------------------------------- an exactly zero MDCT line and the reference's SPL(0) rule
