@@ -188,6 +188,25 @@ CURVE_TAILS = {
 }
 SIGNATURES.update({f"pacx_{kind}_{op}": (ctypes.c_int, [_P, _I64, *head, _P, _P, _P, *tail])
                    for kind, head in CURVE_HEADS.items() for op, tail in CURVE_TAILS.items()})
+
+
+class PacxBucket(ctypes.Structure):
+    """pacx_bucket (include/pacx_bucket.h): a leaky bucket, levels in 1 / 65536 byte"""
+    _fields_ = [("drain_q16", ctypes.c_int64), ("size_bytes", ctypes.c_int64), ("start_q16", ctypes.c_int64)]
+
+
+BUCKET_Q = 16              # levels of a bucket are int64 in units of 2 ** -BUCKET_Q byte
+BUCKET_SIZE_MAX = 1 << 40  # size_bytes of a pacx_bucket at most
+BUCKET_RESULT = ("total", "peak_q16", "peak_hop", "first_over", "end_q16")     # pacx_bucket_result, int64 each
+# The export list of include/pacx_bucket.h, the companion header pacx.h includes (SIGNATURES is pacx.h's own text).  The
+# buffered solves: the channels of a hop behind n_cf, then a plain solve's arguments with the bucket behind the limit
+# and the bucket's result behind the solve's
+BUCKET_SIGNATURES = {"pacx_bucket_scan": (ctypes.c_int, [_P, _I64, ctypes.c_int32, _P, ctypes.POINTER(PacxBucket), _P, _P,
+                                                         _P])}
+BUCKET_SIGNATURES.update({f"pacx_{kind}_solve_bucket": (ctypes.c_int, [_P, _I64, ctypes.c_int32, *head, _P, _P, _P, _I64,
+                                                                       ctypes.POINTER(PacxBucket), _D, _D, _P, _P, _P, _P,
+                                                                       _P, _P])
+                          for kind, head in CURVE_HEADS.items()})
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320
 NMR_HIST_LO, NMR_HIST_STEP = -120.0, 0.5
@@ -245,7 +264,7 @@ def load():
     # resolves it through the RUNPATH to /opt/rocm.)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **BUCKET_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

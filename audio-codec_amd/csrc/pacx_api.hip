@@ -113,6 +113,7 @@ struct pacx_handle {
     char *ws_solve;                   /* [ws_solve_n] the solve's state per segment */
     long long *ws_seg;                /* [3 ws_solve_n] a solve's boundaries [n_seg + 1], then its limits [n_seg]: uploaded by
                                          the segmented solves, written by the init kernel for the plain ones */
+    char *ws_bucket;                  /* the one state of a buffered solve (k_bucket.hip), whatever ws_solve_n */
     long long seg_host_n;             /* segments the pinned staging copy holds  */
     long long *seg_host;              /* [2 seg_host_n + 1] pinned: what ws_seg is uploaded from */
     hipEvent_t ev_seg;                /* the last upload from seg_host           */
@@ -699,7 +700,9 @@ static GrowGroup grow_group(pacx_handle *h, int which)
                 {{(void **)&h->ws_thr, PACX_M_LONG * sizeof(double)}, {(void **)&h->ws_rate_status, sizeof(uint32_t)}}};
     case GROW_SOLVE:
         return {&h->ws_solve_n, nullptr,
-                {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()}, {(void **)&h->ws_seg, 3 * sizeof(long long)}}};
+                {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()},
+                 {(void **)&h->ws_seg, 3 * sizeof(long long)},
+                 {(void **)&h->ws_bucket, pacx_bucket_ws_bytes(), (size_t)1 << 62, 1}}};             /* [1] */
     default:
         return {&h->ws_index_bytes, nullptr, {{(void **)&h->ws_index, 1}}};
     }
@@ -2282,6 +2285,97 @@ extern "C" int pacx_band_solve_peak(pacx_handle *h, int64_t n_cf, const double *
     const PacxSolveStream peak = {limit_bytes, floor, result_stream};
     return solve(h, SOLVE_BAND, "pacx_band_solve_peak", n_cf, 0, 0, nmr, cap, cap_alloc, true, n_seg, seg_first,
                  peak_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream, &peak);
+}
+
+/* ---- a leaky bucket: its level over the hops, and the two solves under it (k_bucket.hip) ---- */
+static int check_bucket(pacx_handle *h, const char *what, int64_t n_hops, int32_t n_ch, const pacx_bucket *b)
+{
+    const int64_t most = 1LL << 30, size_most = 1LL << 40;
+    if (!b)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_ch < 1 || n_hops < 0 || n_hops > most || n_hops * n_ch > most)
+        return fail(h, PACX_E_ARG, std::string(what) + ": n_ch >= 1 and 0 <= n_hops n_ch <= 2^30");
+    if (b->drain_q16 < 0 || b->size_bytes < 0 || b->size_bytes > size_most || b->start_q16 < 0 ||
+        b->start_q16 > b->size_bytes << 16)
+        return fail(h, PACX_E_ARG, std::string(what) + ": a bucket has drain_q16 >= 0, 0 <= size_bytes <= 2^40 and "
+                                                       "0 <= start_q16 <= size_bytes << 16");
+    return PACX_OK;
+}
+
+extern "C" int pacx_bucket_scan(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes, const pacx_bucket *b,
+                                int64_t *level, pacx_bucket_result *result, void *stream)
+{
+    const char *what = "pacx_bucket_scan";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = check_bucket(h, what, n_hops, n_ch, b))
+        return rc;
+    if (!result || (n_hops > 0 && !n_bytes))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_bucket_scan(n_hops, n_ch, n_bytes, *b, level, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+/* the two buffered solves, checked and launched in one place: solve()'s rules for a whole-stream solve and
+   check_bucket's; the picks are the one-segment picks of pacx_*_pick_segments at the state's target word */
+static int solve_bucket(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t n_ch, int32_t row,
+                        int32_t sub_stride, const double *curve, const int32_t *a, const int32_t *b, int64_t limit_bytes,
+                        const pacx_bucket *bucket, double nmr_lo_db, double nmr_hi_db, int32_t *per_cf, int32_t *n_bytes,
+                        uint8_t *capped, pacx_rate_result *result, pacx_bucket_result *bucket_result, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (n_ch < 1 || n_cf % n_ch != 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": n_cf must be a multiple of n_ch >= 1");
+    if (!result || !bucket_result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
+        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    int rc, t_lo, t_hi;
+    if ((rc = check_bucket(h, what, n_cf / n_ch, n_ch, bucket)) ||
+        (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = grow(h, GROW_SOLVE, 1)))
+        return rc;
+    const PacxBucketSolve v = {h->ws_bucket, n_cf, n_ch, t_lo, t_hi, limit_bytes, *bucket, n_bytes, result, bucket_result};
+    pacx_bucket_drive(v, st, [&](const int32_t *target_t) {
+        if (kind == SOLVE_RATE)
+            pacx_launch_rate_pick_segments(n_cf, row, sub_stride, curve, a, b, PACX_SEG_CF_MAX, 0, target_t, 0, per_cf,
+                                           n_bytes, capped, st);
+        else
+            pacx_launch_band_pick_segments(h->T, n_cf, PACX_SEG_CF_MAX, 0, target_t, curve, a, b, per_cf, n_bytes, capped,
+                                           st);
+    });
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_solve_bucket(pacx_handle *h, int64_t n_cf, int32_t n_ch, const double *nmr, const int32_t *cap,
+                                      const int32_t *cap_alloc, int64_t limit_bytes, const pacx_bucket *b,
+                                      double nmr_lo_db, double nmr_hi_db, int32_t *bit_alloc, int32_t *n_bytes,
+                                      uint8_t *capped, pacx_rate_result *result, pacx_bucket_result *bucket_result,
+                                      void *stream)
+{
+    return solve_bucket(h, SOLVE_BAND, "pacx_band_solve_bucket", n_cf, n_ch, 0, 0, nmr, cap, cap_alloc, limit_bytes, b,
+                        nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, bucket_result, stream);
+}
+
+extern "C" int pacx_rate_solve_bucket(pacx_handle *h, int64_t n_cf, int32_t n_ch, int32_t row, int32_t sub_stride,
+                                      const double *worst, const int32_t *bits, const int32_t *steps,
+                                      int64_t limit_bytes, const pacx_bucket *b, double nmr_lo_db, double nmr_hi_db,
+                                      int32_t *budget, int32_t *n_bytes, uint8_t *capped, pacx_rate_result *result,
+                                      pacx_bucket_result *bucket_result, void *stream)
+{
+    return solve_bucket(h, SOLVE_RATE, "pacx_rate_solve_bucket", n_cf, n_ch, row, sub_stride, worst, bits, steps,
+                        limit_bytes, b, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, bucket_result, stream);
 }
 
 /* ---- the size at every target of the grid, and the solve on it ---- */

@@ -288,6 +288,42 @@ void pacx_launch_rate_pick_thresholds(long long n_cf, int row, int sub_stride, l
                                       const int32_t *bits, const int32_t *steps, int32_t *budget, int32_t *n_bytes,
                                       uint8_t *capped, hipStream_t st);
 
+/* k_bucket.hip: the level of a leaky bucket over the hops of n_bytes (pacx_bucket_scan: one launch of one workgroup)
+   and the buffered solve: the plain solve's bisection with the bucket's peak as a second condition */
+void pacx_launch_bucket_scan(long long n_hops, int n_ch, const int32_t *n_bytes, const pacx_bucket &b, int64_t *level,
+                             pacx_bucket_result *result, hipStream_t st);
+struct PacxBucketSolve {
+    void *ws;                         /* one state of pacx_bucket_ws_bytes() bytes */
+    long long n_cf;
+    int n_ch;                         /* n_cf / n_ch hops */
+    int t_lo, t_hi;                   /* the target range on the grid */
+    long long limit;                  /* for the whole batch, and the bucket: kernel arguments */
+    pacx_bucket bucket;
+    const int32_t *n_bytes;           /* what the picks write and the steps scan */
+    pacx_rate_result *result;
+    pacx_bucket_result *bucket_result;
+};
+size_t pacx_bucket_ws_bytes(void);
+const int32_t *pacx_bucket_target(const PacxBucketSolve &v);      /* device: the word a pick reads its target from */
+void pacx_launch_bucket_init(const PacxBucketSolve &v, hipStream_t st);
+void pacx_launch_bucket_step(const PacxBucketSolve &v, int final, hipStream_t st);
+
+/* the driver: init (the target word at t_hi), then pacx_rate_solve_pairs(t_lo, t_hi) pairs of pick(target_t) -- the
+   one-segment pick of pacx_launch_band_pick_segments / pacx_launch_rate_pick_segments at the state's target word -- and
+   the step that scans what it wrote and decides; the last pick runs at the target found and the last step writes both
+   results.  2 pairs + 1 launches (pairs + 1 without frames), whatever the data; nothing waits for the device */
+template <class Pick>
+inline void pacx_bucket_drive(const PacxBucketSolve &v, hipStream_t st, Pick pick)
+{
+    const int pairs = pacx_rate_solve_pairs(v.t_lo, v.t_hi);
+    pacx_launch_bucket_init(v, st);
+    for (int p = 0; p < pairs; ++p) {
+        if (v.n_cf > 0)
+            pick(pacx_bucket_target(v));
+        pacx_launch_bucket_step(v, p == pairs - 1, st);
+    }
+}
+
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
    row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr

@@ -392,12 +392,13 @@ class Encoder:
         out["capped"] = out["capped"].bool()
         return out
 
-    def _solve(self, kind, op, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None):
-        """The six solves: op "solve_segments" with seg_first and one limit per segment, "solve_peak" with those (the
-        limits are then the peaks) and stream_limit for the whole batch, else "solve", the whole stream with its one
-        limit (the plain C entry point).  Checks the curve, makes the outputs, calls pacx_<kind>_<op> and decodes the
-        pacx_rate_result of every segment: t, met, total (int64) in four int32."""
-        what, peak = f"{kind.prefix}_{op}", op == "solve_peak"
+    def _solve(self, kind, op, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None, bucket=None):
+        """The eight solves: op "solve_segments" with seg_first and one limit per segment, "solve_peak" with those (the
+        limits are then the peaks) and stream_limit for the whole batch, "solve_bucket" with bucket = (channels of a
+        hop, the bucket) beside the one limit, else "solve", the whole stream with its one limit (the plain C entry
+        point).  Checks the curve, makes the outputs, calls pacx_<kind>_<op> and decodes the pacx_rate_result of every
+        segment: t, met, total (int64) in four int32."""
+        what, peak, bucketed = f"{kind.prefix}_{op}", op == "solve_peak", op == "solve_bucket"
         segmented = peak or op == "solve_segments"
         checked = self._checked(kind, curve, what)
         n_cf, out = checked[1], self._picked(kind, checked)
@@ -407,10 +408,19 @@ class Encoder:
         else:
             limits = [ctypes.c_int64(int(limit_bytes))]
         n_seg = len(limit) if segmented else 1
-        # a peak solve's floors and the stream's result ride behind the segments' results: one tensor, one copy back
-        result = torch.zeros((n_seg + (n_seg + 3) // 4 + 1 if peak else n_seg, 4), dtype=torch.int32, device=self.device)
+        # a peak solve's floors and the stream's result, a buffered solve's pacx_bucket_result (five int64 in three
+        # rows) ride behind the segments' results: one tensor, one copy back
+        behind = (n_seg + 3) // 4 + 1 if peak else 3 if bucketed else 0
+        result = torch.zeros((n_seg + behind, 4), dtype=torch.int32, device=self.device)
         more = []
-        if peak:
+        if bucketed:
+            if int(limit_bytes) != limit_bytes or limit_bytes < 0:
+                raise ValueError(f"{what}: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+            n_ch = self._hop_channels(what, bucket[0], n_cf)
+            checked = checked[:3] + ([ctypes.c_int32(n_ch)] + checked[3],)          # n_ch goes behind n_cf
+            limits.append(ctypes.byref(self._bucket_struct(what, bucket[1])))
+            more = [_ptr(result), _ptr(result[1:])]                                  # result, bucket_result
+        elif peak:
             if int(stream_limit) != stream_limit or stream_limit < 0:
                 raise ValueError(f"{what}: limit_bytes = {stream_limit!r}: a whole number of bytes, not negative")
             limits.append(ctypes.c_int64(int(stream_limit)))
@@ -429,6 +439,8 @@ class Encoder:
                         "stream_target_nmr_db": float(res[n_seg, 0]) / grid, "stream_met": bool(res[n_seg, 1]),
                         "stream_total_bytes": int(res[n_seg:n_seg + 1, 2:].copy().view(np.int64)[0, 0])})
             out["pinned"] = out["target_nmr_db"] > out["stream_target_nmr_db"]
+        if bucketed:
+            out["bucket"] = self._bucket_result(res[1:].reshape(-1).view(np.int64))
         if not segmented:
             out.update({"target_nmr_db": float(out["target_nmr_db"][0]), "met": bool(out["met"][0]),
                         "total_bytes": int(out["total_bytes"][0])})
@@ -524,6 +536,65 @@ class Encoder:
         that target against the peak), total_bytes, floor_nmr_db, pinned (target above the stream's); and
         stream_target_nmr_db, stream_met, stream_total_bytes for the whole."""
         return self._solve(RATE, "solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
+
+    # ---- a leaky bucket (pacx_bucket_scan and the two buffered solves, include/pacx_bucket.h): bucket is the triple
+    # (drain_q16, size_bytes, start_q16) as pacfile.bucket gives it, levels in 1 / 65536 byte
+    @staticmethod
+    def _hop_channels(what, n_channels, n_cf):
+        """the channels of a hop, checked as the C side checks them against the channel-frames"""
+        n_ch = int(n_channels)
+        if n_ch != n_channels or n_ch < 1 or n_cf % n_ch:
+            raise ValueError(f"{what}: n_channels = {n_channels!r}: at least 1, and the {n_cf} channel-frames a whole "
+                             f"number of hops")
+        return n_ch
+
+    @staticmethod
+    def _bucket_struct(what, bucket):
+        """the triple as a pacx_bucket; what the numbers may be is the C side's to say"""
+        try:
+            drain, size, start = (int(v) for v in bucket)
+            if (drain, size, start) != tuple(bucket) or max(abs(drain), abs(size), abs(start)) >= 1 << 63:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: a bucket is three integers (drain_q16, size_bytes, start_q16)") from None
+        return _lib.PacxBucket(drain, size, start)
+
+    @staticmethod
+    def _bucket_result(words):
+        """pacx_bucket_result as int64 words -> dict of its fields, the levels in bytes as float as well"""
+        out = {k: int(v) for k, v in zip(_lib.BUCKET_RESULT, words)}
+        out.update({"peak_bytes": out["peak_q16"] / 2.0 ** _lib.BUCKET_Q, "end_bytes": out["end_q16"] / 2.0 ** _lib.BUCKET_Q})
+        return out
+
+    def bucket_scan(self, n_bytes, n_channels, bucket, want_level=False):
+        """The level of a leaky bucket over the hops of a stream (pacx_bucket_scan, include/pacx_bucket.h): n_bytes [n_cf]
+        int32 as a pick, a solve or a second pass writes it, n_channels consecutive entries a hop.  Every hop adds
+        its records with their 4-byte prefixes, then drain_q16 leaves, never below empty.  -> dict total (bytes),
+        peak_q16 and peak_hop (the highest level right after a hop's records arrive and the first hop that reaches it;
+        -1: the start level is the peak), first_over (the first hop above size_bytes, -1: none), end_q16 (the level
+        handed to the next piece of the stream: scans in pieces are exact), peak_bytes and end_bytes as float;
+        want_level: also level, int64 device tensor [n_hops] in 1 / 65536 byte."""
+        what = "bucket_scan"
+        nb = torch.as_tensor(n_bytes, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        n_ch = self._hop_channels(what, n_channels, nb.numel())
+        n_hops = nb.numel() // n_ch
+        b = self._bucket_struct(what, bucket)
+        level = self._empty((n_hops,), torch.int64) if want_level else None
+        result = torch.zeros((len(_lib.BUCKET_RESULT),), dtype=torch.int64, device=self.device)
+        self._call("pacx_bucket_scan", ctypes.c_int64(n_hops), n_ch, _ptr(nb), ctypes.byref(b), _ptr(level), _ptr(result),
+                   self._stream())
+        out = self._bucket_result(result.cpu().numpy())
+        if want_level:
+            out["level"] = level
+        return out
+
+    def rate_solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30):
+        """rate_solve under a leaky bucket (pacx_rate_solve_bucket, include/pacx_bucket.h): the same bisection for the
+        smallest target whose body stays within limit_bytes AND whose level in the bucket, n_channels channel-frames
+        a hop, never exceeds size_bytes.  flags: as rate_solve takes them.  -> rate_solve's dict (met False: not even
+        nmr_hi_db gives both) plus bucket, bucket_scan's dict of the n_bytes returned."""
+        return self._solve(RATE, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
+                           bucket=(n_channels, bucket))
 
     # ---- the whole-grid profile of a rate curve and the pick at known targets (pacx_rate_profile and its three
     # companions, include/pacx.h): the band siblings below on the other curve, with their checks
@@ -809,6 +880,12 @@ class Encoder:
         """rate_solve_peak on a band curve (pacx_band_solve_peak, include/pacx.h).  -> dict bit_alloc, n_bytes, capped as
         band_solve and rate_solve_peak's results per segment and for the stream."""
         return self._solve(BAND, "solve_peak", curve, seg_first, peak_bytes, nmr_lo_db, nmr_hi_db, limit_bytes)
+
+    def band_solve_bucket(self, curve, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30):
+        """rate_solve_bucket on a band curve (pacx_band_solve_bucket, include/pacx_bucket.h).  -> band_solve's dict plus
+        bucket, bucket_scan's dict of the n_bytes returned."""
+        return self._solve(BAND, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
+                           bucket=(n_channels, bucket))
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

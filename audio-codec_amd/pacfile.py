@@ -8,6 +8,9 @@ path: scalar mantissas, or the gain-shape coder with or without SBR
   encode_stream() is the batched path: every hop of a stream in one
   pacx_encode_batch + pacx_pack_batch + pacx_gather_body.
 """
+from collections import namedtuple
+from fractions import Fraction
+from math import floor
 from struct import pack
 
 import numpy as np
@@ -470,6 +473,10 @@ class _CurvePath:
     def solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, lo, hi):
         return self._op("solve_peak", curve, seg_first, peak_bytes, limit_bytes, lo, hi)
 
+    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi):
+        """flags: as solve takes them"""
+        return self._op("solve_bucket", curve, n_channels, limit_bytes, bucket, lo, hi)
+
     # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve, its profile, the pick at
     # known targets and the second pass on that pick
     def no_frames(self, max_bits_per_sample):
@@ -548,6 +555,9 @@ class _BudgetPath(_CurvePath):
 
     def solve(self, curve, flags, limit_bytes, lo, hi):
         return self.enc.rate_solve(curve, flags, limit_bytes, lo, hi)
+
+    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi):
+        return self.enc.rate_solve_bucket(curve, flags, n_channels, limit_bytes, bucket, lo, hi)
 
     def encode(self, view, flags, budget):
         return self.enc.encode_pack_budget(view, flags, budget)
@@ -809,6 +819,97 @@ def encode_stream_abr(pcm, sample_rate, kbps_per_channel=None, max_bytes=None, m
                                  block_switching, header_samples, nmr_range_db, allocation, segment_hops,
                                  peak_kbps_per_channel)
     return done[0][0]
+
+
+Bucket = namedtuple("Bucket", "drain_q16 size_bytes start_q16")         # pacx_bucket (include/pacx_bucket.h)
+
+
+def bucket(kbps_per_channel, n_channels, sample_rate, buffer_bytes, start_bytes=0, hop=1024):
+    """The leaky bucket of a decoder or a transport that takes kbps_per_channel out of a buffer of buffer_bytes -> the
+    pacx_bucket triple Bucket(drain_q16, size_bytes, start_q16), levels in 1 / 65536 byte (Encoder.bucket_scan,
+    rate_solve_bucket, band_solve_bucket).  drain_q16 = floor(kbps * 1000 * nCh * hop * 65536 / (8 * sampleRate)), what
+    leaves per block of `hop` samples, in exact rational arithmetic (kbps_per_channel: an int, a Fraction, a string as
+    Fraction takes it, or a float, taken at its exact value): the floor never drains more than the rate does, so a
+    stream that fits this bucket fits the real one.  start_bytes: the level before the first block, at most
+    buffer_bytes.  Pure arithmetic."""
+    try:
+        kbps, start = Fraction(kbps_per_channel), Fraction(start_bytes)
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError("kbps_per_channel and start_bytes are numbers") from None
+    for name, v in (("n_channels", n_channels), ("sample_rate", sample_rate), ("hop", hop)):
+        if isinstance(v, bool) or int(v) != v or v < 1:
+            raise ValueError(f"{name} = {v!r}: a whole number, at least 1")
+    if kbps < 0:
+        raise ValueError("kbps_per_channel must not be negative")
+    if isinstance(buffer_bytes, bool) or int(buffer_bytes) != buffer_bytes or not 0 <= buffer_bytes <= _lib.BUCKET_SIZE_MAX:
+        raise ValueError(f"buffer_bytes = {buffer_bytes!r}: a whole number of bytes in [0, 2^40]")
+    if not 0 <= start <= buffer_bytes:
+        raise ValueError(f"start_bytes = {start_bytes!r}: a level in [0, buffer_bytes]")
+    one = 1 << _lib.BUCKET_Q
+    drain = kbps * 1000 * int(n_channels) * int(hop) * one / (8 * int(sample_rate))
+    if drain >= 1 << 63:
+        raise ValueError(f"kbps_per_channel = {kbps_per_channel!r}: the drain of a block does not fit 64 bits")
+    return Bucket(floor(drain), int(buffer_bytes), floor(start * one))
+
+
+def _buffer_overflows(b, first_over, level_q16, limit, total, hi):
+    """what a buffered average-rate call says when the size fits at the highest target of its range and the buffer
+    does not: the first block above the buffer and its level, in whole bytes rounded up"""
+    return (f"a buffer of {b.size_bytes} bytes cannot be met: at the highest target, {hi:g} dB, the body fits its "
+            f"limit ({total} of {limit} bytes) but block {first_over} brings the level to "
+            f"{-(-level_q16 >> _lib.BUCKET_Q)} bytes, the first block above the buffer")
+
+
+def _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
+                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation, use_vq):
+    """encode_stream_abr_buffered -> (.pac bytes, the solve's dict, the second pass's outputs, the body limit, the
+    bucket, the encoder)"""
+    band = _check_allocation(allocation)
+    if use_vq and not band:
+        raise NotImplementedError("gain-shape streams: allocation 'band' only")
+    lo, hi = _abr_range(nmr_range_db)
+    if not kbps_per_channel > 0:
+        raise ValueError("kbps_per_channel must be positive")
+    pcm = np.ascontiguousarray(pcm)
+    if pcm.ndim != 2:
+        raise ValueError("pcm: int16 [samples, channels]")
+    b = bucket(kbps_per_channel if drain_kbps_per_channel is None else drain_kbps_per_channel, pcm.shape[1],
+               sample_rate, buffer_bytes, start_bytes)
+    cp, enc, view, flags = _rate_stream_setup(pcm, sample_rate, max_kbps_per_channel, block_switching, header_samples,
+                                              use_vq)
+    head = header_bytes(cp)
+    limit = _abr_limit(cp, view, head, kbps_per_channel, None)
+    path = _PATHS[allocation](enc)
+    sol = path.solve_bucket(path.curve(view, flags, cp.targetBitsPerSample), flags, cp.nChannels, limit, b, lo, hi)
+    if not sol["met"] and sol["total_bytes"] > limit:
+        raise ValueError(_unreachable(limit, sol["total_bytes"], hi, head))
+    if not sol["met"]:
+        over = sol["bucket"]["first_over"]
+        level = path.solver.bucket_scan(sol["n_bytes"], cp.nChannels, b, want_level=True)["level"]
+        raise ValueError(_buffer_overflows(b, over, int(level[over].item()), limit, sol["total_bytes"], hi))
+    out = path.second_pass(view, flags, sol)
+    body, total = enc.gather_body(out["payload"], out["n_bytes"])
+    return head + body[:int(total.item())].cpu().numpy().tobytes(), sol, out, limit, b, enc
+
+
+def encode_stream_abr_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None,
+                               start_bytes=0, max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                               nmr_range_db=(-30, 30), allocation="budget", use_vq=False):
+    """encode_stream_abr(kbps_per_channel) for a decoder with a buffer -> .pac bytes: one target NMR for the whole
+    stream, found by the same bisection on the grid of 1/64 dB in nmr_range_db, at which the body stays within
+    kbps_per_channel's size AND the stream plays through a leaky bucket (include/pacx_bucket.h, pacx_bucket_scan): every block's
+    records, their length prefixes included, arrive in a buffer of buffer_bytes that starts at start_bytes, and
+    drain_kbps_per_channel (default: kbps_per_channel) leaves it per block, bucket() says how much exactly; the level
+    right after a block arrives never exceeds buffer_bytes.  The bytes are encode_stream_nmr's at the target found
+    (allocation as there), with use_vq=True encode_stream_vq_nmr's (allocation "band" only).  Unlike segment_hops=, the
+    constraint has no grid: a burst is refused exactly when the buffer cannot absorb it, wherever it lies.  One curve,
+    one solve (Encoder.rate_solve_bucket / band_solve_bucket, on the scalar sibling for gain-shape streams), one
+    second pass.  ValueError when even the highest target of the range does not give both: encode_stream_abr's message
+    if the size does not fit there, else one that names the first block above the buffer, its level and the buffer.
+    A target is one for the whole stream: the loudest stretch the buffer cannot absorb sets the quality of all of it."""
+    return _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
+                                   max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation,
+                                   use_vq)[0]
 
 
 class _Blocks:

@@ -430,6 +430,101 @@ def encode_stream_vq_to_rate(pcm, sample_rate, kbps_per_channel=None, max_bytes=
                            header_samples, nmr_range_db, "band", segment_hops, peak_kbps_per_channel, True)
 
 
+def _rates_kbps(hop_bytes, n_ch, block_seconds):
+    """(mean, maximum) kb/s per channel of the blocks whose body bytes are hop_bytes"""
+    if len(hop_bytes) == 0:
+        return 0.0, 0.0
+    per_block = 8.0 * np.asarray(hop_bytes, np.float64) / block_seconds / n_ch / 1000.0
+    return float(per_block.mean()), float(per_block.max())
+
+
+def encode_stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None, start_bytes=0,
+                            max_kbps_per_channel=320, block_switching=False, header_samples=None, nmr_range_db=(-30, 30),
+                            allocation="budget", use_vq=False):
+    """pacfile.encode_stream_abr_buffered with what the buffer saw: -> (.pac bytes, info).  info, for the n + 2 blocks
+    the driver submits:
+      target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
+      bucket         the pacfile.Bucket of the call;
+      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written);
+      level_bytes    float64 [blocks]: the buffer's level right after every block's records arrive (a dropped hop
+                     brings none and only drains);
+      peak_bytes, peak_block  the highest of them and the first block that reaches it (-1: the start level);
+      end_bytes      the level after the last block has drained;
+      mean_kbps_per_channel, max_kbps_per_channel_seen  the body over the duration of the blocks, and the largest block
+                     at the rate of its own duration;
+      allocation     as given."""
+    from . import pacfile
+    data, sol, out, limit, b, enc = pacfile._encode_stream_buffered(
+        pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes, max_kbps_per_channel,
+        block_switching, header_samples, nmr_range_db, allocation, use_vq)
+    n_ch = np.asarray(pcm).shape[1]
+    n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
+    scan = enc.bucket_scan(out["n_bytes"], n_ch, b, want_level=True)
+    mean, most = _rates_kbps(np.where(n_bytes > 0, n_bytes + 4, 0).sum(axis=1), n_ch, HOP / float(sample_rate))
+    info = {
+        "allocation": allocation,
+        "target_nmr_db": sol["target_nmr_db"],
+        "limit_bytes": limit,
+        "total_bytes": scan["total"],
+        "bucket": b,
+        "n_bytes": sol["n_bytes"].cpu().numpy().reshape(-1, n_ch),
+        "level_bytes": scan["level"].cpu().numpy() / 2.0 ** _lib.BUCKET_Q,
+        "peak_bytes": scan["peak_bytes"],
+        "peak_block": scan["peak_hop"],
+        "end_bytes": scan["end_bytes"],
+        "mean_kbps_per_channel": mean,
+        "max_kbps_per_channel_seen": most,
+    }
+    return data, info
+
+
+def buffer_report(pac_bytes, kbps_per_channel, buffer_bytes, start_bytes=0):
+    """Whether a finished .pac, made anywhere, plays through a leaky bucket (pacfile.bucket: kbps_per_channel leaves a
+    buffer of buffer_bytes per block; the channels, sample rate and block size are the file's): the header is parsed
+    (pacfile.parse_header), the record sizes are read on the device (Encoder.index_body) and the level is their
+    Encoder.bucket_scan.  -> dict
+      bucket       the pacfile.Bucket;   blocks  the blocks in the file;   total_bytes  its body;
+      level_bytes  float64 [blocks]: the level right after every block's records arrive;
+      peak_bytes, peak_block, end_bytes, first_over (the first block above the buffer, -1: none) and fits (bool);
+      mean_kbps_per_channel, max_kbps_per_channel_seen  as encode_stream_to_buffer gives them.
+    A hop the encoder dropped (a short-coded hop with an all-zero sub-block) leaves no record in a body, so the report
+    runs over the records present: the dropped hop's share of draining is missing and every level here is AT OR ABOVE
+    the true one -- a stream that fits by this report fits.  ValueError for a body whose record chain breaks or does
+    not hold whole blocks."""
+    import torch
+    from . import context, pacfile
+    data = bytes(pac_bytes)
+    cp, pos = pacfile.parse_header(data)
+    n_ch = cp.nChannels
+    b = pacfile.bucket(kbps_per_channel, n_ch, cp.sampleRate, buffer_bytes, start_bytes, hop=cp.nMDCTLines)
+    enc = context.encoder_for_params(cp)
+    body = torch.as_tensor(np.frombuffer(data, np.uint8)[pos:].copy(), device=enc.device)
+    if body.numel():
+        _, sizes, result = enc.index_body(body, n_ch)
+        records, used, broke = (int(v) for v in result.cpu().numpy())
+    else:
+        sizes, records, used, broke = torch.zeros((0,), dtype=torch.int32, device=enc.device), 0, 0, -1
+    if broke >= 0 or used != body.numel():
+        raise ValueError(f"the body's record chain breaks at byte {broke if broke >= 0 else used} of {body.numel()}: "
+                         f"{records} records in whole blocks of {n_ch} were read")
+    scan = enc.bucket_scan(sizes[:records], n_ch, b, want_level=True)
+    hop_bytes = (sizes[:records].view(-1, n_ch).to(torch.int64) + 4).sum(dim=1).cpu().numpy()
+    mean, most = _rates_kbps(hop_bytes, n_ch, cp.nMDCTLines / float(cp.sampleRate))
+    return {
+        "bucket": b,
+        "blocks": records // n_ch,
+        "total_bytes": scan["total"],
+        "level_bytes": scan["level"].cpu().numpy() / 2.0 ** _lib.BUCKET_Q,
+        "peak_bytes": scan["peak_bytes"],
+        "peak_block": scan["peak_hop"],
+        "end_bytes": scan["end_bytes"],
+        "first_over": scan["first_over"],
+        "fits": scan["first_over"] < 0,
+        "mean_kbps_per_channel": mean,
+        "max_kbps_per_channel_seen": most,
+    }
+
+
 def rate_curve(pcm, sample_rate, max_kbps_per_channel=320, block_switching=False):
     """The rate-distortion curve of every long block / short sub-block of a stream, for plotting rate against
     quality: -> dict of NumPy arrays for the n + 2 blocks the driver submits,

@@ -1317,6 +1317,11 @@ int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t
                                const int32_t *bit_alloc_in, int32_t *overall_scale, int32_t *bit_alloc,
                                uint8_t *payload, int32_t *n_bytes, uint32_t *status, void *stream);
 
+/* ---- a leaky bucket: the level of a decoder's buffer, and the solves under it ---- */
+/* pacx_bucket_scan, pacx_band_solve_bucket and pacx_rate_solve_bucket (additive exports, ABI 7): declared in the
+   companion header beside this one, which is part of this interface and is included nowhere else */
+#include "pacx_bucket.h"
+
 #ifdef __cplusplus
 }
 #endif
