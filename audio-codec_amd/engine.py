@@ -6,6 +6,7 @@ Reference path replaced: coder/codec.py:225-380 (Encode/EncodeSingleChannel)
 and the window/mdct/psychoac/bitalloc/quantize functions it calls.
 """
 import ctypes
+import os
 
 import numpy as np
 import torch

@@ -21,6 +21,13 @@
  *     default stream) and is asynchronous; the library keeps a grow-only
  *     device workspace per handle (pacx_reserve() sizes it up front so that
  *     no allocation happens inside a timed or graph-captured region);
+ *     a call that has to grow a workspace waits for the whole device first,
+ *     then frees and allocates.  No other call waits for the host, except
+ *     where its own text says so (a segmented or peak solve waits for the
+ *     upload of the one before it, pacx_rate_solve_segments);
+ *   - all calls of one handle belong on one stream: its workspaces and its
+ *     internal streams and events are shared between them, and a call is
+ *     ordered against the one before it by that stream alone;
  *   - one handle per device; handles are independent (no global state).
  *
  * Units: a "channel-frame" (cf) is one EncodeSingleChannel call: 2*nMDCTLines
