@@ -207,6 +207,18 @@ BUCKET_SIGNATURES.update({f"pacx_{kind}_solve_bucket": (ctypes.c_int, [_P, _I64,
                                                                        ctypes.POINTER(PacxBucket), _D, _D, _P, _P, _P, _P,
                                                                        _P, _P])
                           for kind, head in CURVE_HEADS.items()})
+# The export list of include/pacx_bucket_pin.h, the second companion header: the level through every hop (pacx_bucket_scan
+# with `through` behind `level`) and the pinned solves: a buffered solve's arguments with pin_step_t and max_phases
+# behind the range, target_t and phase_of behind capped and the pacx_pin_result {phases, open} behind the bucket's result
+PIN_PHASES_MAX = 16
+PIN_RESULT = ("phases", "open")                                                  # pacx_pin_result, int32 each
+BUCKET_PIN_SIGNATURES = {"pacx_bucket_through": (ctypes.c_int, [_P, _I64, ctypes.c_int32, _P, ctypes.POINTER(PacxBucket), _P,
+                                                                _P, _P, _P])}
+BUCKET_PIN_SIGNATURES.update({f"pacx_{kind}_solve_bucket_pinned": (ctypes.c_int, [_P, _I64, ctypes.c_int32, *head, _P, _P, _P,
+                                                                                  _I64, ctypes.POINTER(PacxBucket), _D, _D,
+                                                                                  ctypes.c_int32, ctypes.c_int32, _P, _P,
+                                                                                  _P, _P, _P, _P, _P, _P, _P])
+                              for kind, head in CURVE_HEADS.items()})
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320
 NMR_HIST_LO, NMR_HIST_STEP = -120.0, 0.5
@@ -264,7 +276,7 @@ def load():
     # resolves it through the RUNPATH to /opt/rocm.)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **BUCKET_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **BUCKET_SIGNATURES, **BUCKET_PIN_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

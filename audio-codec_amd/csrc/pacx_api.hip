@@ -114,6 +114,7 @@ struct pacx_handle {
     long long *ws_seg;                /* [3 ws_solve_n] a solve's boundaries [n_seg + 1], then its limits [n_seg]: uploaded by
                                          the segmented solves, written by the init kernel for the plain ones */
     char *ws_bucket;                  /* the one state of a buffered solve (k_bucket.hip), whatever ws_solve_n */
+    char *ws_pin;                     /* a pinned solve's state, F_h and pins (k_bucket_pin.hip): ws_solve_n hops */
     long long seg_host_n;             /* segments the pinned staging copy holds  */
     long long *seg_host;              /* [2 seg_host_n + 1] pinned: what ws_seg is uploaded from */
     hipEvent_t ev_seg;                /* the last upload from seg_host           */
@@ -702,7 +703,8 @@ static GrowGroup grow_group(pacx_handle *h, int which)
         return {&h->ws_solve_n, nullptr,
                 {{(void **)&h->ws_solve, pacx_rate_solve_ws_bytes()},
                  {(void **)&h->ws_seg, 3 * sizeof(long long)},
-                 {(void **)&h->ws_bucket, pacx_bucket_ws_bytes(), (size_t)1 << 62, 1}}};             /* [1] */
+                 {(void **)&h->ws_bucket, pacx_bucket_ws_bytes(), (size_t)1 << 62, 1},               /* [1] */
+                 {(void **)&h->ws_pin, pacx_pin_ws_unit(), 1, pacx_pin_ws_head() / pacx_pin_ws_unit()}}};
     default:
         return {&h->ws_index_bytes, nullptr, {{(void **)&h->ws_index, 1}}};
     }
@@ -2376,6 +2378,98 @@ extern "C" int pacx_rate_solve_bucket(pacx_handle *h, int64_t n_cf, int32_t n_ch
 {
     return solve_bucket(h, SOLVE_RATE, "pacx_rate_solve_bucket", n_cf, n_ch, row, sub_stride, worst, bits, steps,
                         limit_bytes, b, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, bucket_result, stream);
+}
+
+/* ---- per-block targets under a bucket: the level through every hop and the two pinned solves (k_bucket_pin.hip) ---- */
+extern "C" int pacx_bucket_through(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes,
+                                   const pacx_bucket *b, int64_t *level, int64_t *through, pacx_bucket_result *result,
+                                   void *stream)
+{
+    const char *what = "pacx_bucket_through";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = check_bucket(h, what, n_hops, n_ch, b))
+        return rc;
+    if (!result || (n_hops > 0 && (!n_bytes || !through)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_bucket_through(n_hops, n_ch, n_bytes, *b, level, through, result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+/* the two pinned solves, checked and launched in one place: solve_bucket's rules, the step and the phase count; the
+   picks are those of pacx_*_pick_segments with a segment per hop at the solve's target_t */
+static int solve_bucket_pinned(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t n_ch, int32_t row,
+                               int32_t sub_stride, const double *curve, const int32_t *a, const int32_t *b,
+                               int64_t limit_bytes, const pacx_bucket *bucket, double nmr_lo_db, double nmr_hi_db,
+                               int32_t pin_step_t, int32_t max_phases, int32_t *per_cf, int32_t *n_bytes, uint8_t *capped,
+                               int32_t *target_t, int32_t *phase_of, pacx_rate_result *result,
+                               pacx_bucket_result *bucket_result, pacx_pin_result *pin_result, void *stream)
+{
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = scalar_only(h, what))
+        return rc;
+    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
+        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
+    if (n_ch < 1 || n_cf % n_ch != 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": n_cf must be a multiple of n_ch >= 1");
+    if (!result || !bucket_result || !pin_result ||
+        (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped || !target_t || !phase_of)))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
+        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    if (pin_step_t < 1)
+        return fail(h, PACX_E_ARG, std::string(what) + ": pin_step_t must be at least 1 (grid units of 1/64 dB)");
+    if (max_phases < 1 || max_phases > PACX_PIN_PHASES_MAX)
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_phases must lie in [1, " +
+                                       std::to_string(PACX_PIN_PHASES_MAX) + "]");
+    int rc, t_lo, t_hi;
+    if ((rc = check_bucket(h, what, n_cf / n_ch, n_ch, bucket)) ||
+        (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_hops = n_cf / n_ch;
+    if ((rc = grow(h, GROW_SOLVE, n_hops > 1 ? n_hops : 1)))
+        return rc;
+    const PacxPinSolve v = {h->ws_pin, n_cf, n_ch, t_lo, t_hi, pin_step_t, max_phases, limit_bytes, *bucket, n_bytes,
+                            target_t, phase_of, result, bucket_result, pin_result};
+    pacx_pin_drive(v, st, [&]() {
+        if (kind == SOLVE_RATE)
+            pacx_launch_rate_pick_segments(n_cf, row, sub_stride, curve, a, b, n_ch, 0, target_t, 0, per_cf, n_bytes,
+                                           capped, st);
+        else
+            pacx_launch_band_pick_segments(h->T, n_cf, n_ch, 0, target_t, curve, a, b, per_cf, n_bytes, capped, st);
+    });
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_band_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32_t n_ch, const double *nmr,
+                                             const int32_t *cap, const int32_t *cap_alloc, int64_t limit_bytes,
+                                             const pacx_bucket *b, double nmr_lo_db, double nmr_hi_db, int32_t pin_step_t,
+                                             int32_t max_phases, int32_t *bit_alloc, int32_t *n_bytes, uint8_t *capped,
+                                             int32_t *target_t, int32_t *phase_of, pacx_rate_result *result,
+                                             pacx_bucket_result *bucket_result, pacx_pin_result *pin_result, void *stream)
+{
+    return solve_bucket_pinned(h, SOLVE_BAND, "pacx_band_solve_bucket_pinned", n_cf, n_ch, 0, 0, nmr, cap, cap_alloc,
+                               limit_bytes, b, nmr_lo_db, nmr_hi_db, pin_step_t, max_phases, bit_alloc, n_bytes, capped,
+                               target_t, phase_of, result, bucket_result, pin_result, stream);
+}
+
+extern "C" int pacx_rate_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32_t n_ch, int32_t row, int32_t sub_stride,
+                                             const double *worst, const int32_t *bits, const int32_t *steps,
+                                             int64_t limit_bytes, const pacx_bucket *b, double nmr_lo_db,
+                                             double nmr_hi_db, int32_t pin_step_t, int32_t max_phases, int32_t *budget,
+                                             int32_t *n_bytes, uint8_t *capped, int32_t *target_t, int32_t *phase_of,
+                                             pacx_rate_result *result, pacx_bucket_result *bucket_result,
+                                             pacx_pin_result *pin_result, void *stream)
+{
+    return solve_bucket_pinned(h, SOLVE_RATE, "pacx_rate_solve_bucket_pinned", n_cf, n_ch, row, sub_stride, worst, bits,
+                               steps, limit_bytes, b, nmr_lo_db, nmr_hi_db, pin_step_t, max_phases, budget, n_bytes,
+                               capped, target_t, phase_of, result, bucket_result, pin_result, stream);
 }
 
 /* ---- the size at every target of the grid, and the solve on it ---- */

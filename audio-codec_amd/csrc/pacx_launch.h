@@ -324,6 +324,56 @@ inline void pacx_bucket_drive(const PacxBucketSolve &v, hipStream_t st, Pick pic
     }
 }
 
+/* k_bucket_pin.hip: the level through every hop (pacx_bucket_through: one launch of one workgroup) and the pinned
+   solves of include/pacx_bucket_pin.h: a target per hop, the phase's level or the hop's pin */
+void pacx_launch_bucket_through(long long n_hops, int n_ch, const int32_t *n_bytes, const pacx_bucket &b, int64_t *level,
+                                int64_t *through, pacx_bucket_result *result, hipStream_t st);
+struct PacxPinSolve {
+    void *ws;                         /* pacx_pin_ws_head() + n_hops pacx_pin_ws_unit() bytes: state, F_h, pins */
+    long long n_cf;
+    int n_ch;                         /* n_cf / n_ch hops */
+    int t_lo, t_hi;                   /* the target range on the grid */
+    int pin_step_t, max_phases;
+    long long limit;                  /* for the whole batch, and the bucket: kernel arguments */
+    pacx_bucket bucket;
+    const int32_t *n_bytes;           /* what the picks write and the kernels scan */
+    int32_t *target_t, *phase_of;     /* [n_hops]: what the picks read; the phase that pinned a hop */
+    pacx_rate_result *result;
+    pacx_bucket_result *bucket_result;
+    pacx_pin_result *pin_result;
+};
+size_t pacx_pin_ws_head(void);
+size_t pacx_pin_ws_unit(void);        /* the head is a whole number of units */
+void pacx_launch_pin_init(const PacxPinSolve &v, hipStream_t st);
+void pacx_launch_pin_step(const PacxPinSolve &v, hipStream_t st);
+void pacx_launch_pin_freeze(const PacxPinSolve &v, hipStream_t st);
+void pacx_launch_pin_finish(const PacxPinSolve &v, hipStream_t st);
+
+/* the driver: init (every target t_hi); per phase pacx_rate_solve_pairs(t_lo, t_hi) pairs of pick() -- the pick of
+   pacx_launch_band_pick_segments / pacx_launch_rate_pick_segments with seg_cf = n_ch at v.target_t -- and the step,
+   then the pick at A(q) and the freeze; last the pick at the targets returned and the finish.
+   max_phases (2 pairs + 2) + 3 launches (max_phases (pairs + 1) + 2 without frames), whatever the data; nothing waits
+   for the device.  A finished solve's kernels return at once; its picks still run */
+template <class Pick>
+inline void pacx_pin_drive(const PacxPinSolve &v, hipStream_t st, Pick pick)
+{
+    const int pairs = pacx_rate_solve_pairs(v.t_lo, v.t_hi);
+    pacx_launch_pin_init(v, st);
+    for (int k = 0; k < v.max_phases; ++k) {
+        for (int p = 0; p < pairs; ++p) {
+            if (v.n_cf > 0)
+                pick();
+            pacx_launch_pin_step(v, st);
+        }
+        if (v.n_cf > 0)
+            pick();
+        pacx_launch_pin_freeze(v, st);
+    }
+    if (v.n_cf > 0)
+        pick();
+    pacx_launch_pin_finish(v, st);
+}
+
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
    row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr

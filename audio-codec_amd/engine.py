@@ -597,6 +597,84 @@ class Encoder:
         return self._solve(RATE, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
                            bucket=(n_channels, bucket))
 
+    # ---- per-block targets under a bucket (pacx_bucket_through and the two pinned solves, include/pacx_bucket_pin.h)
+    def bucket_through(self, n_bytes, n_channels, bucket, want_level=False):
+        """The level THROUGH every hop of a leaky bucket (pacx_bucket_through, include/pacx_bucket_pin.h): bucket_scan's
+        arguments and dict, plus through, int64 device tensor [n_hops] in 1 / 65536 byte: the highest level that any
+        stretch of consecutive hops containing the hop brings the buffer to (the start level counts as a stretch that
+        begins before the first hop).  A hop lies in a stretch that overflows exactly when its entry is above
+        size_bytes << 16.  want_level: also level, as bucket_scan gives it."""
+        what = "bucket_through"
+        nb = torch.as_tensor(n_bytes, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        n_ch = self._hop_channels(what, n_channels, nb.numel())
+        n_hops = nb.numel() // n_ch
+        b = self._bucket_struct(what, bucket)
+        level = self._empty((n_hops,), torch.int64) if want_level else None
+        through = self._empty((n_hops,), torch.int64)
+        result = torch.zeros((len(_lib.BUCKET_RESULT),), dtype=torch.int64, device=self.device)
+        self._call("pacx_bucket_through", ctypes.c_int64(n_hops), n_ch, _ptr(nb), ctypes.byref(b), _ptr(level),
+                   _ptr(through), _ptr(result), self._stream())
+        out = self._bucket_result(result.cpu().numpy())
+        out["through"] = through
+        if want_level:
+            out["level"] = level
+        return out
+
+    @staticmethod
+    def _pin_args(what, pin_step_db, max_phases):
+        """the step of a pinned solve in grid units and its phase count, checked as the C side checks them"""
+        try:
+            step = float(pin_step_db) * _lib.RATE_TARGET_GRID
+            ok = step == int(step) and 1 <= step < 1 << 31
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}: pin_step_db = {pin_step_db!r}: a multiple of 1/{_lib.RATE_TARGET_GRID} dB, at "
+                             f"least one of them")
+        if isinstance(max_phases, bool) or not isinstance(max_phases, (int, np.integer)) or \
+                not 1 <= max_phases <= _lib.PIN_PHASES_MAX:
+            raise ValueError(f"{what}: max_phases = {max_phases!r}: a whole number in [1, {_lib.PIN_PHASES_MAX}]")
+        return int(step), int(max_phases)
+
+    def _solve_pinned(self, kind, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db, max_phases):
+        """The two pinned solves: checks the curve, makes the outputs, calls pacx_<kind>_solve_bucket_pinned and decodes
+        the three results, which ride in one tensor: pacx_rate_result, pacx_bucket_result, pacx_pin_result."""
+        what = f"{kind.prefix}_solve_bucket_pinned"
+        step, phases = self._pin_args(what, pin_step_db, max_phases)
+        checked = self._checked(kind, curve, what)
+        n_cf, out = checked[1], self._picked(kind, checked)
+        if int(limit_bytes) != limit_bytes or limit_bytes < 0:
+            raise ValueError(f"{what}: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+        n_ch = self._hop_channels(what, n_channels, n_cf)
+        n_hops = n_cf // n_ch
+        checked = checked[:3] + ([ctypes.c_int32(n_ch)] + checked[3],)              # n_ch goes behind n_cf
+        b = self._bucket_struct(what, bucket)
+        result = torch.zeros((5, 4), dtype=torch.int32, device=self.device)         # 16 + 40 + 8 bytes
+        per_hop = torch.zeros((2, n_hops), dtype=torch.int32, device=self.device)   # target_t, phase_of
+        self._curve_call(what, checked, ctypes.c_int64(int(limit_bytes)), ctypes.byref(b), ctypes.c_double(nmr_lo_db),
+                         ctypes.c_double(nmr_hi_db), ctypes.c_int32(step), ctypes.c_int32(phases),
+                         _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]), _ptr(out["capped"]), _ptr(per_hop[0]),
+                         _ptr(per_hop[1]), _ptr(result), _ptr(result[1:]), _ptr(result[4:]))
+        grid = float(_lib.RATE_TARGET_GRID)
+        res = result.cpu().numpy()
+        out["capped"] = out["capped"].bool()
+        out.update({"target_nmr_db": float(res[0, 0]) / grid, "met": bool(res[0, 1]),
+                    "total_bytes": int(res[:1, 2:].copy().view(np.int64)[0, 0]),
+                    "bucket": self._bucket_result(res[1:].reshape(-1).view(np.int64)),
+                    "target_t": per_hop[0], "phase_of": per_hop[1], "phases": int(res[4, 0]), "open": bool(res[4, 1])})
+        return out
+
+    def rate_solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30,
+                                 pin_step_db=1.0, max_phases=8):
+        """rate_solve_bucket with a target per hop (pacx_rate_solve_bucket_pinned, include/pacx_bucket_pin.h): the
+        stream's target wherever the buffer allows, and where a stretch would overflow it a higher one, pinned phase by
+        phase (at most max_phases; a pinned hop lies within pin_step_db of the lowest level its stretch allows).
+        -> rate_solve_bucket's dict (target_nmr_db: the stream's level, the target of every free hop) plus target_t and
+        phase_of, int32 device tensors [n_hops] (grid units; the phase that pinned the hop, -1: free), phases (the
+        bisections run) and open (True: the last phase allowed still pinned a hop)."""
+        return self._solve_pinned(RATE, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db,
+                                  max_phases)
+
     # ---- the whole-grid profile of a rate curve and the pick at known targets (pacx_rate_profile and its three
     # companions, include/pacx.h): the band siblings below on the other curve, with their checks
     def rate_profile(self, curve, nmr_lo_db=-30, nmr_hi_db=30, out=None):
@@ -887,6 +965,13 @@ class Encoder:
         bucket, bucket_scan's dict of the n_bytes returned."""
         return self._solve(BAND, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
                            bucket=(n_channels, bucket))
+
+    def band_solve_bucket_pinned(self, curve, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30,
+                                 pin_step_db=1.0, max_phases=8):
+        """rate_solve_bucket_pinned on a band curve (pacx_band_solve_bucket_pinned, include/pacx_bucket_pin.h).
+        -> band_solve_bucket's dict plus target_t, phase_of, phases and open."""
+        return self._solve_pinned(BAND, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db,
+                                  max_phases)
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib, codec, context, curves
 from .audiofile import AudioFile
-from .engine import PcmView
+from .engine import Encoder, PcmView
 from .pcmfile import codes_to_fraction
 from .psychoac import AssignMDCTLinesFromFreqLimits, ScaleFactorBands
 
@@ -477,6 +477,10 @@ class _CurvePath:
         """flags: as solve takes them"""
         return self._op("solve_bucket", curve, n_channels, limit_bytes, bucket, lo, hi)
 
+    def solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases):
+        """flags: as solve takes them"""
+        return self._op("solve_bucket_pinned", curve, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases)
+
     # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve, its profile, the pick at
     # known targets and the second pass on that pick
     def no_frames(self, max_bits_per_sample):
@@ -558,6 +562,10 @@ class _BudgetPath(_CurvePath):
 
     def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi):
         return self.enc.rate_solve_bucket(curve, flags, n_channels, limit_bytes, bucket, lo, hi)
+
+    def solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases):
+        return self.enc.rate_solve_bucket_pinned(curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db,
+                                                 max_phases)
 
     def encode(self, view, flags, budget):
         return self.enc.encode_pack_budget(view, flags, budget)
@@ -861,13 +869,16 @@ def _buffer_overflows(b, first_over, level_q16, limit, total, hi):
 
 
 def _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
-                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation, use_vq):
-    """encode_stream_abr_buffered -> (.pac bytes, the solve's dict, the second pass's outputs, the body limit, the
-    bucket, the encoder)"""
+                            max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation, use_vq,
+                            pinned=None):
+    """encode_stream_abr_buffered, or with pinned = (pin_step_db, max_phases) encode_stream_abr_pinned -> (.pac bytes,
+    the solve's dict, the second pass's outputs, the body limit, the bucket, the encoder)"""
     band = _check_allocation(allocation)
     if use_vq and not band:
         raise NotImplementedError("gain-shape streams: allocation 'band' only")
     lo, hi = _abr_range(nmr_range_db)
+    if pinned is not None:
+        Encoder._pin_args("encode_stream_abr_pinned", *pinned)
     if not kbps_per_channel > 0:
         raise ValueError("kbps_per_channel must be positive")
     pcm = np.ascontiguousarray(pcm)
@@ -880,7 +891,11 @@ def _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, dr
     head = header_bytes(cp)
     limit = _abr_limit(cp, view, head, kbps_per_channel, None)
     path = _PATHS[allocation](enc)
-    sol = path.solve_bucket(path.curve(view, flags, cp.targetBitsPerSample), flags, cp.nChannels, limit, b, lo, hi)
+    curve = path.curve(view, flags, cp.targetBitsPerSample)
+    if pinned is None:
+        sol = path.solve_bucket(curve, flags, cp.nChannels, limit, b, lo, hi)
+    else:
+        sol = path.solve_bucket_pinned(curve, flags, cp.nChannels, limit, b, lo, hi, *pinned)
     if not sol["met"] and sol["total_bytes"] > limit:
         raise ValueError(_unreachable(limit, sol["total_bytes"], hi, head))
     if not sol["met"]:
@@ -910,6 +925,24 @@ def encode_stream_abr_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes,
     return _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
                                    max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation,
                                    use_vq)[0]
+
+
+def encode_stream_abr_pinned(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None,
+                             start_bytes=0, max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                             nmr_range_db=(-30, 30), allocation="budget", use_vq=False, pin_step_db=1.0, max_phases=8):
+    """encode_stream_abr_buffered with a target per block -> .pac bytes: the size and the leaky bucket are that call's,
+    word for word, but only the blocks the buffer binds pay for it.  The stream's target holds wherever the buffer
+    allows; a stretch of blocks that would overflow it at that target is pinned at a higher one, phase by phase
+    (include/pacx_bucket_pin.h: Encoder.rate_solve_bucket_pinned / band_solve_bucket_pinned, on the scalar sibling for
+    gain-shape streams): a pinned block lies within pin_step_db (a multiple of 1/64 dB) of the lowest level at which
+    its stretch fits, and at most max_phases (1 ... 16) levels are pinned -- with max_phases=1 the stream is
+    encode_stream_abr_buffered's, with a buffer nothing reaches encode_stream_abr's.  No block ends above the one
+    target of encode_stream_abr_buffered; the assignment written was measured to fit.  Every block is coded as
+    encode_stream_nmr codes it at that block's target (allocation as there).  One curve, one solve, one second pass.
+    ValueError as encode_stream_abr_buffered raises it, in the same words."""
+    return _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
+                                   max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation,
+                                   use_vq, (pin_step_db, max_phases))[0]
 
 
 class _Blocks:

@@ -478,6 +478,47 @@ def encode_stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, dr
     return data, info
 
 
+def encode_stream_to_buffer_pinned(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None,
+                                   start_bytes=0, max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                                   nmr_range_db=(-30, 30), allocation="budget", use_vq=False, pin_step_db=1.0,
+                                   max_phases=8):
+    """pacfile.encode_stream_abr_pinned with what the buffer saw: -> (.pac bytes, info).  info is
+    encode_stream_to_buffer's (target_nmr_db: the stream's level, the target of every free block) and
+      block_target_nmr_db  float64 [blocks]: the target of every block;
+      phase_of             int32 [blocks]: the phase that pinned the block, -1: free;
+      phases, open         the bisections run, and whether the last phase allowed still pinned a block;
+      through_bytes        float64 [blocks]: the highest level any stretch of blocks containing the block reaches."""
+    from . import pacfile
+    data, sol, out, limit, b, enc = pacfile._encode_stream_buffered(
+        pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes, max_kbps_per_channel,
+        block_switching, header_samples, nmr_range_db, allocation, use_vq, (pin_step_db, max_phases))
+    n_ch = np.asarray(pcm).shape[1]
+    n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
+    scan = enc.bucket_through(out["n_bytes"], n_ch, b, want_level=True)
+    mean, most = _rates_kbps(np.where(n_bytes > 0, n_bytes + 4, 0).sum(axis=1), n_ch, HOP / float(sample_rate))
+    one = 2.0 ** _lib.BUCKET_Q
+    info = {
+        "allocation": allocation,
+        "target_nmr_db": sol["target_nmr_db"],
+        "block_target_nmr_db": sol["target_t"].cpu().numpy().astype(np.float64) / _lib.RATE_TARGET_GRID,
+        "phase_of": sol["phase_of"].cpu().numpy(),
+        "phases": sol["phases"],
+        "open": sol["open"],
+        "limit_bytes": limit,
+        "total_bytes": scan["total"],
+        "bucket": b,
+        "n_bytes": sol["n_bytes"].cpu().numpy().reshape(-1, n_ch),
+        "level_bytes": scan["level"].cpu().numpy() / one,
+        "through_bytes": scan["through"].cpu().numpy() / one,
+        "peak_bytes": scan["peak_bytes"],
+        "peak_block": scan["peak_hop"],
+        "end_bytes": scan["end_bytes"],
+        "mean_kbps_per_channel": mean,
+        "max_kbps_per_channel_seen": most,
+    }
+    return data, info
+
+
 def buffer_report(pac_bytes, kbps_per_channel, buffer_bytes, start_bytes=0):
     """Whether a finished .pac, made anywhere, plays through a leaky bucket (pacfile.bucket: kbps_per_channel leaves a
     buffer of buffer_bytes per block; the channels, sample rate and block size are the file's): the header is parsed

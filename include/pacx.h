@@ -1328,6 +1328,8 @@ int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t
 /* pacx_bucket_scan, pacx_band_solve_bucket and pacx_rate_solve_bucket (additive exports, ABI 7): declared in the
    companion header beside this one, which is part of this interface and is included nowhere else */
 #include "pacx_bucket.h"
+/* per-block targets under a bucket (additive exports, ABI 7): the second companion header, behind the first */
+#include "pacx_bucket_pin.h"
 
 #ifdef __cplusplus
 }
