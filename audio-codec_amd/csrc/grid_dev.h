@@ -8,6 +8,7 @@
  *   frame_target, grid_clamp
  *                       the target of a frame (its uniform segment's, or the one given by value) and its grid index
  *   cand_bits, floor_half, wave_scan
+ *   narrow_half         one step of a solve's bisection: the smallest fitting target, mid = hi at the end
  *   PROF_*              the shape of a profile workgroup: 16 waves, the entries a thread owns
  *   band_profile_frame  what one channel-frame of a band curve adds at every entry of the grid
  *   RunWalk, flush_row  a workgroup's contiguous run of frames, segment by segment, and its bytes into a row
@@ -34,6 +35,23 @@ __device__ __forceinline__ int cand_bits(int i) { return i ? i + 1 : 0; }
 __device__ __forceinline__ int floor_half(int a)   /* floor(a / 2), a of either sign */
 {
     return (a - (a < 0 ? 1 : 0)) / 2;
+}
+
+/* One narrowing of the search for the smallest target that fits, in (lo, hi] with hi known to fit: the pick at mid
+   gave `fits`.  -> false: mid is the next target to try; true: the search has ended and mid = hi is its answer.  (The
+   probe of t_hi that opens a search comes here with fits and mid == hi, which leaves the interval as it is.) */
+__device__ __forceinline__ bool narrow_half(int &lo, int &hi, int &mid, bool fits)
+{
+    if (fits)
+        hi = mid;
+    else
+        lo = mid;
+    if (hi - lo > 1) {
+        mid = floor_half(lo + hi);
+        return false;
+    }
+    mid = hi;
+    return true;
 }
 
 /* inclusive sum over the wave's lanes 0 ... lane */
@@ -269,8 +287,8 @@ __device__ __forceinline__ void flush_row(long long (&bytes)[PROF_TILES], int ba
 }
 
 /* the decision of include/pacx.h (pacx_rate_solve) with total(t) = row[t - t_lo] against a limit >= 0: the probe of
-   t_hi, then the bisection; `halvings` bounds it whatever the data: ceil(log2(t_hi - t_lo + 2)).  (k_rate.hip's
-   solve_step takes the same decision launch by launch on a pick's total; tests hold the two together.)
+   t_hi, then the bisection; `halvings` bounds it whatever the data: ceil(log2(t_hi - t_lo + 2)).  (rate_dev.h's
+   solve_decide takes the same decision launch by launch on a pick's total; tests hold the two together.)
    -> the target found, t_hi with met = 0 where the limit cannot be met */
 __device__ __forceinline__ int profile_decide(const unsigned long long *__restrict__ row, long long limit, int t_lo,
                                               int t_hi, int halvings, int &met)

@@ -33,7 +33,8 @@
  *                      hold their floors after the drive above without its last pick; one more state, the stream's,
  *                      is driven by the same solve_step on picks at max(stream target, floor of the frame's segment)
  *                      (k_solve_pick<true>, k_band_pick_seg<true>).
- * RateLds, RateUnit, rate_unit, wave_sum and SolveState live in rate_dev.h: k_band.hip shares them.
+ * RateLds, RateUnit, rate_unit, wave_sum, SolveState and solve_decide live in rate_dev.h: k_band.hip and k_bucket.hip
+ * share them.
  *
  * All arithmetic that decides an integer code goes through pacx_exact.h and is compiled with -ffp-contract=off.
  */
@@ -44,8 +45,8 @@
 #include "pacx_launch.h"
 #include "wave_fft.h"   /* wave_lds_fence */
 #include "quant_dev.h"
-#include "rate_dev.h"   /* RateLds, RateUnit, rate_unit, wave_sum, SolveState */
-#include "pick_dev.h"   /* solve_frame; frame_target, floor_half (grid_dev.h) */
+#include "rate_dev.h"   /* RateLds, RateUnit, rate_unit, wave_sum, SolveState, solve_decide */
+#include "pick_dev.h"   /* solve_frame; frame_target (grid_dev.h) */
 
 using namespace pacx_k;
 
@@ -273,8 +274,8 @@ __global__ __launch_bounds__(64) void k_bitalloc_budget(PacxTables T, const uint
    on the stored curves, a SolveState each; pacx_rate_solve's whole stream is one such stretch ---- */
 constexpr int SOLVE_THREADS = 256;
 
-/* the decision of include/pacx.h on the total the pick before it left, the only one: k_solve_step takes it for every
-   segment.  final: write the result */
+/* solve_decide (rate_dev.h) on the total the pick before it left: k_solve_step takes it for every segment.  final:
+   write the result */
 __device__ __forceinline__ void solve_step(SolveState *s, long long limit, int final, pacx_rate_result *result)
 {
     const unsigned long long total = s->total;
@@ -285,27 +286,7 @@ __device__ __forceinline__ void solve_step(SolveState *s, long long limit, int f
         result->total = (int64_t)total;
         return;
     }
-    if (s->done)
-        return;
-    const bool fits = total <= (unsigned long long)limit;
-    if (s->phase == 0) {
-        if (!fits) {                               /* unreachable: the largest target, met = 0 */
-            s->done = 1;
-            return;                                /* mid stays t_hi */
-        }
-        s->met = 1;
-        s->phase = 1;
-    } else if (fits) {
-        s->hi = s->mid;
-    } else {
-        s->lo = s->mid;
-    }
-    if (s->hi - s->lo > 1) {
-        s->mid = floor_half(s->lo + s->hi);
-    } else {
-        s->mid = s->hi;
-        s->done = 1;
-    }
+    solve_decide(s, total <= (unsigned long long)limit);
 }
 
 /* one thread per segment: the state of a solve before its first pick.  one: the whole-stream solve's table, seg_first

@@ -2289,7 +2289,8 @@ extern "C" int pacx_band_solve_peak(pacx_handle *h, int64_t n_cf, const double *
                  peak_bytes, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, stream, &peak);
 }
 
-/* ---- a leaky bucket: its level over the hops, and the two solves under it (k_bucket.hip) ---- */
+/* ---- a leaky bucket: its level at and through the hops (k_bucket.hip, k_bucket_pin.hip), the buffered solves and
+   the pinned solves with a target per hop under it ---- */
 static int check_bucket(pacx_handle *h, const char *what, int64_t n_hops, int32_t n_ch, const pacx_bucket *b)
 {
     const int64_t most = 1LL << 30, size_most = 1LL << 40;
@@ -2304,27 +2305,55 @@ static int check_bucket(pacx_handle *h, const char *what, int64_t n_hops, int32_
     return PACX_OK;
 }
 
-extern "C" int pacx_bucket_scan(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes, const pacx_bucket *b,
-                                int64_t *level, pacx_bucket_result *result, void *stream)
+/* the two level scans, checked and launched in one place.  wants_through: the scan that also writes the level through
+   every hop (k_bucket_pin.hip) */
+static int bucket_scan(pacx_handle *h, const char *what, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes,
+                       const pacx_bucket *b, int64_t *level, bool wants_through, int64_t *through,
+                       pacx_bucket_result *result, void *stream)
 {
-    const char *what = "pacx_bucket_scan";
     if (!h)
         return PACX_E_ARG;
     if (int rc = check_bucket(h, what, n_hops, n_ch, b))
         return rc;
-    if (!result || (n_hops > 0 && !n_bytes))
+    if (!result || (n_hops > 0 && (!n_bytes || (wants_through && !through))))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
     HIP_TRY(h, hipSetDevice(h->device));
-    pacx_launch_bucket_scan(n_hops, n_ch, n_bytes, *b, level, result, (hipStream_t)stream);
+    if (wants_through)
+        pacx_launch_bucket_through(n_hops, n_ch, n_bytes, *b, level, through, result, (hipStream_t)stream);
+    else
+        pacx_launch_bucket_scan(n_hops, n_ch, n_bytes, *b, level, result, (hipStream_t)stream);
     return post_launch(h, what);
 }
 
-/* the two buffered solves, checked and launched in one place: solve()'s rules for a whole-stream solve and
-   check_bucket's; the picks are the one-segment picks of pacx_*_pick_segments at the state's target word */
+extern "C" int pacx_bucket_scan(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes, const pacx_bucket *b,
+                                int64_t *level, pacx_bucket_result *result, void *stream)
+{
+    return bucket_scan(h, "pacx_bucket_scan", n_hops, n_ch, n_bytes, b, level, false, nullptr, result, stream);
+}
+
+extern "C" int pacx_bucket_through(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes,
+                                   const pacx_bucket *b, int64_t *level, int64_t *through, pacx_bucket_result *result,
+                                   void *stream)
+{
+    return bucket_scan(h, "pacx_bucket_through", n_hops, n_ch, n_bytes, b, level, true, through, result, stream);
+}
+
+/* what a pinned solve takes and gives beyond a buffered one (include/pacx_bucket_pin.h) */
+struct PinArgs {
+    int32_t pin_step_t, max_phases;
+    int32_t *target_t, *phase_of;     /* [n_cf / n_ch] */
+    pacx_pin_result *result;
+};
+
+/* The four solves under a bucket, checked and launched in one place: solve()'s rules for a whole-stream solve and
+   check_bucket's.  Buffered: the picks are the one-segment picks of pacx_*_pick_segments at the state's target word.
+   pin (k_bucket_pin.hip): the step and the phase count are checked too, the workspace holds F_h and a pin per hop,
+   and the picks are those of pacx_*_pick_segments with a segment per hop at the solve's target_t. */
 static int solve_bucket(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t n_ch, int32_t row,
                         int32_t sub_stride, const double *curve, const int32_t *a, const int32_t *b, int64_t limit_bytes,
                         const pacx_bucket *bucket, double nmr_lo_db, double nmr_hi_db, int32_t *per_cf, int32_t *n_bytes,
-                        uint8_t *capped, pacx_rate_result *result, pacx_bucket_result *bucket_result, void *stream)
+                        uint8_t *capped, pacx_rate_result *result, pacx_bucket_result *bucket_result, void *stream,
+                        const PinArgs *pin = nullptr)
 {
     if (!h)
         return PACX_E_ARG;
@@ -2334,29 +2363,44 @@ static int solve_bucket(pacx_handle *h, int kind, const char *what, int64_t n_cf
         return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
     if (n_ch < 1 || n_cf % n_ch != 0)
         return fail(h, PACX_E_ARG, std::string(what) + ": n_cf must be a multiple of n_ch >= 1");
-    if (!result || !bucket_result || (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped)))
+    if (!result || !bucket_result || (pin && !pin->result) ||
+        (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped || (pin && (!pin->target_t || !pin->phase_of)))))
         return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
     if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
         return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
     if (limit_bytes < 0)
         return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    if (pin && pin->pin_step_t < 1)
+        return fail(h, PACX_E_ARG, std::string(what) + ": pin_step_t must be at least 1 (grid units of 1/64 dB)");
+    if (pin && (pin->max_phases < 1 || pin->max_phases > PACX_PIN_PHASES_MAX))
+        return fail(h, PACX_E_ARG, std::string(what) + ": max_phases must lie in [1, " +
+                                       std::to_string(PACX_PIN_PHASES_MAX) + "]");
     int rc, t_lo, t_hi;
     if ((rc = check_bucket(h, what, n_cf / n_ch, n_ch, bucket)) ||
         (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
         return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = grow(h, GROW_SOLVE, 1)))
+    const int64_t n_hops = n_cf / n_ch;
+    if ((rc = grow(h, GROW_SOLVE, pin && n_hops > 1 ? n_hops : 1)))
         return rc;
-    const PacxBucketSolve v = {h->ws_bucket, n_cf, n_ch, t_lo, t_hi, limit_bytes, *bucket, n_bytes, result, bucket_result};
-    pacx_bucket_drive(v, st, [&](const int32_t *target_t) {
+    /* a segment per hop at the pinned solve's targets, else one segment at the state's target word */
+    auto pick = [&](long long seg_cf, const int32_t *target_t) {
         if (kind == SOLVE_RATE)
-            pacx_launch_rate_pick_segments(n_cf, row, sub_stride, curve, a, b, PACX_SEG_CF_MAX, 0, target_t, 0, per_cf,
-                                           n_bytes, capped, st);
+            pacx_launch_rate_pick_segments(n_cf, row, sub_stride, curve, a, b, seg_cf, 0, target_t, 0, per_cf, n_bytes,
+                                           capped, st);
         else
-            pacx_launch_band_pick_segments(h->T, n_cf, PACX_SEG_CF_MAX, 0, target_t, curve, a, b, per_cf, n_bytes, capped,
-                                           st);
-    });
+            pacx_launch_band_pick_segments(h->T, n_cf, seg_cf, 0, target_t, curve, a, b, per_cf, n_bytes, capped, st);
+    };
+    if (pin) {
+        const PacxPinSolve v = {h->ws_pin, n_cf, n_ch, t_lo, t_hi, pin->pin_step_t, pin->max_phases, limit_bytes, *bucket,
+                                n_bytes, pin->target_t, pin->phase_of, result, bucket_result, pin->result};
+        pacx_pin_drive(v, st, [&]() { pick(n_ch, pin->target_t); });
+    } else {
+        const PacxBucketSolve v = {h->ws_bucket, n_cf, n_ch, t_lo, t_hi, limit_bytes, *bucket, n_bytes, result,
+                                   bucket_result};
+        pacx_bucket_drive(v, st, [&](const int32_t *target_t) { pick(PACX_SEG_CF_MAX, target_t); });
+    }
     return post_launch(h, what);
 }
 
@@ -2380,73 +2424,6 @@ extern "C" int pacx_rate_solve_bucket(pacx_handle *h, int64_t n_cf, int32_t n_ch
                         limit_bytes, b, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, bucket_result, stream);
 }
 
-/* ---- per-block targets under a bucket: the level through every hop and the two pinned solves (k_bucket_pin.hip) ---- */
-extern "C" int pacx_bucket_through(pacx_handle *h, int64_t n_hops, int32_t n_ch, const int32_t *n_bytes,
-                                   const pacx_bucket *b, int64_t *level, int64_t *through, pacx_bucket_result *result,
-                                   void *stream)
-{
-    const char *what = "pacx_bucket_through";
-    if (!h)
-        return PACX_E_ARG;
-    if (int rc = check_bucket(h, what, n_hops, n_ch, b))
-        return rc;
-    if (!result || (n_hops > 0 && (!n_bytes || !through)))
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    HIP_TRY(h, hipSetDevice(h->device));
-    pacx_launch_bucket_through(n_hops, n_ch, n_bytes, *b, level, through, result, (hipStream_t)stream);
-    return post_launch(h, what);
-}
-
-/* the two pinned solves, checked and launched in one place: solve_bucket's rules, the step and the phase count; the
-   picks are those of pacx_*_pick_segments with a segment per hop at the solve's target_t */
-static int solve_bucket_pinned(pacx_handle *h, int kind, const char *what, int64_t n_cf, int32_t n_ch, int32_t row,
-                               int32_t sub_stride, const double *curve, const int32_t *a, const int32_t *b,
-                               int64_t limit_bytes, const pacx_bucket *bucket, double nmr_lo_db, double nmr_hi_db,
-                               int32_t pin_step_t, int32_t max_phases, int32_t *per_cf, int32_t *n_bytes, uint8_t *capped,
-                               int32_t *target_t, int32_t *phase_of, pacx_rate_result *result,
-                               pacx_bucket_result *bucket_result, pacx_pin_result *pin_result, void *stream)
-{
-    if (!h)
-        return PACX_E_ARG;
-    if (int rc = scalar_only(h, what))
-        return rc;
-    if (n_cf < 0 || n_cf > 0x7fffffffLL / PACX_SUB)
-        return fail(h, PACX_E_ARG, std::string(what) + ": bad channel-frame count");
-    if (n_ch < 1 || n_cf % n_ch != 0)
-        return fail(h, PACX_E_ARG, std::string(what) + ": n_cf must be a multiple of n_ch >= 1");
-    if (!result || !bucket_result || !pin_result ||
-        (n_cf > 0 && (!curve || !a || !b || !per_cf || !n_bytes || !capped || !target_t || !phase_of)))
-        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
-    if (kind == SOLVE_RATE && (sub_stride < 1 || row < (PACX_SUB - 1) * (long long)sub_stride + 1))
-        return fail(h, PACX_E_ARG, std::string(what) + ": row must hold eight sub-blocks (row >= 7 sub_stride + 1)");
-    if (limit_bytes < 0)
-        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
-    if (pin_step_t < 1)
-        return fail(h, PACX_E_ARG, std::string(what) + ": pin_step_t must be at least 1 (grid units of 1/64 dB)");
-    if (max_phases < 1 || max_phases > PACX_PIN_PHASES_MAX)
-        return fail(h, PACX_E_ARG, std::string(what) + ": max_phases must lie in [1, " +
-                                       std::to_string(PACX_PIN_PHASES_MAX) + "]");
-    int rc, t_lo, t_hi;
-    if ((rc = check_bucket(h, what, n_cf / n_ch, n_ch, bucket)) ||
-        (rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi)))
-        return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n_hops = n_cf / n_ch;
-    if ((rc = grow(h, GROW_SOLVE, n_hops > 1 ? n_hops : 1)))
-        return rc;
-    const PacxPinSolve v = {h->ws_pin, n_cf, n_ch, t_lo, t_hi, pin_step_t, max_phases, limit_bytes, *bucket, n_bytes,
-                            target_t, phase_of, result, bucket_result, pin_result};
-    pacx_pin_drive(v, st, [&]() {
-        if (kind == SOLVE_RATE)
-            pacx_launch_rate_pick_segments(n_cf, row, sub_stride, curve, a, b, n_ch, 0, target_t, 0, per_cf, n_bytes,
-                                           capped, st);
-        else
-            pacx_launch_band_pick_segments(h->T, n_cf, n_ch, 0, target_t, curve, a, b, per_cf, n_bytes, capped, st);
-    });
-    return post_launch(h, what);
-}
-
 extern "C" int pacx_band_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32_t n_ch, const double *nmr,
                                              const int32_t *cap, const int32_t *cap_alloc, int64_t limit_bytes,
                                              const pacx_bucket *b, double nmr_lo_db, double nmr_hi_db, int32_t pin_step_t,
@@ -2454,9 +2431,9 @@ extern "C" int pacx_band_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32
                                              int32_t *target_t, int32_t *phase_of, pacx_rate_result *result,
                                              pacx_bucket_result *bucket_result, pacx_pin_result *pin_result, void *stream)
 {
-    return solve_bucket_pinned(h, SOLVE_BAND, "pacx_band_solve_bucket_pinned", n_cf, n_ch, 0, 0, nmr, cap, cap_alloc,
-                               limit_bytes, b, nmr_lo_db, nmr_hi_db, pin_step_t, max_phases, bit_alloc, n_bytes, capped,
-                               target_t, phase_of, result, bucket_result, pin_result, stream);
+    const PinArgs pin = {pin_step_t, max_phases, target_t, phase_of, pin_result};
+    return solve_bucket(h, SOLVE_BAND, "pacx_band_solve_bucket_pinned", n_cf, n_ch, 0, 0, nmr, cap, cap_alloc, limit_bytes,
+                        b, nmr_lo_db, nmr_hi_db, bit_alloc, n_bytes, capped, result, bucket_result, stream, &pin);
 }
 
 extern "C" int pacx_rate_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32_t n_ch, int32_t row, int32_t sub_stride,
@@ -2467,9 +2444,9 @@ extern "C" int pacx_rate_solve_bucket_pinned(pacx_handle *h, int64_t n_cf, int32
                                              pacx_rate_result *result, pacx_bucket_result *bucket_result,
                                              pacx_pin_result *pin_result, void *stream)
 {
-    return solve_bucket_pinned(h, SOLVE_RATE, "pacx_rate_solve_bucket_pinned", n_cf, n_ch, row, sub_stride, worst, bits,
-                               steps, limit_bytes, b, nmr_lo_db, nmr_hi_db, pin_step_t, max_phases, budget, n_bytes,
-                               capped, target_t, phase_of, result, bucket_result, pin_result, stream);
+    const PinArgs pin = {pin_step_t, max_phases, target_t, phase_of, pin_result};
+    return solve_bucket(h, SOLVE_RATE, "pacx_rate_solve_bucket_pinned", n_cf, n_ch, row, sub_stride, worst, bits, steps,
+                        limit_bytes, b, nmr_lo_db, nmr_hi_db, budget, n_bytes, capped, result, bucket_result, stream, &pin);
 }
 
 /* ---- the size at every target of the grid, and the solve on it ---- */

@@ -2,13 +2,15 @@
  * rate_dev.h -- what the kernels that code to a noise-to-mask target share: k_rate.hip (the budget search, the rate
  * curve, the solve) and k_band.hip (the band-by-band allocation).  One wave per unit -- a long block or a short
  * sub-block: the unit's preamble (lines, line bands, band maxima and band means of the mask into LDS), the wave sum
- * of k_nmr's order, and the few words of state of a solve.  Included with -ffp-contract=off like the files it serves.
+ * of k_nmr's order, and the few words of state of a solve with the decision taken on them (k_bucket.hip shares those
+ * two).  Included with -ffp-contract=off like the files it serves.
  */
 #ifndef PACX_RATE_DEV_H
 #define PACX_RATE_DEV_H
 
 #include <math.h>
 
+#include "grid_dev.h"   /* narrow_half */
 #include "pacx_dev.h"
 #include "wave_fft.h"   /* wave_lds_fence */
 
@@ -120,6 +122,24 @@ struct SolveState {
     int done, met;
     unsigned long long total;                      /* of the pick in flight */
 };
+
+/* the decision of include/pacx.h (pacx_rate_solve) on whether the pick at s->mid fits, the only one: k_rate.hip's
+   solve_step takes it on total <= limit, k_bucket.hip's k_bucket_step with the bucket's peak as a second condition */
+__device__ __forceinline__ void solve_decide(SolveState *s, bool fits)
+{
+    if (s->done)
+        return;
+    if (s->phase == 0) {
+        if (!fits) {                               /* unreachable: the largest target, met = 0 */
+            s->done = 1;
+            return;                                /* mid stays t_hi */
+        }
+        s->met = 1;
+        s->phase = 1;
+    }
+    if (narrow_half(s->lo, s->hi, s->mid, fits))
+        s->done = 1;
+}
 
 /* the segment of channel-frame cf, 0 <= cf < first[n_seg]: the s with first[s] <= cf < first[s + 1] (first[0] = 0,
    non-decreasing, so an empty segment is never the answer).  `steps` halvings, pacx_segment_search_steps(n_seg) of

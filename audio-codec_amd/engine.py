@@ -393,13 +393,30 @@ class Encoder:
         out["capped"] = out["capped"].bool()
         return out
 
-    def _solve(self, kind, op, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None, bucket=None):
-        """The eight solves: op "solve_segments" with seg_first and one limit per segment, "solve_peak" with those (the
-        limits are then the peaks) and stream_limit for the whole batch, "solve_bucket" with bucket = (channels of a
-        hop, the bucket) beside the one limit, else "solve", the whole stream with its one limit (the plain C entry
-        point).  Checks the curve, makes the outputs, calls pacx_<kind>_<op> and decodes the pacx_rate_result of every
-        segment: t, met, total (int64) in four int32."""
-        what, peak, bucketed = f"{kind.prefix}_{op}", op == "solve_peak", op == "solve_bucket"
+    @staticmethod
+    def _whole_bytes(what, limit_bytes):
+        """a limit the C side takes by value"""
+        if int(limit_bytes) != limit_bytes or limit_bytes < 0:
+            raise ValueError(f"{what}: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+        return ctypes.c_int64(int(limit_bytes))
+
+    @staticmethod
+    def _rate_results(res, one=False):
+        """pacx_rate_result words (int32 NumPy array [n, 4]: t, met, total as int64 in two of them) -> dict of NumPy
+        arrays target_nmr_db, met, total_bytes; one: of the first result's numbers"""
+        out = {"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID), "met": res[:, 1] != 0,
+               "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]}
+        if one:
+            out = {"target_nmr_db": float(out["target_nmr_db"][0]), "met": bool(out["met"][0]),
+                   "total_bytes": int(out["total_bytes"][0])}
+        return out
+
+    def _solve(self, kind, op, curve, seg_first, limit_bytes, nmr_lo_db, nmr_hi_db, stream_limit=None):
+        """The six solves: op "solve_segments" with seg_first and one limit per segment, "solve_peak" with those (the
+        limits are then the peaks) and stream_limit for the whole batch, else "solve", the whole stream with its one
+        limit (the plain C entry point).  Checks the curve, makes the outputs, calls pacx_<kind>_<op> and decodes the
+        pacx_rate_result of every segment."""
+        what, peak = f"{kind.prefix}_{op}", op == "solve_peak"
         segmented = peak or op == "solve_segments"
         checked = self._checked(kind, curve, what)
         n_cf, out = checked[1], self._picked(kind, checked)
@@ -409,42 +426,22 @@ class Encoder:
         else:
             limits = [ctypes.c_int64(int(limit_bytes))]
         n_seg = len(limit) if segmented else 1
-        # a peak solve's floors and the stream's result, a buffered solve's pacx_bucket_result (five int64 in three
-        # rows) ride behind the segments' results: one tensor, one copy back
-        behind = (n_seg + 3) // 4 + 1 if peak else 3 if bucketed else 0
-        result = torch.zeros((n_seg + behind, 4), dtype=torch.int32, device=self.device)
-        more = []
-        if bucketed:
-            if int(limit_bytes) != limit_bytes or limit_bytes < 0:
-                raise ValueError(f"{what}: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
-            n_ch = self._hop_channels(what, bucket[0], n_cf)
-            checked = checked[:3] + ([ctypes.c_int32(n_ch)] + checked[3],)          # n_ch goes behind n_cf
-            limits.append(ctypes.byref(self._bucket_struct(what, bucket[1])))
-            more = [_ptr(result), _ptr(result[1:])]                                  # result, bucket_result
-        elif peak:
-            if int(stream_limit) != stream_limit or stream_limit < 0:
-                raise ValueError(f"{what}: limit_bytes = {stream_limit!r}: a whole number of bytes, not negative")
-            limits.append(ctypes.c_int64(int(stream_limit)))
+        # a peak solve's floors and the stream's result ride behind the segments' results: one tensor, one copy back
+        result = torch.zeros((n_seg + ((n_seg + 3) // 4 + 1 if peak else 0), 4), dtype=torch.int32, device=self.device)
+        if peak:
+            limits.append(self._whole_bytes(what, stream_limit))
             more = [_ptr(result[n_seg + 1:]), _ptr(result), _ptr(result[n_seg:])]       # floor, result, result_stream
         else:
             more = [_ptr(result)]
         self._curve_call(what, checked, *limits, ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
                          _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]), _ptr(out["capped"]), *more)
-        grid = float(_lib.RATE_TARGET_GRID)
         res = result.cpu().numpy()
         out["capped"] = out["capped"].bool()
-        out.update({"target_nmr_db": res[:n_seg, 0].astype(np.float64) / grid, "met": res[:n_seg, 1] != 0,
-                    "total_bytes": res[:n_seg, 2:].copy().view(np.int64)[:, 0]})
+        out.update(self._rate_results(res[:n_seg], one=not segmented))
         if peak:
-            out.update({"floor_nmr_db": res[n_seg + 1:].reshape(-1)[:n_seg].astype(np.float64) / grid,
-                        "stream_target_nmr_db": float(res[n_seg, 0]) / grid, "stream_met": bool(res[n_seg, 1]),
-                        "stream_total_bytes": int(res[n_seg:n_seg + 1, 2:].copy().view(np.int64)[0, 0])})
+            out["floor_nmr_db"] = res[n_seg + 1:].reshape(-1)[:n_seg].astype(np.float64) / float(_lib.RATE_TARGET_GRID)
+            out.update({"stream_" + k: v for k, v in self._rate_results(res[n_seg:n_seg + 1], one=True).items()})
             out["pinned"] = out["target_nmr_db"] > out["stream_target_nmr_db"]
-        if bucketed:
-            out["bucket"] = self._bucket_result(res[1:].reshape(-1).view(np.int64))
-        if not segmented:
-            out.update({"target_nmr_db": float(out["target_nmr_db"][0]), "met": bool(out["met"][0]),
-                        "total_bytes": int(out["total_bytes"][0])})
         return out
 
     def rate_solve(self, curve, flags, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
@@ -567,6 +564,21 @@ class Encoder:
         out.update({"peak_bytes": out["peak_q16"] / 2.0 ** _lib.BUCKET_Q, "end_bytes": out["end_q16"] / 2.0 ** _lib.BUCKET_Q})
         return out
 
+    def _bucket_levels(self, what, n_bytes, n_channels, bucket, want_level, want_through):
+        """the two scans: pacx_<what>, which with want_through has one more array to write"""
+        nb = torch.as_tensor(n_bytes, device=self.device).to(torch.int32).contiguous().reshape(-1)
+        n_ch = self._hop_channels(what, n_channels, nb.numel())
+        n_hops = nb.numel() // n_ch
+        b = self._bucket_struct(what, bucket)
+        per_hop = {k: self._empty((n_hops,), torch.int64) for k, want in (("through", want_through), ("level", want_level))
+                   if want}
+        result = torch.zeros((len(_lib.BUCKET_RESULT),), dtype=torch.int64, device=self.device)
+        self._call("pacx_" + what, ctypes.c_int64(n_hops), n_ch, _ptr(nb), ctypes.byref(b), _ptr(per_hop.get("level")),
+                   *([_ptr(per_hop["through"])] if want_through else []), _ptr(result), self._stream())
+        out = self._bucket_result(result.cpu().numpy())
+        out.update(per_hop)
+        return out
+
     def bucket_scan(self, n_bytes, n_channels, bucket, want_level=False):
         """The level of a leaky bucket over the hops of a stream (pacx_bucket_scan, include/pacx_bucket.h): n_bytes [n_cf]
         int32 as a pick, a solve or a second pass writes it, n_channels consecutive entries a hop.  Every hop adds
@@ -575,27 +587,14 @@ class Encoder:
         -1: the start level is the peak), first_over (the first hop above size_bytes, -1: none), end_q16 (the level
         handed to the next piece of the stream: scans in pieces are exact), peak_bytes and end_bytes as float;
         want_level: also level, int64 device tensor [n_hops] in 1 / 65536 byte."""
-        what = "bucket_scan"
-        nb = torch.as_tensor(n_bytes, device=self.device).to(torch.int32).contiguous().reshape(-1)
-        n_ch = self._hop_channels(what, n_channels, nb.numel())
-        n_hops = nb.numel() // n_ch
-        b = self._bucket_struct(what, bucket)
-        level = self._empty((n_hops,), torch.int64) if want_level else None
-        result = torch.zeros((len(_lib.BUCKET_RESULT),), dtype=torch.int64, device=self.device)
-        self._call("pacx_bucket_scan", ctypes.c_int64(n_hops), n_ch, _ptr(nb), ctypes.byref(b), _ptr(level), _ptr(result),
-                   self._stream())
-        out = self._bucket_result(result.cpu().numpy())
-        if want_level:
-            out["level"] = level
-        return out
+        return self._bucket_levels("bucket_scan", n_bytes, n_channels, bucket, want_level, False)
 
     def rate_solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30):
         """rate_solve under a leaky bucket (pacx_rate_solve_bucket, include/pacx_bucket.h): the same bisection for the
         smallest target whose body stays within limit_bytes AND whose level in the bucket, n_channels channel-frames
         a hop, never exceeds size_bytes.  flags: as rate_solve takes them.  -> rate_solve's dict (met False: not even
         nmr_hi_db gives both) plus bucket, bucket_scan's dict of the n_bytes returned."""
-        return self._solve(RATE, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
-                           bucket=(n_channels, bucket))
+        return self._solve_bucket(RATE, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db)
 
     # ---- per-block targets under a bucket (pacx_bucket_through and the two pinned solves, include/pacx_bucket_pin.h)
     def bucket_through(self, n_bytes, n_channels, bucket, want_level=False):
@@ -604,21 +603,7 @@ class Encoder:
         stretch of consecutive hops containing the hop brings the buffer to (the start level counts as a stretch that
         begins before the first hop).  A hop lies in a stretch that overflows exactly when its entry is above
         size_bytes << 16.  want_level: also level, as bucket_scan gives it."""
-        what = "bucket_through"
-        nb = torch.as_tensor(n_bytes, device=self.device).to(torch.int32).contiguous().reshape(-1)
-        n_ch = self._hop_channels(what, n_channels, nb.numel())
-        n_hops = nb.numel() // n_ch
-        b = self._bucket_struct(what, bucket)
-        level = self._empty((n_hops,), torch.int64) if want_level else None
-        through = self._empty((n_hops,), torch.int64)
-        result = torch.zeros((len(_lib.BUCKET_RESULT),), dtype=torch.int64, device=self.device)
-        self._call("pacx_bucket_through", ctypes.c_int64(n_hops), n_ch, _ptr(nb), ctypes.byref(b), _ptr(level),
-                   _ptr(through), _ptr(result), self._stream())
-        out = self._bucket_result(result.cpu().numpy())
-        out["through"] = through
-        if want_level:
-            out["level"] = level
-        return out
+        return self._bucket_levels("bucket_through", n_bytes, n_channels, bucket, want_level, True)
 
     @staticmethod
     def _pin_args(what, pin_step_db, max_phases):
@@ -636,32 +621,29 @@ class Encoder:
             raise ValueError(f"{what}: max_phases = {max_phases!r}: a whole number in [1, {_lib.PIN_PHASES_MAX}]")
         return int(step), int(max_phases)
 
-    def _solve_pinned(self, kind, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db, max_phases):
-        """The two pinned solves: checks the curve, makes the outputs, calls pacx_<kind>_solve_bucket_pinned and decodes
-        the three results, which ride in one tensor: pacx_rate_result, pacx_bucket_result, pacx_pin_result."""
-        what = f"{kind.prefix}_solve_bucket_pinned"
-        step, phases = self._pin_args(what, pin_step_db, max_phases)
+    def _solve_bucket(self, kind, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pinned=None):
+        """The four solves under a bucket, pinned = (pin_step_db, max_phases) for the two with a target per hop: checks
+        the curve, makes the outputs, calls pacx_<kind>_solve_bucket[_pinned] and decodes the results, which ride in
+        one tensor: pacx_rate_result, pacx_bucket_result (five int64 in three rows) and, pinned, pacx_pin_result."""
+        what = f"{kind.prefix}_solve_bucket" + ("" if pinned is None else "_pinned")
+        pin = () if pinned is None else self._pin_args(what, *pinned)
         checked = self._checked(kind, curve, what)
         n_cf, out = checked[1], self._picked(kind, checked)
-        if int(limit_bytes) != limit_bytes or limit_bytes < 0:
-            raise ValueError(f"{what}: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+        limit = self._whole_bytes(what, limit_bytes)
         n_ch = self._hop_channels(what, n_channels, n_cf)
-        n_hops = n_cf // n_ch
         checked = checked[:3] + ([ctypes.c_int32(n_ch)] + checked[3],)              # n_ch goes behind n_cf
         b = self._bucket_struct(what, bucket)
-        result = torch.zeros((5, 4), dtype=torch.int32, device=self.device)         # 16 + 40 + 8 bytes
-        per_hop = torch.zeros((2, n_hops), dtype=torch.int32, device=self.device)   # target_t, phase_of
-        self._curve_call(what, checked, ctypes.c_int64(int(limit_bytes)), ctypes.byref(b), ctypes.c_double(nmr_lo_db),
-                         ctypes.c_double(nmr_hi_db), ctypes.c_int32(step), ctypes.c_int32(phases),
-                         _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]), _ptr(out["capped"]), _ptr(per_hop[0]),
-                         _ptr(per_hop[1]), _ptr(result), _ptr(result[1:]), _ptr(result[4:]))
-        grid = float(_lib.RATE_TARGET_GRID)
+        result = torch.zeros((5 if pin else 4, 4), dtype=torch.int32, device=self.device)
+        per_hop = torch.zeros((2, n_cf // n_ch), dtype=torch.int32, device=self.device) if pin else ()   # target_t, phase_of
+        self._curve_call(what, checked, limit, ctypes.byref(b), ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db),
+                         *(ctypes.c_int32(v) for v in pin), _ptr(out[kind.per_cf.key]), _ptr(out["n_bytes"]),
+                         _ptr(out["capped"]), *(_ptr(t) for t in per_hop), _ptr(result), _ptr(result[1:]),
+                         *([_ptr(result[4:])] if pin else []))
         res = result.cpu().numpy()
         out["capped"] = out["capped"].bool()
-        out.update({"target_nmr_db": float(res[0, 0]) / grid, "met": bool(res[0, 1]),
-                    "total_bytes": int(res[:1, 2:].copy().view(np.int64)[0, 0]),
-                    "bucket": self._bucket_result(res[1:].reshape(-1).view(np.int64)),
-                    "target_t": per_hop[0], "phase_of": per_hop[1], "phases": int(res[4, 0]), "open": bool(res[4, 1])})
+        out.update(self._rate_results(res, one=True), bucket=self._bucket_result(res[1:].reshape(-1).view(np.int64)))
+        if pin:
+            out.update({"target_t": per_hop[0], "phase_of": per_hop[1], "phases": int(res[4, 0]), "open": bool(res[4, 1])})
         return out
 
     def rate_solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30,
@@ -672,8 +654,8 @@ class Encoder:
         -> rate_solve_bucket's dict (target_nmr_db: the stream's level, the target of every free hop) plus target_t and
         phase_of, int32 device tensors [n_hops] (grid units; the phase that pinned the hop, -1: free), phases (the
         bisections run) and open (True: the last phase allowed still pinned a hop)."""
-        return self._solve_pinned(RATE, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db,
-                                  max_phases)
+        return self._solve_bucket(RATE, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db,
+                                  (pin_step_db, max_phases))
 
     # ---- the whole-grid profile of a rate curve and the pick at known targets (pacx_rate_profile and its three
     # companions, include/pacx.h): the band siblings below on the other curve, with their checks
@@ -773,14 +755,11 @@ class Encoder:
         band_solve(curve, ...)'s target_nmr_db, met, total_bytes.  -> dict of those three."""
         n = self._profile_len("profile_solve", nmr_lo_db, nmr_hi_db)
         profile = self._profile_tensor("profile_solve", profile, n)
-        if int(limit_bytes) != limit_bytes or limit_bytes < 0:
-            raise ValueError(f"profile_solve: limit_bytes = {limit_bytes!r}: a whole number of bytes, not negative")
+        limit = self._whole_bytes("profile_solve", limit_bytes)
         result = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
-        self._call_rate("pacx_profile_solve", _ptr(profile), ctypes.c_int64(int(limit_bytes)),
-                        ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), _ptr(result), self._stream())
-        res = result.cpu().numpy()
-        return {"target_nmr_db": float(res[0, 0]) / float(_lib.RATE_TARGET_GRID), "met": bool(res[0, 1]),
-                "total_bytes": int(res[:, 2:].copy().view(np.int64)[0, 0])}
+        self._call_rate("pacx_profile_solve", _ptr(profile), limit, ctypes.c_double(nmr_lo_db),
+                        ctypes.c_double(nmr_hi_db), _ptr(result), self._stream())
+        return self._rate_results(result.cpu().numpy(), one=True)
 
     # ---- a profile per uniform segment of a piece (pacx_band_profile_segments and its three companions, include/pacx.h):
     # frame cf of the piece lies in local segment (first_off + cf) // seg_cf
@@ -859,9 +838,7 @@ class Encoder:
     @staticmethod
     def decode_results(result):
         """pacx_rate_result words (int32 device tensor [n, 4]) -> dict of NumPy arrays target_nmr_db, met, total_bytes"""
-        res = result.cpu().numpy()
-        return {"target_nmr_db": res[:, 0].astype(np.float64) / float(_lib.RATE_TARGET_GRID), "met": res[:, 1] != 0,
-                "total_bytes": res[:, 2:].copy().view(np.int64)[:, 0]}
+        return Encoder._rate_results(result.cpu().numpy())
 
     def profile_clamp_add(self, rows, result, nmr_lo_db=-30, nmr_hi_db=30, out=None):
         """Every row held at its own target's size below that target, summed into one profile (pacx_profile_clamp_add):
@@ -963,15 +940,14 @@ class Encoder:
     def band_solve_bucket(self, curve, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30):
         """rate_solve_bucket on a band curve (pacx_band_solve_bucket, include/pacx_bucket.h).  -> band_solve's dict plus
         bucket, bucket_scan's dict of the n_bytes returned."""
-        return self._solve(BAND, "solve_bucket", curve, None, limit_bytes, nmr_lo_db, nmr_hi_db,
-                           bucket=(n_channels, bucket))
+        return self._solve_bucket(BAND, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db)
 
     def band_solve_bucket_pinned(self, curve, n_channels, limit_bytes, bucket, nmr_lo_db=-30, nmr_hi_db=30,
                                  pin_step_db=1.0, max_phases=8):
         """rate_solve_bucket_pinned on a band curve (pacx_band_solve_bucket_pinned, include/pacx_bucket_pin.h).
         -> band_solve_bucket's dict plus target_t, phase_of, phases and open."""
-        return self._solve_pinned(BAND, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db, pin_step_db,
-                                  max_phases)
+        return self._solve_bucket(BAND, curve, n_channels, limit_bytes, bucket, nmr_lo_db, nmr_hi_db,
+                                  (pin_step_db, max_phases))
 
     def encode_pack_alloc(self, pcm, flags, bit_alloc, out=None, want_mantissa=False):
         """encode_pack() with the mantissa size of every band given by the caller (pacx_encode_pack_alloc_batch):

@@ -473,13 +473,10 @@ class _CurvePath:
     def solve_peak(self, curve, seg_first, peak_bytes, limit_bytes, lo, hi):
         return self._op("solve_peak", curve, seg_first, peak_bytes, limit_bytes, lo, hi)
 
-    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi):
-        """flags: as solve takes them"""
-        return self._op("solve_bucket", curve, n_channels, limit_bytes, bucket, lo, hi)
-
-    def solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases):
-        """flags: as solve takes them"""
-        return self._op("solve_bucket_pinned", curve, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases)
+    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pinned=None):
+        """flags: as solve takes them; pinned = (pin_step_db, max_phases): the solve with a target per hop"""
+        return self._op("solve_bucket" if pinned is None else "solve_bucket_pinned", curve, n_channels, limit_bytes,
+                        bucket, lo, hi, *(pinned or ()))
 
     # what the chunked encode (streaming.HostStreamRateEncoder) calls per chunk: the curve, its profile, the pick at
     # known targets and the second pass on that pick
@@ -560,12 +557,9 @@ class _BudgetPath(_CurvePath):
     def solve(self, curve, flags, limit_bytes, lo, hi):
         return self.enc.rate_solve(curve, flags, limit_bytes, lo, hi)
 
-    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi):
-        return self.enc.rate_solve_bucket(curve, flags, n_channels, limit_bytes, bucket, lo, hi)
-
-    def solve_bucket_pinned(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db, max_phases):
-        return self.enc.rate_solve_bucket_pinned(curve, flags, n_channels, limit_bytes, bucket, lo, hi, pin_step_db,
-                                                 max_phases)
+    def solve_bucket(self, curve, flags, n_channels, limit_bytes, bucket, lo, hi, pinned=None):
+        op = self.enc.rate_solve_bucket if pinned is None else self.enc.rate_solve_bucket_pinned
+        return op(curve, flags, n_channels, limit_bytes, bucket, lo, hi, *(pinned or ()))
 
     def encode(self, view, flags, budget):
         return self.enc.encode_pack_budget(view, flags, budget)
@@ -892,10 +886,7 @@ def _encode_stream_buffered(pcm, sample_rate, kbps_per_channel, buffer_bytes, dr
     limit = _abr_limit(cp, view, head, kbps_per_channel, None)
     path = _PATHS[allocation](enc)
     curve = path.curve(view, flags, cp.targetBitsPerSample)
-    if pinned is None:
-        sol = path.solve_bucket(curve, flags, cp.nChannels, limit, b, lo, hi)
-    else:
-        sol = path.solve_bucket_pinned(curve, flags, cp.nChannels, limit, b, lo, hi, *pinned)
+    sol = path.solve_bucket(curve, flags, cp.nChannels, limit, b, lo, hi, pinned)
     if not sol["met"] and sol["total_bytes"] > limit:
         raise ValueError(_unreachable(limit, sol["total_bytes"], hi, head))
     if not sol["met"]:

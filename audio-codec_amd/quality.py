@@ -438,28 +438,18 @@ def _rates_kbps(hop_bytes, n_ch, block_seconds):
     return float(per_block.mean()), float(per_block.max())
 
 
-def encode_stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None, start_bytes=0,
-                            max_kbps_per_channel=320, block_switching=False, header_samples=None, nmr_range_db=(-30, 30),
-                            allocation="budget", use_vq=False):
-    """pacfile.encode_stream_abr_buffered with what the buffer saw: -> (.pac bytes, info).  info, for the n + 2 blocks
-    the driver submits:
-      target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
-      bucket         the pacfile.Bucket of the call;
-      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written);
-      level_bytes    float64 [blocks]: the buffer's level right after every block's records arrive (a dropped hop
-                     brings none and only drains);
-      peak_bytes, peak_block  the highest of them and the first block that reaches it (-1: the start level);
-      end_bytes      the level after the last block has drained;
-      mean_kbps_per_channel, max_kbps_per_channel_seen  the body over the duration of the blocks, and the largest block
-                     at the rate of its own duration;
-      allocation     as given."""
+def _stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes,
+                      max_kbps_per_channel, block_switching, header_samples, nmr_range_db, allocation, use_vq,
+                      pinned=None):
+    """pacfile._encode_stream_buffered and the scan of what it wrote (pinned: the scan that also gives the level
+    through every block) -> (.pac bytes, encode_stream_to_buffer's info, the solve's dict, the scan's)"""
     from . import pacfile
     data, sol, out, limit, b, enc = pacfile._encode_stream_buffered(
         pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes, max_kbps_per_channel,
-        block_switching, header_samples, nmr_range_db, allocation, use_vq)
+        block_switching, header_samples, nmr_range_db, allocation, use_vq, pinned)
     n_ch = np.asarray(pcm).shape[1]
     n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
-    scan = enc.bucket_scan(out["n_bytes"], n_ch, b, want_level=True)
+    scan = (enc.bucket_scan if pinned is None else enc.bucket_through)(out["n_bytes"], n_ch, b, want_level=True)
     mean, most = _rates_kbps(np.where(n_bytes > 0, n_bytes + 4, 0).sum(axis=1), n_ch, HOP / float(sample_rate))
     info = {
         "allocation": allocation,
@@ -475,6 +465,27 @@ def encode_stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, dr
         "mean_kbps_per_channel": mean,
         "max_kbps_per_channel_seen": most,
     }
+    return data, info, sol, scan
+
+
+def encode_stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None, start_bytes=0,
+                            max_kbps_per_channel=320, block_switching=False, header_samples=None, nmr_range_db=(-30, 30),
+                            allocation="budget", use_vq=False):
+    """pacfile.encode_stream_abr_buffered with what the buffer saw: -> (.pac bytes, info).  info, for the n + 2 blocks
+    the driver submits:
+      target_nmr_db  the target found;   limit_bytes, total_bytes  the body limit and the body written;
+      bucket         the pacfile.Bucket of the call;
+      n_bytes        int32 [blocks, nCh]: the record lengths the solve predicted (the ones written);
+      level_bytes    float64 [blocks]: the buffer's level right after every block's records arrive (a dropped hop
+                     brings none and only drains);
+      peak_bytes, peak_block  the highest of them and the first block that reaches it (-1: the start level);
+      end_bytes      the level after the last block has drained;
+      mean_kbps_per_channel, max_kbps_per_channel_seen  the body over the duration of the blocks, and the largest block
+                     at the rate of its own duration;
+      allocation     as given."""
+    data, info, _, _ = _stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel,
+                                         start_bytes, max_kbps_per_channel, block_switching, header_samples,
+                                         nmr_range_db, allocation, use_vq)
     return data, info
 
 
@@ -488,34 +499,16 @@ def encode_stream_to_buffer_pinned(pcm, sample_rate, kbps_per_channel, buffer_by
       phase_of             int32 [blocks]: the phase that pinned the block, -1: free;
       phases, open         the bisections run, and whether the last phase allowed still pinned a block;
       through_bytes        float64 [blocks]: the highest level any stretch of blocks containing the block reaches."""
-    from . import pacfile
-    data, sol, out, limit, b, enc = pacfile._encode_stream_buffered(
-        pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel, start_bytes, max_kbps_per_channel,
-        block_switching, header_samples, nmr_range_db, allocation, use_vq, (pin_step_db, max_phases))
-    n_ch = np.asarray(pcm).shape[1]
-    n_bytes = out["n_bytes"].cpu().numpy().reshape(-1, n_ch)
-    scan = enc.bucket_through(out["n_bytes"], n_ch, b, want_level=True)
-    mean, most = _rates_kbps(np.where(n_bytes > 0, n_bytes + 4, 0).sum(axis=1), n_ch, HOP / float(sample_rate))
-    one = 2.0 ** _lib.BUCKET_Q
-    info = {
-        "allocation": allocation,
-        "target_nmr_db": sol["target_nmr_db"],
+    data, info, sol, scan = _stream_to_buffer(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel,
+                                              start_bytes, max_kbps_per_channel, block_switching, header_samples,
+                                              nmr_range_db, allocation, use_vq, (pin_step_db, max_phases))
+    info.update({
         "block_target_nmr_db": sol["target_t"].cpu().numpy().astype(np.float64) / _lib.RATE_TARGET_GRID,
         "phase_of": sol["phase_of"].cpu().numpy(),
         "phases": sol["phases"],
         "open": sol["open"],
-        "limit_bytes": limit,
-        "total_bytes": scan["total"],
-        "bucket": b,
-        "n_bytes": sol["n_bytes"].cpu().numpy().reshape(-1, n_ch),
-        "level_bytes": scan["level"].cpu().numpy() / one,
-        "through_bytes": scan["through"].cpu().numpy() / one,
-        "peak_bytes": scan["peak_bytes"],
-        "peak_block": scan["peak_hop"],
-        "end_bytes": scan["end_bytes"],
-        "mean_kbps_per_channel": mean,
-        "max_kbps_per_channel_seen": most,
-    }
+        "through_bytes": scan["through"].cpu().numpy() / 2.0 ** _lib.BUCKET_Q,
+    })
     return data, info
 
 

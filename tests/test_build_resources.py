@@ -50,6 +50,14 @@ HOT = [
     (r"::k_band_profile\(", 128, 4),                     # 1024 threads: 128 registers are all a workgroup may have
     (r"::k_band_profile_seg\(", 128, 4),
     (r"::k_rate_profile<true>\(", None, 8),
+    # the bucket scans (bucket_dev.h), 1024 threads each: past 128 registers, or with a spill, they do not launch at
+    # all.  84 is the largest today; 88 is the next allocation granule of 8 above it
+    (r"::k_bucket_scan\(", 88, None),
+    (r"::k_bucket_step\(", 88, None),
+    (r"::k_bucket_through\(", 88, None),
+    (r"::k_pin_step\(", 88, None),
+    (r"::k_pin_freeze\(", 88, None),
+    (r"::k_pin_finish\(", 88, None),
 ]
 
 

@@ -31,7 +31,7 @@ KINDS = ("band", "rate")
 HOPS = (0, 1, 2, 63, 64, 65, 1023, 1024, 1025, 2049, 4097)      # a wave and the workgroup's 1024 hops, one off either way
 CHANNELS = (1, 2, 3, 8)
 T_LO, T_HI = -30 * 64, 30 * 64
-TOP = (1 << 62) + (1 << 57)                                     # k_bucket.hip: the bound no level reaches
+TOP = (1 << 62) + (1 << 57)                                     # bucket_dev.h: the bound no level reaches
 
 
 @pytest.fixture(scope="module")
