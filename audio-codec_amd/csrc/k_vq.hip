@@ -16,6 +16,16 @@
  *   k_vq_join  short frames: concatenates the 8 sub-block strings behind the
  *              3 flag bits (coder/pacfile.py:575-592) and applies the size
  *              rule (:552-565, which still counts a scale factor per band).
+ *   k_vq_frame<GUARD>  the default path: one workgroup per channel-frame walks
+ *              the trees of ALL its bands level by level and writes the finished
+ *              payload, short frames included (GUARD: handles with
+ *              pacx_config.guard).  Trees beyond its node store: n_bytes = -1.
+ *   k_vq_redo  behind k_vq_frame: k_vq's unit body over the frames it left.
+ *
+ * One split tree, three walkers: vq_shape (depth first), vq_shape_bfs (level by
+ * level; both one wave per band, in k_vq and k_vq_redo) and the level loop of
+ * k_vq_frame.  The split rule is vq_exact.h's; the passes, the node store and the
+ * stream layout of the two level walkers are vq_walk_dev.h's.
  *
  * Why the band strings have static positions: a band that is coded at all
  * uses exactly bitAlloc*nLines bits -- the gain index takes whatever the shape
@@ -111,14 +121,25 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-__device__ __forceinline__ void vq_put64(unsigned *words, int pos, unsigned long long val, int width)
+__device__ __forceinline__ int wave_max_i32(int v)
 {
-    if (width > 32) {
-        put_bits(words, pos, (unsigned)(val >> 32), width - 32);
-        put_bits(words, pos + width - 32, (unsigned)val, 32);
-    } else {
-        put_bits(words, pos, (unsigned)val, width);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        v = max(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ int wave_excl_scan_i32(int v, int lane, int &total)
+{
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off, 64);
+        if (lane >= off)
+            incl += t;
     }
+    total = __shfl(incl, 63, 64);
+    return incl - v;
 }
 
 /* Per-band emission state (uniform across the wave). */
@@ -412,6 +433,8 @@ __device__ __forceinline__ unsigned long long vq_leaf_group(const VqView &V, dou
     return term;
 }
 
+#include "vq_walk_dev.h"   /* the passes and the stream layout of the two level walkers; vq_shape folds with it too */
+
 /* the two children of a bottom split: mid on lanes 0-31, side on lanes 32-63 */
 __device__ __forceinline__ void vq_leaf_pair(const VqView &V, VqOut &o, const double *mid, const double *side,
                                              int n, int bits_mid, int bits_side, int lane)
@@ -450,27 +473,9 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
         if (bits > PACX_VQ_SPLIT_BITS && depth < VQ_DEPTH) {
             const int cut = n / 2, half = n - cut;
             double *mv = reg, *sv = reg + half;
-            double mm = 0.0, ss = 0.0;
-            for (int i = lane; i < half; i += 64) {
-                const double left = (i < cut) ? cur[i] : 0.0;
-                const double right = cur[cut + i];
-                const double m = (left + right) / 2.0;
-                const double s = (left - right) / 2.0;
-                mv[i] = m;
-                sv[i] = s;
-                mm = fma(m, m, mm);
-                ss = fma(s, s, ss);
-            }
-            const double m_l2 = sqrt(wave_sum_f64(mm));
-            const double s_l2 = sqrt(wave_sum_f64(ss));
-            for (int i = lane; i < half; i += 64) {
-                if (m_l2 != 0.0)
-                    mv[i] = mv[i] / m_l2;
-                if (s_l2 != 0.0)
-                    sv[i] = sv[i] / s_l2;
-            }
+            const double q = __longlong_as_double((long long)vq_fold_wide(cur, cut, half, mv, sv, lane));
             wave_lds_fence();
-            const double theta = (m_l2 == 0.0) ? 0.0 : vq_atan(s_l2 / m_l2);
+            const double theta = (q < 0.0) ? 0.0 : vq_atan(q);   /* -1.0: a mid half of norm zero */
             /* the split rule (vq_exact.h): the angle's bits, its code and value, the mid half's bits */
             int a_theta = vq_first_bits(bits, half, ldc(&V.tab.half_log2[half]));
             int a_rest = bits - a_theta;
@@ -551,85 +556,26 @@ __device__ __forceinline__ void vq_shape(const VqView &V, VqOut &o, const double
 }
 
 /* ---- the split tree of one band, level by level ----------------------------- */
-/* vq_shape walks the tree depth first, one node at a time: per node a whole wave runs the
- * scalar arithmetic of a split (two norms, six FP64 divisions, atan, quantise/dequantise of the
- * angle, the bit split) for a handful of useful lanes, and the kernel is bound by its instruction
- * count.  vq_shape_bfs walks the same tree breadth first:
- *   - the nodes of one depth are independent once their parents are split;
- *   - their folds / norms / normalisations run PACKED: P = power of two >= the largest half of the
- *     level, 64/P nodes per pass, one node per aligned block of P lanes.  The xor butterfly over a
- *     block adds the same numbers in the same order as the 64-lane one (plus exact zeros);
- *   - the scalar arithmetic of a level runs once, one node per LANE;
- *   - leaves are coded four or two at a time (vq_leaf_group), whoever their parents are;
- *   - nothing is written while walking: every node keeps its field (value, width); at the end
- *     the subtree widths go bottom-up, the stream positions top-down (the reference writes depth
- *     first: angle, mid subtree, side subtree) and all fields are ORed in at once, one per lane.
- * The split rule of a node is vq_exact.h's, as in vq_shape; returns false without having written
- * anything when the tree does not fit the node store (then vq_shape codes the band). */
+/* vq_shape walks the tree depth first, one node at a time: per node a whole wave runs the scalar arithmetic of a
+ * split (two norms, six FP64 divisions, atan, the angle's quantiser, the bit split) for a handful of useful lanes, and
+ * the kernel is bound by its instruction count.  vq_shape_bfs walks the same tree breadth first with the passes of
+ * vq_walk_dev.h: the folds of a level packed (P = power of two >= its largest half, 64/P nodes per pass), its scalar
+ * arithmetic one node per LANE, its leaves four or two at a time whoever their parents are; nothing is written while
+ * walking, the layout follows at the end.  Returns false without having written anything when the tree does not fit
+ * the node store (then vq_shape codes the band). */
 #define VQ_NC 96                       /* nodes per band tree */
-#define VQ_NODE_BYTES (VQ_NC * 8 + 5 * VQ_NC * 2 + 4 * VQ_NC + 128 + 32)
-struct VqNodes {
-    unsigned long long *val;           /* [NC] field value (a split's |side|/|mid| while its level is open) */
-    unsigned short *nn, *bb, *off, *tot, *pos;   /* [NC] length, bits, vector offset, subtree bits, stream bit */
-    unsigned char *kind, *wid, *kid;   /* [NC] 0 split / 1 leaf / 3 leaf without a field; field width; [2 NC] children */
+struct VqNodes : VqStore<VQ_NC, unsigned char, false> {
     unsigned char *sl, *ll;            /* [64] split / leaf nodes of the open level */
-    unsigned char *lvl;                /* [VQ_DEPTH + 2] first node of every depth */
     __device__ __forceinline__ void bind(unsigned char *p)
     {
-        val = (unsigned long long *)p;
-        nn = (unsigned short *)(p + VQ_NC * 8);
-        bb = nn + VQ_NC;
-        off = bb + VQ_NC;
-        tot = off + VQ_NC;
-        pos = tot + VQ_NC;
-        kind = (unsigned char *)(pos + VQ_NC);
-        wid = kind + VQ_NC;
-        kid = wid + VQ_NC;
-        sl = kid + 2 * VQ_NC;
+        sl = bind_nodes(p);
         ll = sl + 64;
         lvl = ll + 64;
     }
 };
-
-/* a field of up to 64 bits, by ONE lane (fields of different lanes may share words) */
-__device__ __forceinline__ void vq_put_field(unsigned *words, int pos, unsigned long long val, int width)
-{
-    const int w = pos >> 5, t = (pos & 31) + width;
-    if (t <= 32) {
-        atomicOr(&words[w], (unsigned)val << (32 - t));
-    } else if (t <= 64) {
-        const unsigned long long v = val << (64 - t);
-        atomicOr(&words[w], (unsigned)(v >> 32));
-        atomicOr(&words[w + 1], (unsigned)v);
-    } else {
-        const int r = t - 64;
-        const unsigned long long v = val >> r;
-        atomicOr(&words[w], (unsigned)(v >> 32));
-        atomicOr(&words[w + 1], (unsigned)v);
-        atomicOr(&words[w + 2], (unsigned)val << (32 - r));
-    }
-}
-
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = max(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_excl_scan_i32(int v, int lane, int &total)
-{
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off)
-            incl += t;
-    }
-    total = __shfl(incl, 63, 64);
-    return incl - v;
-}
+#define VQ_NODE_BYTES (VqNodes::node_bytes + 128 + 32)
+static_assert(VqNodes::node_bytes == VQ_NC * 8 + 5 * VQ_NC * 2 + 4 * VQ_NC, "a wave's node store is what it was with kid[2 NC]");
+typedef VqTeam<64> VqWave;
 
 __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const double *x0, int n0, int bits0,
                                              double *region, int region_len, const VqNodes &N, int lane)
@@ -644,7 +590,8 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
         N.kind[0] = 1;                                     /* the caller only comes with bits0 > 0 */
         N.wid[0] = 0;
         N.val[0] = 0ull;
-        N.kid[0] = N.kid[1] = 0xFF;
+        N.kid[0] = 0;
+        N.has[0] = 0;
         N.lvl[0] = 0;
     }
     if (bits0 > PACX_VQ_SPLIT_BITS && lane == 0)
@@ -679,73 +626,24 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const unsigned long long big = __builtin_amdgcn_ballot_w64(myn > 32);
             const int nmax = wave_max_i32(myn > 32 ? 0 : myn);
             /* single leaves of more than 32 components (upper levels only) */
-            for (unsigned long long m = big; m; m &= m - 1) {
-                const int k = __builtin_ctzll(m);
-                const int node = N.ll[k];
-                const int n = N.nn[node];
-                int bits = N.bb[node];
-                bits = bits > 32 ? 32 : bits;
-                const int K = ldc(&V.tab.k_of[n * 33 + bits]);
-                const int width = ldc(&V.tab.w_of[n * 33 + bits]);
-                bool ok = true;
-                const unsigned long long idx = vq_leaf_idx(V, cur + N.off[node], n, K, nxt, nxt + n, lane, ok);
-                if (!ok)
-                    undefined = true;
-                if (lane == 0) {
-                    N.val[node] = ok ? idx : 0ull;
-                    N.wid[node] = (unsigned char)width;
-                }
-            }
+            for (unsigned long long m = big; m; m &= m - 1)
+                vq_leaf_whole<false>(V, N, cur, nxt, N.ll[__builtin_ctzll(m)], lane, undefined);
             if (nmax > 0) {
                 const int lw = nmax <= 16 ? 4 : 5;           /* log2 of the group width */
-                const int W = 1 << lw, G = 64 >> lw;
-                /* compact list of the small leaves in lane order */
+                const int G = 64 >> lw;
+                /* compact list of the small leaves in lane order, in the leaf list itself (every lane holds its entry) */
                 const bool small = lane < n_leaf && myn <= 32;
                 const unsigned long long msm = __builtin_amdgcn_ballot_w64(small);
                 const int n_small = __popcll(msm);
                 wave_lds_fence();
                 if (small)
-                    N.sl[__popcll(msm & below)] = (unsigned char)my;   /* the split list is rebuilt below */
+                    N.ll[__popcll(msm & below)] = (unsigned char)my;
                 wave_lds_fence();
                 for (int p0 = 0; p0 < n_small; p0 += G) {
-                    const int g = lane >> lw, l = lane & (W - 1);
+                    const int g = lane >> lw, l = lane & ((1 << lw) - 1);
                     const bool valid = p0 + g < n_small;
-                    const int node = valid ? N.sl[p0 + g] : 0;
-                    const int n = valid ? N.nn[node] : 0;
-                    int bits = valid ? N.bb[node] : 0;
-                    bits = bits > 32 ? 32 : bits;
-                    const int K = valid ? V.tab.k_of[n * 33 + bits] : 0;
-                    const int width = valid ? V.tab.w_of[n * 33 + bits] : 0;
-                    const double x = (valid && l < n) ? cur[N.off[node] + l] : 0.0;
-                    bool ok = false;
-                    unsigned long long term;
-                    if (lw == 4)
-                        term = vq_leaf_group<16>(V, x, n, K < 0 ? 0 : K, l, ok);
-                    else
-                        term = vq_leaf_group<32>(V, x, n, K < 0 ? 0 : K, l, ok);
-                    if (valid && l == 0) {
-                        if (K < 0) {                       /* a 1-dimensional leaf: the reference never returns */
-                            N.kind[node] = 3;
-                            N.wid[node] = 0;
-                            N.val[node] = 0ull;
-                        } else {
-                            N.val[node] = ok ? term : 0ull;
-                            N.wid[node] = (unsigned char)width;
-                        }
-                    }
-                    if (valid && (K < 0 || !ok))
-                        undefined = true;
-                }
-                /* the split list again (the leaf passes borrowed it) */
-                wave_lds_fence();
-                int ns2 = 0;
-                for (int base = lev_b; base < lev_e; base += 64) {
-                    const int j = base + lane;
-                    const int kd = (j < lev_e) ? N.kind[j] : 2;
-                    const unsigned long long ms = __builtin_amdgcn_ballot_w64(kd == 0);
-                    if (kd == 0)
-                        N.sl[ns2 + __popcll(ms & below)] = (unsigned char)j;
-                    ns2 += __popcll(ms);
+                    bool guarded = false;                  /* the band walkers take no margins */
+                    vq_leaf_pass<false, false>(V, N, cur, lw, valid, valid ? N.ll[p0 + g] : 0, l, undefined, guarded);
                 }
                 wave_lds_fence();
             }
@@ -772,37 +670,18 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const int k = __builtin_ctzll(m);
             const int node = N.sl[k];
             const int n = N.nn[node];
-            const double *src = cur + N.off[node];
             const int cut = n / 2, half = n - cut;
-            double *mv = nxt + N.tot[node], *sv = mv + half;
-            double mm = 0.0, ss = 0.0;
-            for (int i = lane; i < half; i += 64) {
-                const double left = (i < cut) ? src[i] : 0.0;
-                const double right = src[cut + i];
-                const double mid = (left + right) / 2.0;
-                const double sd = (left - right) / 2.0;
-                mv[i] = mid;
-                sv[i] = sd;
-                mm = fma(mid, mid, mm);
-                ss = fma(sd, sd, ss);
-            }
-            const double m_l2 = sqrt(wave_sum_f64(mm));
-            const double s_l2 = sqrt(wave_sum_f64(ss));
-            for (int i = lane; i < half; i += 64) {
-                if (m_l2 != 0.0)
-                    mv[i] = mv[i] / m_l2;
-                if (s_l2 != 0.0)
-                    sv[i] = sv[i] / s_l2;
-            }
+            double *mv = nxt + N.tot[node];
+            const unsigned long long ratio = vq_fold_wide(cur + N.off[node], cut, half, mv, mv + half, lane);
             if (lane == 0)
-                N.val[node] = (unsigned long long)__double_as_longlong(m_l2 == 0.0 ? -1.0 : s_l2 / m_l2);
+                N.val[node] = ratio;
         }
         /* the others packed: one node per aligned block of P lanes */
         if (hmax > 0) {
             int lp = 0;
             while ((1 << lp) < hmax)
                 ++lp;
-            const int P = 1 << lp, G = 64 >> lp;
+            const int G = 64 >> lp;
             const bool narrow = lane < n_split && shalf <= 64;
             const unsigned long long mn = __builtin_amdgcn_ballot_w64(narrow);
             const int n_narrow = __popcll(mn);
@@ -810,34 +689,13 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
                 N.ll[__popcll(mn & below)] = (unsigned char)snode;   /* the leaf list is done with */
             wave_lds_fence();
             for (int p0 = 0; p0 < n_narrow; p0 += G) {
-                const int g = lane >> lp, i = lane & (P - 1);
+                const int g = lane >> lp, i = lane & ((1 << lp) - 1);
                 const bool valid = p0 + g < n_narrow;
                 const int node = valid ? N.ll[p0 + g] : 0;
-                const int n = valid ? N.nn[node] : 0;
-                const int cut = n / 2, half = n - cut;
-                const double *src = cur + (valid ? N.off[node] : 0);
-                const bool mine = i < half;
-                const double left = (mine && i < cut) ? src[i] : 0.0;
-                const double right = mine ? src[cut + i] : 0.0;
-                double mid = mine ? (left + right) / 2.0 : 0.0;
-                double sd = mine ? (left - right) / 2.0 : 0.0;
-                double mm = fma(mid, mid, 0.0), ss = fma(sd, sd, 0.0);
-                for (int off = P >> 1; off > 0; off >>= 1) {
-                    mm = mm + __shfl_xor(mm, off, 64);
-                    ss = ss + __shfl_xor(ss, off, 64);
-                }
-                const double m_l2 = sqrt(mm), s_l2 = sqrt(ss);
-                if (m_l2 != 0.0)
-                    mid = mid / m_l2;
-                if (s_l2 != 0.0)
-                    sd = sd / s_l2;
-                if (mine) {
-                    double *mv = nxt + N.tot[node];
-                    mv[i] = mid;
-                    mv[half + i] = sd;
-                }
-                if (valid && i == 0)
-                    N.val[node] = (unsigned long long)__double_as_longlong(m_l2 == 0.0 ? -1.0 : s_l2 / m_l2);
+                bool head;
+                const unsigned long long ratio = vq_fold_packed(N, cur, nxt, lp, valid, node, i, head);
+                if (head)
+                    N.val[node] = ratio;
             }
         }
         wave_lds_fence();
@@ -847,60 +705,15 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
             const int bits = has ? N.bb[snode] : 0;
             const int half = has ? shalf : 1;
             const double q = has ? __longlong_as_double((long long)N.val[snode]) : -1.0;
-            const double theta = (q < 0.0) ? 0.0 : vq_atan(q);
-            const int a_theta = vq_first_bits(bits, half, V.tab.half_log2[half]);
-            int a_rest = bits - a_theta;
-            if (a_rest < 0)
-                a_rest = 0;
-            const double tn = theta / vq_half_pi;
-            double theta_q = 0.0;
-            unsigned long long code = 0ull;
-            int w_theta = 0;
-            if (a_theta > 62) {
-                if (has)
-                    undefined = true;
-            } else if (a_theta > 0) {
-                code = vq_angle_code(tn, a_theta);
-                w_theta = a_theta;
-                theta_q = vq_angle_value(code, a_theta);
-            }
-            int a_mid = 0;
-            if (theta_q != 0.0) {
-                const double lt = vq_log2_tan_tabled(a_theta, theta_q) ? V.log2_tan[vq_log2_tan_slot(a_theta, code)]
-                                                                       : vq_log2_tan(theta_q);
-                a_mid = vq_mid_bits(a_rest, half, lt);
-            }
-            const int a_side = a_rest - a_mid;
-            const int c_mid = (has && a_mid > 0) ? 1 : 0, c_side = (has && a_side > 0) ? 1 : 0;
-            int born;
-            const int first = count + wave_excl_scan_i32(c_mid + c_side, lane, born);
-            if (count + born > VQ_NC)
+            bool guarded = false;
+            const VqSplit s = vq_split_stage<false, false>(has, bits, half, q, lane,
+                                                    [&](int l) { return V.tab.half_log2[l]; },
+                                                    [&](int slot) { return V.log2_tan[slot]; }, [](int) {}, undefined, guarded);
+            if (count + s.born > VQ_NC)
                 return false;
-            if (has) {
-                N.val[snode] = code;
-                N.wid[snode] = (unsigned char)w_theta;
-                N.kid[2 * snode] = c_mid ? (unsigned char)first : 0xFF;
-                N.kid[2 * snode + 1] = c_side ? (unsigned char)(first + c_mid) : 0xFF;
-                const int at = N.tot[snode];
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int a = c ? a_side : a_mid;
-                    if (a <= 0)
-                        continue;
-                    const int id = c ? first + c_mid : first;
-                    const bool splits = a > PACX_VQ_SPLIT_BITS && depth + 1 < VQ_DEPTH;
-                    if (a > PACX_VQ_SPLIT_BITS && !splits)
-                        undefined = true;                  /* deeper than any real tree */
-                    N.nn[id] = (unsigned short)half;
-                    N.bb[id] = (unsigned short)(a > 65535 ? 65535 : a);
-                    N.off[id] = (unsigned short)(at + (c ? half : 0));
-                    N.kind[id] = splits ? 0 : 1;
-                    N.wid[id] = 0;
-                    N.val[id] = 0ull;
-                    N.kid[2 * id] = N.kid[2 * id + 1] = 0xFF;
-                }
-            }
-            count += born;
+            if (has)
+                vq_split_born(N, snode, count + s.rel, half, s, depth, undefined);
+            count += s.born;
         }
         depth += 1;
         if (lane == 0)
@@ -913,57 +726,15 @@ __device__ __forceinline__ bool vq_shape_bfs(const VqView &V, VqOut &o, const do
     if (lane == 0)
         N.lvl[depth + 1] = (unsigned char)count;
     wave_lds_fence();
-    /* field counts ride in nn[] (lengths are not needed any more), field numbers in off[] */
-    for (int d = depth; d >= 0; --d) {
-        const int b = N.lvl[d], e = N.lvl[d + 1];
-        for (int j = b + lane; j < e; j += 64) {
-            const int k0 = N.kid[2 * j], k1 = N.kid[2 * j + 1];
-            int t = N.wid[j], f = (N.kind[j] == 3) ? 0 : 1;
-            if (k0 != 0xFF) { t += N.tot[k0]; f += N.nn[k0]; }
-            if (k1 != 0xFF) { t += N.tot[k1]; f += N.nn[k1]; }
-            N.tot[j] = (unsigned short)t;
-            N.nn[j] = (unsigned short)f;
+    vq_layout<VqWave>(N, depth, lane, [&] {
+        if (lane == 0) {
+            N.pos[0] = (unsigned short)o.pos;
+            N.off[0] = (unsigned short)o.log_n;
         }
-        wave_lds_fence();
-    }
-    if (lane == 0) {
-        N.pos[0] = (unsigned short)o.pos;
-        N.off[0] = (unsigned short)o.log_n;
-    }
-    wave_lds_fence();
-    for (int d = 0; d <= depth; ++d) {
-        const int b = N.lvl[d], e = N.lvl[d + 1];
-        for (int j = b + lane; j < e; j += 64) {
-            const int k0 = N.kid[2 * j], k1 = N.kid[2 * j + 1];
-            int p = N.pos[j] + N.wid[j], r = N.off[j] + ((N.kind[j] == 3) ? 0 : 1);
-            if (k0 != 0xFF) {
-                N.pos[k0] = (unsigned short)p;
-                N.off[k0] = (unsigned short)r;
-                p += N.tot[k0];
-                r += N.nn[k0];
-            }
-            if (k1 != 0xFF) {
-                N.pos[k1] = (unsigned short)p;
-                N.off[k1] = (unsigned short)r;
-            }
-        }
-        wave_lds_fence();
-    }
-    for (int j = lane; j < count; j += 64) {
-        const int w = N.wid[j];
-        unsigned long long v = N.val[j];
-        if (w > 0 && w < 64)
-            v &= (1ull << w) - 1ull;
-        if (w > 0)
-            vq_put_field(o.words, N.pos[j], v, w);
-        if (o.log && N.kind[j] != 3 && N.off[j] < o.log_cap) {
-            pacx_vq_entry e;
-            e.value = v;
-            e.width = w;
-            e.band = o.band;
-            o.log[N.off[j]] = e;
-        }
-    }
+    });
+    vq_put_fields<VqWave>(N, count, lane, o.words, o.log, o.log_cap, [&](int, int at, unsigned long long v, int w) {
+        o.log[at] = pacx_vq_entry{v, w, o.band};
+    });
     if (__builtin_amdgcn_ballot_w64(undefined))
         o.flags |= PACX_ST_VQ_UNDEFINED;
     o.pos += N.tot[0];
@@ -1182,14 +953,8 @@ __device__ __forceinline__ void vq_unit_body(const PacxTables &T, const VqView &
                 const double *x0 = xs + lo;                /* [cnt] shape = x / gain, from phase A */
                 const int before = o.pos;
                 VQ_S(o, 13);
-#if defined(VQ_ONLY_BFS)
-                vq_shape_bfs(V, o, x0, cnt, bits_shape, scr, 2 * cnt + 4 * VQ_DEPTH, N, lane);
-#elif defined(VQ_ONLY_DFS)
-                vq_shape(V, o, x0, cnt, bits_shape, scr, stack, lane);
-#else
                 if (!A.bfs || bits_shape < A.bfs || !vq_shape_bfs(V, o, x0, cnt, bits_shape, scr, 2 * cnt + 4 * VQ_DEPTH, N, lane))
                     vq_shape(V, o, x0, cnt, bits_shape, scr, stack, lane);
-#endif
                 bits_gain += bits_shape - (o.pos - before);
             }
             if (bits_gain < 0)
@@ -1292,31 +1057,18 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQ_OCC) void k_vq_redo(PacxTables T,
 #define VQF_FIXED 4160                 /* words, gains, allocations, starts, ticket, gain bits, roots, counters */
 #define VQF_SMEM (VQF_FIXED + 2 * VQF_BUF * 8 + VQF_NCAP * 8 + 6 * VQF_NCAP * 2 + 4 * VQF_NCAP + 2 * VQF_NLV * 2 + 128 + 64)
 
-struct VqfStore {
-    unsigned long long *val;
-    unsigned short *nn, *bb, *off, *tot, *pos, *kid;
-    unsigned char *kind, *wid, *band, *has;
+struct VqfStore : VqStore<VQF_NCAP, unsigned short, true> {
     unsigned short *ord;               /* [2][NLV] a level's nodes grouped by class (two levels' lists alternate) */
     int *cls;                          /* [2][16] class starts in ord ([9] used) */
-    unsigned short *lvl;               /* [VQ_DEPTH + 2] first node of every depth */
     __device__ __forceinline__ void bind(unsigned char *p)
     {
-        val = (unsigned long long *)p;
-        nn = (unsigned short *)(p + VQF_NCAP * 8);
-        bb = nn + VQF_NCAP;
-        off = bb + VQF_NCAP;
-        tot = off + VQF_NCAP;
-        pos = tot + VQF_NCAP;
-        kid = pos + VQF_NCAP;
-        kind = (unsigned char *)(kid + VQF_NCAP);
-        wid = kind + VQF_NCAP;
-        band = wid + VQF_NCAP;
-        has = band + VQF_NCAP;
-        ord = (unsigned short *)(has + VQF_NCAP);
+        ord = (unsigned short *)bind_nodes(p);
         cls = (int *)(ord + 2 * VQF_NLV);
         lvl = (unsigned short *)(cls + 32);
     }
 };
+static_assert(VQF_FIXED + 2 * VQF_BUF * 8 + VqfStore::node_bytes + 2 * VQF_NLV * 2 + 128 + 64 == VQF_SMEM, "k_vq_frame's LDS");
+typedef VqTeam<64 * VQ_WAVES> VqGroup;
 
 #ifdef PACX_VQ_DEBUG
 #define VQF_SUB(k) do { long long t3_; VQ_NOW_VM(t3_); \
@@ -1661,126 +1413,30 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
                 const int lw = (c == 0) ? 4 : 5, W = 1 << lw;
                 const int g = lane >> lw, l = lane & (W - 1);
                 const bool valid = g < p_n;
-                const int node = valid ? ord_c[p0 + g] : 0;
-                const int n = valid ? N.nn[node] : 0;
-                /* pulse count and index width: looked up here, beside the scalar stage, not in it */
-                int bits = valid ? N.bb[node] : 0;
-                bits = bits > 32 ? 32 : bits;
-#ifdef VQF_STUB_KOF        /* timing experiment only (wrong pulse counts): what the dependent table read in front of a leaf pass costs */
-                const int K = valid ? (bits * 3) / (n > 8 ? 2 : 1) + 1 : 0;
-                const int width = valid ? bits : 0;
-#else
-                const int K = valid ? V.tab.k_of[n * 33 + bits] : 0;
-                const int width = valid ? V.tab.w_of[n * 33 + bits] : 0;
-#endif
-                const double x = (valid && l < n) ? cur[N.off[node] + l] : 0.0;
-                bool ok = false, near = false;
-                unsigned long long term;
-#ifdef VQF_STUB_LEAF       /* timing experiment only (wrong indices): what the small leaves cost */
-                ok = true;
-                term = (unsigned long long)(x != 0.0) + (unsigned long long)K;
-#else
-                if (GUARD) {                       /* the margins are taken by a copy of the leaf code of its own */
-                    if (c == 0)
-                        term = vq_leaf_group<16, true>(V, x, n, K < 0 ? 0 : K, l, ok, true, &near);
-                    else
-                        term = vq_leaf_group<32, true>(V, x, n, K < 0 ? 0 : K, l, ok, true, &near);
-                    guarded = guarded || (valid && near);
-                } else if (c == 0) {
-                    term = vq_leaf_group<16, true>(V, x, n, K < 0 ? 0 : K, l, ok);
-                } else {
-                    term = vq_leaf_group<32, true>(V, x, n, K < 0 ? 0 : K, l, ok);
-                }
-#endif
-                if (valid && l == 0) {
-                    if (K < 0) {                   /* a 1-dimensional leaf: the reference never returns */
-                        N.kind[node] = 3;
-                        N.wid[node] = 0;
-                        N.val[node] = 0ull;
-                    } else {
-                        N.val[node] = ok ? term : 0ull;
-                        N.wid[node] = (unsigned char)width;
-                    }
-                }
-                if (valid && (K < 0 || !ok))
-                    undefined = true;
+                vq_leaf_pass<true, GUARD>(V, N, cur, lw, valid, valid ? ord_c[p0 + g] : 0, l, undefined, guarded);
             } else if (c == 2) {
                 const int node = ord_c[p0];
-                const int n = N.nn[node];
-                int bits = N.bb[node];
-                bits = bits > 32 ? 32 : bits;
-                const int K = ldc(&V.tab.k_of[n * 33 + bits]);
-                const int width = ldc(&V.tab.w_of[n * 33 + bits]);
-                bool ok = true;
-                double *t1 = nxt + N.tot[node];
-                const unsigned long long idx = vq_leaf_idx<true>(V, cur + N.off[node], n, K, t1, t1 + n, lane, ok);
-                if (!ok)
-                    undefined = true;
+                vq_leaf_whole<true>(V, N, cur, nxt + N.tot[node], node, lane, undefined);
                 guarded = guarded || GUARD;         /* whole-wave leaves: no margin is taken, flagged as they come */
-                if (lane == 0) {
-                    N.val[node] = ok ? idx : 0ull;
-                    N.wid[node] = (unsigned char)width;
-                }
             } else if (c < 7) {
-                /* splits packed: one node per aligned block of P lanes */
-                const int lp = c + 0;              /* classes 3..6 = blocks of 8, 16, 32, 64 lanes */
-                const int P = 1 << lp;
+                /* splits packed: classes 3..6 = one node per aligned block of 8, 16, 32, 64 lanes */
+                const int lp = c + 0, P = 1 << lp;
                 const int g = lane >> lp, i = lane & (P - 1);
                 const bool valid = g < p_n;
                 const int node = valid ? ord_c[p0 + g] : 0;
-                const int n = valid ? N.nn[node] : 0;
-                const int cut = n / 2, half = n - cut;
-                const double *src = cur + (valid ? N.off[node] : 0);
-                const bool mine = i < half;
-                const double left = (mine && i < cut) ? src[i] : 0.0;
-                const double right = mine ? src[cut + i] : 0.0;
-                double mid = mine ? (left + right) / 2.0 : 0.0;
-                double sd = mine ? (left - right) / 2.0 : 0.0;
-                double mm = fma(mid, mid, 0.0), ss = fma(sd, sd, 0.0);
-                for (int off = P >> 1; off > 0; off >>= 1) {
-                    mm = mm + __shfl_xor(mm, off, 64);
-                    ss = ss + __shfl_xor(ss, off, 64);
-                }
-                const double m_l2 = sqrt(mm), s_l2 = sqrt(ss);
-                if (m_l2 != 0.0)
-                    mid = mid / m_l2;
-                if (s_l2 != 0.0)
-                    sd = sd / s_l2;
-                if (mine) {
-                    double *mv = nxt + N.tot[node];
-                    mv[i] = mid;
-                    mv[half + i] = sd;
-                }
-                if (valid && i == 0)
-                    N.val[node] = (unsigned long long)__double_as_longlong(m_l2 == 0.0 ? -1.0 : s_l2 / m_l2);
+                bool head;
+                const unsigned long long ratio = vq_fold_packed(N, cur, nxt, lp, valid, node, i, head);
+                if (head)
+                    N.val[node] = ratio;
             } else {
                 /* a split of more than 128 components: lanes strided over the half */
                 const int node = ord_c[p0];
                 const int n = N.nn[node];
-                const double *src = cur + N.off[node];
                 const int cut = n / 2, half = n - cut;
-                double *mv = nxt + N.tot[node], *sv = mv + half;
-                double mm = 0.0, ss = 0.0;
-                for (int i = lane; i < half; i += 64) {
-                    const double left = (i < cut) ? src[i] : 0.0;
-                    const double right = src[cut + i];
-                    const double mid = (left + right) / 2.0;
-                    const double sd = (left - right) / 2.0;
-                    mv[i] = mid;
-                    sv[i] = sd;
-                    mm = fma(mid, mid, mm);
-                    ss = fma(sd, sd, ss);
-                }
-                const double m_l2 = sqrt(wave_sum_f64(mm));
-                const double s_l2 = sqrt(wave_sum_f64(ss));
-                for (int i = lane; i < half; i += 64) {
-                    if (m_l2 != 0.0)
-                        mv[i] = mv[i] / m_l2;
-                    if (s_l2 != 0.0)
-                        sv[i] = sv[i] / s_l2;
-                }
+                double *mv = nxt + N.tot[node];
+                const unsigned long long ratio = vq_fold_wide(cur + N.off[node], cut, half, mv, mv + half, lane);
                 if (lane == 0)
-                    N.val[node] = (unsigned long long)__double_as_longlong(m_l2 == 0.0 ? -1.0 : s_l2 / m_l2);
+                    N.val[node] = ratio;
             }
 #ifdef PACX_VQ_DEBUG
             {
@@ -1833,94 +1489,24 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
             const int half = sn - sn / 2;
             const int bits = has ? N.bb[snode] : 0;
             const double q = has ? __longlong_as_double((long long)N.val[snode]) : -1.0;
-#ifdef VQF_STUB_ATAN       /* timing experiment only (wrong angles) */
-            const double theta = (q < 0.0) ? 0.0 : q / (1.0 + q);
-#else
-            const double theta = (q < 0.0) ? 0.0 : vq_atan(q);
-#endif
-            VQF_SUB(26);
-            const double hl = (half < VQF_HL) ? vqf_half_log2[half] : V.tab.half_log2[half];
-            const int a_theta = vq_first_bits(bits, half, hl);
-            int a_rest = bits - a_theta;
-            if (a_rest < 0)
-                a_rest = 0;
-            const double tn = theta / vq_half_pi;
-            double theta_q = 0.0;
-            unsigned long long code = 0ull;
-            int w_theta = 0;
-            if (!__builtin_amdgcn_ballot_w64(a_theta > 31)) {
-                /* every angle of this chunk has at most 31 bits (all but freak allocations): the 32-bit form */
-                if (a_theta > 0) {
-                    const unsigned c32 = vq_angle_code32(tn, a_theta);
-                    code = c32;
-                    w_theta = a_theta;
-                    theta_q = vq_angle_value32(c32, a_theta);
-                }
-            } else if (a_theta > 62) {
-                if (has)
-                    undefined = true;
-            } else if (a_theta > 0) {
-                code = vq_angle_code(tn, a_theta);
-                w_theta = a_theta;
-                theta_q = vq_angle_value(code, a_theta);
-            }
-            if (GUARD && has && a_theta > 0 && a_theta <= 53 && pacx_quant_guard(tn, a_theta, 1e-13))
-                guarded = true;                              /* the split angle sits at a boundary of its quantiser */
-            VQF_SUB(27);
-            int a_mid = 0;
-            if (theta_q != 0.0) {
-                double lt;
-                if (vq_log2_tan_tabled(a_theta, theta_q)) {
-                    const int at_lt = vq_log2_tan_slot(a_theta, code);
-                    lt = (at_lt < VQF_LT) ? vqf_log2_tan[at_lt] : V.log2_tan[at_lt];
-                } else {
-                    lt = vq_log2_tan(theta_q);
-                }
-                a_mid = vq_mid_bits(a_rest, half, lt);
-            }
-            VQF_SUB(28);
-            const int a_side = a_rest - a_mid;
-            const int c_mid = (has && a_mid > 0) ? 1 : 0, c_side = (has && a_side > 0) ? 1 : 0;
-            int born;
-            const int rel = wave_excl_scan_i32(c_mid + c_side, lane, born);
+            /* the two tables it reads sit in LDS as far as they are commonly needed */
+            const VqSplit s = vq_split_stage<GUARD, true>(
+                has, bits, half, q, lane,
+                [&](int l) { return (l < VQF_HL) ? vqf_half_log2[l] : V.tab.half_log2[l]; },
+                [&](int slot) { return (slot < VQF_LT) ? vqf_log2_tan[slot] : V.log2_tan[slot]; },
+                [&](int k) { VQF_SUB(k); }, undefined, guarded);
             int base = 0;
-            if (lane == 0 && born)
-                base = atomicAdd(&misc[0], born);
+            if (lane == 0 && s.born)
+                base = atomicAdd(&misc[0], s.born);
             base = __shfl(base, 0, 64);
-            if (base + born > VQF_NCAP) {
+            if (base + s.born > VQF_NCAP) {
                 if (lane == 0)
                     misc[1] = 1;
                 continue;
             }
             VQF_SUB(29);
-            if (has) {
-                const int first = base + rel;
-                N.val[snode] = code;
-                N.wid[snode] = (unsigned char)w_theta;
-                N.kid[snode] = (unsigned short)first;
-                N.has[snode] = (unsigned char)(c_mid | (c_side << 1));
-                const int at = N.tot[snode];
-                const int bd = N.band[snode];
-#pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    const int a = c ? a_side : a_mid;
-                    if (a <= 0)
-                        continue;
-                    const int id = c ? first + c_mid : first;
-                    const bool splits = a > PACX_VQ_SPLIT_BITS && depth + 1 < VQ_DEPTH;
-                    if (a > PACX_VQ_SPLIT_BITS && !splits)
-                        undefined = true;                  /* deeper than any real tree */
-                    N.nn[id] = (unsigned short)half;
-                    N.bb[id] = (unsigned short)(a > 65535 ? 65535 : a);
-                    N.off[id] = (unsigned short)(at + (c ? half : 0));
-                    N.kind[id] = splits ? 0 : 1;
-                    N.wid[id] = 0;
-                    N.band[id] = (unsigned char)bd;
-                    N.has[id] = 0;
-                    N.kid[id] = 0;
-                    N.val[id] = 0ull;
-                }
-            }
+            if (has)
+                vq_split_born(N, snode, base + s.rel, half, s, depth, undefined);
 #ifdef PACX_VQ_DEBUG
             {
                 long long t2_;
@@ -2005,65 +1591,23 @@ __global__ __launch_bounds__(64 * VQ_WAVES, VQF_OCC) void k_vq_frame(PacxTables 
     }
 #endif
     __syncthreads();
-    /* ---- subtree widths and field counts bottom-up (counts ride in nn[], field numbers in off[]) */
-    for (int d = depth; d >= 0; --d) {
-        const int b = N.lvl[d], e = N.lvl[d + 1];
-        for (int j = b + tid; j < e; j += 64 * VQ_WAVES) {
-            const int k0 = N.kid[j], hs = N.has[j];
-            int t = N.wid[j], f = (N.kind[j] == 3) ? 0 : 1;
-            if (hs & 1) { t += N.tot[k0]; f += N.nn[k0]; }
-            if (hs & 2) { const int k1 = k0 + (hs & 1); t += N.tot[k1]; f += N.nn[k1]; }
-            N.tot[j] = (unsigned short)t;
-            N.nn[j] = (unsigned short)f;
+    /* ---- subtree widths bottom-up, positions top-down from the bands' static starts */
+    vq_layout<VqGroup>(N, depth, tid, [&] {
+        if (hw_wave == 0 && lane < n_vb && root_s[lane] != 0xFFFF) {
+            N.pos[root_s[lane]] = (unsigned short)start_s[lane];
+            N.off[root_s[lane]] = 0;
         }
-        __syncthreads();
-    }
-    if (hw_wave == 0 && lane < n_vb && root_s[lane] != 0xFFFF) {
-        N.pos[root_s[lane]] = (unsigned short)start_s[lane];
-        N.off[root_s[lane]] = 0;
-    }
-    __syncthreads();
-    for (int d = 0; d <= depth; ++d) {
-        const int b = N.lvl[d], e = N.lvl[d + 1];
-        for (int j = b + tid; j < e; j += 64 * VQ_WAVES) {
-            const int k0 = N.kid[j], hs = N.has[j];
-            int p = N.pos[j] + N.wid[j], r = N.off[j] + ((N.kind[j] == 3) ? 0 : 1);
-            if (hs & 1) {
-                N.pos[k0] = (unsigned short)p;
-                N.off[k0] = (unsigned short)r;
-                p += N.tot[k0];
-                r += N.nn[k0];
-            }
-            if (hs & 2) {
-                const int k1 = k0 + (hs & 1);
-                N.pos[k1] = (unsigned short)p;
-                N.off[k1] = (unsigned short)r;
-            }
-        }
-        __syncthreads();
-    }
+    });
     VQF_T(4);
 #ifdef PACX_VQ_WAITDBG
     VQ_NOW(vqw_p);
 #endif
     /* ---- every field by its own lane */
-    for (int j = tid; j < n_nodes; j += 64 * VQ_WAVES) {
-        const int w = N.wid[j];
-        unsigned long long v = N.val[j];
-        if (w > 0 && w < 64)
-            v &= (1ull << w) - 1ull;
-        if (w > 0)
-            vq_put_field(words, N.pos[j], v, w);
-        if (A.log && N.kind[j] != 3 && N.off[j] < A.log_cap) {
-            const int vb = N.band[j], sj = sub_of(vb);
-            const long long slot = (cf * PACX_SUB + sj) * PACX_MAX_BANDS + (vb - sj * nb);
-            pacx_vq_entry e;
-            e.value = v;
-            e.width = w;
-            e.band = vb - sj * nb;
-            A.log[slot * A.log_cap + N.off[j]] = e;
-        }
-    }
+    vq_put_fields<VqGroup>(N, n_nodes, tid, words, A.log, A.log_cap, [&](int j, int at, unsigned long long v, int w) {
+        const int vb = N.band[j], sj = sub_of(vb);
+        const long long slot = (cf * PACX_SUB + sj) * PACX_MAX_BANDS + (vb - sj * nb);
+        A.log[slot * A.log_cap + at] = pacx_vq_entry{v, w, vb - sj * nb};
+    });
     VQW_P(3);
     /* ---- the gains of all bands side by side (mu-law, QuantizeUniform; the index soaks up the slack) */
     if (wave == 0) {

@@ -40,6 +40,7 @@ HOT = [
     (r"^k_gather_small\(", None, None),
     (r"^void k_vq_frame<(false|true)>\(", 102, 5),                          # gain-shape coder: five workgroups per CU is what it runs on
     (r"^k_vq\(", 128, 4),                                # ... its fallback for trees beyond the node store
+    (r"^k_vq_redo\(", 152, 3),                           # ... the same body behind k_vq_frame, on the default path: 146 today, granule 8
     (r"^k_vq_join\(", None, None),
     (r"^k_vq_dec_frame\(", 102, 5),                      # gain-shape decoder: five workgroups per CU
     (r"^k_vq_dec\(", 168, 3),                            # ... its fallback

@@ -441,6 +441,63 @@ def test_level_walk_equals_depth_first_walk(A, monkeypatch, fresh_handles):
         assert outs[0] == outs[1] == outs[2] == outs[3], kbps
 
 
+def _tone_noise_stream():
+    """the 20-block stereo stream of test_level_walk_equals_depth_first_walk (seed 11)"""
+    rng = np.random.default_rng(11)
+    t = np.arange(20 * 1024)
+    tone = 0.4 * np.sin(2 * np.pi * 440 * t / 48000) + 0.2 * np.sin(2 * np.pi * 5200 * t / 48000)
+    pcm = np.stack([tone + 0.05 * rng.standard_normal(len(t)), 0.3 * rng.standard_normal(len(t))], axis=1)
+    return np.clip(np.round(pcm * 20000), -32767, 32767).astype(np.int16)
+
+
+@pytest.mark.parametrize("kbps", [128, 448])
+def test_guard_level_walk_equals_band_walkers(A, monkeypatch, fresh_handles, kbps):
+    """k_vq_frame<true>, the instantiation a handle with pacx_config.guard launches, against the two band walkers
+    (which take no margins: k_vq_redo flags what it codes) and against the handle without the guard: payload bytes,
+    n_bytes and final allocations are equal in all four encodes, the status words differ in PACX_ST_GUARD alone."""
+    pcm = _tone_noise_stream()[:6 * 1024]
+
+    def encode(guard):
+        enc = A.engine.Encoder(48000, kbps / 48.0, use_vq=True, use_sbr=kbps < 128, guard=guard)
+        planar = A.pacfile.device_stream(enc, pcm)
+        flags = enc.transient_flags(planar, len(pcm) // 1024, 1024)[1]
+        o = enc.encode_vq(A.engine.PcmView.stream(planar, 1024), flags)
+        return {k: o[k].cpu().numpy() for k in ("payload", "n_bytes", "bit_alloc", "status")}
+
+    want = encode(False)
+    nb = want["n_bytes"]
+    assert nb.max() > 0 and not (want["status"] & A._lib.ST_GUARD).any()
+    for frame, bfs in ((None, None), ("0", "1"), ("0", "0")):
+        _set_env(A, monkeypatch, {"PACX_VQ_FRAME": frame, "PACX_VQ_BFS": bfs})
+        got = encode(True)
+        assert np.array_equal(got["n_bytes"], nb), (frame, bfs)
+        assert np.array_equal(got["bit_alloc"], want["bit_alloc"]), (frame, bfs)
+        assert all(np.array_equal(got["payload"][i, :nb[i]], want["payload"][i, :nb[i]]) for i in range(len(nb))), (frame, bfs)
+        assert np.array_equal(got["status"] & ~A._lib.ST_GUARD, want["status"]), (frame, bfs)
+        if frame is None and kbps == 448:              # whole-wave leaves flag as they come: k_vq_frame<true> ran
+            assert (got["status"] & A._lib.ST_GUARD).any()
+    _set_env(A, monkeypatch, {})
+
+
+def test_band_walker_beyond_its_node_store(A, monkeypatch, fresh_handles):
+    """The limits of vq_shape_bfs's node store (VQ_NC = 96 nodes in unsigned char, 64 splits / 64 leaves per level):
+    a band beyond them is coded by vq_shape, the others level by level, and both give the oracle's bytes.  Two hops of
+    the mono tone-plus-noise stream at 448 kb/s are four blocks of 17 bands; the oracle's split recursion
+    (pac_oracle_vq.encode_stream_vq(trace=...)) gives the 363-line band 127 nodes in every block (64 leaves on its
+    last level: at that limit, over the node limit), the 149-line band 101, 97, 93 and 89 nodes -- on both sides of
+    96 -- and every other band 63 nodes or fewer."""
+    from oracle import pac_oracle_vq as pv
+    pcm = _tone_noise_stream()[:2 * 1024, :1]
+    want = pv.encode_stream_vq(pcm, 48000, 448)
+    outs = []
+    for bfs in ("1", "0"):
+        _set_env(A, monkeypatch, {"PACX_VQ_FRAME": "0", "PACX_VQ_BFS": bfs})
+        outs.append(A.pacfile.encode_stream(pcm, 48000, 448, block_switching=True, use_vq=True, use_sbr=False))
+    _set_env(A, monkeypatch, {})
+    assert outs[0] == outs[1]
+    assert outs[0] == want, describe_diff(outs[0], want)
+
+
 def test_frame_decoder_equals_band_decoder(A, monkeypatch, fresh_handles):
     """k_vq_dec_frame (bands parsed one per lane, one leaf per lane, in-place combine; the default) and k_vq_dec
     (a wave per band, depth first; PACX_VQ_DEC_FRAME=0; also what takes the blocks whose trees do not fit the
