@@ -219,6 +219,19 @@ BUCKET_PIN_SIGNATURES.update({f"pacx_{kind}_solve_bucket_pinned": (ctypes.c_int,
                                                                                   ctypes.c_int32, ctypes.c_int32, _P, _P,
                                                                                   _P, _P, _P, _P, _P, _P, _P])
                               for kind, head in CURVE_HEADS.items()})
+# The export list of include/pacx_bucket_kept.h, the third companion header: the buffered solve for a stream in chunks.  The
+# bytes of a pick on a kept curve at n_targets targets (a pick_thresholds call with n_targets, target_t on the device
+# and n_bytes_t [n_targets][n_cf] in place of the target and the three outputs), the scans of those rows folded into
+# acc, and the tree of the bisection's next decisions on the caller's state block
+BUCKET_TREE_LEVELS_MAX, BUCKET_TREE_TARGETS, BUCKET_TREE_STATE_BYTES = 5, 31, 128
+BUCKET_KEPT_SIGNATURES = {f"pacx_{kind}_bytes_thresholds": (ctypes.c_int, [_P, _I64, *head, _P, _P, _P, _D, _D, ctypes.c_int32,
+                                                                           _P, _P, _P])
+                          for kind, head in CURVE_HEADS.items()}
+BUCKET_KEPT_SIGNATURES.update({
+    "pacx_bucket_scan_targets": (ctypes.c_int, [_P, _I64, ctypes.c_int32, ctypes.c_int32, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "pacx_bucket_tree_begin": (ctypes.c_int, [_P, ctypes.POINTER(PacxBucket), _D, _D, ctypes.c_int32, _P, _P, _P, _P]),
+    "pacx_bucket_tree_step": (ctypes.c_int, [_P, _I64, ctypes.POINTER(PacxBucket), ctypes.c_int32, _P, _P, _P, _P, _P, _P]),
+})
 # the summary of pacx_nmr_summary (include/pacx.h): uint64 [2][NMR_MAX_BANDS][NMR_SUMMARY_WORDS]
 NMR_MAX_BANDS, NMR_COUNT, NMR_AUDIBLE, NMR_MAX, NMR_HIST, NMR_HIST_BINS = 32, 0, 1, 2, 3, 320
 NMR_HIST_LO, NMR_HIST_STEP = -120.0, 0.5
@@ -276,7 +289,8 @@ def load():
     # resolves it through the RUNPATH to /opt/rocm.)
     import torch  # noqa: F401
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **BUCKET_SIGNATURES, **BUCKET_PIN_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **BUCKET_SIGNATURES, **BUCKET_PIN_SIGNATURES,
+                              **BUCKET_KEPT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -31,7 +31,7 @@ RESOURCES = os.path.join(OBJ, "resources.json")
 SOURCES = ["pacx_api.hip", "k_mdct.hip", "k_psy.hip", "k_quant.hip", "k_misc.hip", "k_mdct2.hip", "k_decode.hip",
            "k_vq.hip", "k_vq_dec.hip", "k_mdct3.hip", "k_index.hip", "k_nmr.hip", "k_rate.hip", "k_band.hip",
            "k_vq_band.hip", "k_profile.hip", "k_seg_profile.hip", "k_rate_profile.hip", "k_kept.hip",
-           "k_bucket.hip", "k_bucket_pin.hip"]
+           "k_bucket.hip", "k_bucket_pin.hip", "k_bucket_kept.hip"]
 # -ffp-contract=off: integer codes must follow the reference's individually
 # rounded double operations; FMAs are written explicitly where wanted.
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off",
@@ -44,7 +44,7 @@ def _hipcc():
 
 def _headers():
     hs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    hs += [os.path.join(HERE, "..", "include", f) for f in ("pacx.h", "pacx_bucket.h", "pacx_bucket_pin.h")]
+    hs += [os.path.join(HERE, "..", "include", f) for f in ("pacx.h", "pacx_bucket.h", "pacx_bucket_pin.h", "pacx_bucket_kept.h")]
     return hs
 
 

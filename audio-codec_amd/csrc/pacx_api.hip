@@ -2849,6 +2849,139 @@ extern "C" int pacx_rate_pick_thresholds_segments(pacx_handle *h, int64_t n_cf, 
                           first_off, nmr_lo_db, nmr_hi_db, target_t, nullptr, budget, n_bytes, capped, stream);
 }
 
+/* ---- the buffered solve for a stream in chunks, on kept curves (k_bucket_kept.hip, include/pacx_bucket_kept.h) ---- */
+static int tree_targets(pacx_handle *h, const char *what, int32_t n_targets)
+{
+    if (n_targets < 1 || n_targets > PACX_BUCKET_TREE_TARGETS)
+        return fail(h, PACX_E_ARG, std::string(what) + ": n_targets must lie in [1, " +
+                                       std::to_string(PACX_BUCKET_TREE_TARGETS) + "]");
+    return PACX_OK;
+}
+
+extern "C" int pacx_band_bytes_thresholds(pacx_handle *h, int64_t n_cf, const uint16_t *e, const int32_t *cap,
+                                          const uint8_t *cap_alloc, double nmr_lo_db, double nmr_hi_db, int32_t n_targets,
+                                          const int32_t *target_t, int32_t *n_bytes_t, void *stream)
+{
+    const char *what = "pacx_band_bytes_thresholds";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = segments_by_value(h, what, n_cf, PACX_SEG_CF_MAX, 0))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (int rc = tree_targets(h, what, n_targets))
+        return rc;
+    if (n_cf > 0 && (!e || !cap || !cap_alloc || !target_t || !n_bytes_t))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (!aligned16(e))
+        return fail(h, PACX_E_ARG, std::string(what) + ": e must be 16-byte aligned");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_band_bytes_thresholds(h->T, n_cf, n_targets, target_t, t_lo, t_hi, e, cap, cap_alloc, n_bytes_t,
+                                      (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_rate_bytes_thresholds(pacx_handle *h, int64_t n_cf, int32_t row, int32_t sub_stride, const uint16_t *e,
+                                          const int32_t *bits, const int32_t *steps, double nmr_lo_db, double nmr_hi_db,
+                                          int32_t n_targets, const int32_t *target_t, int32_t *n_bytes_t, void *stream)
+{
+    const char *what = "pacx_rate_bytes_thresholds";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = rate_rows(h, what, n_cf, PACX_SEG_CF_MAX, 0, row, sub_stride))
+        return rc;
+    if (int rc = profile_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    if (int rc = tree_targets(h, what, n_targets))
+        return rc;
+    if (n_cf > 0 && (!e || !bits || !steps || !target_t || !n_bytes_t))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_cf == 0)
+        return PACX_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_rate_bytes_thresholds(n_cf, row, sub_stride, n_targets, target_t, t_lo, t_hi, e, bits, steps, n_bytes_t,
+                                      (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_bucket_scan_targets(pacx_handle *h, int64_t n_hops, int32_t n_ch, int32_t n_targets,
+                                        const int32_t *n_bytes_t, int64_t row_stride, int64_t drain_q16,
+                                        int64_t size_bytes, int64_t hop_off, pacx_bucket_result *acc, void *stream)
+{
+    const char *what = "pacx_bucket_scan_targets";
+    if (!h)
+        return PACX_E_ARG;
+    const pacx_bucket b = {drain_q16, size_bytes, 0};                 /* every target starts where its acc ended */
+    if (int rc = check_bucket(h, what, n_hops, n_ch, &b))
+        return rc;
+    if (int rc = tree_targets(h, what, n_targets))
+        return rc;
+    if (hop_off < 0 || hop_off > (1LL << 30) - n_hops)
+        return fail(h, PACX_E_ARG, std::string(what) + ": hop_off >= 0 and hop_off + n_hops <= 2^30");
+    if (n_hops > 0 && row_stride < n_hops * n_ch)
+        return fail(h, PACX_E_ARG, std::string(what) + ": row_stride must hold a row (row_stride >= n_hops n_ch)");
+    if (!acc || (n_hops > 0 && !n_bytes_t))
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (n_hops == 0)
+        return PACX_OK;                            /* the piece of no hop leaves every acc as it is */
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_bucket_scan_targets(n_hops, n_ch, n_targets, n_bytes_t, row_stride, drain_q16, size_bytes, hop_off, acc,
+                                    (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+/* what the two tree calls refuse alike */
+static int tree_args(pacx_handle *h, const char *what, const pacx_bucket *b, int32_t levels, const void *state,
+                     const int32_t *target_t, const pacx_bucket_result *acc)
+{
+    if (!b || !state || !target_t || !acc)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (levels < 1 || levels > PACX_BUCKET_TREE_LEVELS_MAX)
+        return fail(h, PACX_E_ARG, std::string(what) + ": levels must lie in [1, " +
+                                       std::to_string(PACX_BUCKET_TREE_LEVELS_MAX) + "]");
+    return check_bucket(h, what, 0, 1, b);
+}
+
+extern "C" int pacx_bucket_tree_begin(pacx_handle *h, const pacx_bucket *b, double nmr_lo_db, double nmr_hi_db,
+                                      int32_t levels, void *state, int32_t *target_t, pacx_bucket_result *acc,
+                                      void *stream)
+{
+    const char *what = "pacx_bucket_tree_begin";
+    if (!h)
+        return PACX_E_ARG;
+    int t_lo, t_hi;
+    if (int rc = tree_args(h, what, b, levels, state, target_t, acc))
+        return rc;
+    if (int rc = solve_range(h, what, nmr_lo_db, nmr_hi_db, &t_lo, &t_hi))
+        return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_bucket_tree_begin(state, t_lo, t_hi, levels, b->start_q16, target_t, acc, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
+extern "C" int pacx_bucket_tree_step(pacx_handle *h, int64_t limit_bytes, const pacx_bucket *b, int32_t levels,
+                                     void *state, int32_t *target_t, pacx_bucket_result *acc, pacx_rate_result *result,
+                                     pacx_bucket_result *bucket_result, void *stream)
+{
+    const char *what = "pacx_bucket_tree_step";
+    if (!h)
+        return PACX_E_ARG;
+    if (int rc = tree_args(h, what, b, levels, state, target_t, acc))
+        return rc;
+    if (!result || !bucket_result)
+        return fail(h, PACX_E_ARG, std::string(what) + ": null pointer");
+    if (limit_bytes < 0)
+        return fail(h, PACX_E_ARG, std::string(what) + ": negative limit");
+    HIP_TRY(h, hipSetDevice(h->device));
+    pacx_launch_bucket_tree_step(state, limit_bytes, b->size_bytes, b->start_q16, levels, target_t, acc, result,
+                                 bucket_result, (hipStream_t)stream);
+    return post_launch(h, what);
+}
+
 extern "C" int pacx_nmr_summary(pacx_handle *h, int64_t n_cf, int n_channels, const uint8_t *frame_flags,
                                 const double *nmr_db, uint64_t *summary, void *stream)
 {

@@ -374,6 +374,25 @@ inline void pacx_pin_drive(const PacxPinSolve &v, hipStream_t st, Pick pick)
     pacx_launch_pin_finish(v, st);
 }
 
+/* k_bucket_kept.hip: the buffered solve for a stream in chunks (include/pacx_bucket_kept.h).  The bytes of a pick on a
+   kept curve at n_targets grid targets read from the device (n_bytes_t [n_targets][n_cf]; targets clamped into
+   [t_lo, t_hi]), the scans of n_targets rows folded into acc, and the tree of the bisection's decisions on the
+   caller's state block.  One launch each; nothing waits for the device */
+void pacx_launch_band_bytes_thresholds(const PacxTables &T, long long n_cf, int n_targets, const int32_t *target_t,
+                                       int t_lo, int t_hi, const uint16_t *e, const int32_t *cap, const uint8_t *cap_alloc,
+                                       int32_t *n_bytes_t, hipStream_t st);
+void pacx_launch_rate_bytes_thresholds(long long n_cf, int row, int sub_stride, int n_targets, const int32_t *target_t,
+                                       int t_lo, int t_hi, const uint16_t *e, const int32_t *bits, const int32_t *steps,
+                                       int32_t *n_bytes_t, hipStream_t st);
+void pacx_launch_bucket_scan_targets(long long n_hops, int n_ch, int n_targets, const int32_t *n_bytes_t,
+                                     long long row_stride, long long drain_q16, long long size_bytes, long long hop_off,
+                                     pacx_bucket_result *acc, hipStream_t st);
+void pacx_launch_bucket_tree_begin(void *state, int t_lo, int t_hi, int levels, long long start_q16, int32_t *target_t,
+                                   pacx_bucket_result *acc, hipStream_t st);
+void pacx_launch_bucket_tree_step(void *state, long long limit, long long size_bytes, long long start_q16, int levels,
+                                  int32_t *target_t, pacx_bucket_result *acc, pacx_rate_result *result,
+                                  pacx_bucket_result *bucket_result, hipStream_t st);
+
 /* k_vq_band.hip: what pacx_vq_band_curve_batch does around its passes through the gain-shape coder, its decoder and
    k_nmr.  cap / budget int32 [n_cf][8] (-1 / 0 where there is no unit); alloc, cap_alloc int32 [n_cf][band_stride];
    row float64 [n_cf][band_stride], k_nmr's; status_front: the front end's words, status_pass: the pass's own (nullptr

@@ -926,6 +926,131 @@ class Encoder:
         """rate_pick_segments on a kept curve (pacx_rate_pick_thresholds_segments).  -> rate_pick's dict."""
         return self._pick_segments(RATE, kept, seg_cf, first_off, target_t, kept=True)
 
+    # ---- the buffered solve for a stream in chunks, on kept curves (include/pacx_bucket_kept.h): a chunk's bytes at
+    # every target of a pass, the scans of those targets carried from chunk to chunk, the tree of the next decisions
+    def _tree_targets(self, what, target_t):
+        """1 ... 31 grid targets -> a contiguous int32 device tensor [n]"""
+        if isinstance(target_t, torch.Tensor):
+            t = target_t
+            if t.dtype != torch.int32 or t.ndim != 1 or t.device != torch.device(self.device) or not t.is_contiguous():
+                raise ValueError(f"{what}: targets on the device are a contiguous int32 tensor [n_targets]")
+        else:
+            host = np.asarray(target_t)
+            if host.ndim != 1 or not np.array_equal(host, np.round(host)) or (np.abs(host) > 2 ** 26).any():
+                raise ValueError(f"{what}: target_t [n_targets], whole grid units")
+            t = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
+        if not 1 <= t.numel() <= _lib.BUCKET_TREE_TARGETS:
+            raise ValueError(f"{what}: between 1 and {_lib.BUCKET_TREE_TARGETS} targets")
+        return t
+
+    def _bytes_thresholds(self, kind, kept, target_t, out):
+        what = kind.prefix + "_bytes_thresholds"
+        checked = self._checked(kind, kept, what, True)
+        n_cf, t = checked[1], self._tree_targets(what, target_t)
+        shape = (t.numel(), n_cf)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or \
+                out.device != torch.device(self.device) or not out.is_contiguous():
+            raise ValueError(f"{what}: out is a contiguous int32 device tensor {list(shape)}")
+        self._curve_call(what, checked, *self._kept_range(what, kept), ctypes.c_int32(t.numel()), _ptr(t), _ptr(out))
+        return out
+
+    def band_bytes_thresholds(self, kept, target_t, out=None):
+        """The n_bytes of band_pick_thresholds at several targets in one pass over the kept curve
+        (pacx_band_bytes_thresholds, include/pacx_bucket_kept.h): target_t, 1 ... 31 whole grid units (64 per dB, clamped
+        into the curve's range) -- a sequence, or an int32 device tensor [n_targets].  -> int32 device tensor
+        [n_targets, n_cf] (`out`, if given), row m what band_pick_thresholds gives as n_bytes at target_t[m] / 64 dB."""
+        return self._bytes_thresholds(BAND, kept, target_t, out)
+
+    def rate_bytes_thresholds(self, kept, target_t, out=None):
+        """band_bytes_thresholds on a kept rate curve (pacx_rate_bytes_thresholds): row m is rate_pick_thresholds'
+        n_bytes at target_t[m] / 64 dB."""
+        return self._bytes_thresholds(RATE, kept, target_t, out)
+
+    @staticmethod
+    def bucket_no_hop(bucket, n=1):
+        """the scan of no hop from the bucket's start level, n times: int64 NumPy array [n, 5] in the order of
+        _lib.BUCKET_RESULT -- what bucket_scan_targets starts from"""
+        start = int(bucket[2])
+        return np.tile(np.array([0, start, -1, -1, start], np.int64), (int(n), 1))
+
+    def bucket_scan_targets(self, n_bytes_t, n_channels, drain_q16, size_bytes, hop_off, acc):
+        """bucket_scan of one piece of a stream at several targets, folded into the scans of the pieces before it
+        (pacx_bucket_scan_targets): n_bytes_t int32 device tensor [n_targets, n_cf] (rows may lie further apart), row m
+        the piece's n_bytes at target m; acc int64 device tensor [n_targets, 5] in the order of _lib.BUCKET_RESULT,
+        in and out; hop_off: the hops of the stream before the piece.  Row m's scan starts at acc[m]'s end_q16.  From
+        bucket_no_hop() on, acc[m] after the pieces of a stream in order is bucket_scan of the whole row.  -> acc."""
+        what = "bucket_scan_targets"
+        nb = n_bytes_t
+        if not isinstance(nb, torch.Tensor) or nb.dtype != torch.int32 or nb.ndim != 2 or \
+                nb.device != torch.device(self.device) or (nb.shape[1] > 1 and nb.stride(1) != 1) or \
+                (nb.shape[0] > 1 and nb.stride(0) < nb.shape[1]):
+            raise ValueError(f"{what}: n_bytes_t is an int32 device tensor [n_targets, n_cf] with contiguous rows")
+        n, n_cf = nb.shape
+        n_ch = self._hop_channels(what, n_channels, n_cf)
+        if not isinstance(acc, torch.Tensor) or acc.dtype != torch.int64 or tuple(acc.shape) != (n, len(_lib.BUCKET_RESULT)) \
+                or acc.device != torch.device(self.device) or not acc.is_contiguous():
+            raise ValueError(f"{what}: acc is a contiguous int64 device tensor [{n}, {len(_lib.BUCKET_RESULT)}]")
+        if int(hop_off) != hop_off:
+            raise ValueError(f"{what}: hop_off = {hop_off!r}: a whole number of hops")
+        self._call("pacx_" + what, ctypes.c_int64(n_cf // n_ch), n_ch, n, _ptr(nb),
+                   ctypes.c_int64(nb.stride(0) if n > 1 else max(n_cf, 1)), ctypes.c_int64(int(drain_q16)),
+                   ctypes.c_int64(int(size_bytes)), ctypes.c_int64(int(hop_off)), _ptr(acc), self._stream())
+        return acc
+
+    @staticmethod
+    def _tree_levels(what, levels):
+        if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or \
+                not 1 <= levels <= _lib.BUCKET_TREE_LEVELS_MAX:
+            raise ValueError(f"{what}: levels = {levels!r}: a whole number in [1, {_lib.BUCKET_TREE_LEVELS_MAX}]")
+        return int(levels)
+
+    @staticmethod
+    def bucket_tree_passes(nmr_lo_db, nmr_hi_db, levels):
+        """the passes of a solve on this range with this many decisions a pass: ceil((P - 1) / levels), P the pairs of
+        rate_solve_bucket, 2 + ceil(log2(G + 1))"""
+        g = int(round((float(nmr_hi_db) - float(nmr_lo_db)) * _lib.RATE_TARGET_GRID)) + 1
+        return -(-(1 + (g).bit_length()) // int(levels))
+
+    def bucket_tree_begin(self, bucket, nmr_lo_db=-30, nmr_hi_db=30, levels=4, tree=None):
+        """Start a buffered solve whose probes are evaluated a tree at a time (pacx_bucket_tree_begin,
+        include/pacx_bucket_kept.h).  -> tree, a dict of device tensors the caller hands to every call of the solve
+        (made here, or the one given, used again): state (uint8 [128]), target_t (int32 [31], the first 2^levels - 1 the
+        targets of the next pass in heap order), acc (int64 [31, 5], every row the scan of no hop), result (the two
+        results, read by bucket_tree_result)."""
+        what = "bucket_tree_begin"
+        levels = self._tree_levels(what, levels)
+        b = self._bucket_struct(what, bucket)
+        if tree is None:
+            tree = {"state": torch.zeros((_lib.BUCKET_TREE_STATE_BYTES,), dtype=torch.uint8, device=self.device),
+                    "target_t": torch.zeros((_lib.BUCKET_TREE_TARGETS,), dtype=torch.int32, device=self.device),
+                    "acc": torch.zeros((_lib.BUCKET_TREE_TARGETS, len(_lib.BUCKET_RESULT)), dtype=torch.int64,
+                                       device=self.device),
+                    "result": torch.zeros((4, 4), dtype=torch.int32, device=self.device)}
+        self._call("pacx_" + what, ctypes.byref(b), ctypes.c_double(nmr_lo_db), ctypes.c_double(nmr_hi_db), levels,
+                   _ptr(tree["state"]), _ptr(tree["target_t"]), _ptr(tree["acc"]), self._stream())
+        return tree
+
+    def bucket_tree_step(self, limit_bytes, bucket, levels, tree):
+        """The decisions a pass allows (pacx_bucket_tree_step): walks tree["acc"] -- row k the scan of the whole stream at
+        tree["target_t"][k], as bucket_scan_targets leaves it -- from slot 0 by rate_solve_bucket's decision, at most
+        `levels` times, then writes the next pass's targets, resets acc and writes the results.  Nothing is read
+        back.  -> tree."""
+        what = "bucket_tree_step"
+        levels = self._tree_levels(what, levels)
+        b = self._bucket_struct(what, bucket)
+        self._call("pacx_" + what, self._whole_bytes(what, limit_bytes), ctypes.byref(b), levels, _ptr(tree["state"]),
+                   _ptr(tree["target_t"]), _ptr(tree["acc"]), _ptr(tree["result"]), _ptr(tree["result"][1:]),
+                   self._stream())
+        return tree
+
+    def bucket_tree_result(self, tree):
+        """the results of the last bucket_tree_step, read back: dict target_nmr_db, met, total_bytes and bucket
+        (bucket_scan's dict): rate_solve_bucket's once bucket_tree_passes() steps have run"""
+        res = tree["result"].cpu().numpy()
+        return dict(self._rate_results(res, one=True), bucket=self._bucket_result(res[1:].reshape(-1).view(np.int64)))
+
     def band_solve_segments(self, curve, seg_first, limit_bytes, nmr_lo_db=-30, nmr_hi_db=30):
         """band_solve with one limit and one target per stretch of consecutive channel-frames
         (pacx_band_solve_segments, include/pacx.h); segments and results as rate_solve_segments.  -> dict bit_alloc,

@@ -501,6 +501,10 @@ class _CurvePath:
 
     pick_kept, pick_kept_segments = pick, pick_segments
 
+    def bytes_kept(self, kept, target_t, out=None):
+        """the n_bytes of pick() on a kept curve at several grid targets at once"""
+        return self._op("bytes_thresholds", kept, target_t, out=out)
+
     def second_pass(self, view, flags, pick):
         """pick: what a pick or a solve returned"""
         return self.encode(view, flags, pick[self.kind.per_cf.key])
@@ -1134,6 +1138,72 @@ def encode_stream_abr_kept(pcm, sample_rate, kbps_per_channel=None, max_bytes=No
     return b"".join(iter_encode_abr_kept(pcm, sample_rate, kbps_per_channel, max_bytes, chunk_hops,
                                          max_kbps_per_channel, block_switching, header_samples, nmr_range_db, use_vq,
                                          segment_hops, peak_kbps_per_channel, allocation, curve_store))
+
+
+def iter_encode_abr_buffered_kept(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None,
+                                  start_bytes=0, max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                                  nmr_range_db=(-30, 30), allocation="budget", use_vq=False, chunk_hops=4096,
+                                  curve_store=None, levels=4):
+    """encode_stream_abr_buffered_kept piece by piece: the file's header, then the bodies of the chunks in order.  The
+    arguments are checked, the stream is analysed and the target solved when this is called; the second pass runs as
+    the iterator is consumed."""
+    from .streaming import HostStreamRateEncoder
+    # encode_stream_abr_buffered's refusals, in its order; then the chunked call's and the store's: no encoder yet
+    band = _check_allocation(allocation)
+    if use_vq and not band:
+        raise NotImplementedError("gain-shape streams: allocation 'band' only")
+    _abr_range(nmr_range_db)
+    if not kbps_per_channel > 0:
+        raise ValueError("kbps_per_channel must be positive")
+    if pcm.ndim != 2:
+        raise ValueError("pcm: int16 [samples, channels]")
+    b = bucket(kbps_per_channel if drain_kbps_per_channel is None else drain_kbps_per_channel, pcm.shape[1],
+               sample_rate, buffer_bytes, start_bytes)
+    cp, head, make = _abr_chunked_setup(pcm, sample_rate, chunk_hops, max_kbps_per_channel, block_switching,
+                                        header_samples, nmr_range_db, use_vq, allocation)
+    levels = Encoder._tree_levels("levels", levels)
+    blocks = len(pcm) // 1024 + 2
+    limit = _abr_limit(cp, _Blocks(blocks), head, kbps_per_channel, None)
+    if curve_store is not None:
+        HostStreamRateEncoder.check_store(curve_store, blocks * cp.nChannels * _kept_bytes_per_cf(cp, allocation),
+                                          "curve_store")
+    hr = make()
+    hr.keep_curves(curve_store).analyse(pcm)
+    sol = hr.solve_bucket(limit, b, levels)
+    if not sol["met"] and sol["total_bytes"] > limit:
+        raise ValueError(_unreachable(limit, sol["total_bytes"], hr.hi, head))
+    if not sol["met"]:
+        # the one thing the message needs that the solve does not carry: the level at the first block above the buffer
+        over = sol["bucket"]["first_over"]
+        raise ValueError(_buffer_overflows(b, over, hr.level_at(hr.hi, b, over), limit, sol["total_bytes"], hr.hi))
+
+    def parts():
+        yield head
+        for body in hr.encode(pcm, sol["target_nmr_db"], use_kept=True):
+            yield body.tobytes()
+    return parts()
+
+
+def encode_stream_abr_buffered_kept(pcm, sample_rate, kbps_per_channel, buffer_bytes, drain_kbps_per_channel=None,
+                                    start_bytes=0, max_kbps_per_channel=320, block_switching=False, header_samples=None,
+                                    nmr_range_db=(-30, 30), allocation="budget", use_vq=False, chunk_hops=4096,
+                                    curve_store=None, levels=4):
+    """encode_stream_abr_buffered for a stream too long for one batch -> the same .pac bytes, the same two ValueErrors
+    in the same words, from host memory to host memory in chunks of chunk_hops blocks with every chunk's curve taken
+    once.  The parameters are encode_stream_abr_buffered's, in its order, then encode_stream_abr_kept's chunk_hops and
+    curve_store, and levels.  pcm: anything that slices to int16 [n, nCh] pieces (an np.memmap included), n a multiple
+    of 1024 and at least 1024.  The first pass keeps every chunk's curve as 16-bit thresholds
+    (streaming.HostStreamRateEncoder.keep_curves, analyse); the solve walks the kept chunks once per `levels`
+    decisions of encode_stream_abr_buffered's bisection (HostStreamRateEncoder.solve_bucket,
+    include/pacx_bucket_kept.h: 13, 7, 5, 4, 3 passes over the store for levels 1 ... 5 on the default range, the PCM
+    untouched); the second pass picks from the kept curves at the target found.  Device memory stays bounded by the
+    chunk.  The chunked call's refusals (chunk_hops, a range above 128 dB, an empty stream) and a curve_store that is
+    too small, read-only or not uint8 are raised before any GPU work.  iter_encode_abr_buffered_kept gives the same
+    bytes piece by piece."""
+    return b"".join(iter_encode_abr_buffered_kept(pcm, sample_rate, kbps_per_channel, buffer_bytes,
+                                                  drain_kbps_per_channel, start_bytes, max_kbps_per_channel,
+                                                  block_switching, header_samples, nmr_range_db, allocation, use_vq,
+                                                  chunk_hops, curve_store, levels))
 
 
 def encode_stream_vq_nmr(pcm, sample_rate, target_nmr_db, max_kbps_per_channel=320, block_switching=False,

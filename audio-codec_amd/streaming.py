@@ -564,6 +564,93 @@ class HostStreamRateEncoder:
                 "target_nmr_db": np.maximum(floor, stream["target_nmr_db"]), "pinned": floor > stream["target_nmr_db"],
                 "floor_met": seg["met"], "floor_total_bytes": seg["total_bytes"], "worst_above": seg["worst_above"]}
 
+    # ------------------------------------------------------------------ the buffered solve on the kept curves
+    def _kept_pieces(self):
+        """(blocks before, blocks) of every chunk the last analyse() wrote into the store, the tail chunk last"""
+        hops = self.kept["hops"]
+        return [(h0, min(self.F, hops - h0)) for h0 in range(0, hops, self.F)] + [(hops, 2)]
+
+    def _kept_up(self, k, blocks_before, n):
+        """a chunk's kept bytes from the store into dev_kept[k], on the copy-in stream behind the kernels that last read
+        it; ev_in[k] stands for the copy"""
+        per_block = self.kept["per_block"]
+        at, kb = blocks_before * per_block, n * per_block
+        self.ev_in[k].synchronize()                                    # the copy that last read host_kept[k] is done
+        self.host_kept[k].numpy()[:kb] = self.kept["store"][at:at + kb]
+        with torch.cuda.stream(self.s_in):
+            self.s_in.wait_event(self.ev_k[k])
+            self.dev_kept[k][:kb].copy_(self.host_kept[k][:kb], non_blocking=True)
+            self.ev_in[k].record(self.s_in)
+
+    def _need_kept(self, what):
+        if self.keep is None or self.kept is None:
+            raise RuntimeError(f"{what}: after keep_curves() and analyse()")
+
+    def solve_bucket(self, limit_bytes, bucket, levels=4):
+        """Encoder.band_solve_bucket's / rate_solve_bucket's decision for the stream of the last analyse(), from the
+        curves it kept (keep_curves(); RuntimeError otherwise): one target for the stream under limit_bytes and the
+        leaky bucket `bucket` (pacfile.bucket).  The bisection's path is walked `levels` decisions (1 ... 5) a pass
+        (include/pacx_bucket_kept.h): per pass every chunk's kept bytes go up on the copy-in stream, the kernel stream
+        takes the chunk's bytes at the pass's 2^levels - 1 targets (Encoder.band_bytes_thresholds /
+        rate_bytes_thresholds) and carries every target's scan over the chunk (bucket_scan_targets), and behind the last
+        chunk the tree step decides (bucket_tree_step).  Encoder.bucket_tree_passes(lo, hi, levels) passes, 4 at the
+        defaults; the host waits for no result until the one read-back at the end.  -> dict target_nmr_db, met,
+        total_bytes and bucket (Encoder.bucket_scan's dict at that target)."""
+        from .engine import Encoder
+        what = "solve_bucket"
+        self._need_kept(what)
+        levels = Encoder._tree_levels(what, levels)                    # refused before any GPU work
+        Encoder._whole_bytes(what, limit_bytes)
+        Encoder._bucket_struct(what, bucket)
+        solver = self.path.solver
+        drain, size = int(bucket[0]), int(bucket[1])
+        n_t = (1 << levels) - 1
+        dev = self.enc.device
+        if not hasattr(self, "bytes_t"):
+            self.bytes_t = torch.empty(_lib.BUCKET_TREE_TARGETS * self.n_cf, dtype=torch.int32, device=dev)
+            self.tree = None
+        torch.cuda.synchronize(dev)                                    # a new pass over the stream
+        with torch.cuda.stream(self.s_k):
+            self.tree = tree = solver.bucket_tree_begin(bucket, self.lo, self.hi, levels, tree=self.tree)
+        pieces, i = self._kept_pieces(), 0
+        for _ in range(solver.bucket_tree_passes(self.lo, self.hi, levels)):
+            for before, n in pieces:
+                k, i = i % self.depth, i + 1
+                self._kept_up(k, before, n)
+                n_cf = n * self.n_ch
+                with torch.cuda.stream(self.s_k):
+                    self.s_k.wait_event(self.ev_in[k])
+                    rows = self.path.bytes_kept(self._kept_views(k, n), tree["target_t"][:n_t],
+                                                out=self.bytes_t[:n_t * n_cf].view(n_t, n_cf))
+                    solver.bucket_scan_targets(rows, self.n_ch, drain, size, before, tree["acc"][:n_t])
+                    self.ev_k[k].record(self.s_k)
+            with torch.cuda.stream(self.s_k):
+                solver.bucket_tree_step(limit_bytes, bucket, levels, tree)
+        with torch.cuda.stream(self.s_k):
+            return solver.bucket_tree_result(tree)
+
+    def level_at(self, target_nmr_db, bucket, hop):
+        """the bucket's level right after block `hop` arrives with the stream of the last analyse() picked at
+        target_nmr_db, in 1 / 65536 byte: the kept chunks up to that block, one after the other, through the pick at
+        one target and Encoder.bucket_scan(want_level=True), the start level of a chunk carried by the host -- a wait per
+        chunk, for the path that ends in an error message.  The blocks before `hop` must not overflow the bucket."""
+        self._need_kept("level_at")
+        solver, start = self.path.solver, int(bucket[2])
+        torch.cuda.synchronize(self.enc.device)
+        for i, (before, n) in enumerate(self._kept_pieces()):
+            k = i % self.depth
+            self._kept_up(k, before, n)
+            with torch.cuda.stream(self.s_k):
+                self.s_k.wait_event(self.ev_in[k])
+                pick = self.path.pick(self._kept_views(k, n), float(target_nmr_db))
+                scan = solver.bucket_scan(pick["n_bytes"], self.n_ch, (int(bucket[0]), int(bucket[1]), start),
+                                          want_level=True)
+                self.ev_k[k].record(self.s_k)
+                if before <= hop < before + n:
+                    return int(scan["level"][hop - before].item())
+            start = scan["end_q16"]
+        raise ValueError(f"level_at: block {hop} is not one of the stream's {self.kept['hops'] + 2}")
+
     def _result(self, k):
         """the body of the chunk in slot k: a uint8 NumPy view of pinned memory, valid until the slot is used again"""
         self.ev_out[k].synchronize()

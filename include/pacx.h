@@ -1330,6 +1330,8 @@ int pacx_encode_vq_alloc_batch(pacx_handle *h, const pacx_pcm *in, const uint8_t
 #include "pacx_bucket.h"
 /* per-block targets under a bucket (additive exports, ABI 7): the second companion header, behind the first */
 #include "pacx_bucket_pin.h"
+/* the buffered solve in chunks, on kept thresholds (additive exports, ABI 7): the third companion header */
+#include "pacx_bucket_kept.h"
 
 #ifdef __cplusplus
 }
